@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- env-steps/s of the batched 2048 step path on N MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--boards B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--boards B] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over the whole batch: step_kernel advances every board by one action
 (move + score + spawn + done + auto-reset), reading the action from, and writing reward/terminated to, [K][B]
@@ -66,6 +66,7 @@ HBM_PEAK_GBS = 8000.0             # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 SEED = 42
 REF_PORT_RATIO = 3.53            # oracle.cpu_ref.RefEnv steps/s over the reference's Game2048Env.step steps/s
 AGE_STEPS = 64                    # fused steps that bring a freshly reset batch to the steady-state mix of episode ages
+DUMP_SAMPLE = 1 << 18             # boards --dump-outputs writes at most (88 B each: 22 MiB)
 
 
 def parse_args():
@@ -93,7 +94,14 @@ def parse_args():
     ap.add_argument("--gather", choices=["summary", "full"], default="summary",
                     help="N > 1: what the once-per-rollout all-gather ships -- the per-rank return summary "
                          "(g2048_stats) or every board's last episodic return (int32[B])")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them left its caller as DIR/<name>.npy: reward, "
+                         "terminated, boards (exponents), score and board_index, in float32 / float64, of rank 0's shard -- "
+                         f"every board up to {DUMP_SAMPLE}, else a fixed seeded sample of {DUMP_SAMPLE} boards")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def host_cpu_info() -> dict:
@@ -227,6 +235,28 @@ def traffic_for_current_sources(boards: int):
     if boards != (1 << 20) or t.get("csrc_sha16") != prov["current_csrc"]:
         return None, prov
     return t.get("bytes_per_launch"), prov
+
+
+def dump_sample(n: int):
+    """Sorted indices of the boards --dump-outputs writes: all n up to DUMP_SAMPLE, else a sample fixed by SEED."""
+    import numpy as np
+    if n <= DUMP_SAMPLE:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(SEED).choice(n, DUMP_SAMPLE, replace=False))
+
+
+def write_outputs(dirname: str, captured: dict, board_offset: int) -> None:
+    """--dump-outputs: the device buffers ``captured`` behind the timed region, sampled and written as .npy files."""
+    import numpy as np
+    idx = dump_sample(captured["reward"].numel())
+    arrays = {"board_index": (board_offset + idx).astype(np.float64),
+              "reward": captured["reward"].cpu().numpy()[idx].astype(np.float32),
+              "terminated": captured["terminated"].cpu().numpy()[idx].astype(np.float32),
+              "boards": captured["boards"].cpu().numpy()[idx].astype(np.float32),
+              "score": captured["score"].cpu().numpy()[idx].astype(np.float64)}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def free_port() -> int:
@@ -459,6 +489,15 @@ def main():
         for j0 in range(0, W, 8):                        # same kernel, same outputs as the timed steps
             kk = min(8, W - j0)
             wplans.append(eng.prepare_rollout(wa[j0:j0 + kk], reward=wr[:kk], terminated=wt[:kk]))
+    # --dump-outputs: what the LAST timed step left its caller (its reward / terminated rows, the boards and their scores),
+    # copied aside right behind THE timed region -- the repeat regions below run the same steps again -- into buffers
+    # allocated here, outside every timed region
+    captured = None
+    if args.dump_outputs and rank == 0:
+        captured = {"reward": torch.empty(B, dtype=torch.float32, device=dev),
+                    "terminated": torch.empty(B, dtype=torch.uint8, device=dev),
+                    "boards": torch.empty((B, 4, 4), dtype=torch.uint8, device=dev),
+                    "score": torch.empty(B, dtype=torch.int32, device=dev)}
 
     # ---- device warm-up on a scratch engine (every rank): not steps of the benchmarked engine, whose own warm-up is
     #      exactly the W steps below.  SUSTAINED 128-launch trains of the same kernel in the same configuration: shader
@@ -540,6 +579,11 @@ def main():
     elapsed, kernel_region_ms, collective_ms, gathered, sync_after_us = timed_region()   # THE timed region: `value`
     if gathered is not None:
         gathered = gathered.clone()          # (the direct exchange gathers into ONE buffer, which the repeat regions below overwrite)
+    if captured is not None:
+        captured["reward"].copy_(reward[K - 1])
+        captured["terminated"].copy_(terminated[K - 1])
+        eng.boards(out=captured["boards"])
+        eng.scores(out=captured["score"])
     timed_chains = eng.chains_used
     # sanity inside the bench: the rollout really happened (episodes finished, rewards written) -- the engine's books as
     # they stand after THE timed region (what the gathered summaries describe)
@@ -960,6 +1004,9 @@ def main():
             out["cpu_baseline"]["reference_estimate"] = {"value": port / REF_PORT_RATIO, "unit": "env-steps/s", "cores": 1,
                                                          "basis": f"oracle.cpu_ref.RefEnv on 1 core of this box / {REF_PORT_RATIO} "
                                                                   "(RefEnv / reference Game2048Env.step, both 1 core, build container)"}
+
+    if captured is not None:
+        write_outputs(args.dump_outputs, captured, shard.offset)
 
     # The JSON line must be the LAST thing on stdout.  RCCL prints a version banner through C stdio, which a pipe only
     # flushes at exit -- after Python's own buffer -- and under torch.distributed.run every rank shares one stdout: so

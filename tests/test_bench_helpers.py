@@ -75,6 +75,9 @@ def test_bench_script_runs_its_main():
     bench_py = os.path.join(ROOT, "bench.py")
     out = subprocess.run([sys.executable, bench_py, "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "--gpus" in out.stdout and "--steps" in out.stdout and "--warmup" in out.stdout
+    assert "--dump-outputs" in out.stdout
+    out = subprocess.run([sys.executable, bench_py, "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "--steps must be at least 1" in out.stderr      # refused before anything runs
     import torch
     if not torch.cuda.is_available():
         out = subprocess.run([sys.executable, bench_py, "--steps", "2", "--warmup", "1"], capture_output=True, text=True,
@@ -100,6 +103,16 @@ elif mode == "fail1":
     time.sleep(60)                                   # "stuck in a collective": the launcher must stop it
 elif mode == "nojson":
     pass
+elif mode == "gloo":                                 # a real rendezvous: every rank's id reaches rank 0
+    import torch
+    import torch.distributed as dist
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    ids = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+    dist.all_gather(ids, torch.tensor([rank]))
+    dist.barrier()
+    if rank == 0:
+        print(json.dumps({"n_gpus": world, "ranks": [int(t) for t in ids]}))
+    dist.destroy_process_group()
 """
 
 
@@ -122,6 +135,38 @@ def test_launcher_relays_rank0_json_as_the_last_stdout_line(tmp_path):
     assert "banner from rank 0" in out.stdout and "trailing noise from rank 0" in lines[:-1]
     assert "banner from rank 1" in out.stderr and "banner from rank 2" in out.stderr      # other ranks: stderr
     assert "banner from rank 1" not in out.stdout
+
+
+def test_launcher_rendezvous_of_eight_ranks(tmp_path):
+    """The rendezvous `python bench.py --gpus 8` needs, without a GPU: eight ranks started by launch_ranks meet in one
+    gloo process group, all-gather their ids, and rank 0's JSON line comes back LAST with exit code 0.  (On the GPU
+    machine the rehearsal runs four ranks: a shared MI355X takes at most six processes with the device open.)"""
+    out = _run_launcher(tmp_path, "gloo", n=8)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert json.loads(out.stdout.strip().splitlines()[-1]) == {"n_gpus": 8, "ranks": list(range(8))}
+
+
+def test_dump_outputs_writer_samples_a_fixed_set_of_boards(tmp_path):
+    """bench.py --dump-outputs: every array float32 / float64, the per-board arrays of one fixed sorted sample (the same
+    from run to run, so two builds compare output for output), the board index global, at most 64 MB in all."""
+    import numpy as np
+    import torch
+    for n in (1000, bench.DUMP_SAMPLE + 4097):
+        idx = bench.dump_sample(n)
+        assert np.array_equal(idx, bench.dump_sample(n)) and len(idx) == min(n, bench.DUMP_SAMPLE)
+        assert np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+        rs = np.random.default_rng(n)
+        host = {"reward": rs.integers(0, 1 << 12, n).astype(np.float32), "terminated": rs.integers(0, 2, n).astype(np.uint8),
+                "boards": rs.integers(0, 18, (n, 4, 4)).astype(np.uint8), "score": rs.integers(0, 1 << 24, n).astype(np.int32)}
+        d = tmp_path / f"dump_{n}"
+        bench.write_outputs(str(d), {k: torch.from_numpy(v) for k, v in host.items()}, board_offset=3 * n)
+        got = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert sorted(got) == ["board_index", "boards", "reward", "score", "terminated"]
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert sum(a.nbytes for a in got.values()) <= 64 << 20
+        assert np.array_equal(got["board_index"], 3 * n + idx)
+        for k, v in host.items():
+            assert got[k].shape == v[idx].shape and np.array_equal(got[k], v[idx]), k
 
 
 def test_launcher_propagates_the_worst_exit_code_and_stops_stuck_ranks(tmp_path):
