@@ -15,9 +15,9 @@ ENV_ID = "2048-v0"  # the reference's registration id (env/__init__.py:3-6)
 
 
 def __getattr__(name):
-    if name == "Batched2048":  # needs torch + a GPU; imported on first use
-        from .batched import Batched2048
-        return Batched2048
+    if name in ("Batched2048", "afterstates", "Afterstates"):  # need torch + a GPU; imported on first use
+        from . import batched
+        return getattr(batched, name)
     raise AttributeError(name)
 
 

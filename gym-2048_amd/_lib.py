@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libg2048_hip.so")
 
 ACT_RANDOM, ACT_U8, ACT_I32, ACT_I64 = 0, 1, 2, 3
 OBS_U8, OBS_F16, OBS_F32 = 0, 1, 2
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class G2048Error(RuntimeError):
@@ -47,6 +47,17 @@ class HostIO(C.Structure):
         ("boards", C.c_void_p),
         ("terminal_boards", C.c_void_p),
         ("scores", C.c_void_p),
+    ]
+
+
+class AfterstateIO(C.Structure):
+    """g2048_afterstate_io (include/g2048.h): device pointers, NULL = not wanted."""
+    _fields_ = [
+        ("boards", C.c_void_p),
+        ("score", C.c_void_p),
+        ("legal", C.c_void_p),
+        ("obs", C.c_void_p),
+        ("obs_dtype", C.c_int32),
     ]
 
 
@@ -101,6 +112,8 @@ SIGNATURES = {
     "g2048_move": (C.c_int, [_E, C.c_void_p, _i32, C.c_int, C.c_void_p, C.c_void_p, _S]),
     "g2048_query": (C.c_int, [_E, C.c_void_p, C.c_void_p, _S]),
     "g2048_legal_actions": (C.c_int, [_E, C.c_void_p, _S]),
+    "g2048_afterstates": (C.c_int, [_E, C.POINTER(AfterstateIO), _S]),
+    "g2048_afterstates_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(AfterstateIO), _S]),
     "g2048_add_tile": (C.c_int, [_E, _u32, _S]),
     "g2048_fill_random_actions": (C.c_int, [_E, _u64, _u32, C.c_void_p, _S]),
     "g2048_onehot": (C.c_int, [_E, C.c_void_p, _i32, _S]),

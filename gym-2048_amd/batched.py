@@ -10,15 +10,68 @@ int64 tile values.  Actions: 0 up, 1 right, 2 down, 3 left (game2048_env.py:196)
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import G2048Error, HostIO, StepIO, Stats, check
+from ._lib import AfterstateIO, G2048Error, HostIO, StepIO, Stats, check
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}
 _OBS_DTYPES = {torch.uint8: _lib.OBS_U8, torch.float16: _lib.OBS_F16, torch.float32: _lib.OBS_F32}
+
+
+class Afterstates(NamedTuple):
+    """What the four moves of every board produce, before the spawn (``g2048_afterstates``).  Device tensors; a field
+    that is None was not asked for (``out``) -- ``obs`` is None unless an ``obs_dtype`` was given."""
+    boards: Optional[torch.Tensor]   # uint8 [n, 4, 16]: afterstate d of board i (the board itself where d is illegal)
+    score: Optional[torch.Tensor]    # int32 [n, 4]: merge score of move d, 0 where illegal
+    legal: Optional[torch.Tensor]    # uint8 [n]: bit d = move d legal (legal_actions())
+    obs: Optional[torch.Tensor]      # [n, 4, 16, 4, 4] stack() of each afterstate; .view(4n, 16, 4, 4) feeds a network
+
+
+def _afterstate_io(n, device, obs_dtype, out):
+    """(AfterstateIO, Afterstates) for n boards: ``out`` checked field by field, or freshly allocated outputs."""
+    if out is None:
+        out = Afterstates(torch.empty((n, 4, 16), dtype=torch.uint8, device=device),
+                          torch.empty((n, 4), dtype=torch.int32, device=device),
+                          torch.empty(n, dtype=torch.uint8, device=device),
+                          None if obs_dtype is None else torch.empty((n, 4, 16, 4, 4), dtype=obs_dtype, device=device))
+    else:
+        out = Afterstates(*out)
+        if obs_dtype is not None and (out.obs is None or out.obs.dtype != obs_dtype):
+            raise ValueError("obs_dtype does not match out.obs (leave obs_dtype None when passing out)")
+    want = {"boards": ((n, 4, 16), (torch.uint8,)), "score": ((n, 4), (torch.int32,)), "legal": ((n,), (torch.uint8,)),
+            "obs": ((n, 4, 16, 4, 4), tuple(_OBS_DTYPES))}
+    io = AfterstateIO()
+    for name, (shape, dtypes) in want.items():
+        t = getattr(out, name)
+        if t is None:
+            continue
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype not in dtypes or not t.is_contiguous()
+                or t.device != device):
+            raise ValueError(f"out.{name} must be a contiguous {shape} tensor of {' / '.join(map(str, dtypes))} on {device}")
+        setattr(io, name, t.data_ptr())
+    if out.obs is not None:
+        io.obs_dtype = _OBS_DTYPES[out.obs.dtype]
+    return io, out
+
+
+def afterstates(boards, obs_dtype=None, out=None) -> Afterstates:
+    """Afterstates of plain boards (``g2048_afterstates_plain``): ``boards`` is a device ``uint8`` tensor ``[n, 16]`` or
+    ``[n, 4, 4]`` of exponents (taken mod 32) -- replay-buffer rows, a search frontier.  No engine; enqueued on the current
+    stream of the boards' device.  See :class:`Afterstates` and :meth:`Batched2048.afterstates`."""
+    if (not isinstance(boards, torch.Tensor) or boards.dtype != torch.uint8 or boards.device.type != "cuda"
+            or boards.dim() not in (2, 3) or tuple(boards.shape[1:]) not in ((16,), (4, 4)) or not boards.is_contiguous()):
+        raise ValueError("boards must be a contiguous uint8 [n, 16] or [n, 4, 4] tensor on a GPU")
+    n = boards.shape[0]
+    io, out = _afterstate_io(n, boards.device, obs_dtype, out)
+    lib = _lib.load()
+    with torch.cuda.device(boards.device):
+        stream = C.c_void_p(torch.cuda.current_stream(boards.device).cuda_stream)
+        check(lib.g2048_afterstates_plain(boards.data_ptr(), n, C.byref(io), stream))
+    return out
 
 
 class _DeviceView:
@@ -674,6 +727,17 @@ class Batched2048:
         if out.dtype != torch.uint8 or out.shape != (self.n_envs,) or not out.is_contiguous() or out.device != self.device:
             raise ValueError(f"out must be a contiguous uint8 [{self.n_envs}] tensor on the engine's device")
         check(self._lib.g2048_legal_actions(self._h, out.data_ptr(), self._stream()))
+        return out
+
+    def afterstates(self, obs_dtype=None, out=None) -> Afterstates:
+        """The four trial moves of every board in one launch, KEEPING the boards they produce (slide and merge, before
+        the spawn): ``Afterstates(boards [n,4,16] uint8, score [n,4] int32, legal [n] uint8, obs)`` on the engine's
+        stream.  An illegal direction gives the board unchanged, score 0, bit clear (game2048_env.py:224,236-239).
+        ``obs_dtype`` (torch.uint8 / float16 / float32) adds ``stack()`` of each afterstate, ``[n,4,16,4,4]``.  ``out``:
+        a preallocated ``Afterstates`` (fields that are None are not written).  Touches no record, clock, statistic or
+        randomness."""
+        io, out = _afterstate_io(self.n_envs, self.device, obs_dtype, out)
+        check(self._lib.g2048_afterstates(self._h, C.byref(io), self._stream()))
         return out
 
     def isend_numpy(self) -> np.ndarray:

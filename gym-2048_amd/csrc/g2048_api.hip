@@ -293,7 +293,7 @@ extern "C" {
 
 const char *g2048_last_error(void) { return g_error; }
 
-int g2048_abi_version(void) { return 15; }
+int g2048_abi_version(void) { return 16; }
 
 int g2048_create(uint64_t n_boards, int device, uint64_t seed, uint64_t board_offset, g2048_engine **out)
 {
@@ -1058,6 +1058,54 @@ int g2048_legal_actions(const g2048_engine *e, uint8_t *mask_out, void *stream)
         return fail(G2048_ERR_INVALID, "NULL argument");
     G2048_HIP(hipSetDevice(e->device));
     G2048_HIP(g2048::launch_legal_mask(e->st.boards, static_cast<uint32_t>(e->n), mask_out, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+} // extern "C"
+
+// g2048_afterstate_io -> the kernel's outputs, or G2048_ERR_INVALID (before any HIP call: works without a device)
+static int afterstate_out(const g2048_afterstate_io *io, g2048::AfterstateOut *o)
+{
+    if (!io)
+        return fail(G2048_ERR_INVALID, "io is NULL");
+    if (!io->boards && !io->score && !io->legal && !io->obs)
+        return fail(G2048_ERR_INVALID, "g2048_afterstate_io requests no output (boards, score, legal and obs are all NULL)");
+    if ((reinterpret_cast<uintptr_t>(io->boards) | reinterpret_cast<uintptr_t>(io->score) | reinterpret_cast<uintptr_t>(io->obs)) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: afterstate boards, score and obs need 16 bytes");
+    if (io->obs && (io->obs_dtype < G2048_OBS_U8 || io->obs_dtype > G2048_OBS_F32))
+        return fail(G2048_ERR_INVALID, "unknown obs_dtype %d", io->obs_dtype);
+    *o = g2048::AfterstateOut{reinterpret_cast<uint4 *>(io->boards), reinterpret_cast<uint4 *>(io->score), io->legal, io->obs,
+                              io->obs ? static_cast<uint32_t>(io->obs_dtype) : 0u};
+    return G2048_OK;
+}
+
+extern "C" {
+
+int g2048_afterstates(const g2048_engine *e, const g2048_afterstate_io *io, void *stream)
+{
+    if (int rc = usable(e))
+        return rc;
+    g2048::AfterstateOut o;
+    if (int rc = afterstate_out(io, &o))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(g2048::launch_afterstates(e->st.boards, static_cast<uint32_t>(e->n), false, o, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_afterstates_plain(const uint8_t *boards, uint64_t n, const g2048_afterstate_io *io, void *stream)
+{
+    if (!boards)
+        return fail(G2048_ERR_INVALID, "boards is NULL");
+    if (reinterpret_cast<uintptr_t>(boards) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: boards need 16 bytes");
+    if (n == 0 || n > 0xffffff00ull) // (32-bit board indices, whole 256-lane blocks: the cap of g2048_create)
+        return fail(G2048_ERR_INVALID, "n=%llu: need 1 <= n <= 2^32 - 256", (unsigned long long)n);
+    g2048::AfterstateOut o;
+    if (int rc = afterstate_out(io, &o))
+        return rc;
+    G2048_HIP(g2048::launch_afterstates(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), true, o,
+                                        static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 

@@ -85,6 +85,16 @@ hipError_t launch_move(uint4 *boards, uint32_t n, const void *actions, int actio
 hipError_t launch_query(const uint4 *boards, uint32_t n, uint32_t max_exp, uint8_t *isend_out, uint8_t *highest_out,
                         hipStream_t s);
 hipError_t launch_legal_mask(const uint4 *boards, uint32_t n, uint8_t *mask_out, hipStream_t s);
+// g2048_afterstates: outputs of the four trial moves (g2048_afterstate_io, checked by the caller; NULL = not wanted)
+struct AfterstateOut {
+    uint4 *boards;      // [n][4] afterstate cells, one 16-byte chunk per direction
+    uint4 *score;       // [n] four int32 merge scores per chunk
+    uint8_t *legal;     // [n] bit d = move d legal
+    void *obs;          // [n][4][16][4][4] of obs_dtype
+    uint32_t obs_dtype; // G2048_OBS_*
+};
+// `plain`: `boards` holds plain exponents (taken mod 32) rather than engine records
+hipError_t launch_afterstates(const uint4 *boards, uint32_t n, bool plain, const AfterstateOut &o, hipStream_t s);
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s);
 // the same three in numpy-RNG mode (a.st.rng != NULL)
 hipError_t launch_seed_numpy(uint64_t *planes, uint32_t n, uint64_t first_seed, hipStream_t s);

@@ -20,6 +20,8 @@
 #include "g2048_pcg64.h"
 
 #include <atomic>
+#include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 
@@ -1318,6 +1320,98 @@ __global__ void __launch_bounds__(kBlock) onehot_kernel(const uint4 *__restrict_
     }
 }
 
+// ---------------------------------------------------------------------------- afterstates
+// The four trial moves of legal_mask_kernel, keeping what they produce (g2048_afterstates): per board the afterstate of
+// every direction (4 x 16 B), the four merge scores (16 B), the legality mask (1 B) and, when asked, stack() of the four
+// afterstates (4 x 256 / 512 / 1 024 B).  One board per lane, move_sel with the LDS selector rows as in step_body; an
+// illegal direction leaves the board unchanged with gain 0 (:224,:236-239).  Nothing is written back: the records, the
+// clock, the episode slots and the randomness are not touched.  PLAIN: the input is plain exponents (taken mod 32)
+// instead of engine records (whose deficit bits are dropped); OBS: o.obs is set (the one-hot code is compiled only into
+// the kernels that write it: it doubles the VGPR count).
+//
+// Stores.  The scores of consecutive lanes are consecutive 16-byte rows and the masks consecutive bytes: coalesced as
+// they are.  The afterstates are 64 B per lane.  STAGED parks the wave's 256 afterstates in LDS (4 KiB, afterstate
+// 4 * lane + d) and writes them as four fully coalesced 16-byte streaming stores (store s, lane l: chunk s * 64 + l),
+// the scheme of emit_onehot; otherwise each lane stores its own four chunks (every store at a 64-B lane stride).  The
+// observation of the same 256 afterstates is always written from LDS: emit_onehot_as over four quarters of 64.
+// Occupancy with an observation is capped at 2 workgroups per CU like the other observation writers (kObsOccupancyPad):
+// here the static LDS is 18 KiB, so the pad that makes a workgroup own 64 KiB is 46 KiB -- below the 48 KiB that needs
+// no opt-in.
+constexpr uint32_t kAfterstateStaticLds = sizeof(WaveTables) * (kBlock / 64) + sizeof(Cells16) * kBlock * 4u;
+constexpr uint32_t kAfterstateObsPad = 64u * 1024u - kAfterstateStaticLds;
+static_assert(kAfterstateObsPad <= 48u * 1024u, "afterstate occupancy pad needs the dynamic-LDS opt-in");
+
+template <bool PLAIN, bool STAGED, bool OBS>
+__global__ void __launch_bounds__(kBlock) afterstates_kernel(const uint4 *__restrict__ boards, uint32_t n, const AfterstateOut o)
+{
+    __shared__ WaveTables s_tables[kBlock / 64];
+    __shared__ Cells16 s_after[kBlock * 4];
+    const uint2 piece = load_tables_piece();
+    const uint32_t i_raw = blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = i_raw < n;
+    const uint32_t i = valid ? i_raw : n - 1u; // lanes past the end move a copy of the last board and store nothing
+    const Board in = load_board_nt(boards, i);
+    const LdsTables tb = stage_tables(s_tables, piece);
+    const Board cells = PLAIN ? Board{{in.r[0] & kCellBits, in.r[1] & kCellBits, in.r[2] & kCellBits, in.r[3] & kCellBits}}
+                              : record_cells(in);
+    Board after[4];
+    uint32_t gain[4], mask = 0;
+#pragma unroll
+    for (uint32_t d = 0; d < 4u; ++d) {
+        after[d] = cells;
+        if (move_sel(after[d], tb.move_sel(d), gain[d])) // false: after[d] == cells, gain 0
+            mask |= 1u << d;
+    }
+    if (valid && o.legal)
+        o.legal[i] = static_cast<uint8_t>(mask);
+    if (valid && o.score)
+        store_chunk_nt(o.score, i, gain[0], gain[1], gain[2], gain[3]);
+
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave_first = __builtin_amdgcn_readfirstlane(i_raw & ~63u);
+    const uint32_t n_after = wave_first < n ? 4u * (n - wave_first < 64u ? n - wave_first : 64u) : 0u; // this wave's
+    Cells16 *recs = s_after + (threadIdx.x & ~63u) * 4u;
+    if (STAGED || OBS) {
+#pragma unroll
+        for (uint32_t d = 0; d < 4u; ++d) {
+            Cells16 &r = recs[lane * 4u + d];
+            r.r[0] = after[d].r[0], r.r[1] = after[d].r[1], r.r[2] = after[d].r[2], r.r[3] = after[d].r[3];
+        }
+        // same-wave LDS accesses execute in program order; the fences keep the compiler from reordering them
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (o.boards) {
+        if (STAGED) {
+#pragma unroll
+            for (uint32_t s = 0; s < 4u; ++s) {
+                const uint32_t j = s * 64u + lane;
+                if (j < n_after)
+                    store_chunk_nt(o.boards, static_cast<uint64_t>(wave_first) * 4u + j, recs[j].r[0], recs[j].r[1],
+                                   recs[j].r[2], recs[j].r[3]);
+            }
+        } else if (valid) {
+#pragma unroll
+            for (uint32_t d = 0; d < 4u; ++d)
+                store_chunk_nt(o.boards, static_cast<uint64_t>(i) * 4u + d, after[d].r[0], after[d].r[1], after[d].r[2],
+                               after[d].r[3]);
+        }
+    }
+    if (OBS) {
+        // quarter q = afterstates 64q .. 64q + 63 of the wave: one emit_onehot piece of 16 / 32 / 64 KiB
+        for (uint32_t q = 0; q < 4u && 64u * q < n_after; ++q) {
+            const uint32_t n_q = n_after - 64u * q < 64u ? n_after - 64u * q : 64u;
+            uint4 *out = static_cast<uint4 *>(o.obs) + ((static_cast<uint64_t>(wave_first) * 4u + 64u * q) << (4u + o.obs_dtype));
+            if (o.obs_dtype == 0u)
+                emit_onehot_as<0, false>(recs + 64u * q, out, lane, n_q);
+            else if (o.obs_dtype == 1u)
+                emit_onehot_as<1, false>(recs + 64u * q, out, lane, n_q);
+            else
+                emit_onehot_as<2, false>(recs + 64u * q, out, lane, n_q);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------- augmentation
 // training_data.augment() (training_data.py:257-299) for board pairs on the device: the eight
 // symmetries [orig, hflip, rot1(orig), rot1(hflip), rot2(..), rot2(..), rot3(..), rot3(..)] with the
@@ -1845,6 +1939,34 @@ hipError_t launch_legal_mask(const uint4 *boards, uint32_t n, uint8_t *mask_out,
     if (n == 0)
         return hipSuccess;
     hipLaunchKernelGGL(legal_mask_kernel, grid_for(n), dim3(kBlock), 0, s, boards, n, mask_out);
+    return hipGetLastError();
+}
+
+// Stores of the afterstate cells: staged through LDS (the default) or straight from the lanes
+// (G2048_AFTERSTATE_STORES=direct, a measurement knob read once per process: tools/afterstate_probe.py A/Bs the two).
+hipError_t launch_afterstates(const uint4 *boards, uint32_t n, bool plain, const AfterstateOut &o, hipStream_t s)
+{
+    if (n == 0)
+        return hipSuccess;
+    static const bool direct = [] {
+        const char *v = std::getenv("G2048_AFTERSTATE_STORES");
+        return v && std::strcmp(v, "direct") == 0;
+    }();
+    const dim3 g = grid_for(n), b(kBlock);
+#define G2048_AFTER(PLAIN, STAGED)                                                                                      \
+    do {                                                                                                                \
+        if (o.obs)                                                                                                      \
+            hipLaunchKernelGGL((afterstates_kernel<PLAIN, STAGED, true>), g, b, kAfterstateObsPad, s, boards, n, o);    \
+        else                                                                                                            \
+            hipLaunchKernelGGL((afterstates_kernel<PLAIN, STAGED, false>), g, b, 0, s, boards, n, o);                   \
+    } while (0)
+    switch ((plain ? 2 : 0) + (direct ? 0 : 1)) {
+    case 0: G2048_AFTER(false, false); break;
+    case 1: G2048_AFTER(false, true); break;
+    case 2: G2048_AFTER(true, false); break;
+    default: G2048_AFTER(true, true); break;
+    }
+#undef G2048_AFTER
     return hipGetLastError();
 }
 

@@ -292,6 +292,30 @@ int g2048_query(const g2048_engine *e, uint8_t *isend_out, uint8_t *highest_out,
  * policy masks its logits with; one launch instead of four g2048_move(trial) calls.  Boards are not modified. */
 int g2048_legal_actions(const g2048_engine *e, uint8_t *mask_out, void *stream);
 
+/* Afterstates: the board each of the four moves produces (slide and merge, before the spawn), without committing to
+ * any of them.  Direction d = 0..3 as in g2048_move; an illegal direction follows g2048_move(trial) and the reference
+ * (game2048_env.py:224,236-239): its afterstate is the input board unchanged, its score 0 and its legal bit clear.
+ * All pointers are device pointers; NULL = not wanted, but at least one output must be given. */
+typedef struct {
+    uint8_t *boards;    /* [n][4][16] afterstate cells, direction-major within a board; 16-byte aligned */
+    int32_t *score;     /* [n][4] merge score of each move (:253-254), 0 where illegal; 16-byte aligned */
+    uint8_t *legal;     /* [n] bit d = move d is legal: the value g2048_legal_actions writes */
+    void *obs;          /* [n][4][16][4][4] of obs_dtype: stack() (:17-32) of each afterstate, so that it reads as
+                         * [4n][16][4][4]; 16-byte aligned */
+    int32_t obs_dtype;  /* G2048_OBS_*; ignored when obs is NULL */
+} g2048_afterstate_io;
+
+/* All four trial moves of every board in ONE launch, keeping what they produce: what the reference's data tools get
+ * from a second env by set_board + step per move (gather_training_data.py:141-145, the lookahead of :77-87;
+ * add_rewards_to_training_data.py:54-58) and what an afterstate learner or a search node expands.  Reads the engine's
+ * live records (the score deficit is ignored); consumes no randomness, leaves the records, the clock and the episode
+ * bookkeeping alone, in either RNG mode.  Enqueued on `stream`: no allocation, no synchronisation. */
+int g2048_afterstates(const g2048_engine *e, const g2048_afterstate_io *io, void *stream);
+/* The same for n plain boards (uint8[n][16] exponents, device memory, 16-byte aligned; taken mod 32 as in
+ * g2048_set_boards) -- replay-buffer rows or a search frontier.  Needs no engine; runs on the current device.
+ * 1 <= n <= 2^32 - 256. */
+int g2048_afterstates_plain(const uint8_t *boards, uint64_t n, const g2048_afterstate_io *io, void *stream);
+
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream);
