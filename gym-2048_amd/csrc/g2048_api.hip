@@ -97,10 +97,9 @@ struct g2048_engine {
     // completion word (its own 64-byte pinned, device-mapped, coherent block): published by the device, polled by the host
     unsigned long long *done_host = nullptr, *done_dev = nullptr;
     unsigned long long done_count = 0;
-    // two-chain rollouts (g2048_set_chains): the side stream, its fork / join events and its launch thread
+    // two-chain rollouts (g2048_set_chains): the side stream, its launch thread and the fork / join tickets
     int chains = 1;
     SideChain *side = nullptr; // the device's shared side chain (a reference is held while chains == 2 was ever set)
-    hipEvent_t fork_event = nullptr, join_event = nullptr;
     unsigned long long *chain_flags = nullptr; // device memory (256 B): [0] fork ticket, [16] join ticket (own cache lines), [24] scratch
     unsigned long long chain_seq = 0;
     // a ticket wait that ran out (flag_wait_kernel) reports here: 64 bytes of pinned, coherent host memory, checked at
@@ -109,8 +108,6 @@ struct g2048_engine {
     // the measurement / test knobs of the two-chain form, read from the environment by g2048_set_chains (NOT per rollout)
     uint32_t chain_min_steps = 0;      // G2048_TWO_CHAIN_MIN_STEPS: split every rollout of at least that many steps (0: the warm / cold rule)
     uint32_t chain_wait_polls = g2048::kFlagWaitPolls; // G2048_FLAG_WAIT_POLLS: bound of a ticket wait, ~1 us per poll
-    bool chain_any_priority = false;   // G2048_CHAIN_ANY_PRIORITY: also split on a caller's stream of the side stream's priority
-    bool chain_by_events = false;      // G2048_CHAIN_SYNC=events: fork / join by HIP events instead of tickets
     // set when a call left the engine in a state its caller cannot know (a two-chain rollout that failed half-way):
     // every later call fails with this message instead of continuing on half-stepped boards
     int poisoned = 0;
@@ -400,10 +397,6 @@ int g2048_destroy(g2048_engine *e)
     }
     if (e->slab) {
         (void)hipSetDevice(e->device);
-        if (e->fork_event)
-            (void)hipEventDestroy(e->fork_event);
-        if (e->join_event)
-            (void)hipEventDestroy(e->join_event);
         bool any_graph = false;
         for (auto &entry : e->graphs)
             any_graph = any_graph || entry.g.exec;
@@ -548,6 +541,18 @@ int g2048_reset(g2048_engine *e, int new_transaction, uint32_t first_slot, const
     return G2048_OK;
 }
 
+// One step in the engine's RNG mode.  numpy mode: its resets run behind the step kernel, so the plain boards (boards_out)
+// come from the export kernel.
+static hipError_t launch_engine_step(const g2048_engine *e, const g2048::StepArgs &a, int action_dtype, hipStream_t s)
+{
+    if (!e->st.rng)
+        return g2048::launch_step(a, action_dtype, s);
+    hipError_t err = g2048::launch_step_numpy(a, action_dtype, s);
+    if (err == hipSuccess && a.boards_out)
+        err = g2048::launch_export_boards(e->st.boards, a.n, a.boards_out, s);
+    return err;
+}
+
 int g2048_step(g2048_engine *e, const g2048_step_io *io, int auto_reset, void *stream)
 {
     if (int rc = usable(e))
@@ -557,14 +562,7 @@ int g2048_step(g2048_engine *e, const g2048_step_io *io, int auto_reset, void *s
     G2048_HIP(hipSetDevice(e->device));
     e->t += 1;
     e->fresh = 0;
-    const g2048::StepArgs a = make_args(e, io, auto_reset);
-    if (e->st.rng) {
-        G2048_HIP(g2048::launch_step_numpy(a, io->action_dtype, static_cast<hipStream_t>(stream)));
-        if (a.boards_out) // this mode's resets run behind the step kernel: the plain boards come from the export kernel
-            G2048_HIP(g2048::launch_export_boards(e->st.boards, a.n, a.boards_out, static_cast<hipStream_t>(stream)));
-    } else {
-        G2048_HIP(g2048::launch_step(a, io->action_dtype, static_cast<hipStream_t>(stream)));
-    }
+    G2048_HIP(launch_engine_step(e, make_args(e, io, auto_reset), io->action_dtype, static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 
@@ -625,9 +623,7 @@ static int ensure_side_chain(g2048_engine *e)
         return G2048_OK;
     if (e->device < 0 || e->device >= 64)
         return fail(G2048_ERR_INVALID, "two chains are available on devices 0..63");
-    if (!e->chain_flags) { // the engine's own fork / join tickets (and events, for G2048_CHAIN_SYNC=events)
-        G2048_HIP(hipEventCreateWithFlags(&e->fork_event, hipEventDisableTiming));
-        G2048_HIP(hipEventCreateWithFlags(&e->join_event, hipEventDisableTiming));
+    if (!e->chain_flags) { // the engine's own fork / join tickets
         G2048_HIP(hipMalloc(reinterpret_cast<void **>(&e->chain_flags), 256));
         G2048_HIP(hipMemset(e->chain_flags, 0, 256));
         G2048_HIP(hipStreamSynchronize(nullptr)); // (the fill is only enqueued, and not ordered against non-blocking streams)
@@ -712,9 +708,6 @@ int g2048_set_chains(g2048_engine *e, int chains)
         v = std::getenv("G2048_FLAG_WAIT_POLLS");
         const long polls = v ? std::atol(v) : 0l;
         e->chain_wait_polls = polls > 0 && polls < 0x7fffffffl ? static_cast<uint32_t>(polls) : g2048::kFlagWaitPolls;
-        e->chain_any_priority = std::getenv("G2048_CHAIN_ANY_PRIORITY") != nullptr;
-        v = std::getenv("G2048_CHAIN_SYNC");
-        e->chain_by_events = v && std::strcmp(v, "events") == 0;
     }
     e->chains = chains;
     return G2048_OK;
@@ -726,14 +719,22 @@ const char *g2048_graph_status(const g2048_engine *e) { return e ? e->graph_off_
 int g2048_get_chains(const g2048_engine *e) { return e ? e->chains : 0; }
 int g2048_get_chains_used(const g2048_engine *e) { return e ? e->last_rollout_chains : 0; }
 
-static g2048_engine::GraphKey graph_key_of(const g2048_engine *e, uint32_t k_steps, const g2048_step_io *io, uint64_t stride,
-                                           int auto_reset, const g2048::StepArgs &a0)
+// The one test of whether a rollout may be replayed from a cached graph: the form is on, the batch is small enough
+// (graph_max_boards), the train long enough and its configuration one that step_graph_kernel supports.  When it may,
+// *a0 is the launch arguments of step 0 (their clock is not used: a graph reads it through graph_t_dev) and *key is what
+// the graph's frozen kernel arguments depend on.
+static bool graph_key_for(const g2048_engine *e, uint32_t k_steps, const g2048_step_io *io, uint64_t stride, int auto_reset,
+                          g2048::StepArgs *a0, g2048_engine::GraphKey *key)
 {
-    g2048_engine::GraphKey key;
-    key.k_steps = k_steps; key.stride = stride; key.seed = e->seed; key.board_offset = e->board_offset;
-    key.actions = io->actions; key.reward = io->reward; key.terminated = io->terminated; key.last_record = a0.st.last_record;
-    key.action_dtype = io->action_dtype; key.auto_reset = auto_reset ? 1 : 0; key.illegal_reward = e->illegal_reward;
-    return key;
+    if (!e->graph_enabled || e->n > e->graph_max_boards || k_steps < kGraphMinSteps)
+        return false;
+    *a0 = make_args(e, io, auto_reset);
+    if (!g2048::rollout_graph_supported(*a0))
+        return false;
+    key->k_steps = k_steps; key->stride = stride; key->seed = e->seed; key->board_offset = e->board_offset;
+    key->actions = io->actions; key->reward = io->reward; key->terminated = io->terminated; key->last_record = a0->st.last_record;
+    key->action_dtype = io->action_dtype; key->auto_reset = auto_reset ? 1 : 0; key->illegal_reward = e->illegal_reward;
+    return true;
 }
 
 static g2048_engine::GraphEntry *find_graph(g2048_engine *e, const g2048_engine::GraphKey &key)
@@ -782,138 +783,90 @@ int g2048_rollout_prepare(g2048_engine *e, uint32_t k_steps, const g2048_step_io
     if (int rc = check_io(io))
         return rc;
     G2048_HIP(hipSetDevice(e->device));
-    if (!e->graph_enabled || e->n > e->graph_max_boards || k_steps < kGraphMinSteps)
-        return G2048_OK; // this rollout is launched kernel by kernel whatever happens: nothing to prepare
-    g2048_step_io s0 = *io;
-    const g2048::StepArgs a0 = make_args(e, &s0, auto_reset);
-    if (!g2048::rollout_graph_supported(a0))
-        return G2048_OK;
-    const g2048_engine::GraphKey key = graph_key_of(e, k_steps, io, stride, auto_reset, a0);
-    if (!find_graph(e, key))
+    g2048::StepArgs a0;
+    g2048_engine::GraphKey key; // (a rollout that cannot be replayed is launched kernel by kernel: nothing to prepare)
+    if (graph_key_for(e, k_steps, io, stride, auto_reset, &a0, &key) && !find_graph(e, key))
         (void)build_graph(e, key, a0, io->action_dtype, k_steps, stride);
     return G2048_OK;
 }
 
-int g2048_rollout(g2048_engine *e, uint32_t k_steps, const g2048_step_io *io, uint64_t stride, int auto_reset,
-                  void *stream)
+// Is `s` capturing a graph -- or can the runtime not tell (its error is cleared)?  Either way no other thread may launch
+// for this rollout and no cached graph is replayed.  (refuse_capture asks the same question but goes on when it cannot
+// tell.)
+static bool capturing_or_unknown(hipStream_t s)
 {
-    if (int rc = usable(e))
-        return rc;
-    if (int rc = check_io(io))
-        return rc;
-    G2048_HIP(hipSetDevice(e->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (k_steps == 0)
-        return G2048_OK;
-    // ---- two chains: the batch is cut at a block boundary and each half gets its own stream and launch thread.
-    //      Spawn-stream mode only (the numpy-RNG planes are indexed with the engine's board count), not while the
-    //      caller captures a graph (another thread must not launch during a global capture), and only when both halves
-    //      are whole blocks of work.  A rollout can only be split when ALL its k_steps actions are supplied up front, and
-    //      the split only pays from kTwoChainMinSteps steps: a caller that steps one action at a time (ppo_train.py) never
-    //      gets here, whatever g2048_set_chains said.
-    const uint32_t n = static_cast<uint32_t>(e->n);
-    const uint32_t first_half = (n / 2u) & ~255u;
-    bool two = e->chains == 2 && e->side && !e->st.rng && first_half >= 256u && k_steps >= 2;
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;
+    }
+    return st != hipStreamCaptureStatusNone;
+}
+
+// The launch arguments of step j of a rollout whose first step plays transaction t0 + 1 (make_args alone would read
+// e->t, which already stands at the end of the rollout).
+struct RolloutSteps {
+    const g2048_engine *e;
+    const g2048_step_io *io;
+    uint64_t stride;
+    int auto_reset;
+    uint64_t t0;
+    g2048::StepArgs operator()(uint32_t j) const
+    {
+        const g2048_step_io sj = io_of_step(*io, j, stride);
+        g2048::StepArgs a = make_args(e, &sj, auto_reset);
+        const uint64_t t = t0 + 1u + j;
+        a.t_lo = static_cast<uint32_t>(t);
+        a.t_hi = static_cast<uint32_t>(t >> 32);
+        return a;
+    }
+};
+
+// Two chains: the batch is cut at a block boundary and each half gets its own stream and launch thread.  Spawn-stream
+// mode only (the numpy-RNG planes are indexed with the engine's board count), not while the caller captures a graph
+// (another thread must not launch during a global capture), and only when both halves are whole blocks of work.  A
+// rollout can only be split when ALL its k_steps actions are supplied up front, and the split only pays from
+// kTwoChainMinSteps steps: a caller that steps one action at a time (ppo_train.py) never gets here, whatever
+// g2048_set_chains said.
+static bool use_two_chains(g2048_engine *e, uint32_t k_steps, hipStream_t s)
+{
+    const uint32_t first_half = (static_cast<uint32_t>(e->n) / 2u) & ~255u;
+    if (e->chains != 2 || !e->side || e->st.rng || first_half < 256u || k_steps < 2)
+        return false;
     // warm: the side chain had work until recently; need: the rollout length from which the split pays right now
-    const bool warm = two && steady_now_ns() < e->side->busy_until_ns.load(std::memory_order_relaxed);
+    const bool warm = steady_now_ns() < e->side->busy_until_ns.load(std::memory_order_relaxed);
     const uint32_t need = e->chain_min_steps ? e->chain_min_steps : warm ? kTwoChainMinSteps : kTwoChainColdMinSteps;
-    if (two && k_steps < need) {
+    if (k_steps < need) {
         // Too short to split.  A rollout within reach of the threshold still wakes a sleeping launcher, so that a loop of
         // such rollouts finds it spinning when one of them qualifies; short ones (a step at a time) leave it asleep -- an
         // idle core is not spent on a caller that cannot use the second chain.
         if (k_steps >= kTwoChainMinSteps / 2u && e->side->launcher.sleeping.load())
             e->side->launcher.nudge();
-        two = false;
+        return false;
     }
-    if (two) {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &st) != hipSuccess) {
-            (void)hipGetLastError();
-            two = false;
-        } else if (st != hipStreamCaptureStatusNone) {
-            two = false;
-        }
+    if (capturing_or_unknown(s))
+        return false;
+    // A caller's stream at the side stream's own priority may be given the SAME hardware queue by the runtime, and
+    // streams that share one run in submission order: the caller's wait for the join ticket could then sit in front of
+    // the side launches it waits for.  Such a stream gets one chain.  (Streams of other priorities have their own
+    // queues; one runtime call per rollout.)
+    if (s == nullptr)
+        return true;
+    int prio = 0;
+    if (hipStreamGetPriority(s, &prio) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
     }
-    if (two) {
-        // A caller's stream at the side stream's own priority may be given the SAME hardware queue by the runtime, and
-        // streams that share one run in submission order: the caller's wait for the join ticket could then sit in front of
-        // the side launches it waits for.  Such a stream gets one chain.  (Streams of other priorities have their own
-        // queues; one runtime call per rollout.)
-        if (s != nullptr && !e->chain_any_priority) {
-            int prio = 0;
-            if (hipStreamGetPriority(s, &prio) != hipSuccess) {
-                (void)hipGetLastError();
-                two = false;
-            } else if (prio == e->side->priority) {
-                two = false;
-            }
-        }
-    }
-    e->last_rollout_chains = two ? 2 : 1;
-    const uint64_t t0 = e->t;
-    e->t += k_steps;
-    e->fresh = 0;
-    auto args_of = [e, io, stride, auto_reset, t0](uint32_t j) {
-        const g2048_step_io sj = io_of_step(*io, j, stride);
-        g2048::StepArgs a = make_args(e, &sj, auto_reset);
-        const uint64_t t = t0 + 1u + j; // (make_args read e->t, which already stands at the end of the rollout)
-        a.t_lo = static_cast<uint32_t>(t);
-        a.t_hi = static_cast<uint32_t>(t >> 32);
-        return a;
-    };
-    if (!two && e->graph_enabled && n <= e->graph_max_boards && k_steps >= kGraphMinSteps) {
-        // ---- same buffers as last time (or a prepared plan): replay the cached graph of this launch train
-        const g2048::StepArgs a0 = args_of(0);
-        if (g2048::rollout_graph_supported(a0)) {
-            const g2048_engine::GraphKey key = graph_key_of(e, k_steps, io, stride, auto_reset, a0);
-            hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-            const bool capturing = hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone;
-            if (capturing)
-                (void)hipGetLastError();
-            g2048_engine::GraphEntry *have = capturing ? nullptr : find_graph(e, key);
-            if (!capturing && !have && key == e->graph_seen) // the second rollout over these buffers in a row: worth a graph
-                have = build_graph(e, key, a0, io->action_dtype, k_steps, stride);
-            e->graph_seen = key;
-            if (have) {
-                const hipError_t err = g2048::launch_rollout_graph(have->g, t0 + 1u, s);
-                if (err == hipSuccess) {
-                    have->last_stream = s;
-                    ++e->graph_replays;
-                    return G2048_OK;
-                }
-                // no step was enqueued (the launch of a graph is all or nothing; at most the one-lane clock write went out,
-                // which nobody else reads): fall through to stream launches
-                (void)hipGetLastError();
-                g2048::destroy_rollout_graph(have->g);
-                e->graph_enabled = 0;
-                snprintf(e->graph_off_reason, sizeof e->graph_off_reason, "hipGraphLaunch of a cached %u-step rollout failed: %s",
-                         k_steps, hipGetErrorString(err));
-            }
-        }
-    }
-    if (!two) {
-        for (uint32_t j = 0; j < k_steps; ++j) {
-            const g2048::StepArgs a = args_of(j);
-            hipError_t err;
-            if (e->st.rng) {
-                err = g2048::launch_step_numpy(a, io->action_dtype, s);
-                if (err == hipSuccess && a.boards_out)
-                    err = g2048::launch_export_boards(e->st.boards, a.n, a.boards_out, s);
-            } else {
-                err = g2048::launch_step(a, io->action_dtype, s);
-            }
-            if (err != hipSuccess) {
-                // steps 0 .. j-1 are enqueued and will run: the clock says so, and the caller gets the error
-                e->t = t0 + j;
-                return fail(G2048_ERR_HIP, "launch of step %u of %u failed: %s", j, k_steps, hipGetErrorString(err));
-            }
-        }
-        return G2048_OK;
-    }
-    // fork / join: the side stream starts where the caller's stream stands, and whatever the caller enqueues next runs
-    // after both halves.  By tickets in device memory (flag_set_kernel / flag_wait_kernel) -- or, G2048_CHAIN_SYNC=events,
-    // by HIP events (the portable form; ~30 us more latency per rollout on this runtime).
-    const bool by_flags = !e->chain_by_events;
+    return prio != e->side->priority;
+}
+
+// Fork / join by tickets in device memory (flag_set_kernel / flag_wait_kernel): the side stream starts where the caller's
+// stream stands, and whatever the caller enqueues next runs after both halves.
+static int rollout_two_chains(g2048_engine *e, uint32_t k_steps, const RolloutSteps &args_of, hipStream_t s)
+{
+    const int dtype = args_of.io->action_dtype;
+    const uint32_t n = static_cast<uint32_t>(e->n);
+    const uint32_t first_half = (n / 2u) & ~255u;
     SideChain *sc = e->side;
     std::lock_guard<std::mutex> side_in_use(sc->use); // (another engine of this device may be using the side chain)
     hipStream_t side_stream = sc->stream;
@@ -922,36 +875,27 @@ int g2048_rollout(g2048_engine *e, uint32_t k_steps, const g2048_step_io *io, ui
     unsigned long long *err_word = e->chain_err_dev;
     const uint32_t polls = e->chain_wait_polls;
     {   // nothing has been launched yet: a failure here leaves the engine as it was
-        hipError_t err;
-        if (by_flags) {
-            err = g2048::launch_flag_set(fork_flag, seq, s); // enqueued BEFORE the side thread can enqueue its wait
-        } else {
-            err = hipEventRecord(e->fork_event, s);
-            if (err == hipSuccess)
-                err = hipStreamWaitEvent(side_stream, e->fork_event, 0);
-        }
+        const hipError_t err = g2048::launch_flag_set(fork_flag, seq, s); // enqueued BEFORE the side thread can enqueue its wait
         if (err != hipSuccess) {
-            e->t = t0;
+            e->t = args_of.t0;
             return fail(G2048_ERR_HIP, "cannot fork the two chains: %s", hipGetErrorString(err));
         }
     }
     SideLauncher *w = &sc->launcher;
-    const int dtype = io->action_dtype;
     // The caller's chain gets a HEAD START of one launch (~3.3 us of host time, about half a half-batch kernel): two
     // chains that start together run their load phases together, like one big kernel.
     hipError_t mine = g2048::launch_step(part_of(args_of(0), dtype, 0u, first_half), dtype, s);
-    const uint64_t ticket = w->post([e, w, args_of, k_steps, dtype, first_half, n, fork_flag, join_flag, seq, side_stream, by_flags,
-                                     err_word, polls]() -> int {
+    const uint64_t ticket = w->post([e, w, args_of, k_steps, dtype, first_half, n, fork_flag, join_flag, seq, side_stream, err_word,
+                                     polls]() -> int {
         if (hipSetDevice(e->device) != hipSuccess) {
             snprintf(w->error, sizeof w->error, "the side launch thread could not select device %d", e->device);
             return G2048_ERR_HIP;
         }
-        hipError_t err = by_flags ? g2048::launch_flag_wait(fork_flag, seq, err_word, polls, side_stream) : hipSuccess;
+        hipError_t err = g2048::launch_flag_wait(fork_flag, seq, err_word, polls, side_stream);
         for (uint32_t j = 0; j < k_steps && err == hipSuccess; ++j)
             err = g2048::launch_step(part_of(args_of(j), dtype, first_half, n - first_half), dtype, side_stream);
         // the join ticket goes out even after a failed launch: the caller's stream must never wait for a ticket nobody sets
-        const hipError_t tail = by_flags ? g2048::launch_flag_set(join_flag, seq, side_stream)
-                                         : hipEventRecord(e->join_event, side_stream);
+        const hipError_t tail = g2048::launch_flag_set(join_flag, seq, side_stream);
         if (err == hipSuccess)
             err = tail;
         if (err != hipSuccess) {
@@ -965,7 +909,7 @@ int g2048_rollout(g2048_engine *e, uint32_t k_steps, const g2048_step_io *io, ui
     const int theirs = w->wait(ticket); // (the side thread has ISSUED its launches; nothing waits for the device here)
     // The JOIN is enqueued whatever happened above: side-stream kernels that were launched may still be writing the
     // engine's and the caller's buffers, and whatever the caller enqueues next on `stream` must come after them.
-    hipError_t join = by_flags ? g2048::launch_flag_wait(join_flag, seq, err_word, polls, s) : hipStreamWaitEvent(s, e->join_event, 0);
+    const hipError_t join = g2048::launch_flag_wait(join_flag, seq, err_word, polls, s);
     // the side stream has ~k_steps half-batch kernels ahead of it (they are only enqueued): warm until they are done + a bit
     sc->busy_until_ns.store(steady_now_ns() + static_cast<int64_t>((k_steps * (4.0e-6 * n + 0.5) + kSideWarmWindowUs) * 1000.0),
                             std::memory_order_relaxed);
@@ -981,6 +925,74 @@ int g2048_rollout(g2048_engine *e, uint32_t k_steps, const g2048_step_io *io, ui
         return poison(e, what);
     }
     return G2048_OK;
+}
+
+// Same buffers as last time (or a prepared plan): replay the cached graph of this launch train.  Returns whether it
+// served the rollout; when it did not, nothing of it has been enqueued.
+static bool rollout_from_graph(g2048_engine *e, uint32_t k_steps, const RolloutSteps &args_of, hipStream_t s)
+{
+    g2048::StepArgs a0;
+    g2048_engine::GraphKey key;
+    if (!graph_key_for(e, k_steps, args_of.io, args_of.stride, args_of.auto_reset, &a0, &key))
+        return false;
+    const bool capturing = capturing_or_unknown(s);
+    g2048_engine::GraphEntry *have = capturing ? nullptr : find_graph(e, key);
+    if (!capturing && !have && key == e->graph_seen) // the second rollout over these buffers in a row: worth a graph
+        have = build_graph(e, key, a0, args_of.io->action_dtype, k_steps, args_of.stride);
+    e->graph_seen = key;
+    if (!have)
+        return false;
+    const hipError_t err = g2048::launch_rollout_graph(have->g, args_of.t0 + 1u, s);
+    if (err == hipSuccess) {
+        have->last_stream = s;
+        ++e->graph_replays;
+        return true;
+    }
+    // no step was enqueued (the launch of a graph is all or nothing; at most the one-lane clock write went out, which
+    // nobody else reads): the caller falls through to stream launches
+    (void)hipGetLastError();
+    g2048::destroy_rollout_graph(have->g);
+    e->graph_enabled = 0;
+    snprintf(e->graph_off_reason, sizeof e->graph_off_reason, "hipGraphLaunch of a cached %u-step rollout failed: %s", k_steps,
+             hipGetErrorString(err));
+    return false;
+}
+
+// One chain of k stream launches on the caller's stream.
+static int rollout_launch_train(g2048_engine *e, uint32_t k_steps, const RolloutSteps &args_of, hipStream_t s)
+{
+    for (uint32_t j = 0; j < k_steps; ++j) {
+        const hipError_t err = launch_engine_step(e, args_of(j), args_of.io->action_dtype, s);
+        if (err != hipSuccess) {
+            // steps 0 .. j-1 are enqueued and will run: the clock says so, and the caller gets the error
+            e->t = args_of.t0 + j;
+            return fail(G2048_ERR_HIP, "launch of step %u of %u failed: %s", j, k_steps, hipGetErrorString(err));
+        }
+    }
+    return G2048_OK;
+}
+
+int g2048_rollout(g2048_engine *e, uint32_t k_steps, const g2048_step_io *io, uint64_t stride, int auto_reset,
+                  void *stream)
+{
+    if (int rc = usable(e))
+        return rc;
+    if (int rc = check_io(io))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (k_steps == 0)
+        return G2048_OK;
+    const bool two = use_two_chains(e, k_steps, s);
+    e->last_rollout_chains = two ? 2 : 1;
+    const RolloutSteps args_of{e, io, stride, auto_reset, e->t};
+    e->t += k_steps;
+    e->fresh = 0;
+    if (two)
+        return rollout_two_chains(e, k_steps, args_of, s);
+    if (rollout_from_graph(e, k_steps, args_of, s))
+        return G2048_OK;
+    return rollout_launch_train(e, k_steps, args_of, s);
 }
 
 int g2048_rollout_fused(g2048_engine *e, uint32_t k_steps, const g2048_step_io *io, uint64_t stride, int auto_reset,

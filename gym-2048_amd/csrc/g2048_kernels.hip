@@ -20,8 +20,6 @@
 #include "g2048_pcg64.h"
 
 #include <atomic>
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 
@@ -1330,10 +1328,11 @@ __global__ void __launch_bounds__(kBlock) onehot_kernel(const uint4 *__restrict_
 // the kernels that write it: it doubles the VGPR count).
 //
 // Stores.  The scores of consecutive lanes are consecutive 16-byte rows and the masks consecutive bytes: coalesced as
-// they are.  The afterstates are 64 B per lane.  STAGED parks the wave's 256 afterstates in LDS (4 KiB, afterstate
-// 4 * lane + d) and writes them as four fully coalesced 16-byte streaming stores (store s, lane l: chunk s * 64 + l),
-// the scheme of emit_onehot; otherwise each lane stores its own four chunks (every store at a 64-B lane stride).  The
-// observation of the same 256 afterstates is always written from LDS: emit_onehot_as over four quarters of 64.
+// they are.  The afterstates are 64 B per lane: the wave's 256 afterstates are parked in LDS (4 KiB, afterstate
+// 4 * lane + d) and written as four fully coalesced 16-byte streaming stores (store s, lane l: chunk s * 64 + l), the
+// scheme of emit_onehot -- 2.7x faster at 2^20 boards and 3.4x at 2^24 than each lane storing its own four chunks at a
+// 64-B lane stride (profiles/r07_afterstates_probe.txt).  The observation of the same 256 afterstates is written from
+// LDS too: emit_onehot_as over four quarters of 64.
 // Occupancy with an observation is capped at 2 workgroups per CU like the other observation writers (kObsOccupancyPad):
 // here the static LDS is 18 KiB, so the pad that makes a workgroup own 64 KiB is 46 KiB -- below the 48 KiB that needs
 // no opt-in.
@@ -1341,7 +1340,7 @@ constexpr uint32_t kAfterstateStaticLds = sizeof(WaveTables) * (kBlock / 64) + s
 constexpr uint32_t kAfterstateObsPad = 64u * 1024u - kAfterstateStaticLds;
 static_assert(kAfterstateObsPad <= 48u * 1024u, "afterstate occupancy pad needs the dynamic-LDS opt-in");
 
-template <bool PLAIN, bool STAGED, bool OBS>
+template <bool PLAIN, bool OBS>
 __global__ void __launch_bounds__(kBlock) afterstates_kernel(const uint4 *__restrict__ boards, uint32_t n, const AfterstateOut o)
 {
     __shared__ WaveTables s_tables[kBlock / 64];
@@ -1371,30 +1370,21 @@ __global__ void __launch_bounds__(kBlock) afterstates_kernel(const uint4 *__rest
     const uint32_t wave_first = __builtin_amdgcn_readfirstlane(i_raw & ~63u);
     const uint32_t n_after = wave_first < n ? 4u * (n - wave_first < 64u ? n - wave_first : 64u) : 0u; // this wave's
     Cells16 *recs = s_after + (threadIdx.x & ~63u) * 4u;
-    if (STAGED || OBS) {
 #pragma unroll
-        for (uint32_t d = 0; d < 4u; ++d) {
-            Cells16 &r = recs[lane * 4u + d];
-            r.r[0] = after[d].r[0], r.r[1] = after[d].r[1], r.r[2] = after[d].r[2], r.r[3] = after[d].r[3];
-        }
-        // same-wave LDS accesses execute in program order; the fences keep the compiler from reordering them
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (uint32_t d = 0; d < 4u; ++d) {
+        Cells16 &r = recs[lane * 4u + d];
+        r.r[0] = after[d].r[0], r.r[1] = after[d].r[1], r.r[2] = after[d].r[2], r.r[3] = after[d].r[3];
     }
+    // same-wave LDS accesses execute in program order; the fences keep the compiler from reordering them
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (o.boards) {
-        if (STAGED) {
 #pragma unroll
-            for (uint32_t s = 0; s < 4u; ++s) {
-                const uint32_t j = s * 64u + lane;
-                if (j < n_after)
-                    store_chunk_nt(o.boards, static_cast<uint64_t>(wave_first) * 4u + j, recs[j].r[0], recs[j].r[1],
-                                   recs[j].r[2], recs[j].r[3]);
-            }
-        } else if (valid) {
-#pragma unroll
-            for (uint32_t d = 0; d < 4u; ++d)
-                store_chunk_nt(o.boards, static_cast<uint64_t>(i) * 4u + d, after[d].r[0], after[d].r[1], after[d].r[2],
-                               after[d].r[3]);
+        for (uint32_t s = 0; s < 4u; ++s) {
+            const uint32_t j = s * 64u + lane;
+            if (j < n_after)
+                store_chunk_nt(o.boards, static_cast<uint64_t>(wave_first) * 4u + j, recs[j].r[0], recs[j].r[1],
+                               recs[j].r[2], recs[j].r[3]);
         }
     }
     if (OBS) {
@@ -1942,30 +1932,22 @@ hipError_t launch_legal_mask(const uint4 *boards, uint32_t n, uint8_t *mask_out,
     return hipGetLastError();
 }
 
-// Stores of the afterstate cells: staged through LDS (the default) or straight from the lanes
-// (G2048_AFTERSTATE_STORES=direct, a measurement knob read once per process: tools/afterstate_probe.py A/Bs the two).
 hipError_t launch_afterstates(const uint4 *boards, uint32_t n, bool plain, const AfterstateOut &o, hipStream_t s)
 {
     if (n == 0)
         return hipSuccess;
-    static const bool direct = [] {
-        const char *v = std::getenv("G2048_AFTERSTATE_STORES");
-        return v && std::strcmp(v, "direct") == 0;
-    }();
     const dim3 g = grid_for(n), b(kBlock);
-#define G2048_AFTER(PLAIN, STAGED)                                                                                      \
+#define G2048_AFTER(PLAIN)                                                                                              \
     do {                                                                                                                \
         if (o.obs)                                                                                                      \
-            hipLaunchKernelGGL((afterstates_kernel<PLAIN, STAGED, true>), g, b, kAfterstateObsPad, s, boards, n, o);    \
+            hipLaunchKernelGGL((afterstates_kernel<PLAIN, true>), g, b, kAfterstateObsPad, s, boards, n, o);            \
         else                                                                                                            \
-            hipLaunchKernelGGL((afterstates_kernel<PLAIN, STAGED, false>), g, b, 0, s, boards, n, o);                   \
+            hipLaunchKernelGGL((afterstates_kernel<PLAIN, false>), g, b, 0, s, boards, n, o);                           \
     } while (0)
-    switch ((plain ? 2 : 0) + (direct ? 0 : 1)) {
-    case 0: G2048_AFTER(false, false); break;
-    case 1: G2048_AFTER(false, true); break;
-    case 2: G2048_AFTER(true, false); break;
-    default: G2048_AFTER(true, true); break;
-    }
+    if (plain)
+        G2048_AFTER(true);
+    else
+        G2048_AFTER(false);
 #undef G2048_AFTER
     return hipGetLastError();
 }

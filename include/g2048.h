@@ -224,9 +224,9 @@ int g2048_rollout(g2048_engine *e, uint32_t k_steps, const g2048_step_io *io, ui
  * tail of the other's: 9.4 -> 8.2 us per step at 2^20 boards, 5.6 -> 4.8 at 2^19, nothing below 2^19 or at 2^24
  * (tools/ubench/overlap.hip).  The side stream is forked from and joined back into `stream` inside every
  * g2048_rollout call -- by one-wave kernels that publish / await a ticket in device memory, which cost this runtime
- * ~17 us less latency per rollout than an event record + hipStreamWaitEvent pair (G2048_CHAIN_SYNC=events selects
- * those) -- so callers see ordinary stream order.  Applies to g2048_rollout in spawn-stream mode with at least 512
- * boards, when the rollout is long enough to pay: from 12 steps while the device's side chain is WARM (it had work
+ * ~17 us less latency per rollout than an event record + hipStreamWaitEvent pair -- so callers see ordinary stream
+ * order.  Applies to g2048_rollout in spawn-stream mode with at least 512 boards, when
+ * the rollout is long enough to pay: from 12 steps while the device's side chain is WARM (it had work
  * within the last ~50 ms: two chains cost ~6 us per rollout and save ~1.2 us per step at 2^20 boards), from 64 steps when
  * it is COLD (a stream that has idled for a few hundred milliseconds starts its first kernels ~40 us late).  Everything
  * else (g2048_step, shorter rollouts, numpy-RNG mode, a capturing stream, a caller's stream created at the device's
@@ -236,8 +236,8 @@ int g2048_rollout(g2048_engine *e, uint32_t k_steps, const g2048_step_io *io, ui
  * Default: 1 -- the form is OPT-IN: it starts a launch thread per device (which spins for G2048_SIDE_SPIN_US microseconds,
  * default 200, after a job before it sleeps; rollouts of fewer than 6 steps leave it asleep) and can only ever fire for a
  * single g2048_rollout of >= 12 steps whose actions are all supplied up front -- never for a caller that steps one action
- * at a time.  The knobs (G2048_TWO_CHAIN_MIN_STEPS, G2048_CHAIN_SYNC, G2048_CHAIN_ANY_PRIORITY, G2048_FLAG_WAIT_POLLS) are
- * read by THIS call, once.  Failure behaviour: a ticket wait is bounded (2^26 polls of ~1 us); one that runs out reports
+ * at a time.  The knobs (G2048_TWO_CHAIN_MIN_STEPS, G2048_FLAG_WAIT_POLLS) are read by THIS call, once.  Failure
+ * behaviour: a ticket wait is bounded (2^26 polls of ~1 us); one that runs out reports
  * through pinned host memory and EVERY later call on the engine returns G2048_ERR_HIP (its chains ran unordered); a
  * rollout whose launches fail half-way still enqueues its join and leaves the engine refusing further calls.  A profiler
  * that serialises kernels across queues (rocprofv3 --pmc) makes the tickets wait for each other: use one chain there. */

@@ -17,7 +17,6 @@ afterstates (+ scores, legality mask, optionally the one-hot of each):
 --summary KERNEL_TRACE_CSV [--pmc-csv COUNTER_CSV]: no GPU; per afterstates_kernel instantiation and grid size, the mean
   dispatch time of the trace, the fraction of the 8 TB/s peak on the byte model, and (with the counter CSV) the measured
   FETCH_SIZE / WRITE_SIZE per board against the model.
-G2048_AFTERSTATE_STORES=direct in the environment selects the unstaged stores (the A/B of the kernel's LDS staging).
 """
 from __future__ import annotations
 
@@ -132,12 +131,12 @@ def summarize(trace_csv, pmc_csv=None):
             continue
         boards = int(r["Grid_Size_X"]) if "Grid_Size_X" in r else int(r["Grid_Size"])
         ns = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
-        flags = re.search(r"afterstates_kernel<(\w+), (\w+), (\w+)>", name).groups()
+        flags = tuple(re.search(r"afterstates_kernel<([^>]*)>", name).group(1).split(", "))  # (PLAIN, [STAGED,] OBS)
         groups.setdefault((flags, boards), []).append(ns)
     print("kernel                                  boards      calls  mean_us  bytes/board  frac_8TB/s")
     for (flags, boards), v in sorted(groups.items()):
         us = sum(v) / len(v) / 1e3
-        per = 97 if obs_bytes[flags[2]] == 0 else None
+        per = 97 if obs_bytes[flags[-1]] == 0 else None
         frac = f"{per * boards / (us * 1e-6) / PEAK:.3f}" if per else "(obs: see dtype)"
         print(f"afterstates_kernel<{', '.join(flags)}>  {boards:>10} {len(v):>6} {us:>8.2f}  {per or '97+obs':>11}  {frac}")
     if pmc_csv:
@@ -163,7 +162,6 @@ def main():
         return summarize(args.summary, args.pmc_csv)
     import __graft_entry__ as ge
     ge.build_hip()
-    stores = os.environ.get("G2048_AFTERSTATE_STORES", "staged")
     rows = []
     for name in args.points.split(","):
         log2n, dt = POINTS[name]
@@ -194,7 +192,7 @@ def main():
             for k, fn in fns.items():
                 samples[k].append(time_calls(fn, reps[k]))
         med = {k: statistics.median(v) for k, v in samples.items()}
-        row = dict(point=name, boards=p.n, obs=str(dt).replace("torch.", "") if dt else None, stores=stores,
+        row = dict(point=name, boards=p.n, obs=str(dt).replace("torch.", "") if dt else None,
                    bytes_per_board=97 + OBS_BYTES[dt], reps=reps,
                    us={k: round(v, 2) for k, v in med.items()},
                    us_min_max={k: [round(min(v), 2), round(max(v), 2)] for k, v in samples.items()},
