@@ -533,24 +533,8 @@ int g2048_reset(g2048_engine *e, int new_transaction, uint32_t first_slot, const
     if (new_transaction)
         e->t += 1;
     e->fresh = 0;
-    const g2048::StepArgs a = make_args(e, nullptr, 0);
-    if (e->st.rng)
-        G2048_HIP(g2048::launch_reset_numpy(a, mask, static_cast<hipStream_t>(stream)));
-    else
-        G2048_HIP(g2048::launch_reset(a, first_slot, mask, static_cast<hipStream_t>(stream)));
+    G2048_HIP(g2048::launch_reset(make_args(e, nullptr, 0), first_slot, mask, static_cast<hipStream_t>(stream)));
     return G2048_OK;
-}
-
-// One step in the engine's RNG mode.  numpy mode: its resets run behind the step kernel, so the plain boards (boards_out)
-// come from the export kernel.
-static hipError_t launch_engine_step(const g2048_engine *e, const g2048::StepArgs &a, int action_dtype, hipStream_t s)
-{
-    if (!e->st.rng)
-        return g2048::launch_step(a, action_dtype, s);
-    hipError_t err = g2048::launch_step_numpy(a, action_dtype, s);
-    if (err == hipSuccess && a.boards_out)
-        err = g2048::launch_export_boards(e->st.boards, a.n, a.boards_out, s);
-    return err;
 }
 
 int g2048_step(g2048_engine *e, const g2048_step_io *io, int auto_reset, void *stream)
@@ -562,7 +546,7 @@ int g2048_step(g2048_engine *e, const g2048_step_io *io, int auto_reset, void *s
     G2048_HIP(hipSetDevice(e->device));
     e->t += 1;
     e->fresh = 0;
-    G2048_HIP(launch_engine_step(e, make_args(e, io, auto_reset), io->action_dtype, static_cast<hipStream_t>(stream)));
+    G2048_HIP(g2048::launch_step(make_args(e, io, auto_reset), io->action_dtype, static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 
@@ -962,7 +946,7 @@ static bool rollout_from_graph(g2048_engine *e, uint32_t k_steps, const RolloutS
 static int rollout_launch_train(g2048_engine *e, uint32_t k_steps, const RolloutSteps &args_of, hipStream_t s)
 {
     for (uint32_t j = 0; j < k_steps; ++j) {
-        const hipError_t err = launch_engine_step(e, args_of(j), args_of.io->action_dtype, s);
+        const hipError_t err = g2048::launch_step(args_of(j), args_of.io->action_dtype, s);
         if (err != hipSuccess) {
             // steps 0 .. j-1 are enqueued and will run: the clock says so, and the caller gets the error
             e->t = args_of.t0 + j;
@@ -1009,7 +993,7 @@ int g2048_rollout_fused(g2048_engine *e, uint32_t k_steps, const g2048_step_io *
     G2048_HIP(hipSetDevice(e->device));
     e->t += 1; // transaction of the first fused step
     e->fresh = 0;
-    g2048::StepArgs a = make_args(e, io, auto_reset); // (numpy-RNG mode: a.st.rng selects rollout_fused_numpy_kernel)
+    g2048::StepArgs a = make_args(e, io, auto_reset);
     a.k_steps = k_steps;
     G2048_HIP(g2048::launch_rollout_fused(a, io->action_dtype, stride, static_cast<hipStream_t>(stream)));
     e->t += k_steps - 1;
@@ -1027,10 +1011,7 @@ int g2048_rollout_random(g2048_engine *e, uint32_t k_steps, void *stream)
     e->fresh = 0;
     g2048::StepArgs a = make_args(e, nullptr, 1);
     a.k_steps = k_steps;
-    if (e->st.rng) // numpy-RNG mode: the fused form of that mode with the synthetic policy and no per-step output
-        G2048_HIP(g2048::launch_rollout_fused(a, G2048_ACT_RANDOM, 0, static_cast<hipStream_t>(stream)));
-    else
-        G2048_HIP(g2048::launch_rollout_random(a, static_cast<hipStream_t>(stream)));
+    G2048_HIP(g2048::launch_rollout_random(a, static_cast<hipStream_t>(stream)));
     e->t += k_steps - 1;
     return G2048_OK;
 }
@@ -1127,11 +1108,7 @@ int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream)
         return rc;
     G2048_HIP(hipSetDevice(e->device));
     e->fresh = 0;
-    const g2048::StepArgs a = make_args(e, nullptr, 0);
-    if (e->st.rng)
-        G2048_HIP(g2048::launch_add_tile_numpy(a, static_cast<hipStream_t>(stream)));
-    else
-        G2048_HIP(g2048::launch_add_tile(a, slot, static_cast<hipStream_t>(stream)));
+    G2048_HIP(g2048::launch_add_tile(make_args(e, nullptr, 0), slot, static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 
@@ -1164,23 +1141,12 @@ int g2048_onehot(const g2048_engine *e, void *out, int32_t obs_dtype, void *stre
     return G2048_OK;
 }
 
-static int copy_out(const g2048_engine *e, void *dst, const void *src, size_t bytes, void *stream)
+// A synchronous copy between the engine's device memory and the caller's host buffer (the engine's side is never NULL).
+static int copy_sync(const g2048_engine *e, void *dst, const void *src, size_t bytes, void *stream)
 {
     if (int rc = usable(e))
         return rc;
-    if (!dst)
-        return fail(G2048_ERR_INVALID, "NULL argument");
-    G2048_HIP(hipSetDevice(e->device));
-    G2048_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, static_cast<hipStream_t>(stream)));
-    G2048_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-static int copy_in(g2048_engine *e, void *dst, const void *src, size_t bytes, void *stream)
-{
-    if (int rc = usable(e))
-        return rc;
-    if (!src)
+    if (!dst || !src)
         return fail(G2048_ERR_INVALID, "NULL argument");
     G2048_HIP(hipSetDevice(e->device));
     G2048_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, static_cast<hipStream_t>(stream)));
@@ -1351,7 +1317,7 @@ int g2048_step_host(g2048_engine *e, int auto_reset, void *stream)
     const unsigned long long want = ++e->done_count;
     if (e->st.rng) { // numpy-RNG mode: step (+ compacted resets), then boards + scores + the completion word
         a.boards_out = nullptr;
-        G2048_HIP(g2048::launch_step_numpy(a, io.action_dtype, s));
+        G2048_HIP(g2048::launch_step(a, io.action_dtype, s));
         G2048_HIP(g2048::launch_fetch(e->st.boards, a.n, reinterpret_cast<uint4 *>(d.boards), d.scores, e->done_dev, want, s));
     } else {
         a.done_seq = e->done_dev;
@@ -1488,127 +1454,115 @@ static int enter_device_of(DeviceScope &scope, const void *const *bufs, int n_bu
     return G2048_OK;
 }
 
-// The engine keeps RECORDS (cells + packed score deficit); the plain views are produced / consumed by
-// small kernels, through the staging buffer when the caller's buffer is host memory.
-int g2048_get_boards(const g2048_engine *ce, uint8_t *buf, void *stream)
+// The engine keeps RECORDS (cells + packed score deficit); the plain views -- board cells uint8[n][16] and int32[n]
+// scores, `width` 16 and 4 bytes per board -- are produced / consumed by small kernels, `launch`ed on the caller's buffer
+// when it is device memory (which needs `width`-byte alignment; stream-ordered, no synchronisation) and on the staging
+// buffer with a synchronous copy when it is host memory.
+
+// The checks every view transfer starts with; *device: `buf` is device memory.
+static int view_entry(const g2048_engine *e, const void *buf, size_t width, const char *reads_last, bool *device)
 {
-    g2048_engine *e = const_cast<g2048_engine *>(ce);
     if (int rc = usable(e))
         return rc;
     if (!buf)
         return fail(G2048_ERR_INVALID, "NULL argument");
+    if (reads_last)
+        if (int rc = need_last_records(e, reads_last))
+            return rc;
     G2048_HIP(hipSetDevice(e->device));
+    *device = is_device_ptr(buf);
+    if (*device && (reinterpret_cast<uintptr_t>(buf) & (width - 1)))
+        return fail(G2048_ERR_INVALID, "device %s buffers must be %zu-byte aligned", width == 16 ? "board" : "score", width);
+    return G2048_OK;
+}
+
+// `reads_last`: the name of an entry point whose view comes from the terminal records, which the engine must keep
+static int export_view(const g2048_engine *ce, void *buf, size_t width, const char *reads_last, void *stream,
+                       hipError_t (*launch)(const g2048_engine *e, void *view, hipStream_t s))
+{
+    g2048_engine *e = const_cast<g2048_engine *>(ce);
+    bool device = false;
+    if (int rc = view_entry(e, buf, width, reads_last, &device))
+        return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t n = static_cast<uint32_t>(e->n);
-    if (is_device_ptr(buf)) {
-        if (reinterpret_cast<uintptr_t>(buf) & 15u)
-            return fail(G2048_ERR_INVALID, "device board buffers must be 16-byte aligned");
-        G2048_HIP(g2048::launch_export_boards(e->st.boards, n, reinterpret_cast<uint4 *>(buf), s));
+    if (device) {
+        G2048_HIP(launch(e, buf, s));
         return G2048_OK; // device destination: ready in stream order
     }
     if (int rc = ensure_scratch(e))
         return rc;
-    G2048_HIP(g2048::launch_export_boards(e->st.boards, n, static_cast<uint4 *>(e->scratch), s));
-    return copy_out(e, buf, e->scratch, e->n * 16, stream);
+    G2048_HIP(launch(e, e->scratch, s));
+    return copy_sync(e, buf, e->scratch, e->n * width, stream);
+}
+
+// `vet_host`: checks the values of a host buffer before anything is copied (NULL: none)
+static int import_view(g2048_engine *e, const void *buf, size_t width, int (*vet_host)(const g2048_engine *e, const void *buf),
+                       void *stream, hipError_t (*launch)(const g2048_engine *e, const void *view, hipStream_t s))
+{
+    bool device = false;
+    if (int rc = view_entry(e, buf, width, nullptr, &device))
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (device) {
+        G2048_HIP(launch(e, buf, s));
+        return G2048_OK;
+    }
+    if (vet_host)
+        if (int rc = vet_host(e, buf))
+            return rc;
+    if (int rc = ensure_scratch(e))
+        return rc;
+    if (int rc = copy_sync(e, e->scratch, buf, e->n * width, stream))
+        return rc;
+    G2048_HIP(launch(e, e->scratch, s));
+    G2048_HIP(hipStreamSynchronize(s)); // the staging buffer must be free again when this returns
+    return G2048_OK;
+}
+
+// a record holds a score of 24 bits
+static int vet_scores(const g2048_engine *e, const void *buf)
+{
+    const int32_t *scores = static_cast<const int32_t *>(buf);
+    for (uint64_t i = 0; i < e->n; ++i)
+        if (scores[i] < 0 || scores[i] > 0x00ffffff)
+            return fail(G2048_ERR_INVALID, "score %d of board %llu is outside 0 .. 2^24-1", scores[i], (unsigned long long)i);
+    return G2048_OK;
+}
+
+int g2048_get_boards(const g2048_engine *e, uint8_t *buf, void *stream)
+{
+    return export_view(e, buf, 16, nullptr, stream, [](const g2048_engine *en, void *view, hipStream_t s) {
+        return g2048::launch_export_boards(en->st.boards, static_cast<uint32_t>(en->n), static_cast<uint4 *>(view), s);
+    });
 }
 
 int g2048_set_boards(g2048_engine *e, const uint8_t *buf, void *stream)
 {
-    if (int rc = usable(e))
-        return rc;
-    if (!buf)
-        return fail(G2048_ERR_INVALID, "NULL argument");
-    G2048_HIP(hipSetDevice(e->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t n = static_cast<uint32_t>(e->n);
-    const uint4 *src = reinterpret_cast<const uint4 *>(buf);
-    if (!is_device_ptr(buf)) {
-        if (int rc = ensure_scratch(e))
-            return rc;
-        if (int rc = copy_in(e, e->scratch, buf, e->n * 16, stream))
-            return rc;
-        src = static_cast<const uint4 *>(e->scratch);
-    } else if (reinterpret_cast<uintptr_t>(buf) & 15u) {
-        return fail(G2048_ERR_INVALID, "device board buffers must be 16-byte aligned");
-    }
-    G2048_HIP(g2048::launch_import_boards(e->st.boards, n, src, s));
-    if (src == e->scratch) // the staging buffer must be free again when this returns
-        G2048_HIP(hipStreamSynchronize(s));
-    return G2048_OK;
+    return import_view(e, buf, 16, nullptr, stream, [](const g2048_engine *en, const void *view, hipStream_t s) {
+        return g2048::launch_import_boards(en->st.boards, static_cast<uint32_t>(en->n), static_cast<const uint4 *>(view), s);
+    });
 }
 
-int g2048_get_scores(const g2048_engine *ce, int32_t *buf, void *stream)
+int g2048_get_scores(const g2048_engine *e, int32_t *buf, void *stream)
 {
-    g2048_engine *e = const_cast<g2048_engine *>(ce);
-    if (int rc = usable(e))
-        return rc;
-    if (!buf)
-        return fail(G2048_ERR_INVALID, "NULL argument");
-    G2048_HIP(hipSetDevice(e->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t n = static_cast<uint32_t>(e->n);
-    if (is_device_ptr(buf)) {
-        if (reinterpret_cast<uintptr_t>(buf) & 3u)
-            return fail(G2048_ERR_INVALID, "device score buffers must be 4-byte aligned");
-        G2048_HIP(g2048::launch_export_scores(e->st.boards, n, buf, s));
-        return G2048_OK; // device destination: ready in stream order
-    }
-    if (int rc = ensure_scratch(e))
-        return rc;
-    G2048_HIP(g2048::launch_export_scores(e->st.boards, n, static_cast<int32_t *>(e->scratch), s));
-    return copy_out(e, buf, e->scratch, e->n * 4, stream);
+    return export_view(e, buf, 4, nullptr, stream, [](const g2048_engine *en, void *view, hipStream_t s) {
+        return g2048::launch_export_scores(en->st.boards, static_cast<uint32_t>(en->n), static_cast<int32_t *>(view), s);
+    });
 }
 
 int g2048_set_scores(g2048_engine *e, const int32_t *buf, void *stream)
 {
-    if (int rc = usable(e))
-        return rc;
-    if (!buf)
-        return fail(G2048_ERR_INVALID, "NULL argument");
-    G2048_HIP(hipSetDevice(e->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t n = static_cast<uint32_t>(e->n);
-    const int32_t *src = buf;
-    if (!is_device_ptr(buf)) {
-        for (uint64_t i = 0; i < e->n; ++i)
-            if (buf[i] < 0 || buf[i] > 0x00ffffff)
-                return fail(G2048_ERR_INVALID, "score %d of board %llu is outside 0 .. 2^24-1", buf[i], (unsigned long long)i);
-        if (int rc = ensure_scratch(e))
-            return rc;
-        if (int rc = copy_in(e, e->scratch, buf, e->n * 4, stream))
-            return rc;
-        src = static_cast<const int32_t *>(e->scratch);
-    } else if (reinterpret_cast<uintptr_t>(buf) & 3u) {
-        return fail(G2048_ERR_INVALID, "device score buffers must be 4-byte aligned");
-    }
-    G2048_HIP(g2048::launch_import_scores(e->st.boards, n, src, e->st.ep_counters, s));
-    if (src == e->scratch)
-        G2048_HIP(hipStreamSynchronize(s));
-    return G2048_OK;
+    return import_view(e, buf, 4, vet_scores, stream, [](const g2048_engine *en, const void *view, hipStream_t s) {
+        return g2048::launch_import_scores(en->st.boards, static_cast<uint32_t>(en->n), static_cast<const int32_t *>(view),
+                                           en->st.ep_counters, s);
+    });
 }
 
-int g2048_get_last_scores(const g2048_engine *ce, int32_t *buf, void *stream)
+int g2048_get_last_scores(const g2048_engine *e, int32_t *buf, void *stream)
 {
-    g2048_engine *e = const_cast<g2048_engine *>(ce);
-    if (int rc = usable(e))
-        return rc;
-    if (!buf)
-        return fail(G2048_ERR_INVALID, "NULL argument");
-    if (int rc = need_last_records(e, "g2048_get_last_scores"))
-        return rc;
-    G2048_HIP(hipSetDevice(e->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t n = static_cast<uint32_t>(e->n);
-    if (is_device_ptr(buf)) {
-        if (reinterpret_cast<uintptr_t>(buf) & 3u)
-            return fail(G2048_ERR_INVALID, "device score buffers must be 4-byte aligned");
-        G2048_HIP(g2048::launch_export_last_scores(e->st, n, buf, s));
-        return G2048_OK; // device destination: ready in stream order
-    }
-    if (int rc = ensure_scratch(e))
-        return rc;
-    G2048_HIP(g2048::launch_export_last_scores(e->st, n, static_cast<int32_t *>(e->scratch), s));
-    return copy_out(e, buf, e->scratch, e->n * 4, stream);
+    return export_view(e, buf, 4, "g2048_get_last_scores", stream, [](const g2048_engine *en, void *view, hipStream_t s) {
+        return g2048::launch_export_last_scores(en->st, static_cast<uint32_t>(en->n), static_cast<int32_t *>(view), s);
+    });
 }
 
 void *g2048_records_ptr(const g2048_engine *e) { return e ? e->st.boards : nullptr; }
@@ -1691,7 +1645,7 @@ int g2048_set_numpy_rng(g2048_engine *e, const uint64_t *planes, void *stream)
     }
     if (int rc = ensure_numpy_rng(e))
         return rc;
-    return copy_in(e, e->st.rng, planes, e->n * 40, stream);
+    return copy_sync(e, e->st.rng, planes, e->n * 40, stream);
 }
 
 int g2048_seed_numpy(g2048_engine *e, uint64_t base_seed, void *stream)
@@ -1709,7 +1663,7 @@ int g2048_get_numpy_rng(const g2048_engine *e, uint64_t *planes, void *stream)
 {
     if (!e || !e->st.rng)
         return fail(G2048_ERR_INVALID, "engine is not in numpy-RNG mode");
-    return copy_out(e, planes, e->st.rng, e->n * 40, stream);
+    return copy_sync(e, planes, e->st.rng, e->n * 40, stream);
 }
 
 int g2048_augment(const uint8_t *boards, const uint8_t *next_boards, const uint8_t *actions, uint64_t n,
@@ -1746,10 +1700,10 @@ int g2048_get_state(const g2048_engine *e, void *host_buf, void *stream)
                   (e->st.rng ? 1u : 0u) | (e->track_last ? 0u : 2u)}; // flags: 1 = numpy-RNG planes follow, 2 = no terminal records
     std::memcpy(host_buf, &h, sizeof h);
     char *body = static_cast<char *>(host_buf) + sizeof h;
-    if (int rc = copy_out(e, body, e->slab, e->slab_bytes, stream))
+    if (int rc = copy_sync(e, body, e->slab, e->slab_bytes, stream))
         return rc;
     if (e->st.rng)
-        return copy_out(e, body + e->slab_bytes, e->st.rng, e->n * 40, stream);
+        return copy_sync(e, body + e->slab_bytes, e->st.rng, e->n * 40, stream);
     return G2048_OK;
 }
 
@@ -1785,7 +1739,7 @@ int g2048_set_state(g2048_engine *e, const void *host_buf, uint64_t blob_bytes, 
     e->illegal_reward = h.illegal_reward;
     e->track_last = (h.reserved & 2u) ? 0 : 1;
     const char *body = static_cast<const char *>(host_buf) + sizeof h;
-    if (int rc = copy_in(e, e->slab, body, e->slab_bytes, stream))
+    if (int rc = copy_sync(e, e->slab, body, e->slab_bytes, stream))
         return rc;
     if (h.reserved & 1u) // the blob carries numpy-RNG planes
         return g2048_set_numpy_rng(e, reinterpret_cast<const uint64_t *>(body + e->slab_bytes), stream);

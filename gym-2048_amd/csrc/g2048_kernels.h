@@ -65,6 +65,7 @@ struct StatsOut {
     long long return_sum;          // sum of the final scores of ALL finished episodes (exact)
 };
 
+// Launchers that take StepArgs run the kernel of the engine's RNG mode: numpy-RNG mode when a.st.rng is set.
 hipError_t launch_reset(const StepArgs &a, uint32_t first_slot, const uint8_t *mask, hipStream_t s);
 hipError_t launch_step(const StepArgs &a, int action_dtype, hipStream_t s);
 hipError_t launch_rollout_random(const StepArgs &a, hipStream_t s);
@@ -96,11 +97,8 @@ struct AfterstateOut {
 // `plain`: `boards` holds plain exponents (taken mod 32) rather than engine records
 hipError_t launch_afterstates(const uint4 *boards, uint32_t n, bool plain, const AfterstateOut &o, hipStream_t s);
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s);
-// the same three in numpy-RNG mode (a.st.rng != NULL)
+// numpy-RNG mode: every board's PCG64 generator, seeded as numpy seeds it, into the DeviceState::rng planes
 hipError_t launch_seed_numpy(uint64_t *planes, uint32_t n, uint64_t first_seed, hipStream_t s);
-hipError_t launch_reset_numpy(const StepArgs &a, const uint8_t *mask, hipStream_t s);
-hipError_t launch_step_numpy(const StepArgs &a, int action_dtype, hipStream_t s);
-hipError_t launch_add_tile_numpy(const StepArgs &a, hipStream_t s);
 hipError_t launch_fill_actions(uint8_t *out, uint32_t n, uint32_t board_offset, uint32_t seed_lo, uint32_t seed_hi,
                                uint64_t t_first, uint32_t k_steps, hipStream_t s);
 hipError_t launch_onehot(const uint4 *boards, uint32_t n, void *out, int obs_dtype, hipStream_t s);

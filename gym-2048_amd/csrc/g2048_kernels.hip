@@ -359,10 +359,11 @@ static_assert(sizeof(WaveTables) * (kBlock / 64) + sizeof(uint4) * kBlock + kObs
 
 // Dynamic LDS above 48 KiB is opt-in per kernel and per device.  Returns the pad to launch with: kObsOccupancyPad where
 // the device granted it, 0 where it did not (a part with less LDS, a runtime that refuses) -- the kernel is then merely
-// not occupancy-capped, instead of every observation-writing launch failing.
-template <class Kernel>
-static uint32_t obs_pad_for(Kernel kernel, std::atomic<signed char> (&state)[64])
+// not occupancy-capped, instead of every observation-writing launch failing.  Asked once per kernel and device.
+template <auto Kernel>
+static uint32_t obs_pad_for()
 {
+    static std::atomic<signed char> state[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
         dev = 0;
@@ -370,7 +371,7 @@ static uint32_t obs_pad_for(Kernel kernel, std::atomic<signed char> (&state)[64]
     //  both find it unset both ask the runtime, which is idempotent)
     signed char known = state[dev].load(std::memory_order_acquire);
     if (known == 0) {
-        const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                    static_cast<int>(kObsOccupancyPad));
         if (err != hipSuccess)
             (void)hipGetLastError(); // not sticky: the launch below goes ahead without the pad
@@ -1841,60 +1842,95 @@ __global__ void __launch_bounds__(kSummaryThreads) returns_summary_kernel(const 
 // -------------------------------------------------------------------------------- launchers
 static inline dim3 grid_for(uint64_t items) { return dim3(static_cast<uint32_t>((items + kBlock - 1) / kBlock)); }
 
+// One lane per item in blocks of kBlock, `lds` bytes of dynamic LDS; nothing to do for n == 0.
+template <class... Params, class... Args>
+static hipError_t launch_1d(void (*kernel)(Params...), uint64_t n, uint32_t lds, hipStream_t s, Args... args)
+{
+    if (n == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(kernel, grid_for(n), dim3(kBlock), lds, s, args...);
+    return hipGetLastError();
+}
+
+// f(std::integral_constant<int, V>()) for the runtime value v = V in FIRST..LAST (an action dtype, an obs dtype): one
+// instantiation of f per value in the range.  Any other v is hipErrorInvalidValue.
+template <int FIRST, int LAST, class F>
+static hipError_t dispatch(int v, F &&f)
+{
+    if constexpr (FIRST > LAST)
+        return hipErrorInvalidValue;
+    else
+        return v == FIRST ? f(std::integral_constant<int, FIRST>()) : dispatch<FIRST + 1, LAST>(v, f);
+}
+
+// f(act, std::bool_constant<FULL>()) for the template arguments <ACT, FULL> of the step kernels
+template <class F>
+static hipError_t dispatch_step(int action_dtype, bool full, F &&f)
+{
+    return dispatch<0, 3>(action_dtype, [&](auto act) { return full ? f(act, std::true_type()) : f(act, std::false_type()); });
+}
+
 hipError_t launch_reset(const StepArgs &a, uint32_t first_slot, const uint8_t *mask, hipStream_t s)
 {
-    if (a.n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(reset_kernel, grid_for(a.n), dim3(kBlock), 0, s, a, first_slot, mask);
-    return hipGetLastError();
+    if (a.st.rng)
+        return launch_1d(reset_numpy_kernel, a.n, 0, s, a, mask);
+    return launch_1d(reset_kernel, a.n, 0, s, a, first_slot, mask);
+}
+
+// The outputs of step_kernel's STD configuration: reward and terminated, nothing optional, no max tile
+static bool standard_outputs(const StepArgs &a)
+{
+    return a.reward && a.terminated && !a.illegal && !a.highest && !a.terminal_boards && a.max_exp == 0 && !a.boards_out &&
+           !a.done_seq;
+}
+
+static StepTail step_tail(const StepArgs &a)
+{
+    return StepTail{a.terminated, a.st.last_record, a.illegal, a.highest, a.terminal_boards, a.illegal_reward, a.max_exp,
+                    a.auto_reset, a.obs, a.obs_dtype, a.boards_out, a.done_seq, a.done_value, a.action_err};
+}
+
+template <int ACT, bool FULL, bool STD, bool OBS>
+static void enqueue_step(const StepArgs &a, hipStream_t s)
+{
+    constexpr auto kernel = step_kernel<ACT, FULL, STD, OBS>;
+    uint32_t pad = 0u;
+    if constexpr (OBS)
+        pad = obs_pad_for<kernel>();
+    hipLaunchKernelGGL(kernel, grid_for(a.n), dim3(kBlock), pad, s, a.st.boards, a.actions, a.st.ep_counters, a.board_offset,
+                       a.seed_lo, a.seed_hi, a.t_lo, a.t_hi, a.n, a.reward, step_tail(a));
 }
 
 hipError_t launch_step(const StepArgs &a, int action_dtype, hipStream_t s)
 {
     if (a.n == 0)
         return hipSuccess;
-    const dim3 g = grid_for(a.n), b(kBlock);
-    const bool full = a.n % kBlock == 0;
-    const StepTail tail{a.terminated, a.st.last_record, a.illegal, a.highest, a.terminal_boards, a.illegal_reward, a.max_exp,
-                        a.auto_reset, a.obs, a.obs_dtype, a.boards_out, a.done_seq, a.done_value, a.action_err};
-#define G2048_STEP_LAUNCH(ACT, FULL, STD, OBS)                                                                          \
-    do {                                                                                                                \
-        uint32_t pad = 0u;                                                                                              \
-        if (OBS) {                                                                                                      \
-            static std::atomic<signed char> pad_state[64] = {};                                                                      \
-            pad = obs_pad_for(&step_kernel<ACT, FULL, STD, OBS>, pad_state);                                            \
-        }                                                                                                               \
-        hipLaunchKernelGGL((step_kernel<ACT, FULL, STD, OBS>), g, b, pad, s, a.st.boards,                               \
-                           a.actions, a.st.ep_counters, a.board_offset, a.seed_lo, a.seed_hi, a.t_lo, a.t_hi, a.n,      \
-                           a.reward, tail);                                                                             \
-    } while (0)
-#define G2048_STEP(ACT, FULL)                                                                                           \
-    do {                                                                                                                \
-        if (standard && a.obs)                                                                                          \
-            G2048_STEP_LAUNCH(ACT, FULL, true, true);                                                                   \
-        else if (standard)                                                                                              \
-            G2048_STEP_LAUNCH(ACT, FULL, true, false);                                                                  \
-        else if (a.obs)                                                                                                 \
-            G2048_STEP_LAUNCH(ACT, FULL, false, true);                                                                  \
-        else                                                                                                            \
-            G2048_STEP_LAUNCH(ACT, FULL, false, false);                                                                 \
-    } while (0)
-    const bool standard = a.reward && a.terminated && !a.illegal && !a.highest && !a.terminal_boards && a.max_exp == 0 &&
-                          !a.boards_out && !a.done_seq && !(a.action_err && action_dtype != 0);
-    switch (action_dtype * 2 + (full ? 1 : 0)) {
-    case 0: G2048_STEP(0, false); break;
-    case 1: G2048_STEP(0, true); break;
-    case 2: G2048_STEP(1, false); break;
-    case 3: G2048_STEP(1, true); break;
-    case 4: G2048_STEP(2, false); break;
-    case 5: G2048_STEP(2, true); break;
-    case 6: G2048_STEP(3, false); break;
-    case 7: G2048_STEP(3, true); break;
-#undef G2048_STEP
-#undef G2048_STEP_LAUNCH
-    default: return hipErrorInvalidValue;
+    if (a.st.rng) {
+        // numpy-RNG mode: a block's resets run after its steps, so the observation and the plain boards come from the
+        // stand-alone kernels behind it
+        hipError_t err = dispatch<0, 3>(action_dtype, [&](auto act) {
+            hipLaunchKernelGGL(step_numpy_kernel<act>, dim3((a.n + kNumpyBlock - 1u) / kNumpyBlock), dim3(kNumpyBlock), 0, s, a);
+            return a.obs ? launch_onehot(a.st.boards, a.n, a.obs, static_cast<int>(a.obs_dtype), s) : hipGetLastError();
+        });
+        if (err == hipSuccess && a.boards_out)
+            err = launch_export_boards(a.st.boards, a.n, a.boards_out, s);
+        return err;
     }
-    if (a.done_seq && g.x > 1) // a one-block launch has published the word itself
+    const bool standard = standard_outputs(a) && !(a.action_err && action_dtype != 0);
+    const hipError_t known = dispatch_step(action_dtype, a.n % kBlock == 0, [&](auto act, auto full) {
+        if (standard && a.obs)
+            enqueue_step<act, full, true, true>(a, s);
+        else if (standard)
+            enqueue_step<act, full, true, false>(a, s);
+        else if (a.obs)
+            enqueue_step<act, full, false, true>(a, s);
+        else
+            enqueue_step<act, full, false, false>(a, s);
+        return hipSuccess;
+    });
+    if (known != hipSuccess)
+        return known;
+    if (a.done_seq && grid_for(a.n).x > 1) // a one-block launch has published the word itself
         hipLaunchKernelGGL(signal_kernel, dim3(1), dim3(64), 0, s, a.done_seq, a.done_value);
     return hipGetLastError();
 }
@@ -1904,76 +1940,42 @@ hipError_t launch_move(uint4 *boards, uint32_t n, const void *actions, int actio
 {
     if (n == 0)
         return hipSuccess;
-    const dim3 g = grid_for(n), b(kBlock);
     const uint32_t tr = trial ? 1u : 0u;
-    switch (action_dtype) {
-    case 1: hipLaunchKernelGGL(move_kernel<1>, g, b, 0, s, boards, n, actions, tr, score_out, legal_out); break;
-    case 2: hipLaunchKernelGGL(move_kernel<2>, g, b, 0, s, boards, n, actions, tr, score_out, legal_out); break;
-    case 3: hipLaunchKernelGGL(move_kernel<3>, g, b, 0, s, boards, n, actions, tr, score_out, legal_out); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch<1, 3>(action_dtype, // (no move_kernel<0>: a move needs an action buffer)
+                          [&](auto act) { return launch_1d(move_kernel<act>, n, 0, s, boards, n, actions, tr, score_out, legal_out); });
 }
 
 hipError_t launch_query(const uint4 *boards, uint32_t n, uint32_t max_exp, uint8_t *isend_out, uint8_t *highest_out,
                         hipStream_t s)
 {
-    if (n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(query_kernel, grid_for(n), dim3(kBlock), 0, s, boards, n, max_exp, isend_out, highest_out);
-    return hipGetLastError();
+    return launch_1d(query_kernel, n, 0, s, boards, n, max_exp, isend_out, highest_out);
 }
 
 hipError_t launch_legal_mask(const uint4 *boards, uint32_t n, uint8_t *mask_out, hipStream_t s)
 {
-    if (n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(legal_mask_kernel, grid_for(n), dim3(kBlock), 0, s, boards, n, mask_out);
-    return hipGetLastError();
+    return launch_1d(legal_mask_kernel, n, 0, s, boards, n, mask_out);
 }
 
 hipError_t launch_afterstates(const uint4 *boards, uint32_t n, bool plain, const AfterstateOut &o, hipStream_t s)
 {
-    if (n == 0)
-        return hipSuccess;
-    const dim3 g = grid_for(n), b(kBlock);
-#define G2048_AFTER(PLAIN)                                                                                              \
-    do {                                                                                                                \
-        if (o.obs)                                                                                                      \
-            hipLaunchKernelGGL((afterstates_kernel<PLAIN, true>), g, b, kAfterstateObsPad, s, boards, n, o);            \
-        else                                                                                                            \
-            hipLaunchKernelGGL((afterstates_kernel<PLAIN, false>), g, b, 0, s, boards, n, o);                           \
-    } while (0)
-    if (plain)
-        G2048_AFTER(true);
-    else
-        G2048_AFTER(false);
-#undef G2048_AFTER
-    return hipGetLastError();
+    auto go = [&](auto plain_c) {
+        if (o.obs)
+            return launch_1d(afterstates_kernel<plain_c, true>, n, kAfterstateObsPad, s, boards, n, o);
+        return launch_1d(afterstates_kernel<plain_c, false>, n, 0, s, boards, n, o);
+    };
+    return plain ? go(std::true_type()) : go(std::false_type());
 }
 
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s)
 {
-    if (a.n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(add_tile_kernel, grid_for(a.n), dim3(kBlock), 0, s, a, slot);
-    return hipGetLastError();
+    if (a.st.rng)
+        return launch_1d(add_tile_numpy_kernel, a.n, 0, s, a);
+    return launch_1d(add_tile_kernel, a.n, 0, s, a, slot);
 }
 
 hipError_t launch_seed_numpy(uint64_t *planes, uint32_t n, uint64_t first_seed, hipStream_t s)
 {
-    if (n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(seed_numpy_kernel, grid_for(n), dim3(kBlock), 0, s, planes, n, first_seed);
-    return hipGetLastError();
-}
-
-hipError_t launch_reset_numpy(const StepArgs &a, const uint8_t *mask, hipStream_t s)
-{
-    if (a.n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(reset_numpy_kernel, grid_for(a.n), dim3(kBlock), 0, s, a, mask);
-    return hipGetLastError();
+    return launch_1d(seed_numpy_kernel, n, 0, s, planes, n, first_seed);
 }
 
 // ---- a k-step launch train as a CACHED hipGraph (small batches)
@@ -1984,23 +1986,7 @@ hipError_t launch_reset_numpy(const StepArgs &a, const uint8_t *mask, hipStream_
 // than launching the same train once), replaying it one set_clock_kernel launch (the new clock value) + one hipGraphLaunch.
 bool rollout_graph_supported(const StepArgs &a)
 {
-    return a.n != 0 && a.reward && a.terminated && !a.illegal && !a.highest && !a.terminal_boards && a.max_exp == 0 && !a.boards_out &&
-           !a.done_seq && !a.obs && !a.st.rng && !a.action_err;
-}
-
-static void *step_graph_function(int action_dtype, bool full)
-{
-    switch (action_dtype * 2 + (full ? 1 : 0)) {
-    case 0: return reinterpret_cast<void *>(step_graph_kernel<0, false>);
-    case 1: return reinterpret_cast<void *>(step_graph_kernel<0, true>);
-    case 2: return reinterpret_cast<void *>(step_graph_kernel<1, false>);
-    case 3: return reinterpret_cast<void *>(step_graph_kernel<1, true>);
-    case 4: return reinterpret_cast<void *>(step_graph_kernel<2, false>);
-    case 5: return reinterpret_cast<void *>(step_graph_kernel<2, true>);
-    case 6: return reinterpret_cast<void *>(step_graph_kernel<3, false>);
-    case 7: return reinterpret_cast<void *>(step_graph_kernel<3, true>);
-    default: return nullptr;
-    }
+    return a.n != 0 && standard_outputs(a) && !a.obs && !a.st.rng && !a.action_err;
 }
 
 void destroy_rollout_graph(RolloutGraph &g)
@@ -2018,8 +2004,12 @@ hipError_t build_rollout_graph(const StepArgs &first, int action_dtype, uint32_t
                                RolloutGraph *out)
 {
     static const size_t act_bytes[4] = {0, 1, 4, 8};
-    void *fn = step_graph_function(action_dtype, first.n % kBlock == 0);
-    if (!fn || !rollout_graph_supported(first) || !t_dev || !out)
+    void *fn = nullptr;
+    const hipError_t known = dispatch_step(action_dtype, first.n % kBlock == 0, [&](auto act, auto full) {
+        fn = reinterpret_cast<void *>(step_graph_kernel<act, full>);
+        return hipSuccess;
+    });
+    if (known != hipSuccess || !rollout_graph_supported(first) || !t_dev || !out)
         return hipErrorInvalidValue;
     RolloutGraph g{};
     g.t_dev = t_dev;
@@ -2035,8 +2025,10 @@ hipError_t build_rollout_graph(const StepArgs &first, int action_dtype, uint32_t
         uint32_t board_offset = first.board_offset, seed_lo = first.seed_lo, seed_hi = first.seed_hi, n = first.n, jj = j;
         const unsigned long long *t_ptr = t_dev;
         float *reward = first.reward + off;
-        StepTail tail{first.terminated + off, first.st.last_record, nullptr, nullptr, nullptr, first.illegal_reward, 0u, first.auto_reset,
-                      nullptr, 0u, nullptr, nullptr, 0ull, nullptr};
+        StepTail tail = step_tail(first); // (the standard configuration: its optional outputs are NULL)
+        tail.terminated += off;
+        tail.obs_dtype = 0u;
+        tail.done_value = 0ull;
         void *args[11] = {&boards, &actions, &ep, &board_offset, &seed_lo, &seed_hi, &t_ptr, &n, &jj, &reward, &tail};
         hipKernelNodeParams kp{};
         kp.func = fn;
@@ -2069,62 +2061,22 @@ hipError_t launch_rollout_graph(RolloutGraph &g, unsigned long long t_first, hip
     return hipGraphLaunch(g.exec, s);
 }
 
-hipError_t launch_step_numpy(const StepArgs &a, int action_dtype, hipStream_t s)
-{
-    if (a.n == 0)
-        return hipSuccess;
-    const dim3 g((a.n + kNumpyBlock - 1u) / kNumpyBlock), b(kNumpyBlock);
-    switch (action_dtype) {
-    case 0: hipLaunchKernelGGL(step_numpy_kernel<0>, g, b, 0, s, a); break;
-    case 1: hipLaunchKernelGGL(step_numpy_kernel<1>, g, b, 0, s, a); break;
-    case 2: hipLaunchKernelGGL(step_numpy_kernel<2>, g, b, 0, s, a); break;
-    case 3: hipLaunchKernelGGL(step_numpy_kernel<3>, g, b, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
-    if (a.obs) // the observation of this mode comes from the stand-alone kernel (the block's resets run after its steps)
-        return launch_onehot(a.st.boards, a.n, a.obs, static_cast<int>(a.obs_dtype), s);
-    return hipGetLastError();
-}
-
-hipError_t launch_add_tile_numpy(const StepArgs &a, hipStream_t s)
-{
-    if (a.n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(add_tile_numpy_kernel, grid_for(a.n), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-
 hipError_t launch_rollout_fused(const StepArgs &a, int action_dtype, uint64_t stride, hipStream_t s)
 {
     if (a.n == 0 || a.k_steps == 0)
         return hipSuccess;
-    const dim3 g = grid_for(a.n), b(kBlock);
-    if (a.st.rng) { // numpy-RNG mode: the lanes of a wavefront drift in time (rollout_fused_numpy_kernel)
-        switch (action_dtype) {
-        case 0: hipLaunchKernelGGL(rollout_fused_numpy_kernel<0>, g, b, 0, s, a, stride); break;
-        case 1: hipLaunchKernelGGL(rollout_fused_numpy_kernel<1>, g, b, 0, s, a, stride); break;
-        case 2: hipLaunchKernelGGL(rollout_fused_numpy_kernel<2>, g, b, 0, s, a, stride); break;
-        case 3: hipLaunchKernelGGL(rollout_fused_numpy_kernel<3>, g, b, 0, s, a, stride); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (action_dtype) {
-    case 0: hipLaunchKernelGGL(rollout_fused_kernel<0>, g, b, 0, s, a, stride); break;
-    case 1: hipLaunchKernelGGL(rollout_fused_kernel<1>, g, b, 0, s, a, stride); break;
-    case 2: hipLaunchKernelGGL(rollout_fused_kernel<2>, g, b, 0, s, a, stride); break;
-    case 3: hipLaunchKernelGGL(rollout_fused_kernel<3>, g, b, 0, s, a, stride); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch<0, 3>(action_dtype, [&](auto act) {
+        if (a.st.rng) // numpy-RNG mode: the lanes of a wavefront drift in time (rollout_fused_numpy_kernel)
+            return launch_1d(rollout_fused_numpy_kernel<act>, a.n, 0, s, a, stride);
+        return launch_1d(rollout_fused_kernel<act>, a.n, 0, s, a, stride);
+    });
 }
 
 hipError_t launch_rollout_random(const StepArgs &a, hipStream_t s)
 {
-    if (a.n == 0 || a.k_steps == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(rollout_random_kernel, grid_for(a.n), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+    if (a.st.rng) // numpy-RNG mode: the fused form of that mode with the synthetic policy and no per-step output
+        return launch_rollout_fused(a, 0, 0, s);
+    return a.k_steps == 0 ? hipSuccess : launch_1d(rollout_random_kernel, a.n, 0, s, a);
 }
 
 hipError_t launch_fill_actions(uint8_t *out, uint32_t n, uint32_t board_offset, uint32_t seed_lo, uint32_t seed_hi,
@@ -2146,26 +2098,10 @@ hipError_t launch_onehot(const uint4 *boards, uint32_t n, void *out, int obs_dty
 {
     if (n == 0)
         return hipSuccess;
-    uint4 *o = static_cast<uint4 *>(out);
-    switch (obs_dtype) {
-    case 0: {
-        const uint64_t chunks = static_cast<uint64_t>(n) * 16;
-        hipLaunchKernelGGL(onehot_kernel<0>, grid_for(chunks), dim3(kBlock), 0, s, boards, chunks, o);
-        break;
-    }
-    case 1: {
-        const uint64_t chunks = static_cast<uint64_t>(n) * 32;
-        hipLaunchKernelGGL(onehot_kernel<1>, grid_for(chunks), dim3(kBlock), 0, s, boards, chunks, o);
-        break;
-    }
-    case 2: {
-        const uint64_t chunks = static_cast<uint64_t>(n) * 64;
-        hipLaunchKernelGGL(onehot_kernel<2>, grid_for(chunks), dim3(kBlock), 0, s, boards, chunks, o);
-        break;
-    }
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch<0, 2>(obs_dtype, [&](auto obs) {
+        const uint64_t chunks = static_cast<uint64_t>(n) * (16u << obs); // 16-byte chunks: 16 / 32 / 64 per board
+        return launch_1d(onehot_kernel<obs>, chunks, 0, s, boards, chunks, static_cast<uint4 *>(out));
+    });
 }
 
 hipError_t launch_augment(const uint4 *boards, const uint4 *next_boards, const uint8_t *actions, uint32_t n,
@@ -2202,51 +2138,33 @@ hipError_t launch_stats(const DeviceState &st, uint32_t n, unsigned long long *p
 
 hipError_t launch_export_boards(const uint4 *records, uint32_t n, uint4 *cells_out, hipStream_t s)
 {
-    if (n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(export_boards_kernel, grid_for(n), dim3(kBlock), 0, s, records, n, cells_out);
-    return hipGetLastError();
+    return launch_1d(export_boards_kernel, n, 0, s, records, n, cells_out);
 }
 
 hipError_t launch_import_boards(uint4 *records, uint32_t n, const uint4 *cells_in, hipStream_t s)
 {
-    if (n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(import_boards_kernel, grid_for(n), dim3(kBlock), 0, s, records, n, cells_in);
-    return hipGetLastError();
+    return launch_1d(import_boards_kernel, n, 0, s, records, n, cells_in);
 }
 
 hipError_t launch_export_scores(const uint4 *records, uint32_t n, int32_t *scores_out, hipStream_t s)
 {
-    if (n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(export_scores_kernel, grid_for(n), dim3(kBlock), 0, s, records, n, scores_out);
-    return hipGetLastError();
+    return launch_1d(export_scores_kernel, n, 0, s, records, n, scores_out);
 }
 
 hipError_t launch_import_scores(uint4 *records, uint32_t n, const int32_t *scores_in, unsigned long long *ep_counters,
                                 hipStream_t s)
 {
-    if (n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(import_scores_kernel, grid_for(n), dim3(kBlock), 0, s, records, n, scores_in, ep_counters);
-    return hipGetLastError();
+    return launch_1d(import_scores_kernel, n, 0, s, records, n, scores_in, ep_counters);
 }
 
 hipError_t launch_clear_stats(const DeviceState &st, uint32_t n, hipStream_t s)
 {
-    if (n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(clear_stats_kernel, grid_for(n), dim3(kBlock), 0, s, st, n);
-    return hipGetLastError();
+    return launch_1d(clear_stats_kernel, n, 0, s, st, n);
 }
 
 hipError_t launch_export_last_scores(const DeviceState &st, uint32_t n, int32_t *out, hipStream_t s)
 {
-    if (n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(export_last_scores_kernel, grid_for(n), dim3(kBlock), 0, s, st.last_record, n, out);
-    return hipGetLastError();
+    return launch_1d(export_last_scores_kernel, n, 0, s, st.last_record, n, out);
 }
 
 // get_board + self.score of every board in one launch, for the host-resident path
@@ -2295,10 +2213,7 @@ hipError_t launch_signal(unsigned long long *done_seq, unsigned long long done_v
 hipError_t launch_canonicalize(uint4 *boards, uint4 *next_boards, uint8_t *actions, uint32_t n, uint8_t *sym_out,
                                hipStream_t s)
 {
-    if (n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(canonicalize_kernel, grid_for(n), dim3(kBlock), 0, s, boards, next_boards, actions, n, sym_out);
-    return hipGetLastError();
+    return launch_1d(canonicalize_kernel, n, 0, s, boards, next_boards, actions, n, sym_out);
 }
 
 } // namespace g2048
