@@ -61,6 +61,19 @@ class AfterstateIO(C.Structure):
     ]
 
 
+class SearchIO(C.Structure):
+    """g2048_search_io (include/g2048.h): depth, weights and device output pointers (NULL = not wanted)."""
+    _fields_ = [
+        ("depth", C.c_uint32),
+        ("base", C.c_int32),
+        ("w_empty", C.c_int32),
+        ("w_merge", C.c_int32),
+        ("w_mono", C.c_int32),
+        ("action", C.c_void_p),
+        ("value", C.c_void_p),
+    ]
+
+
 class Stats(C.Structure):
     """g2048_stats (include/g2048.h)."""
     _fields_ = [
@@ -114,6 +127,8 @@ SIGNATURES = {
     "g2048_legal_actions": (C.c_int, [_E, C.c_void_p, _S]),
     "g2048_afterstates": (C.c_int, [_E, C.POINTER(AfterstateIO), _S]),
     "g2048_afterstates_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(AfterstateIO), _S]),
+    "g2048_expectimax": (C.c_int, [_E, C.POINTER(SearchIO), _S]),
+    "g2048_expectimax_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(SearchIO), _S]),
     "g2048_add_tile": (C.c_int, [_E, _u32, _S]),
     "g2048_fill_random_actions": (C.c_int, [_E, _u64, _u32, C.c_void_p, _S]),
     "g2048_onehot": (C.c_int, [_E, C.c_void_p, _i32, _S]),

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import AfterstateIO, G2048Error, HostIO, StepIO, Stats, check
+from ._lib import AfterstateIO, G2048Error, HostIO, SearchIO, StepIO, Stats, check
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}
 _OBS_DTYPES = {torch.uint8: _lib.OBS_U8, torch.float16: _lib.OBS_F16, torch.float32: _lib.OBS_F32}
@@ -71,6 +71,65 @@ def afterstates(boards, obs_dtype=None, out=None) -> Afterstates:
     with torch.cuda.device(boards.device):
         stream = C.c_void_p(torch.cuda.current_stream(boards.device).cuda_stream)
         check(lib.g2048_afterstates_plain(boards.data_ptr(), n, C.byref(io), stream))
+    return out
+
+
+class SearchWeights(NamedTuple):
+    """Integer weights of the expectimax heuristic (include/g2048.h G2048_SEARCH_*): ``base`` in 0..2^24, the others in
+    0..65535.  H(b) = base + sum over the 4 rows and 4 columns of w_empty * empty + w_merge * merge + w_mono * mono."""
+    base: int = 4096
+    w_empty: int = 256
+    w_merge: int = 128
+    w_mono: int = 16
+
+
+class Search(NamedTuple):
+    """Result of ``expectimax`` (``g2048_expectimax``).  Device tensors; a field that is None was not asked for (``out``)."""
+    action: Optional[torch.Tensor]  # uint8 [n]: the smallest direction of largest value; 0 when no move is legal
+    value: Optional[torch.Tensor]   # int32 [n, 4]: C_depth(move(b, d)), -1 where d is illegal
+
+
+def _search_io(n, device, depth, weights, out):
+    """(SearchIO, Search) for n boards: arguments checked, ``out`` checked field by field or freshly allocated."""
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 1 <= int(depth) <= 3:
+        raise ValueError(f"depth must be 1, 2 or 3, not {depth!r}")
+    w = SearchWeights() if weights is None else SearchWeights(*weights)
+    for name, v, hi in zip(w._fields, w, (1 << 24, 65535, 65535, 65535)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= hi:
+            raise ValueError(f"weights.{name} must be an int in 0..{hi}, not {v!r}")
+    if out is None:
+        out = Search(torch.empty(n, dtype=torch.uint8, device=device), torch.empty((n, 4), dtype=torch.int32, device=device))
+    else:
+        out = Search(*out)
+        if out.action is None and out.value is None:
+            raise ValueError("out requests no output (action and value are both None)")
+    io = SearchIO(int(depth), *(int(v) for v in w))
+    for name, shape, dtype in (("action", (n,), torch.uint8), ("value", (n, 4), torch.int32)):
+        t = getattr(out, name)
+        if t is None:
+            continue
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()
+                or t.device != device):
+            raise ValueError(f"out.{name} must be a contiguous {shape} tensor of {dtype} on {device}")
+        setattr(io, name, t.data_ptr())
+    return io, out
+
+
+def expectimax(boards, depth=2, weights=None, out=None) -> Search:
+    """Expectimax search of plain boards (``g2048_expectimax_plain``): ``boards`` is a device
+    ``uint8`` tensor ``[n, 16]`` or ``[n, 4, 4]`` of exponents (taken mod 32).  ``depth`` 1..3 move plies, each followed
+    by a chance node over every spawn; ``weights`` a :class:`SearchWeights` (defaults when None); ``out`` a preallocated
+    :class:`Search` (a field that is None is not written).  One launch, enqueued on the current stream of the boards'
+    device.  Returns ``Search(action [n] uint8, value [n, 4] int32)``."""
+    if (not isinstance(boards, torch.Tensor) or boards.dtype != torch.uint8 or boards.device.type != "cuda"
+            or boards.dim() not in (2, 3) or tuple(boards.shape[1:]) not in ((16,), (4, 4)) or not boards.is_contiguous()):
+        raise ValueError("boards must be a contiguous uint8 [n, 16] or [n, 4, 4] tensor on a GPU")
+    n = boards.shape[0]
+    io, out = _search_io(n, boards.device, depth, weights, out)
+    lib = _lib.load()
+    with torch.cuda.device(boards.device):
+        stream = C.c_void_p(torch.cuda.current_stream(boards.device).cuda_stream)
+        check(lib.g2048_expectimax_plain(boards.data_ptr(), n, C.byref(io), stream))
     return out
 
 
@@ -738,6 +797,14 @@ class Batched2048:
         randomness."""
         io, out = _afterstate_io(self.n_envs, self.device, obs_dtype, out)
         check(self._lib.g2048_afterstates(self._h, C.byref(io), self._stream()))
+        return out
+
+    def expectimax(self, depth=2, weights=None, out=None) -> Search:
+        """Expectimax search of the live boards (``g2048_expectimax``): ``Search(action [n] uint8, value [n, 4] int32)``
+        on the engine's stream, as :func:`expectimax`.  ``step(search.action)`` plays the searched move.  Touches no
+        record, clock, statistic or randomness; the engine's ``max_tile`` is not modelled."""
+        io, out = _search_io(self.n_envs, self.device, depth, weights, out)
+        check(self._lib.g2048_expectimax(self._h, C.byref(io), self._stream()))
         return out
 
     def isend_numpy(self) -> np.ndarray:

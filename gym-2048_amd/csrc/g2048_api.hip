@@ -1102,6 +1102,62 @@ int g2048_afterstates_plain(const uint8_t *boards, uint64_t n, const g2048_after
     return G2048_OK;
 }
 
+} // extern "C"
+
+// g2048_search_io -> the kernel's arguments, or G2048_ERR_INVALID (before any HIP call: works without a device)
+static int search_args(const g2048_search_io *io, g2048::SearchArgs *a)
+{
+    if (!io)
+        return fail(G2048_ERR_INVALID, "io is NULL");
+    if (!io->action && !io->value)
+        return fail(G2048_ERR_INVALID, "g2048_search_io requests no output (action and value are both NULL)");
+    if (reinterpret_cast<uintptr_t>(io->value) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: search value needs 16 bytes");
+    if (io->depth < 1 || io->depth > G2048_SEARCH_MAX_DEPTH)
+        return fail(G2048_ERR_INVALID, "depth=%u: need 1 <= depth <= %d", io->depth, G2048_SEARCH_MAX_DEPTH);
+    if (io->base < 0 || io->base > (1 << 24))
+        return fail(G2048_ERR_INVALID, "base=%d: need 0 <= base <= 2^24", io->base);
+    const int32_t w[3] = {io->w_empty, io->w_merge, io->w_mono};
+    const char *names[3] = {"w_empty", "w_merge", "w_mono"};
+    for (int k = 0; k < 3; ++k)
+        if (w[k] < 0 || w[k] > 65535)
+            return fail(G2048_ERR_INVALID, "%s=%d: need 0 <= %s <= 65535", names[k], w[k], names[k]);
+    *a = g2048::SearchArgs{static_cast<uint32_t>(io->base), static_cast<uint32_t>(io->w_empty), static_cast<uint32_t>(io->w_merge),
+                           static_cast<uint32_t>(io->w_mono), io->action, io->value};
+    return G2048_OK;
+}
+
+extern "C" {
+
+int g2048_expectimax(const g2048_engine *e, const g2048_search_io *io, void *stream)
+{
+    if (int rc = usable(e))
+        return rc;
+    g2048::SearchArgs a;
+    if (int rc = search_args(io, &a))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(g2048::launch_expectimax(e->st.boards, static_cast<uint32_t>(e->n), io->depth, false, a,
+                                       static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_expectimax_plain(const uint8_t *boards, uint64_t n, const g2048_search_io *io, void *stream)
+{
+    if (!boards)
+        return fail(G2048_ERR_INVALID, "boards is NULL");
+    if (reinterpret_cast<uintptr_t>(boards) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: boards need 16 bytes");
+    if (n == 0 || n > 0xffffff00ull) // (32-bit board indices, as g2048_afterstates_plain)
+        return fail(G2048_ERR_INVALID, "n=%llu: need 1 <= n <= 2^32 - 256", (unsigned long long)n);
+    g2048::SearchArgs a;
+    if (int rc = search_args(io, &a))
+        return rc;
+    G2048_HIP(g2048::launch_expectimax(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), io->depth, true, a,
+                                       static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream)
 {
     if (int rc = usable(e))

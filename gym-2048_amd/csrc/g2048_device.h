@@ -404,6 +404,132 @@ G2048_DEV bool move_sel(Board &bd, const MoveSel &s, uint32_t &score)
     return changed;
 }
 
+// ------------------------------------------------------------------------- expectimax search
+// g2048_expectimax (include/g2048.h).  Everything is an integer, so every split of the tree across
+// lanes gives the same bits.  For a line L = (a0, a1, a2, a3) (a row left to right or a column top to bottom):
+//   empty(L) = #{a_i = 0}, merge(L) = #{i < 3 : a_i = a_{i+1} != 0},
+//   inc(L) = sum over a_i <= a_{i+1} of a_i + a_{i+1}, dec(L) the same over a_i >= a_{i+1}, mono(L) = max(inc, dec);
+//   H(b) = base + sum over the 8 lines of w_empty * empty + w_merge * merge + w_mono * mono          (< 2^27)
+//   V_0 = H;  V_d(b) = max over legal m of C_d(move(b, m)), 0 when no move is legal;
+//   C_d(a) = floor(sum over empty c of (9 V_{d-1}(a, c = 1) + V_{d-1}(a, c = 2)) / (10 E(a)))        (sum < 2^35)
+// Exponents may reach 34 (31 + three merges): every byte stays below 0x80 and a line's inc / dec below 256.
+struct SearchWeights {
+    uint32_t base, w_empty, w_merge, w_mono;
+};
+constexpr uint32_t kSearchBase = 4096, kSearchEmpty = 256, kSearchMerge = 128, kSearchMono = 16; // = G2048_SEARCH_* (g2048.h)
+
+// Four lines at once (byte l of a, b, c, d = 1st .. 4th cell of line l): merge pairs and sum of mono over the lines.
+G2048_DEV void line_terms(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t &merges, uint32_t &mono)
+{
+    const uint32_t eab = z80(a ^ b) & nz80(a), ebc = z80(b ^ c) & nz80(b), ecd = z80(c ^ d) & nz80(c);
+    merges += g2048_popc(eab | (ebc >> 1) | (ecd >> 2));
+    // x <= y per byte: ((y | 0x80) - x) keeps bit 7 (no byte borrows, all bytes < 0x80)
+    const uint32_t ab = a + b, bc = b + c, cd = c + d; // <= 68 per byte
+    const uint32_t le_ab = mask7(((b | kHigh1) - a) & kHigh1), ge_ab = mask7(((a | kHigh1) - b) & kHigh1);
+    const uint32_t le_bc = mask7(((c | kHigh1) - b) & kHigh1), ge_bc = mask7(((b | kHigh1) - c) & kHigh1);
+    const uint32_t le_cd = mask7(((d | kHigh1) - c) & kHigh1), ge_cd = mask7(((c | kHigh1) - d) & kHigh1);
+    const uint32_t inc = (ab & le_ab) + (bc & le_bc) + (cd & le_cd); // <= 204 per byte: no carry out of a byte
+    const uint32_t dec = (ab & ge_ab) + (bc & ge_bc) + (cd & ge_cd);
+    // max per line in 16-bit fields (the byte trick of max4 needs values below 0x80)
+    const uint32_t ie = inc & 0x00ff00ffu, io = (inc >> 8) & 0x00ff00ffu;
+    const uint32_t de = dec & 0x00ff00ffu, dv = (dec >> 8) & 0x00ff00ffu;
+    const uint32_t ge_e = ((ie | 0x80008000u) - de) & 0x80008000u, ge_o = ((io | 0x80008000u) - dv) & 0x80008000u;
+    const uint32_t s = bfi(ge_e - (ge_e >> 15), ie, de) + bfi(ge_o - (ge_o >> 15), io, dv);
+    mono += (s & 0xffffu) + (s >> 16);
+}
+
+G2048_DEV uint32_t heuristic(const Board &bd, const SearchWeights &w)
+{
+    uint32_t merges = 0, mono = 0;
+    line_terms(bd.r[0], bd.r[1], bd.r[2], bd.r[3], merges, mono); // columns: byte l of r[i] = cell (i, l)
+    const Board t = transpose(bd);
+    line_terms(t.r[0], t.r[1], t.r[2], t.r[3], merges, mono);     // rows
+    return w.base + w.w_empty * (2u * count_empty(bd)) + w.w_merge * merges + w.w_mono * mono;
+}
+
+// Empty cells as a bit set: bit 8j + i for cell (i, j) -- register i, byte j.
+G2048_DEV uint32_t empty_bits(const Board &bd)
+{
+    return (z80(bd.r[0]) >> 7) | (z80(bd.r[1]) >> 6) | (z80(bd.r[2]) >> 5) | (z80(bd.r[3]) >> 4);
+}
+
+// `bd` with exponent v in the empty cell of bit p (of empty_bits)
+G2048_DEV Board place(const Board &bd, uint32_t p, uint32_t v)
+{
+    const uint32_t tile = v << (p & 24u), i = p & 7u;
+    return Board{{bd.r[0] | (i == 0u ? tile : 0u), bd.r[1] | (i == 1u ? tile : 0u), bd.r[2] | (i == 2u ? tile : 0u),
+                  bd.r[3] | (i == 3u ? tile : 0u)}};
+}
+
+template <int D, class Tables> G2048_DEV uint32_t search_value(const Board &bd, const SearchWeights &w, const Tables &tb);
+
+// Part of the chance-node sum of afterstate `a`: the items t = sub, sub + K, ... of the 2E items (item t = empty cell
+// t / 2 in bit order, spawn exponent 1 + t % 2 with weight 9 / 1).  K lanes with sub = 0 .. K-1 cover the whole sum.
+template <int D, class Tables>
+G2048_DEV uint64_t chance_partial(const Board &a, uint32_t sub, uint32_t K, const SearchWeights &w, const Tables &tb)
+{
+    uint32_t m = empty_bits(a), skipped = 0;
+    const uint32_t items = 2u * g2048_popc(m);
+    uint64_t sum = 0;
+#pragma unroll 1
+    for (uint32_t t = sub; t < items; t += K) {
+#pragma unroll 1
+        for (; skipped < (t >> 1); ++skipped)
+            m &= m - 1u;
+        const uint32_t v = 1u + (t & 1u);
+        sum += static_cast<uint64_t>(v == 1u ? 9u : 1u) * search_value<D - 1>(place(a, g2048_ctz(m), v), w, tb);
+    }
+    return sum;
+}
+
+// C_D(a); a must have an empty cell
+template <int D, class Tables> G2048_DEV uint32_t chance_value(const Board &a, const SearchWeights &w, const Tables &tb)
+{
+    return static_cast<uint32_t>(chance_partial<D>(a, 0u, 1u, w, tb) / (10u * count_empty(a)));
+}
+
+// V_D(b): the move selectors come from `tb` (LDS rows on the device) with a run-time index, so the four moves are one
+// loop body and the depths D .. 1 one inlined body each -- no recursion and no per-lane array at run time.
+template <int D, class Tables> G2048_DEV uint32_t search_value(const Board &bd, const SearchWeights &w, const Tables &tb)
+{
+    if constexpr (D == 0) {
+        return heuristic(bd, w);
+    } else {
+        uint32_t best = 0;
+#pragma unroll 1
+        for (uint32_t m = 0; m < 4u; ++m) {
+            Board a = bd;
+            uint32_t gain;
+            if (move_sel(a, tb.move_sel(m), gain)) {
+                const uint32_t c = chance_value<D>(a, w, tb);
+                best = c > best ? c : best;
+            }
+        }
+        return best;
+    }
+}
+
+// Root choice as one unsigned max: (value + 1) << 2 orders by value (illegal -1 lowest), 3 - m breaks ties to the
+// smallest m.  value < 2^27, so the key fits 32 bits.
+G2048_DEV uint32_t search_key(int32_t value, uint32_t m) { return (static_cast<uint32_t>(value + 1) << 2) | (3u - m); }
+G2048_DEV uint32_t search_key_action(uint32_t key) { return 3u - (key & 3u); }
+
+// The root: value[m] = C_D(move(b, m)) or -1 when m is illegal, action = the smallest m with the largest value (0 when
+// no move is legal).  One thread; the kernels split the same sums across lanes (chance_partial).
+template <int D, class Tables>
+G2048_DEV uint32_t search_root(const Board &cells, const SearchWeights &w, const Tables &tb, int32_t value[4])
+{
+    uint32_t best_key = 0;
+    for (uint32_t m = 0; m < 4u; ++m) {
+        Board a = cells;
+        uint32_t gain;
+        value[m] = move_sel(a, tb.move_sel(m), gain) ? static_cast<int32_t>(chance_value<D>(a, w, tb)) : -1;
+        const uint32_t key = search_key(value[m], m);
+        best_key = key > best_key ? key : best_key;
+    }
+    return search_key_action(best_key);
+}
+
 // ------------------------------------------------------------------- the 16-byte board RECORD
 // What the engine keeps per board in HBM is ONE 16-byte record: bits [4:0] of byte j = exponent of
 // cell j (0..31), and the 24-bit SCORE DEFICIT d in the three spare bits [7:5] of bytes 8..15

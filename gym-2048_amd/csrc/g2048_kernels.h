@@ -96,6 +96,14 @@ struct AfterstateOut {
 };
 // `plain`: `boards` holds plain exponents (taken mod 32) rather than engine records
 hipError_t launch_afterstates(const uint4 *boards, uint32_t n, bool plain, const AfterstateOut &o, hipStream_t s);
+// g2048_expectimax: weights and outputs (g2048_search_io, checked by the caller; NULL = not wanted)
+struct SearchArgs {
+    uint32_t base, w_empty, w_merge, w_mono; // = g2048::SearchWeights (g2048_device.h)
+    uint8_t *action; // [n]
+    int32_t *value;  // [n][4]
+};
+// depth 1..3; `plain` as in launch_afterstates
+hipError_t launch_expectimax(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const SearchArgs &a, hipStream_t s);
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s);
 // numpy-RNG mode: every board's PCG64 generator, seeded as numpy seeds it, into the DeviceState::rng planes
 hipError_t launch_seed_numpy(uint64_t *planes, uint32_t n, uint64_t first_seed, hipStream_t s);

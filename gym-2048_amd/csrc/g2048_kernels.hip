@@ -1403,6 +1403,52 @@ __global__ void __launch_bounds__(kBlock) afterstates_kernel(const uint4 *__rest
     }
 }
 
+// ---------------------------------------------------------------------------- expectimax
+// g2048_expectimax: the depth-D search of g2048_device.h ("expectimax search") for every board.  A board is a group of G
+// lanes, K = G / 4 per root direction d; lane `sub` of direction d sums the chance items sub, sub + K, ... of that
+// direction's afterstate (chance_partial), the K partial sums meet in an xor-shuffle tree and the four directions pick
+// the action with one more max over the group.  Depth 1 (about 2E leaves per direction) takes G = 4; depths 2 and 3
+// (about 4 * 2E times as many per level) spread one board over a whole wave, G = 64, so 2^12 boards are already 4 096
+// waves.  The sums are integers: every split gives the same bits as search_root on the host.  Lanes stride over the
+// boards when n * G exceeds the grid cap (kSearchMaxLanes).  Nothing is written back: no record, clock, episode slot or
+// randomness is touched.  PLAIN: plain exponents (mod 32) instead of engine records.
+constexpr uint64_t kSearchMaxLanes = 1ull << 24;
+
+template <int D, bool PLAIN>
+__global__ void __launch_bounds__(kBlock) expectimax_kernel(const uint4 *__restrict__ boards, uint32_t n, const SearchArgs a)
+{
+    constexpr uint32_t G = D == 1 ? 4u : 64u, K = G / 4u;
+    __shared__ WaveTables s_tables[kBlock / 64];
+    const LdsTables tb = stage_tables(s_tables, load_tables_piece());
+    const SearchWeights w{a.base, a.w_empty, a.w_merge, a.w_mono};
+    const uint32_t j = threadIdx.x % G, d = j / K, sub = j % K;
+    const uint32_t stride = gridDim.x * (kBlock / G);
+    // a group's G lanes hold the same i, so they leave the loop together and every shuffle stays inside live groups
+    for (uint64_t i = (static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x) / G; i < n; i += stride) {
+        const Board in = load_board(boards, static_cast<uint32_t>(i));
+        const Board cells = PLAIN ? Board{{in.r[0] & kCellBits, in.r[1] & kCellBits, in.r[2] & kCellBits, in.r[3] & kCellBits}}
+                                  : record_cells(in);
+        Board after = cells;
+        uint32_t gain;
+        const bool legal = move_sel(after, tb.move_sel(d), gain);
+        uint64_t part = 0;
+        if (legal)
+            part = chance_partial<D>(after, sub, K, w, tb);
+#pragma unroll
+        for (uint32_t o = K / 2u; o > 0u; o >>= 1)
+            part += __shfl_xor(part, o);
+        const int32_t value = legal ? static_cast<int32_t>(part / (10u * count_empty(after))) : -1;
+        uint32_t key = search_key(value, d), other = __shfl_xor(key, K);
+        key = other > key ? other : key;
+        other = __shfl_xor(key, 2u * K);
+        key = other > key ? other : key;
+        if (sub == 0u && a.value)
+            a.value[i * 4u + d] = value;
+        if (j == 0u && a.action)
+            a.action[i] = static_cast<uint8_t>(search_key_action(key));
+    }
+}
+
 // ---------------------------------------------------------------------------- augmentation
 // training_data.augment() (training_data.py:257-299) for board pairs on the device: the eight
 // symmetries [orig, hflip, rot1(orig), rot1(hflip), rot2(..), rot2(..), rot3(..), rot3(..)] with the
@@ -1964,6 +2010,16 @@ hipError_t launch_afterstates(const uint4 *boards, uint32_t n, bool plain, const
         return launch_1d(afterstates_kernel<plain_c, false>, n, 0, s, boards, n, o);
     };
     return plain ? go(std::true_type()) : go(std::false_type());
+}
+
+hipError_t launch_expectimax(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const SearchArgs &a, hipStream_t s)
+{
+    return dispatch<1, 3>(static_cast<int>(depth), [&](auto dc) {
+        const uint64_t want = static_cast<uint64_t>(n) * (dc == 1 ? 4u : 64u), lanes = want < kSearchMaxLanes ? want : kSearchMaxLanes;
+        if (plain)
+            return launch_1d(expectimax_kernel<dc, true>, lanes, 0, s, boards, n, a);
+        return launch_1d(expectimax_kernel<dc, false>, lanes, 0, s, boards, n, a);
+    });
 }
 
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s)

@@ -79,6 +79,34 @@ class Transitions:
         return cls(exp_to_values(order(xs)).reshape(-1, 4, 4), order(acts).reshape(-1),
                    order(rew).reshape(-1), exp_to_values(order(nxt)).reshape(-1, 4, 4), order(done).reshape(-1))
 
+    @classmethod
+    def record_search(cls, engine, n_steps, depth=2, weights=None):
+        """Play ``n_steps`` expectimax moves on a ``Batched2048`` and record every transition: a behaviour-cloning data
+        set in the reference's CSV format (``export_csv``), with a search in place of the person at the keyboard of
+        gather_training_data.py.  Each step's action is ``engine.expectimax(depth, weights).action`` of that step's
+        boards, written straight into the recorded action row.  Rows as in :meth:`record`: env-major, and
+        ``next_board`` of a step that ends an episode is the terminal board."""
+        import torch
+
+        from .batched import Search
+        k, n = int(n_steps), engine.n_envs
+        xs = torch.empty((k, n, 16), dtype=torch.uint8, device=engine.device)
+        nxt = torch.empty_like(xs)
+        acts = torch.empty((k, n), dtype=torch.uint8, device=engine.device)
+        rew = torch.empty((k, n), dtype=torch.float32, device=engine.device)
+        done = torch.empty((k, n), dtype=torch.uint8, device=engine.device)
+        for j in range(k):
+            xs[j].copy_(engine.boards().reshape(n, 16))
+            engine.expectimax(depth, weights, out=Search(acts[j], None))
+            engine.step(acts[j], auto_reset=True, want_info=True)
+            rew[j].copy_(engine.reward)
+            done[j].copy_(engine.terminated)
+            nxt[j].copy_(torch.where(engine.terminated.bool().unsqueeze(1), engine.terminal_boards,
+                                     engine.boards().reshape(n, 16)))
+        order = lambda t: t.transpose(0, 1).contiguous().cpu().numpy()  # noqa: E731  env-major
+        return cls(exp_to_values(order(xs)).reshape(-1, 4, 4), order(acts).reshape(-1),
+                   order(rew).reshape(-1), exp_to_values(order(nxt)).reshape(-1, 4, 4), order(done).reshape(-1))
+
     # ------------------------------------------------------------------ returns
     def discounted_return(self, gamma=0.9):
         """training_data.py:104-124 (rows in game order; ``done`` ends an episode)."""

@@ -316,6 +316,36 @@ int g2048_afterstates(const g2048_engine *e, const g2048_afterstate_io *io, void
  * 1 <= n <= 2^32 - 256. */
 int g2048_afterstates_plain(const uint8_t *boards, uint64_t n, const g2048_afterstate_io *io, void *stream);
 
+/* Expectimax search: the best move of every board by a depth-`depth` search of moves and chance nodes, in integers
+ * (INTEGRATION.md §7).  Directions as in g2048_move; the engine's max_tile is not modelled.  For a line L = (a0..a3)
+ * (a row read left to right, a column top to bottom): empty = #{a_i = 0}, merge = #{i < 3: a_i = a_{i+1} != 0},
+ * inc = sum over a_i <= a_{i+1} of (a_i + a_{i+1}), dec the same over a_i >= a_{i+1}, mono = max(inc, dec);
+ *   H(b)   = base + sum over the 4 rows and 4 columns of (w_empty * empty + w_merge * merge + w_mono * mono)
+ *   V_0    = H;  V_d(b) = max over legal m of C_d(move(b, m)), 0 when no move is legal
+ *   C_d(a) = floor(sum over empty cells c of (9 V_{d-1}(a + a 2 in c) + V_{d-1}(a + a 4 in c)) / (10 E(a)))
+ * with cells as exponents (a 2 is exponent 1) and E(a) the number of empty cells.
+ * Outputs: value[m] = C_depth(move(b, m)), -1 where m is illegal; action = the smallest m of largest value, 0 when no
+ * move is legal (every value -1).  Exact: the same bits however the work is split.  All pointers are device pointers;
+ * NULL = not wanted, but at least one output must be given. */
+#define G2048_SEARCH_BASE 4096
+#define G2048_SEARCH_EMPTY 256
+#define G2048_SEARCH_MERGE 128
+#define G2048_SEARCH_MONO 16
+#define G2048_SEARCH_MAX_DEPTH 3
+typedef struct g2048_search_io {
+    uint32_t depth;                          /* 1..G2048_SEARCH_MAX_DEPTH */
+    int32_t base, w_empty, w_merge, w_mono;  /* base 0..2^24, the others 0..65535 (defaults G2048_SEARCH_*) */
+    uint8_t *action;                         /* [n], or NULL */
+    int32_t *value;                          /* [n][4], 16-byte aligned, or NULL */
+} g2048_search_io;
+
+/* One launch over the engine's live records (the score deficit is ignored), enqueued on `stream`: consumes no
+ * randomness, leaves the records, the clock and the episode bookkeeping alone, in either RNG mode. */
+int g2048_expectimax(const g2048_engine *e, const g2048_search_io *io, void *stream);
+/* The same for n plain boards (uint8[n][16] exponents, device memory, 16-byte aligned; taken mod 32 as in
+ * g2048_afterstates_plain).  Needs no engine; runs on the current device.  1 <= n <= 2^32 - 256. */
+int g2048_expectimax_plain(const uint8_t *boards, uint64_t n, const g2048_search_io *io, void *stream);
+
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream);
