@@ -8,7 +8,11 @@ reward, max_tile, auto_reset; then 12-40 calls chosen among
   fused rollout of k steps (pipelined action loads: every tail length occurs)
   rollout_random(k)
   step_host (host-resident I/O)
-  masked reset, set_boards, set_scores, state save / restore into a second engine
+  masked reset, set_boards (exponents mod 32), set_scores, state save / restore into a second engine
+  the read-only and board-only calls: legal_actions, query, move (trial, or committed: the afterstate is kept),
+  afterstates (a random subset of outputs, a random observation dtype or none) and expectimax (depth 1, 2 at n <= 512),
+  each against the oracle's row table (tests/move_lut.py), the plain form or the host build of the search
+  (tests/host_search)
 and after every call the boards, scores, last returns, episode counts and the exact return sum (both statistics flavours)
     python tests/fuzz_parity.py [seconds=120] [seed=0]          (G2048_FUZZ_STREAMS=1: every case on its own non-default stream)"""
 import ctypes as C
@@ -26,14 +30,29 @@ import torch
 import __graft_entry__ as ge
 
 ge.build()
+import tempfile
+
 from gym2048_amd import _lib
-from gym2048_amd.batched import Batched2048, parse_stats
-from oracle import OracleBatch
+from gym2048_amd.batched import Afterstates, Batched2048, afterstates, parse_stats
+from move_lut import build_row_lut, lut_afterstates, onehot_ref
+from oracle import OracleBatch, load as load_oracle
+from test_search_host import build_search_check, host_search
 
 rs = np.random.default_rng(0)
 DT = {0: torch.uint8, 1: torch.float16, 2: torch.float32}
 ADT = [torch.uint8, torch.int32, torch.int64]
 counts = {}
+
+
+_refs = {}
+
+
+def refs():
+    """(row table, host search build), made on first use."""
+    if not _refs:
+        _refs["lut"] = build_row_lut(load_oracle())
+        _refs["search"] = build_search_check(tempfile.mkdtemp(prefix="fuzz_search_"))
+    return _refs["lut"], _refs["search"]
 
 
 def bump(name, by=1):
@@ -53,6 +72,60 @@ def check_state(eng, ora, where, always_auto_reset=False):
         assert st["return_sum"] == ora.finished_return_sum, where
     ro = parse_stats(eng.episode_stats_device(returns_only=True))
     assert (ro["episodes"], ro["illegal_ends"], ro["return_sum"]) == (st["episodes"], st["illegal_ends"], st["return_sum"]), where
+
+
+def read_only_call(eng, ora, kind, where):
+    """One of the calls that read the boards without stepping them, checked against the oracle's boards; a committed
+    move updates the oracle's boards from the row table."""
+    n, dev = eng.n_envs, eng.device
+    lut, hs = refs()
+    new, score, mask = lut_afterstates(ora.boards, lut)
+    rows = np.arange(n)
+    if kind == "legal":
+        assert np.array_equal(eng.legal_actions().cpu().numpy(), mask), where
+    elif kind == "query":
+        end, hi = (x.cpu().numpy() for x in eng.query())
+        top = ora.boards.max(1)
+        want = ((top == ora.max_exp) & (ora.max_exp != 0)) | ((ora.boards != 0).all(1) & (mask == 0))
+        assert np.array_equal(hi, top) and np.array_equal(end, want.astype(np.uint8)), where
+    elif kind in ("move_trial", "move"):
+        a = rs.integers(0, 4, n)
+        sc, legal = eng.move(torch.as_tensor(a).to(ADT[int(rs.integers(0, 3))]), trial=(kind == "move_trial"))
+        assert np.array_equal(sc.cpu().numpy(), score[rows, a]), where
+        assert np.array_equal(legal.cpu().numpy(), (mask >> a) & 1), where
+        if kind == "move":          # the chosen afterstate is kept (no spawn), the score is not touched
+            assert np.array_equal(eng.get_boards().reshape(n, 16), new[rows, a]), where
+            ora.boards[:] = new[rows, a]
+    elif kind == "afterstates":
+        od = int(rs.integers(-1, 3))
+        names = ("boards", "score", "legal", "obs")
+        keep = [rs.random() < 0.6 for _ in names]
+        keep[int(rs.integers(0, 4 if od >= 0 else 3))] = True
+        if od < 0:
+            keep[3] = False
+        shapes = ((n, 4, 16), (n, 4), (n,), (n, 4, 16, 4, 4))
+        dts = (torch.uint8, torch.int32, torch.uint8, DT[od] if od >= 0 else None)
+        out = Afterstates(*(torch.empty(sh, dtype=dt, device=dev) if k else None for k, sh, dt in zip(keep, shapes, dts)))
+        got = eng.afterstates(out=out)
+        plain = afterstates(torch.as_tensor(ora.boards).to(dev), obs_dtype=DT[od] if od >= 0 else None)
+        torch.cuda.synchronize()
+        for k, name in zip(keep, names):
+            if not k:
+                assert getattr(got, name) is None, where
+                continue
+            assert torch.equal(getattr(got, name), getattr(plain, name)), (where, name)
+        for name, want in (("boards", new), ("score", score), ("legal", mask)):
+            assert np.array_equal(getattr(plain, name).cpu().numpy(), want), (where, name)
+        if od >= 0:
+            assert torch.equal(plain.obs, onehot_ref(torch.as_tensor(new).to(dev), DT[od])), where
+        bump(f"afterstates_obs{od}")
+    else:
+        depth = 2 if n <= 512 and rs.random() < 0.5 else 1
+        w = None if rs.random() < 0.5 else (int(rs.integers(0, 1 << 24)), *(int(x) for x in rs.integers(0, 65536, 3)))
+        s = eng.expectimax(depth, w)
+        act, val = host_search(hs, ora.boards, depth, (4096, 256, 128, 16) if w is None else w)
+        assert np.array_equal(s.action.cpu().numpy(), act) and np.array_equal(s.value.cpu().numpy(), val), where
+        bump(f"expectimax_depth{depth}")
 
 
 def one_case(case):
@@ -83,8 +156,9 @@ def one_case(case):
     tag = f"case {case}: n={n} seed={seed} offset={offset} irw={irw} max_tile={max_tile} auto_reset={auto_reset} numpy={numpy_mode} chains={chains}"
     replay_bufs = replay_plan = None
     for call in range(int(rs.integers(12, 40))):
-        kind = str(rs.choice(["step", "rollout", "fused", "random", "host", "mask_reset", "set_boards", "state", "set_scores", "replay"],
-                             p=[0.26, 0.16, 0.13, 0.08, 0.1, 0.06, 0.04, 0.06, 0.03, 0.08]))
+        kind = str(rs.choice(["step", "rollout", "fused", "random", "host", "mask_reset", "set_boards", "state", "set_scores", "replay",
+                              "legal", "query", "move_trial", "move", "afterstates", "expectimax"],
+                             p=[0.21, 0.13, 0.1, 0.06, 0.08, 0.05, 0.04, 0.05, 0.03, 0.06, 0.03, 0.03, 0.03, 0.03, 0.04, 0.03]))
         if numpy_mode and kind in ("mask_reset", "replay"):   # unmaskable oracle reset / spawn-stream-only graph replays
             kind = "step"                                      # (fused and random rollouts exist in numpy-RNG mode since round 6)
         where = f"{tag} call {call} {kind}"
@@ -178,8 +252,11 @@ def one_case(case):
             ora.reset(mask=mask)
         elif kind == "set_boards":
             b = (rs.integers(0, 12, (n, 16)) * (rs.random((n, 16)) < 0.6)).astype(np.uint8)
-            eng.set_boards(b)
+            high = (rs.integers(0, 8, (n, 16)) << 5).astype(np.uint8) if rs.random() < 0.5 else 0   # taken mod 32
+            eng.set_boards(b | high)
             ora.boards[:] = b
+        elif kind in ("legal", "query", "move_trial", "move", "afterstates", "expectimax"):
+            read_only_call(eng, ora, kind, where)
         elif kind == "set_scores":
             sc = rs.integers(0, 1 << 20, n).astype(np.int32)
             eng.set_scores(sc if rs.random() < 0.5 else torch.as_tensor(sc).to(dev))

@@ -14,6 +14,7 @@ import numpy as np
 from oracle.cpu_ref import IllegalMoveError, RefEnv
 
 DEFAULT_WEIGHTS = (4096, 256, 128, 16)  # base, w_empty, w_merge, w_mono
+MAX_WEIGHTS = (1 << 24, 65535, 65535, 65535)  # the largest the API accepts
 
 
 def lines(b):
@@ -68,28 +69,75 @@ def value(b, d, w):
 
 
 @lru_cache(maxsize=None)
-def chance(a, d, w):
-    """C_d(a): floor of the 9:1 weighted mean over the empty cells (a 2 is exponent 1, a 4 exponent 2)."""
-    empties = [c for c in range(16) if a[c] == 0]
+def chance_total(a, d, w):
+    """The undivided sum of C_d(a): 9 V(a + 2) + V(a + 4) over the empty cells (a 2 is exponent 1, a 4 exponent 2)."""
     total = 0
-    for c in empties:
-        two = a[:c] + (1,) + a[c + 1:]
-        four = a[:c] + (2,) + a[c + 1:]
-        total += 9 * value(two, d - 1, w) + value(four, d - 1, w)
-    return total // (10 * len(empties))
+    for c in range(16):
+        if a[c] == 0:
+            total += 9 * value(a[:c] + (1,) + a[c + 1:], d - 1, w) + value(a[:c] + (2,) + a[c + 1:], d - 1, w)
+    return total
+
+
+def chance(a, d, w):
+    """C_d(a): floor of the 9:1 weighted mean over the empty cells."""
+    return chance_total(a, d, w) // (10 * sum(1 for x in a if x == 0))
+
+
+def _plain(board):
+    return tuple(int(x) % 32 for x in np.asarray(board).reshape(16))
 
 
 def search(board, depth, w=DEFAULT_WEIGHTS):
     """(action, values[4]) of one board: values[m] = C_depth(move(b, m)), -1 if illegal; action = smallest argmax,
     0 when nothing is legal."""
-    b = tuple(int(x) % 32 for x in np.asarray(board).reshape(16))
-    w = tuple(int(x) for x in w)
+    b, w = _plain(board), tuple(int(x) for x in w)
     vals = []
     for m in range(4):
         a, legal = _move_cached(b, m)
         vals.append(chance(a, depth, w) if legal else -1)
     action = max(range(4), key=lambda m: (vals[m], -m))
     return action, vals
+
+
+def root_totals(board, depth, w=DEFAULT_WEIGHTS):
+    """The four undivided root chance sums of ``search``: chance_total(move(b, m)), None where m is illegal."""
+    b, w = _plain(board), tuple(int(x) for x in w)
+    out = []
+    for m in range(4):
+        a, legal = _move_cached(b, m)
+        out.append(chance_total(a, depth, w) if legal else None)
+    return out
+
+
+@lru_cache(maxsize=None)
+def _max_exp_value(b, d):
+    top = max(b)
+    if d > 0:
+        for m in range(4):
+            a, legal = _move_cached(b, m)
+            if legal:
+                top = max(top, _max_exp_chance(a, d))
+    return top
+
+
+@lru_cache(maxsize=None)
+def _max_exp_chance(a, d):
+    top = max(a)
+    for c in range(16):
+        if a[c] == 0:
+            top = max(top, _max_exp_value(a[:c] + (1,) + a[c + 1:], d - 1), _max_exp_value(a[:c] + (2,) + a[c + 1:], d - 1))
+    return top
+
+
+def max_exponent(board, depth):
+    """The largest exponent on any board the depth-``depth`` search of ``board`` visits (merges can push it past 31)."""
+    b = _plain(board)
+    top = max(b)
+    for m in range(4):
+        a, legal = _move_cached(b, m)
+        if legal:
+            top = max(top, _max_exp_chance(a, depth))
+    return top
 
 
 def search_batch(boards, depth, w=DEFAULT_WEIGHTS):

@@ -4,11 +4,13 @@ import numpy as np
 import pytest
 
 import search_ref as ref
-from test_search_host import build_search_check, host_search, random_boards, trajectory_boards
+from move_lut import build_row_lut, lut_afterstates, onehot_ref
+from test_search_host import afterstate_empties, build_search_check, high_boards, host_search, random_boards, trajectory_boards
 
 pytestmark = pytest.mark.gpu
 
 ODD_W = (12345, 7, 65535, 3)
+SEARCH_MAX_LANES = 1 << 24  # kSearchMaxLanes (g2048_kernels.hip): the grid cap past which expectimax_kernel strides
 
 
 @pytest.fixture(scope="module")
@@ -169,3 +171,177 @@ def test_record_search(g, torch_cuda, tmp_path):
     for f in ("x", "action", "reward", "next_x", "done"):
         assert np.array_equal(getattr(back, f), getattr(tr, f)), f
     assert back.to_csv_text() == tr.to_csv_text()
+
+
+# ---------------------------------------------------------------------------------------------- edges of the kernels
+def mid_game(m, seed, max_empty=16):
+    """m distinct boards of the golden trajectories with at most ``max_empty`` empty cells."""
+    traj = trajectory_boards()
+    traj = traj[(traj == 0).sum(1) <= max_empty]
+    return traj[np.random.default_rng(seed).choice(len(traj), m, replace=False)]
+
+
+def periodic(torch, base, n):
+    """uint8 [n, 16] on the device: board i = base[i % m]."""
+    b = torch.as_tensor(np.ascontiguousarray(base, dtype=np.uint8)).cuda()
+    return b.repeat(-(-n // len(b)), 1)[:n]
+
+
+def assert_periodic(torch, s, host, n, chunk=1 << 20):
+    """Every row i of the Search ``s`` equals the host result of base[i % m], compared on the device chunk by chunk."""
+    ha, hv = (torch.as_tensor(np.ascontiguousarray(x)).cuda() for x in host)
+    m = len(ha)
+    for k in range(0, n, chunk):
+        idx = torch.arange(k, min(n, k + chunk), device="cuda") % m
+        bad = (s.action[k:k + chunk] != ha[idx]) | (s.value[k:k + chunk] != hv[idx]).any(1)
+        if bool(bad.any()):
+            i = k + int(bad.nonzero()[0, 0])
+            raise AssertionError(f"board {i} (base row {i % m}) differs: {s.action[i].item()} {s.value[i].tolist()} vs "
+                                 f"{host[0][i % m]} {host[1][i % m].tolist()}")
+
+
+GRID_STRIDE = {1: ((1 << 22) + 4133, 4099), 2: ((1 << 18) + 4133, 4099), 3: ((1 << 18) + 37, 257)}  # depth: (n, period m)
+
+
+@pytest.mark.parametrize("depth", [1, 2, 3])
+def test_grid_stride_passes(g, torch_cuda, hs, depth):
+    """n * G lanes past the grid cap: every board after the first pass is reached by the kernel's stride loop, the last
+    pass ragged.  Periodic batch with an odd period, so the boards one stride apart are different boards; both forms."""
+    torch = torch_cuda
+    n, m = GRID_STRIDE[depth]
+    stride = SEARCH_MAX_LANES // (4 if depth == 1 else 64)          # boards per pass
+    assert n > stride and n % stride != 0                           # a second pass, and a ragged last one
+    if depth == 1:
+        base = np.unique(random_boards(2 * m, 80), axis=0)
+        base = base[np.random.default_rng(81).choice(len(base), m, replace=False)]
+    else:
+        base = mid_game(m, 80 + depth, 16 if depth == 2 else 6)
+    assert len(np.unique(base, axis=0)) == m and m % 2 == 1
+    boards = periodic(torch, base, n)
+    eng = g.Batched2048(n)
+    try:
+        eng.set_boards(boards)
+        for w in (None, ODD_W) if depth == 1 else (None,):
+            host = host_search(hs, base, depth, ref.DEFAULT_WEIGHTS if w is None else w)
+            r = np.arange(m)   # a kernel that read or wrote board i +- stride instead of i would not go unnoticed
+            assert (host[1] != host[1][(r + stride) % m]).any(1).mean() > 0.5
+            for form in ("plain", "engine"):
+                s = g.expectimax(boards, depth, w) if form == "plain" else eng.expectimax(depth, w)
+                torch.cuda.synchronize()
+                assert_periodic(torch, s, host, n)
+                del s
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("depth,n", [(2, 4096), (3, 64)])
+def test_wide_sums(g, torch_cuda, hs, depth, n):
+    """The largest weights on boards with exponents 26..31 and 5..10 empty cells: most root chance sums are wider than
+    32 bits, so the 64-bit partial sums of the K = 16 lanes of a direction must meet whole in the xor-shuffle tree."""
+    torch = torch_cuda
+    boards = high_boards(n, 90 + depth, (5, 10))
+    host = host_search(hs, boards, depth, ref.MAX_WEIGHTS)
+    val = host[1].astype(np.int64)
+    wide = (val >= 0) & (val * 10 * afterstate_empties(boards) >= 1 << 32)   # value * 10E <= the undivided sum
+    assert wide.sum() * 4 >= (val >= 0).sum(), (wide.sum(), (val >= 0).sum())
+    assert_same(device_search(g, torch, boards, depth, ref.MAX_WEIGHTS), host)
+    eng = g.Batched2048(n)
+    try:
+        eng.set_boards(boards)
+        s = eng.expectimax(depth, ref.MAX_WEIGHTS)
+        torch.cuda.synchronize()
+        assert_same((s.action.cpu().numpy(), s.value.cpu().numpy()), host)
+    finally:
+        eng.close()
+
+
+@pytest.fixture(scope="module")
+def row_lut(oracle_lib):
+    return build_row_lut(oracle_lib)
+
+
+def test_engine_forms_with_full_score_deficits(g, torch_cuda, hs, row_lut):
+    """Random 24-bit scores fill the spare bits of bytes 8..15 of the records (r[3] included).  Every engine-form reader
+    must drop them: expectimax at depths 1..3, afterstates (every output, every obs dtype), legal_actions, query,
+    move(trial=True) and observe_onehot each equal their plain form or the row table on get_boards()."""
+    torch = torch_cuda
+    n = 2048 + 37
+    boards = mid_game(n, 100, 8)
+    boards[:64] = random_boards(64, 101, max_exp=17)               # near-empty and full boards too
+    boards[64:96, 5] = 11                                          # the engine's max tile (2048) is reached
+    rng = np.random.default_rng(102)
+    scores = rng.integers(0, 1 << 24, n).astype(np.int32)
+    eng = g.Batched2048(n, seed=3, max_tile=2048)
+    try:
+        eng.set_boards(boards)
+        eng.set_scores(scores)
+        rec = eng.records().cpu().numpy()
+        assert np.array_equal(rec & 0x1F, boards) and np.array_equal(eng.get_scores(), scores)
+        assert (rec[:, 12:16] & 0xE0).any(1).mean() > 0.5 and (rec[:, 8:12] & 0xE0).any(1).mean() > 0.5
+        assert not (rec[:, :8] & 0xE0).any()
+        cells = eng.get_boards().reshape(n, 16)
+        assert np.array_equal(cells, boards)
+        dev = torch.as_tensor(cells).cuda()
+        for depth in (1, 2, 3):
+            s, p = eng.expectimax(depth), g.expectimax(dev, depth)
+            torch.cuda.synchronize()
+            assert torch.equal(s.action, p.action) and torch.equal(s.value, p.value), depth
+            if depth == 1:
+                assert_same((s.action.cpu().numpy(), s.value.cpu().numpy()), host_search(hs, cells, 1))
+        new, score, mask = lut_afterstates(cells, row_lut)
+        for dt in (None, torch.uint8, torch.float16, torch.float32):
+            a, p = eng.afterstates(obs_dtype=dt), g.afterstates(dev, obs_dtype=dt)
+            torch.cuda.synchronize()
+            for name in ("boards", "score", "legal") + (("obs",) if dt is not None else ()):
+                assert torch.equal(getattr(a, name), getattr(p, name)), (dt, name)
+            assert np.array_equal(a.boards.cpu().numpy(), new) and np.array_equal(a.score.cpu().numpy(), score)
+            assert np.array_equal(a.legal.cpu().numpy(), mask)
+            if dt is not None:
+                assert torch.equal(a.obs, onehot_ref(torch.as_tensor(new).cuda(), dt)), dt
+        assert np.array_equal(eng.legal_actions().cpu().numpy(), mask)
+        end, hi = (x.cpu().numpy() for x in eng.query())
+        assert np.array_equal(hi, cells.max(1))
+        assert np.array_equal(end, ((cells.max(1) == 11) | ((cells != 0).all(1) & (mask == 0))).astype(np.uint8))
+        assert (cells.max(1) == 11).sum() >= 32 and (cells.max(1) > 11).any() and end.any() and not end.all()
+        for d in range(4):
+            sc, legal = eng.move(torch.full((n,), d, dtype=(torch.uint8, torch.int32, torch.int64, torch.int64)[d], device="cuda"),
+                                 trial=True)
+            assert np.array_equal(sc.cpu().numpy(), score[:, d]) and np.array_equal(legal.cpu().numpy(), (mask >> d) & 1), d
+        for dt in (torch.uint8, torch.float16, torch.float32):
+            assert torch.equal(eng.observe_onehot(dt), onehot_ref(dev, dt)), dt
+        torch.cuda.synchronize()
+        assert np.array_equal(eng.records().cpu().numpy(), rec)        # none of these writes a record
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("n", [1, 3, 63, 65, 4097])
+def test_sentinel_tails_every_output_subset(g, torch_cuda, hs, n):
+    """Each requested output is the head of a larger buffer filled with a sentinel: nothing past n is written, a field
+    passed as None stays None, and what is written equals the host build.  Depths 1..3 (3 at small n), both forms."""
+    torch = torch_cuda
+    boards = mid_game(n, 110 + n, 6)
+    dev = torch.as_tensor(boards).cuda()
+    eng = g.Batched2048(n)
+    try:
+        eng.set_boards(boards)
+        for depth in (1, 2, 3) if n <= 65 else (1, 2):
+            host = host_search(hs, boards, depth)
+            for subset in (("action",), ("value",), ("action", "value")):
+                for form in ("plain", "engine"):
+                    act_buf = torch.full((n + 4096,), 0xA5, dtype=torch.uint8, device="cuda")
+                    val_buf = torch.full((4 * n + 4096,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+                    out = g.Search(act_buf[:n] if "action" in subset else None,
+                                   val_buf[:4 * n].view(n, 4) if "value" in subset else None)
+                    res = g.expectimax(dev, depth, out=out) if form == "plain" else eng.expectimax(depth, out=out)
+                    torch.cuda.synchronize()
+                    where = (depth, subset, form)
+                    assert (res.action is None) == ("action" not in subset) and (res.value is None) == ("value" not in subset)
+                    if "action" in subset:
+                        assert np.array_equal(act_buf[:n].cpu().numpy(), host[0]), where
+                    assert bool((act_buf[n if "action" in subset else 0:] == 0xA5).all()), where
+                    if "value" in subset:
+                        assert np.array_equal(val_buf[:4 * n].view(n, 4).cpu().numpy(), host[1]), where
+                    assert bool((val_buf[4 * n if "value" in subset else 0:] == 0x5A5A5A5A).all()), where
+    finally:
+        eng.close()

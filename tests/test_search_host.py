@@ -55,6 +55,36 @@ def random_boards(n, seed, max_exp=17):
     return np.where(rng.random((n, 16)) < density, b, 0).astype(np.uint8)
 
 
+def high_boards(n, seed, empties, lo=26, hi=31, full_rows=0):
+    """Exponents lo..hi with ``empties`` = (fewest, most) empty cells, a horizontal pair of ``hi`` (a merge makes hi + 1)
+    and a vertical pair of a random exponent in every board; the first ``full_rows`` rows are all ``hi`` (merged twice:
+    hi + 2; two such rows, merged a third time: hi + 3)."""
+    rng = np.random.default_rng(seed)
+    b = rng.integers(lo, hi + 1, size=(n, 16)).astype(np.uint8)
+    for x in b:
+        r, c = rng.integers(full_rows, 4), rng.integers(0, 3)
+        keep = list(range(4 * full_rows)) + [4 * r + c, 4 * r + c + 1]
+        x[keep] = hi
+        r2, c2 = rng.integers(0, 3), rng.integers(0, 4)
+        while 4 * r2 + c2 in keep or 4 * r2 + c2 + 4 in keep:
+            r2, c2 = rng.integers(0, 3), rng.integers(0, 4)
+        x[[4 * r2 + c2, 4 * r2 + c2 + 4]] = rng.integers(lo, hi + 1)
+        keep = set(keep) | {4 * r2 + c2, 4 * r2 + c2 + 4}
+        free = [k for k in range(16) if k not in keep]
+        x[rng.choice(free, int(rng.integers(empties[0], empties[1] + 1)), replace=False)] = 0
+    return b
+
+
+def afterstate_empties(boards):
+    """int [n, 4]: empty cells of move(b, d) by the Python reference, 0 where d is illegal."""
+    out = np.zeros((len(boards), 4), np.int64)
+    for i, b in enumerate(np.asarray(boards).reshape(-1, 16)):
+        for d in range(4):
+            a, legal = ref.move(tuple(int(x) % 32 for x in b), d)
+            out[i, d] = sum(1 for x in a if x == 0) if legal else 0
+    return out
+
+
 def trajectory_boards(every=1):
     out = [load_golden(t)["boards"].reshape(-1, 16)[::every] for t in TRAJECTORIES]
     return np.unique(np.concatenate(out), axis=0)
@@ -146,3 +176,34 @@ def test_lane_split(hs, depth, K):
         boards = boards[(boards == 0).sum(1) <= 6][:2]
     _, val = host_search(hs, boards, depth)
     assert np.array_equal(host_split(hs, boards, depth, K), val)
+
+
+@pytest.mark.parametrize("w", [ref.DEFAULT_WEIGHTS, ref.MAX_WEIGHTS], ids=["default", "max"])
+def test_near_top_exponents_depth2_depth3(hs, w):
+    """Exponents 26..31 with equal neighbours: the merges inside the tree make exponents 32..34, which the byte tricks of
+    line_terms / shift4 must carry (the header's claim).  Depth 2 on 12 boards, depth 3 on 3 (few empty cells)."""
+    b2 = np.concatenate([high_boards(6, 40, (1, 5)), high_boards(6, 42, (1, 4), full_rows=1)])
+    b3 = high_boards(2, 41, (1, 3), full_rows=2)
+    check(hs, b2, 2, w)
+    check(hs, b3, 3, w)
+    # the inputs reach the edge: every tree goes past 31, the depth-2 trees to 33, the depth-3 trees to 34
+    tops2, tops3 = [ref.max_exponent(b, 2) for b in b2], [ref.max_exponent(b, 3) for b in b3]
+    assert min(tops2) >= 32 and max(tops2) == 33 and tops3 == [34] * len(b3), (tops2, tops3)
+
+
+@pytest.mark.parametrize("depth,n", [(2, 40), (3, 3)])
+def test_lane_split_wide_sums(hs, depth, n):
+    """The kernels' split at K = 16 with the largest weights, where a root's chance sum is wider than 32 bits: the
+    64-bit partial sums of 16 lanes must add up to the one-lane sum."""
+    boards = high_boards(n, 50 + depth, (6, 10))
+    _, val = host_search(hs, boards, depth, ref.MAX_WEIGHTS)
+    assert np.array_equal(host_split(hs, boards, depth, 16, ref.MAX_WEIGHTS), val)
+    E = afterstate_empties(boards)
+    # value = floor(total / 10E), so value * 10E <= total: these roots summed past 2^32
+    wide = (val >= 0) & (val.astype(np.int64) * 10 * E >= 1 << 32)
+    assert wide.sum() * 4 >= (val >= 0).sum(), (wide.sum(), (val >= 0).sum())
+    if depth == 2:  # the undivided sums themselves, from the Python reference
+        totals = [ref.root_totals(b, 2, ref.MAX_WEIGHTS) for b in boards[:6]]
+        assert max(t for row in totals for t in row if t is not None) >= 1 << 32
+        for row, v, e in zip(totals, val, E):
+            assert [-1 if t is None else t // (10 * k) for t, k in zip(row, e)] == v.tolist()
