@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from episode_slots import StateBlob
 
 pytestmark = pytest.mark.gpu
 I64x16 = C.c_int64 * 16
@@ -234,16 +235,14 @@ def test_episode_slot_carries_into_the_high_dwords(torch_cuda):
         ora.step(None)
     st0 = eng.episode_stats()
     assert st0["return_sum"] == ora.finished_return_sum and st0["episodes"] == int(ora.ep_count.sum())
-    state = eng.state_dict()
-    blob = state["blob"].copy()
-    header, up = 56, lambda x: (x + 255) & ~255             # StateHeader; slab = records | terminal records | slots | stats
-    slots = blob[header + 2 * up(n * 16): header + 2 * up(n * 16) + (n // 64) * 32].view(np.uint32).reshape(n // 64, 8)
+    blob = StateBlob(eng)                                    # (tests/episode_slots.py: the slab layout, checked)
+    slots = blob.slots                                       # [n // 64, 8]: n = 4096 leaves no padding slot
     old = slots.astype(np.int64)
     assert not slots[:, 4:7].any()                           # nothing has carried yet
     near = np.uint32(0xFFFFFFF0)
     slots[:, 0:3] = near                                     # episodes.lo, illegal_ends.lo, G.lo of every wavefront
     shift = ((int(near) - old[:, 0]).sum(), (int(near) - old[:, 1]).sum(), (int(near) - old[:, 2]).sum())
-    eng.load_state_dict(dict(state, blob=blob))
+    blob.load_into(eng)
     st1 = eng.episode_stats()
     assert st1["episodes"] == st0["episodes"] + shift[0] and st1["illegal_ends"] == st0["illegal_ends"] + shift[1]
     assert st1["return_sum"] == st0["return_sum"] + shift[2]
@@ -256,7 +255,7 @@ def test_episode_slot_carries_into_the_high_dwords(torch_cuda):
     assert st2["episodes"] - st1["episodes"] == int(ora.ep_count.sum()) - ep0 > 64 * 30 // 20
     assert st2["illegal_ends"] - st1["illegal_ends"] == ill0
     assert st2["return_sum"] - st1["return_sum"] == ora.finished_return_sum - ret0 > 0
-    raw = eng.state_dict()["blob"][header + 2 * up(n * 16): header + 2 * up(n * 16) + (n // 64) * 32].view(np.uint32).reshape(-1, 8)
+    raw = StateBlob(eng).slots
     assert (raw[:, 4] == 1).all() and (raw[:, 6] == 1).all() and (raw[:, 5] == 1).all()      # carried, once
     # ---- a fused rollout across the accumulator fold
     eng2, ora2 = Batched2048(512, seed=seed), OracleBatch(512, seed)
