@@ -16,6 +16,7 @@
 #include <cstring>
 #include <dlfcn.h>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -43,30 +44,124 @@ int fail(int code, const char *fmt, ...)
 using g2048::SideLauncher;
 using g2048::cpu_relax;
 
+// The engine's memory is held by two owner types; each frees what it holds when it is destroyed or reset, and its
+// alloc() is the one place that memory of its kind is allocated.  alloc() does nothing when the owner already holds a
+// buffer (every buffer of an engine has one size for the engine's lifetime), and names `what` the buffer is for when it
+// fails.
+
+// Device memory.  `zero`: cleared before alloc() returns -- hipMemset only ENQUEUES the fill (on the null stream: 3 us
+// for a call that takes 1.4 ms on 8 GiB, tools/memset_probe.py), and a caller's non-blocking stream -- every torch
+// stream but the default one -- is not ordered behind the null stream, so alloc() waits for it.
+struct DeviceBuffer {
+    void *p = nullptr;
+
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer &) = delete;
+    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+    ~DeviceBuffer() { (void)reset(); }
+    template <class T> T *as() const { return static_cast<T *>(p); }
+
+    int alloc(size_t bytes, const char *what, bool zero = false)
+    {
+        if (p)
+            return G2048_OK;
+        hipError_t err = hipMalloc(&p, bytes);
+        if (err != hipSuccess) {
+            p = nullptr;
+            return fail(G2048_ERR_NOMEM, "hipMalloc(%zu) for %s failed: %s", bytes, what, hipGetErrorString(err));
+        }
+        if (zero) {
+            err = hipMemset(p, 0, bytes);
+            if (err == hipSuccess)
+                err = hipStreamSynchronize(nullptr);
+            if (err != hipSuccess) {
+                (void)reset();
+                return fail(G2048_ERR_HIP, "hipMemset of %s failed: %s", what, hipGetErrorString(err));
+            }
+        }
+        return G2048_OK;
+    }
+
+    hipError_t reset()
+    {
+        const hipError_t err = p ? hipFree(p) : hipSuccess;
+        p = nullptr;
+        return err;
+    }
+};
+
+// Pinned, device-mapped, coherent host memory: its host address and the device's alias of it.  Zeroed by alloc().
+struct PinnedBlock {
+    void *host = nullptr, *dev = nullptr;
+
+    PinnedBlock() = default;
+    PinnedBlock(const PinnedBlock &) = delete;
+    PinnedBlock &operator=(const PinnedBlock &) = delete;
+    ~PinnedBlock()
+    {
+        if (host)
+            (void)hipHostFree(host);
+    }
+    explicit operator bool() const { return host != nullptr; }
+
+    int alloc(size_t bytes, const char *what)
+    {
+        if (host)
+            return G2048_OK;
+        void *h = nullptr;
+        hipError_t err = hipHostMalloc(&h, bytes, hipHostMallocMapped | hipHostMallocCoherent);
+        if (err != hipSuccess)
+            return fail(G2048_ERR_NOMEM, "hipHostMalloc(%zu) for %s failed: %s", bytes, what, hipGetErrorString(err));
+        err = hipHostGetDevicePointer(&dev, h, 0);
+        if (err != hipSuccess) {
+            (void)hipHostFree(h);
+            dev = nullptr;
+            return fail(G2048_ERR_HIP, "hipHostGetDevicePointer for %s failed: %s", what, hipGetErrorString(err));
+        }
+        std::memset(h, 0, bytes);
+        host = h;
+        return G2048_OK;
+    }
+};
+
 // ONE side chain per device and process, shared by every engine on that device that runs two chains: the side stream
 // (highest priority), its launch thread, and the time its last work is expected to end.  Shared so that it stays WARM:
 // a stream that has idled for a few hundred milliseconds starts its next kernels late (a forced two-chain 20-step
 // rollout takes 175 us after 0.2 ms of idle, 184-186 after 5-50 ms, 223 after 300 ms -- one chain: 195-209;
 // tools/chain_gap_probe.py), and e.g. a warm-up on one engine should leave the chain ready for the next engine.  `use`
-// serialises the engines' rollouts on it (an engine itself is single-threaded by contract).
+// serialises the engines' rollouts on it (an engine itself is single-threaded by contract).  The engines own it; it
+// ends with the last of them.
 struct SideChain {
     SideLauncher launcher;
     hipStream_t stream = nullptr;
     std::mutex use;
     std::atomic<int64_t> busy_until_ns{0}; // steady-clock time the side stream's queued work is expected to have ended + the warm window
-    int device = 0, refs = 0;
+    int device = 0;
     int priority = 0; // of `stream`: the highest the device offers
+
+    ~SideChain()
+    {
+        launcher.stop();
+        if (stream) {
+            (void)hipSetDevice(device);
+            // its launches retired first: destroyed with launches the runtime had not yet retired, the stream kept the
+            // slab they used (the chain tickets are in it) from being freed -- one slab per engine, measured
+            (void)hipStreamSynchronize(stream);
+            (void)hipStreamDestroy(stream);
+        }
+    }
 };
 
 std::mutex g_side_mutex;
-SideChain *g_side[64] = {};
+std::weak_ptr<SideChain> g_side[64]; // the side chain of each device, while an engine holds it
 
 int64_t steady_now_ns()
 {
     return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// "\0G2048v5": records carry the score, 4-word episode slots for whole 512-lane blocks, the summary scratch behind them.
+// "\0G2048v5": records carry the score, 4-word episode slots for whole 512-lane blocks, the bytes of the engine's work
+// memory behind them (written as zeros, ignored when read back).
 // v4 (ABI 14) is the same games in a slab of another size; v3 and older were played under the spawn rule before ABI 14
 // (g2048.h "Randomness"): a game saved under the old rule would continue differently under the new one.  Both are refused
 // with the reason instead of silently resumed.
@@ -83,28 +178,33 @@ struct g2048_engine {
     int fresh = 1;        // nothing consumed from the stream since seeding
     float illegal_reward = 0.0f; // game2048_env.py:53
     uint32_t max_exp = 0;        // game2048_env.py:54 (0 = None)
-    void *slab = nullptr;
-    size_t slab_bytes = 0;
-    g2048::DeviceState st{};
+    // ONE slab (g2048_create), zeroed at create.  GAME region -- what a state blob carries: boards | last_record |
+    // ep_counters, then the engine's own work memory (statistics struct, summary scratch, graph clock), which a blob
+    // holds as zeros.  WORKSPACE region behind it: statistics partials, chain tickets.
+    DeviceBuffer slab;
+    size_t game_bytes = 0; // size of the game region
+    size_t kept_bytes = 0; // boards | last_record | ep_counters: the bytes of the game region a state blob restores
+    g2048::DeviceState st{}; // st.rng is set (numpy-RNG mode) exactly while `rng` holds the planes
     g2048::StatsOut *stats_dev = nullptr;
-    unsigned long long *stats_partials = nullptr; // stage-1 output of the statistics reduction
-    unsigned long long *summary_scratch = nullptr; // partials + "last one out" counters of the one-launch returns summary (in the slab: zero)
-    void *scratch = nullptr; // staging for host-side get/set of boards and scores (16 B per board), lazily
-    // host-resident I/O (g2048_host_io_map): one block of pinned, device-mapped, coherent host memory
-    void *host_base = nullptr;
+    unsigned long long *summary_scratch = nullptr; // partials + "last one out" counters of the one-launch returns summary (zero between launches)
+    unsigned long long *stats_partials = nullptr;  // stage-1 output of the statistics reduction
+    DeviceBuffer rng;     // numpy-RNG mode: the five PCG64 planes plus the per-wavefront lists of finished boards
+    DeviceBuffer scratch; // staging for host-side get/set of boards and scores (16 B per board), lazily
+    DeviceBuffer returns; // send buffer of the all-gather (int32[n]), lazily; NOT the staging buffer: a collective
+                          // in flight on one stream must not be clobbered by a get_* call on another
+    // host-resident I/O (g2048_host_io_map)
+    PinnedBlock host_block;
     g2048_host_io host_io{};          // host addresses handed to the caller
     g2048_host_io host_io_dev{};      // the same arrays as the device sees them
-    // completion word (its own 64-byte pinned, device-mapped, coherent block): published by the device, polled by the host
-    unsigned long long *done_host = nullptr, *done_dev = nullptr;
-    unsigned long long done_count = 0;
+    // the words the device reports to the host through (HostWord), each on its own 64-byte line; allocated on first
+    // need by any of them: a word no kernel was ever given stays zero
+    PinnedBlock words;
+    unsigned long long done_count = 0; // tickets published to the completion word so far
     // two-chain rollouts (g2048_set_chains): the side stream, its launch thread and the fork / join tickets
     int chains = 1;
-    SideChain *side = nullptr; // the device's shared side chain (a reference is held while chains == 2 was ever set)
-    unsigned long long *chain_flags = nullptr; // device memory (256 B): [0] fork ticket, [16] join ticket (own cache lines), [24] scratch
+    std::shared_ptr<SideChain> side; // the device's shared side chain (held once chains == 2 was ever set)
+    unsigned long long *chain_flags = nullptr; // in the workspace (256 B): [0] fork ticket, [16] join ticket (own cache lines), [24] scratch
     unsigned long long chain_seq = 0;
-    // a ticket wait that ran out (flag_wait_kernel) reports here: 64 bytes of pinned, coherent host memory, checked at
-    // the entry of every call on the engine
-    unsigned long long *chain_err_host = nullptr, *chain_err_dev = nullptr;
     // the measurement / test knobs of the two-chain form, read from the environment by g2048_set_chains (NOT per rollout)
     uint32_t chain_min_steps = 0;      // G2048_TWO_CHAIN_MIN_STEPS: split every rollout of at least that many steps (0: the warm / cold rule)
     uint32_t chain_wait_polls = g2048::kFlagWaitPolls; // G2048_FLAG_WAIT_POLLS: bound of a ticket wait, ~1 us per poll
@@ -147,13 +247,9 @@ struct g2048_engine {
     int graph_enabled = 1;              // G2048_ROLLOUT_GRAPH=0 (read by g2048_create) turns the form off; a failing graph call too
     char graph_off_reason[200] = "";    // ... and says why here (g2048_graph_status)
     uint64_t graph_replays = 0;         // rollouts served from the cached graph (g2048_get_graph_replays)
-    // strict actions (g2048_set_strict_actions): 64 bytes of pinned, coherent host memory a step kernel reports an action
-    // outside 0..3 to; read (and cleared) at the entry of the next call on the engine
+    // strict actions (g2048_set_strict_actions): a step kernel reports an action outside 0..3 to kActionErrWord
     int strict_actions = 0;
-    unsigned long long *action_err_host = nullptr, *action_err_dev = nullptr;
     int track_last = 1;   // keep the terminal record of every board's most recent finished episode (g2048_set_last_records)
-    int32_t *returns = nullptr; // send buffer of the all-gather (int32[n]), lazily; NOT the staging buffer: a collective
-                                // in flight on one stream must not be clobbered by a get_* call on another
 };
 
 namespace {
@@ -168,12 +264,29 @@ struct StateHeader {
 
 size_t align_up(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
+// The words of g2048_engine::words: the completion word (published by the device, polled by the host), where a
+// two-chain ticket wait that ran out reports (flag_wait_kernel), and where a step kernel reports an action outside 0..3
+// under strict actions.  The two error words are checked at the entry of every call on the engine (usable).
+enum HostWord { kDoneWord = 0, kChainErrWord = 1, kActionErrWord = 2 };
+
+unsigned long long *host_word(const g2048_engine *e, HostWord w) { return static_cast<unsigned long long *>(e->words.host) + 8 * w; }
+unsigned long long *dev_word(const g2048_engine *e, HostWord w) { return static_cast<unsigned long long *>(e->words.dev) + 8 * w; }
+
+int ensure_words(g2048_engine *e) { return e->words.alloc(3 * 64, "the completion, chain timeout and strict-actions words"); }
+
+// the device state as the kernels should see it: no terminal-record array when the engine does not keep them
+g2048::DeviceState tracked_state(const g2048_engine *e)
+{
+    g2048::DeviceState st = e->st;
+    if (!e->track_last)
+        st.last_record = nullptr; // the kernels skip the terminal-record store
+    return st;
+}
+
 g2048::StepArgs make_args(const g2048_engine *e, const g2048_step_io *io, int auto_reset)
 {
     g2048::StepArgs a{};
-    a.st = e->st;
-    if (!e->track_last)
-        a.st.last_record = nullptr; // the kernels skip the terminal-record store
+    a.st = tracked_state(e);
     if (io) {
         a.actions = io->actions;
         a.reward = io->reward;
@@ -185,7 +298,7 @@ g2048::StepArgs make_args(const g2048_engine *e, const g2048_step_io *io, int au
         a.obs_dtype = static_cast<uint32_t>(io->obs_dtype);
         a.boards_out = reinterpret_cast<uint4 *>(io->boards_out);
     }
-    a.action_err = e->strict_actions ? e->action_err_dev : nullptr;
+    a.action_err = e->strict_actions ? dev_word(e, kActionErrWord) : nullptr;
     a.n = static_cast<uint32_t>(e->n);
     a.board_offset = static_cast<uint32_t>(e->board_offset);
     a.seed_lo = static_cast<uint32_t>(e->seed);
@@ -196,15 +309,6 @@ g2048::StepArgs make_args(const g2048_engine *e, const g2048_step_io *io, int au
     a.max_exp = e->max_exp;
     a.auto_reset = auto_reset ? 1u : 0u;
     return a;
-}
-
-// the device state as the kernels should see it: no terminal-record array when the engine does not keep them
-g2048::DeviceState tracked_state(const g2048_engine *e)
-{
-    g2048::DeviceState st = e->st;
-    if (!e->track_last)
-        st.last_record = nullptr;
-    return st;
 }
 
 int need_last_records(const g2048_engine *e, const char *what)
@@ -225,15 +329,16 @@ int usable(const g2048_engine *e)
         return fail(G2048_ERR_INVALID, "engine is NULL");
     if (e->poisoned)
         return fail(G2048_ERR_HIP, "%s", e->poison_msg);
-    if (e->chain_err_host && __atomic_load_n(e->chain_err_host, __ATOMIC_ACQUIRE) != 0ull)
-        return fail(G2048_ERR_HIP, "a two-chain rollout's ordering ticket (%llu) did not arrive within the wait's bound "
-                                   "(%u polls of ~1 us): its chains ran unordered from there on, the engine's boards and "
-                                   "the rollout's outputs are undefined -- destroy the engine",
-                    __atomic_load_n(e->chain_err_host, __ATOMIC_ACQUIRE), e->chain_wait_polls);
-    if (e->action_err_host) {
+    if (e->words) {
+        const unsigned long long *chain_err = host_word(e, kChainErrWord);
+        if (__atomic_load_n(chain_err, __ATOMIC_ACQUIRE) != 0ull)
+            return fail(G2048_ERR_HIP, "a two-chain rollout's ordering ticket (%llu) did not arrive within the wait's bound "
+                                       "(%u polls of ~1 us): its chains ran unordered from there on, the engine's boards and "
+                                       "the rollout's outputs are undefined -- destroy the engine",
+                        __atomic_load_n(chain_err, __ATOMIC_ACQUIRE), e->chain_wait_polls);
         // strict actions: a step kernel that has COMPLETED by now saw an action outside 0..3.  Reported once, by this call
         // (which does nothing else), and cleared; the step itself played the action's low two bits.
-        const unsigned long long w = __atomic_exchange_n(e->action_err_host, 0ull, __ATOMIC_ACQ_REL);
+        const unsigned long long w = __atomic_exchange_n(host_word(e, kActionErrWord), 0ull, __ATOMIC_ACQ_REL);
         if (w != 0ull)
             return fail(G2048_ERR_INVALID, "strict actions: an earlier step was given an action outside 0..3 (e.g. global board %u, "
                                            "low byte 0x%02x); that step played the action's low two bits (the reference, "
@@ -326,6 +431,7 @@ int g2048_create(uint64_t n_boards, int device, uint64_t seed, uint64_t board_of
     }
 
     const size_t n = n_boards;
+    // game region (the layout tests/episode_slots.py decodes)
     const size_t off_boards = 0;
     const size_t off_last_record = off_boards + align_up(n * 16);
     const size_t off_counters = off_last_record + align_up(n * 16);
@@ -334,38 +440,26 @@ int g2048_create(uint64_t n_boards, int device, uint64_t seed, uint64_t board_of
     const size_t n_counters = ((n + g2048::kSlotBlockLanes - 1) / g2048::kSlotBlockLanes) * (g2048::kSlotBlockLanes / 64) * g2048::kSlotWords;
     const size_t off_stats = off_counters + align_up(n_counters * sizeof(unsigned long long));
     const size_t off_summary = off_stats + align_up(sizeof(g2048::StatsOut));
+    // the clock word of the cached rollout graphs: in the slab, so that building one allocates nothing
     const size_t off_graph_t = off_summary + align_up(g2048::kSummaryScratchWords * sizeof(unsigned long long));
-    e->slab_bytes = off_graph_t + 256; // the clock word of the cached rollout graphs: here, so that building one allocates nothing
-    err = hipMalloc(&e->slab, e->slab_bytes);
-    if (err != hipSuccess) {
-        const size_t wanted = e->slab_bytes;
+    // workspace region
+    const size_t off_partials = off_graph_t + 256;
+    const size_t off_chain = off_partials + align_up(g2048::kStatsPartialWords * sizeof(unsigned long long));
+    if (int rc = e->slab.alloc(off_chain + 256, "the engine's boards and work memory", true)) {
         delete e;
-        return fail(G2048_ERR_NOMEM, "hipMalloc(%zu) failed: %s", wanted, hipGetErrorString(err));
+        return rc;
     }
-    // hipMemset of device memory only ENQUEUES the fill (on the null stream: 3 us for a call that takes 1.4 ms on 8 GiB,
-    // tools/memset_probe.py), and a caller's non-blocking stream -- every torch stream but the default one -- is not
-    // ordered behind the null stream: without the wait the engine's first kernels could run before the clear.
-    err = hipMemset(e->slab, 0, e->slab_bytes);
-    if (err == hipSuccess)
-        err = hipStreamSynchronize(nullptr);
-    if (err != hipSuccess) {
-        (void)hipFree(e->slab);
-        delete e;
-        return fail(G2048_ERR_HIP, "hipMemset failed: %s", hipGetErrorString(err));
-    }
-    err = hipMalloc(reinterpret_cast<void **>(&e->stats_partials), g2048::kStatsPartialWords * sizeof(unsigned long long));
-    if (err != hipSuccess) {
-        (void)hipFree(e->slab);
-        delete e;
-        return fail(G2048_ERR_NOMEM, "hipMalloc of the statistics scratch failed: %s", hipGetErrorString(err));
-    }
-    char *base = static_cast<char *>(e->slab);
+    e->game_bytes = off_partials;
+    e->kept_bytes = off_stats;
+    char *base = e->slab.as<char>();
     e->st.boards = reinterpret_cast<uint4 *>(base + off_boards);
     e->st.last_record = reinterpret_cast<uint4 *>(base + off_last_record);
     e->st.ep_counters = reinterpret_cast<unsigned long long *>(base + off_counters);
     e->stats_dev = reinterpret_cast<g2048::StatsOut *>(base + off_stats);
     e->summary_scratch = reinterpret_cast<unsigned long long *>(base + off_summary);
     e->graph_t_dev = reinterpret_cast<unsigned long long *>(base + off_graph_t);
+    e->stats_partials = reinterpret_cast<unsigned long long *>(base + off_partials);
+    e->chain_flags = reinterpret_cast<unsigned long long *>(base + off_chain);
     if (!e->graph_enabled)
         snprintf(e->graph_off_reason, sizeof e->graph_off_reason, "G2048_ROLLOUT_GRAPH=0 in the environment of g2048_create");
     *out = e;
@@ -376,56 +470,18 @@ int g2048_destroy(g2048_engine *e)
 {
     if (!e)
         return G2048_OK;
-    hipError_t err = hipSuccess;
-    if (e->side) {
-        SideChain *dead = nullptr;
-        {
-            std::lock_guard<std::mutex> lock(g_side_mutex);
-            if (--e->side->refs == 0) {
-                dead = e->side;
-                g_side[dead->device] = nullptr;
-            }
-        }
-        if (dead) {
-            dead->launcher.stop();
-            (void)hipSetDevice(dead->device);
-            if (dead->stream)
-                (void)hipStreamDestroy(dead->stream);
-            delete dead;
-        }
-        e->side = nullptr;
-    }
-    if (e->slab) {
-        (void)hipSetDevice(e->device);
-        bool any_graph = false;
-        for (auto &entry : e->graphs)
-            any_graph = any_graph || entry.g.exec;
-        if (any_graph)
-            (void)hipDeviceSynchronize(); // a replay may still be running: an executable graph is destroyed only at rest (the
-                                          // hipFree of the slab below waits for the device anyway)
-        for (auto &entry : e->graphs)
-            g2048::destroy_rollout_graph(entry.g);
-        if (e->chain_flags)
-            (void)hipFree(e->chain_flags);
-        if (e->chain_err_host)
-            (void)hipHostFree(e->chain_err_host);
-        if (e->action_err_host)
-            (void)hipHostFree(e->action_err_host);
-        if (e->st.rng)
-            (void)hipFree(e->st.rng);
-        if (e->scratch)
-            (void)hipFree(e->scratch);
-        if (e->returns)
-            (void)hipFree(e->returns);
-        if (e->host_base)
-            (void)hipHostFree(e->host_base);
-        if (e->done_host)
-            (void)hipHostFree(e->done_host);
-        if (e->stats_partials)
-            (void)hipFree(e->stats_partials);
-        err = hipFree(e->slab);
-    }
-    delete e;
+    (void)hipSetDevice(e->device);
+    e->side.reset(); // (the last engine of the device ends its side chain)
+    bool any_graph = false;
+    for (auto &entry : e->graphs)
+        any_graph = any_graph || entry.g.exec;
+    if (any_graph)
+        (void)hipDeviceSynchronize(); // a replay may still be running: an executable graph is destroyed only at rest (freeing
+                                      // the slab below waits for the device anyway)
+    for (auto &entry : e->graphs)
+        g2048::destroy_rollout_graph(entry.g);
+    const hipError_t err = e->slab.reset();
+    delete e; // (the owners free the rest: after the slab, so with the device at rest)
     if (err != hipSuccess)
         return fail(G2048_ERR_HIP, "hipFree failed: %s", hipGetErrorString(err));
     return G2048_OK;
@@ -494,20 +550,10 @@ int g2048_set_strict_actions(g2048_engine *e, int enable)
 {
     if (int rc = usable(e))
         return rc;
-    if (enable && !e->action_err_host) {
+    if (enable) {
         G2048_HIP(hipSetDevice(e->device));
-        void *host = nullptr, *dev = nullptr;
-        hipError_t err = hipHostMalloc(&host, 64, hipHostMallocMapped | hipHostMallocCoherent);
-        if (err != hipSuccess)
-            return fail(G2048_ERR_NOMEM, "hipHostMalloc(64) for the action error word failed: %s", hipGetErrorString(err));
-        err = hipHostGetDevicePointer(&dev, host, 0);
-        if (err != hipSuccess) {
-            (void)hipHostFree(host);
-            return fail(G2048_ERR_HIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(err));
-        }
-        std::memset(host, 0, 64);
-        e->action_err_host = static_cast<unsigned long long *>(host);
-        e->action_err_dev = static_cast<unsigned long long *>(dev);
+        if (int rc = ensure_words(e))
+            return rc;
     }
     e->strict_actions = enable ? 1 : 0;
     return G2048_OK;
@@ -607,31 +653,17 @@ static int ensure_side_chain(g2048_engine *e)
         return G2048_OK;
     if (e->device < 0 || e->device >= 64)
         return fail(G2048_ERR_INVALID, "two chains are available on devices 0..63");
-    if (!e->chain_flags) { // the engine's own fork / join tickets
-        G2048_HIP(hipMalloc(reinterpret_cast<void **>(&e->chain_flags), 256));
-        G2048_HIP(hipMemset(e->chain_flags, 0, 256));
-        G2048_HIP(hipStreamSynchronize(nullptr)); // (the fill is only enqueued, and not ordered against non-blocking streams)
-    }
-    if (!e->chain_err_host) { // where a ticket wait that ran out reports (flag_wait_kernel)
-        void *host = nullptr, *dev = nullptr;
-        hipError_t err = hipHostMalloc(&host, 64, hipHostMallocMapped | hipHostMallocCoherent);
-        if (err != hipSuccess)
-            return fail(G2048_ERR_NOMEM, "hipHostMalloc(64) for the chains' error word failed: %s", hipGetErrorString(err));
-        err = hipHostGetDevicePointer(&dev, host, 0);
-        if (err != hipSuccess) {
-            (void)hipHostFree(host);
-            return fail(G2048_ERR_HIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(err));
-        }
-        std::memset(host, 0, 64);
-        e->chain_err_host = static_cast<unsigned long long *>(host);
-        e->chain_err_dev = static_cast<unsigned long long *>(dev);
-    }
+    if (int rc = ensure_words(e)) // (a ticket wait that runs out reports to kChainErrWord)
+        return rc;
     std::lock_guard<std::mutex> lock(g_side_mutex);
-    SideChain *sc = g_side[e->device];
+    std::shared_ptr<SideChain> sc = g_side[e->device].lock();
     if (!sc) {
-        sc = new (std::nothrow) SideChain;
-        if (!sc)
+        // (a failure below returns with `sc` the only owner: ~SideChain undoes whatever was set up)
+        try {
+            sc = std::make_shared<SideChain>();
+        } catch (const std::bad_alloc &) {
             return fail(G2048_ERR_NOMEM, "out of host memory");
+        }
         sc->device = e->device;
         // The side stream is created at the HIGHEST priority the device offers.  In a process that also holds an RCCL
         // communicator (dozens of hardware queues) a normal-priority side queue shares its slot by time slices and the
@@ -641,10 +673,8 @@ static int ensure_side_chain(g2048_engine *e)
         hipError_t err = hipDeviceGetStreamPriorityRange(&least, &greatest);
         if (err == hipSuccess)
             err = hipStreamCreateWithPriority(&sc->stream, hipStreamNonBlocking, greatest);
-        if (err != hipSuccess) {
-            delete sc;
+        if (err != hipSuccess)
             return fail(G2048_ERR_HIP, "cannot create the side stream: %s", hipGetErrorString(err));
-        }
         sc->priority = greatest;
         SideLauncher *w = &sc->launcher;
         w->spin_us = g2048::side_spin_us_from_env(); // 200 us unless the caller opted into a longer window
@@ -661,16 +691,11 @@ static int ensure_side_chain(g2048_engine *e)
                 (void)g2048::launch_flag_set(scratch_flag, 0ull, side_stream);
             return hipStreamSynchronize(side_stream) == hipSuccess ? G2048_OK : G2048_ERR_HIP;
         });
-        if (w->wait(ticket) != G2048_OK) {
-            w->stop();
-            (void)hipStreamDestroy(sc->stream);
-            delete sc;
+        if (w->wait(ticket) != G2048_OK)
             return fail(G2048_ERR_HIP, "the side launch thread could not reach device %d", e->device);
-        }
         g_side[e->device] = sc;
     }
-    ++sc->refs;
-    e->side = sc;
+    e->side = std::move(sc);
     return G2048_OK;
 }
 
@@ -851,12 +876,12 @@ static int rollout_two_chains(g2048_engine *e, uint32_t k_steps, const RolloutSt
     const int dtype = args_of.io->action_dtype;
     const uint32_t n = static_cast<uint32_t>(e->n);
     const uint32_t first_half = (n / 2u) & ~255u;
-    SideChain *sc = e->side;
+    SideChain *sc = e->side.get();
     std::lock_guard<std::mutex> side_in_use(sc->use); // (another engine of this device may be using the side chain)
     hipStream_t side_stream = sc->stream;
     const unsigned long long seq = ++e->chain_seq;
     unsigned long long *fork_flag = e->chain_flags, *join_flag = e->chain_flags + 16;
-    unsigned long long *err_word = e->chain_err_dev;
+    unsigned long long *err_word = dev_word(e, kChainErrWord);
     const uint32_t polls = e->chain_wait_polls;
     {   // nothing has been launched yet: a failure here leaves the engine as it was
         const hipError_t err = g2048::launch_flag_set(fork_flag, seq, s); // enqueued BEFORE the side thread can enqueue its wait
@@ -1211,46 +1236,19 @@ static int copy_sync(const g2048_engine *e, void *dst, const void *src, size_t b
 }
 
 // ------------------------------------------------------------------------- host-resident I/O
-static int ensure_done_word(g2048_engine *e)
-{
-    if (e->done_host)
-        return G2048_OK;
-    void *host = nullptr, *dev = nullptr;
-    hipError_t err = hipHostMalloc(&host, 64, hipHostMallocMapped | hipHostMallocCoherent);
-    if (err != hipSuccess)
-        return fail(G2048_ERR_NOMEM, "hipHostMalloc(64) for the completion word failed: %s", hipGetErrorString(err));
-    err = hipHostGetDevicePointer(&dev, host, 0);
-    if (err != hipSuccess) {
-        (void)hipHostFree(host);
-        return fail(G2048_ERR_HIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(err));
-    }
-    std::memset(host, 0, 64);
-    e->done_host = static_cast<unsigned long long *>(host);
-    e->done_dev = static_cast<unsigned long long *>(dev);
-    return G2048_OK;
-}
-
 static int ensure_host_io(g2048_engine *e)
 {
-    if (int rc = ensure_done_word(e))
+    if (int rc = ensure_words(e)) // (the completion word)
         return rc;
-    if (e->host_base)
+    if (e->host_block)
         return G2048_OK;
     const size_t n = e->n;
     auto up = [](size_t x) { return (x + 63) & ~static_cast<size_t>(63); };
     const size_t off_act = 0, off_rew = up(off_act + 8 * n), off_term = up(off_rew + 4 * n), off_ill = up(off_term + n),
                  off_high = up(off_ill + n), off_boards = up(off_high + n), off_tb = up(off_boards + 16 * n),
                  off_sc = up(off_tb + 16 * n), bytes = up(off_sc + 4 * n);
-    void *host = nullptr, *dev = nullptr;
-    hipError_t err = hipHostMalloc(&host, bytes, hipHostMallocMapped | hipHostMallocCoherent);
-    if (err != hipSuccess)
-        return fail(G2048_ERR_NOMEM, "hipHostMalloc(%zu) failed: %s", bytes, hipGetErrorString(err));
-    err = hipHostGetDevicePointer(&dev, host, 0);
-    if (err != hipSuccess) {
-        (void)hipHostFree(host);
-        return fail(G2048_ERR_HIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(err));
-    }
-    std::memset(host, 0, bytes);
+    if (int rc = e->host_block.alloc(bytes, "the host-resident I/O arrays"))
+        return rc;
     auto fill = [&](g2048_host_io &io, char *b) {
         io.actions = reinterpret_cast<int64_t *>(b + off_act);
         io.reward = reinterpret_cast<float *>(b + off_rew);
@@ -1261,9 +1259,8 @@ static int ensure_host_io(g2048_engine *e)
         io.terminal_boards = reinterpret_cast<uint8_t *>(b + off_tb);
         io.scores = reinterpret_cast<int32_t *>(b + off_sc);
     };
-    fill(e->host_io, static_cast<char *>(host));
-    fill(e->host_io_dev, static_cast<char *>(dev));
-    e->host_base = host;
+    fill(e->host_io, static_cast<char *>(e->host_block.host));
+    fill(e->host_io_dev, static_cast<char *>(e->host_block.dev));
     return G2048_OK;
 }
 
@@ -1300,8 +1297,9 @@ static int wait_done(g2048_engine *e, unsigned long long want, hipStream_t s)
     using clock = std::chrono::steady_clock;
     clock::time_point started{}, last_check{};
     bool armed = false;
+    const unsigned long long *done = host_word(e, kDoneWord);
     for (uint64_t spins = 0;; ++spins) {
-        if (__atomic_load_n(e->done_host, __ATOMIC_ACQUIRE) >= want)
+        if (__atomic_load_n(done, __ATOMIC_ACQUIRE) >= want)
             return G2048_OK;
         cpu_relax();
         if ((spins & 0xfffffu) == 0xfffffu) { // every ~million polls
@@ -1313,7 +1311,7 @@ static int wait_done(g2048_engine *e, unsigned long long want, hipStream_t s)
                 last_check = now;
                 const hipError_t q = hipStreamQuery(s);
                 if (q == hipSuccess) // everything on the stream has finished: the word must be there
-                    return __atomic_load_n(e->done_host, __ATOMIC_ACQUIRE) >= want
+                    return __atomic_load_n(done, __ATOMIC_ACQUIRE) >= want
                                ? G2048_OK
                                : fail(G2048_ERR_HIP, "the device finished without publishing the completion word");
                 if (q != hipErrorNotReady)
@@ -1343,7 +1341,7 @@ int g2048_step_host(g2048_engine *e, int auto_reset, void *stream)
 {
     if (int rc = usable(e))
         return rc;
-    if (!e->host_base)
+    if (!e->host_block)
         return fail(G2048_ERR_INVALID, "call g2048_host_io_map first (the actions are read from its buffer)");
     G2048_HIP(hipSetDevice(e->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1374,9 +1372,9 @@ int g2048_step_host(g2048_engine *e, int auto_reset, void *stream)
     if (e->st.rng) { // numpy-RNG mode: step (+ compacted resets), then boards + scores + the completion word
         a.boards_out = nullptr;
         G2048_HIP(g2048::launch_step(a, io.action_dtype, s));
-        G2048_HIP(g2048::launch_fetch(e->st.boards, a.n, reinterpret_cast<uint4 *>(d.boards), d.scores, e->done_dev, want, s));
+        G2048_HIP(g2048::launch_fetch(e->st.boards, a.n, reinterpret_cast<uint4 *>(d.boards), d.scores, dev_word(e, kDoneWord), want, s));
     } else {
-        a.done_seq = e->done_dev;
+        a.done_seq = dev_word(e, kDoneWord);
         a.done_value = want;
         G2048_HIP(g2048::launch_step(a, io.action_dtype, s));
     }
@@ -1387,7 +1385,7 @@ int g2048_fetch_host(g2048_engine *e, void *stream)
 {
     if (int rc = usable(e))
         return rc;
-    if (!e->host_base)
+    if (!e->host_block)
         return fail(G2048_ERR_INVALID, "call g2048_host_io_map first");
     G2048_HIP(hipSetDevice(e->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1395,7 +1393,7 @@ int g2048_fetch_host(g2048_engine *e, void *stream)
         return rc;
     const unsigned long long want = ++e->done_count;
     G2048_HIP(g2048::launch_fetch(e->st.boards, static_cast<uint32_t>(e->n), reinterpret_cast<uint4 *>(e->host_io_dev.boards),
-                                  e->host_io_dev.scores, e->done_dev, want, s));
+                                  e->host_io_dev.scores, dev_word(e, kDoneWord), want, s));
     return wait_done(e, want, s);
 }
 
@@ -1409,10 +1407,10 @@ int g2048_stream_signal(g2048_engine *e, void *stream, uint64_t *ticket)
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = refuse_capture(s, "g2048_stream_signal"))
         return rc;
-    if (int rc = ensure_done_word(e))
+    if (int rc = ensure_words(e))
         return rc;
     const unsigned long long want = ++e->done_count;
-    G2048_HIP(g2048::launch_signal(e->done_dev, want, s));
+    G2048_HIP(g2048::launch_signal(dev_word(e, kDoneWord), want, s));
     *ticket = want;
     return G2048_OK;
 }
@@ -1421,7 +1419,7 @@ int g2048_stream_wait(g2048_engine *e, uint64_t ticket, void *stream)
 {
     if (int rc = usable(e))
         return rc;
-    if (!e->done_host || ticket == 0 || ticket > e->done_count)
+    if (!e->words || ticket == 0 || ticket > e->done_count)
         return fail(G2048_ERR_INVALID, "ticket %llu was not issued by g2048_stream_signal on this engine",
                     (unsigned long long)ticket);
     return wait_done(e, ticket, static_cast<hipStream_t>(stream));
@@ -1437,32 +1435,6 @@ static bool is_device_ptr(const void *p)
         return false;
     }
     return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-
-static int ensure_scratch(g2048_engine *e)
-{
-    if (e->scratch)
-        return G2048_OK;
-    hipError_t err = hipMalloc(&e->scratch, e->n * 16);
-    if (err != hipSuccess) {
-        e->scratch = nullptr;
-        return fail(G2048_ERR_NOMEM, "hipMalloc(%zu) for the host staging buffer failed: %s", (size_t)(e->n * 16),
-                    hipGetErrorString(err));
-    }
-    return G2048_OK;
-}
-
-static int ensure_returns(g2048_engine *e)
-{
-    if (e->returns)
-        return G2048_OK;
-    hipError_t err = hipMalloc(reinterpret_cast<void **>(&e->returns), e->n * 4);
-    if (err != hipSuccess) {
-        e->returns = nullptr;
-        return fail(G2048_ERR_NOMEM, "hipMalloc(%zu) for the all-gather send buffer failed: %s", (size_t)(e->n * 4),
-                    hipGetErrorString(err));
-    }
-    return G2048_OK;
 }
 
 // Engine-less entry points (g2048_augment, g2048_canonicalize) launch on the device their buffers live on, whatever
@@ -1545,10 +1517,10 @@ static int export_view(const g2048_engine *ce, void *buf, size_t width, const ch
         G2048_HIP(launch(e, buf, s));
         return G2048_OK; // device destination: ready in stream order
     }
-    if (int rc = ensure_scratch(e))
+    if (int rc = e->scratch.alloc(e->n * 16, "the host staging buffer"))
         return rc;
-    G2048_HIP(launch(e, e->scratch, s));
-    return copy_sync(e, buf, e->scratch, e->n * width, stream);
+    G2048_HIP(launch(e, e->scratch.p, s));
+    return copy_sync(e, buf, e->scratch.p, e->n * width, stream);
 }
 
 // `vet_host`: checks the values of a host buffer before anything is copied (NULL: none)
@@ -1566,11 +1538,11 @@ static int import_view(g2048_engine *e, const void *buf, size_t width, int (*vet
     if (vet_host)
         if (int rc = vet_host(e, buf))
             return rc;
-    if (int rc = ensure_scratch(e))
+    if (int rc = e->scratch.alloc(e->n * 16, "the host staging buffer"))
         return rc;
-    if (int rc = copy_sync(e, e->scratch, buf, e->n * width, stream))
+    if (int rc = copy_sync(e, e->scratch.p, buf, e->n * width, stream))
         return rc;
-    G2048_HIP(launch(e, e->scratch, s));
+    G2048_HIP(launch(e, e->scratch.p, s));
     G2048_HIP(hipStreamSynchronize(s)); // the staging buffer must be free again when this returns
     return G2048_OK;
 }
@@ -1674,17 +1646,12 @@ int g2048_returns_summary_async(const g2048_engine *e, g2048_stats *device_out, 
     return stats_async(e, device_out, true, stream);
 }
 
-// numpy-RNG mode state: the five PCG64 planes plus the per-wavefront lists of finished boards, one allocation
+// numpy-RNG mode on: the planes' owner and the launchers' flag, st.rng, are set together
 static int ensure_numpy_rng(g2048_engine *e)
 {
-    if (e->st.rng)
-        return G2048_OK;
-    void *p = nullptr;
-    const size_t bytes = g2048::numpy_rng_bytes(e->n);
-    hipError_t err = hipMalloc(&p, bytes);
-    if (err != hipSuccess)
-        return fail(G2048_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(err));
-    e->st.rng = static_cast<uint64_t *>(p);
+    if (int rc = e->rng.alloc(g2048::numpy_rng_bytes(e->n), "the numpy-RNG planes"))
+        return rc;
+    e->st.rng = e->rng.as<uint64_t>();
     return G2048_OK;
 }
 
@@ -1693,10 +1660,9 @@ int g2048_set_numpy_rng(g2048_engine *e, const uint64_t *planes, void *stream)
     if (int rc = usable(e))
         return rc;
     G2048_HIP(hipSetDevice(e->device));
-    if (!planes) { // back to the spawn stream
-        if (e->st.rng)
-            G2048_HIP(hipFree(e->st.rng));
+    if (!planes) { // back to the spawn stream: the owner and the flag are cleared together
         e->st.rng = nullptr;
+        G2048_HIP(e->rng.reset());
         return G2048_OK;
     }
     if (int rc = ensure_numpy_rng(e))
@@ -1743,7 +1709,7 @@ int g2048_augment(const uint8_t *boards, const uint8_t *next_boards, const uint8
 
 uint64_t g2048_state_bytes(const g2048_engine *e)
 {
-    return e ? sizeof(StateHeader) + e->slab_bytes + (e->st.rng ? e->n * 40 : 0) : 0;
+    return e ? sizeof(StateHeader) + e->game_bytes + (e->st.rng ? e->n * 40 : 0) : 0;
 }
 
 int g2048_get_state(const g2048_engine *e, void *host_buf, void *stream)
@@ -1756,10 +1722,11 @@ int g2048_get_state(const g2048_engine *e, void *host_buf, void *stream)
                   (e->st.rng ? 1u : 0u) | (e->track_last ? 0u : 2u)}; // flags: 1 = numpy-RNG planes follow, 2 = no terminal records
     std::memcpy(host_buf, &h, sizeof h);
     char *body = static_cast<char *>(host_buf) + sizeof h;
-    if (int rc = copy_sync(e, body, e->slab, e->slab_bytes, stream))
+    if (int rc = copy_sync(e, body, e->slab.p, e->kept_bytes, stream))
         return rc;
+    std::memset(body + e->kept_bytes, 0, e->game_bytes - e->kept_bytes); // the engine's work memory is not state
     if (e->st.rng)
-        return copy_sync(e, body + e->slab_bytes, e->st.rng, e->n * 40, stream);
+        return copy_sync(e, body + e->game_bytes, e->st.rng, e->n * 40, stream);
     return G2048_OK;
 }
 
@@ -1780,7 +1747,7 @@ int g2048_set_state(g2048_engine *e, const void *host_buf, uint64_t blob_bytes, 
                     (h.magic == 0x3476383430324700ull ? " = a blob written by ABI 14: same games, another slab layout -- save it again "
                     "with g2048_get_boards / g2048_get_scores and re-create" : ""),
                     (unsigned long long)h.n, (unsigned long long)e->n);
-    const uint64_t want = sizeof(StateHeader) + e->slab_bytes + ((h.reserved & 1u) ? e->n * 40 : 0);
+    const uint64_t want = sizeof(StateHeader) + e->game_bytes + ((h.reserved & 1u) ? e->n * 40 : 0);
     if (blob_bytes != want)
         return fail(G2048_ERR_INVALID, "state blob is %llu bytes, this engine's state is %llu",
                     (unsigned long long)blob_bytes, (unsigned long long)want);
@@ -1795,10 +1762,10 @@ int g2048_set_state(g2048_engine *e, const void *host_buf, uint64_t blob_bytes, 
     e->illegal_reward = h.illegal_reward;
     e->track_last = (h.reserved & 2u) ? 0 : 1;
     const char *body = static_cast<const char *>(host_buf) + sizeof h;
-    if (int rc = copy_sync(e, e->slab, body, e->slab_bytes, stream))
+    if (int rc = copy_sync(e, e->slab.p, body, e->kept_bytes, stream)) // (what follows in the game region is ignored)
         return rc;
     if (h.reserved & 1u) // the blob carries numpy-RNG planes
-        return g2048_set_numpy_rng(e, reinterpret_cast<const uint64_t *>(body + e->slab_bytes), stream);
+        return g2048_set_numpy_rng(e, reinterpret_cast<const uint64_t *>(body + e->game_bytes), stream);
     return g2048_set_numpy_rng(e, nullptr, stream);
 }
 
@@ -1964,12 +1931,12 @@ int g2048_allgather_returns(const g2048_engine *ce, g2048_comm *c, int32_t *out,
     if (int rc = need_last_records(e, "g2048_allgather_returns"))
         return rc;
     G2048_HIP(hipSetDevice(e->device));
-    if (int rc = ensure_returns(e))
+    if (int rc = e->returns.alloc(e->n * 4, "the all-gather send buffer"))
         return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // the returns are the scores of last_record: materialise int32[n] in the engine's send buffer, then ONE
     // all-gather (equal shards: rank r's n returns land at out[r * n]), all on the caller's stream
-    int32_t *send = e->returns;
+    int32_t *send = e->returns.as<int32_t>();
     G2048_HIP(g2048::launch_export_last_scores(e->st, static_cast<uint32_t>(e->n), send, s));
     G2048_NCCL(g_rccl.AllGather(send, out, e->n, ncclInt32, c->comm, s));
     return G2048_OK;
@@ -2064,9 +2031,9 @@ int g2048_allgather_returns_local(g2048_comm_local *c, g2048_engine *const *engi
     }
     for (int r = 0; r < n_engines; ++r) {
         G2048_HIP(hipSetDevice(c->devices[r]));
-        if (int rc = ensure_returns(engines[r]))
+        if (int rc = engines[r]->returns.alloc(engines[r]->n * 4, "the all-gather send buffer"))
             return rc;
-        G2048_HIP(g2048::launch_export_last_scores(engines[r]->st, static_cast<uint32_t>(engines[r]->n), engines[r]->returns,
+        G2048_HIP(g2048::launch_export_last_scores(engines[r]->st, static_cast<uint32_t>(engines[r]->n), engines[r]->returns.as<int32_t>(),
                                                    static_cast<hipStream_t>(streams ? streams[r] : nullptr)));
     }
     ncclResult_t res = g_rccl.GroupStart();
@@ -2075,7 +2042,7 @@ int g2048_allgather_returns_local(g2048_comm_local *c, g2048_engine *const *engi
             res = ncclUnhandledCudaError;
             break;
         }
-        res = g_rccl.AllGather(engines[r]->returns, outs[r], engines[r]->n, ncclInt32, c->comms[r],
+        res = g_rccl.AllGather(engines[r]->returns.as<int32_t>(), outs[r], engines[r]->n, ncclInt32, c->comms[r],
                                static_cast<hipStream_t>(streams ? streams[r] : nullptr));
     }
     const ncclResult_t end = g_rccl.GroupEnd();

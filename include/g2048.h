@@ -430,7 +430,10 @@ int g2048_augment(const uint8_t *boards, const uint8_t *next_boards, const uint8
 
 /* Checkpoint / resume of the complete engine state (boards, scores, episode bookkeeping, seed,
  * clock, configuration) as one host blob of g2048_state_bytes() bytes.  The reference checkpoints
- * only models; its env state hooks are get_board/set_board (game2048_env.py:282-288). */
+ * only models; its env state hooks are get_board/set_board (game2048_env.py:282-288).
+ * The blob holds the game only: the bytes of the engine's work memory in it (statistics output, summary
+ * scratch, graph clock) are written as zeros and ignored by g2048_set_state, so engines in the same game
+ * state write the same blob. */
 uint64_t g2048_state_bytes(const g2048_engine *e);
 int g2048_get_state(const g2048_engine *e, void *host_buf, void *stream);
 /* blob_bytes = size of host_buf; magic, board count, size and header fields are validated.  Blobs written before ABI 14

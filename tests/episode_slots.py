@@ -1,8 +1,9 @@
 """Test helper: the episode slots and the terminal records inside a ``Batched2048.state_dict()`` blob.
 
-The blob is the 56-byte ``StateHeader`` followed by the engine's slab (g2048_create): board records, terminal records,
-the episode slots, the statistics struct, the returns-summary scratch and the graph clock word, each region starting on
-a 256-byte boundary; in numpy-RNG mode the five generator planes (40 bytes per board) follow the slab.  A slot holds
+The blob is the 56-byte ``StateHeader`` followed by the game region of the engine's slab (g2048_create): board records,
+terminal records, the episode slots, the statistics struct, the returns-summary scratch and the graph clock word, each
+region starting on a 256-byte boundary (the last three are the engine's work memory: zeros in a blob, ignored on load);
+in numpy-RNG mode the five generator planes (40 bytes per board) follow.  A slot holds
 four 64-bit counters of 64 boards as eight dwords, the four low halves first: {episodes, illegal_ends, G, pending}.
 There are slots for whole 512-lane blocks (the block of step_numpy_kernel), so a batch that is not a multiple of 512
 has padding slots behind the ``n_waves`` ones the readers sum.
@@ -38,7 +39,7 @@ def n_slots(n: int) -> int:
 
 
 def slab_offsets(n: int) -> dict:
-    """Byte offsets of the regions inside the slab (not counting the header) and the slab's size."""
+    """Byte offsets of the regions inside the blob's game region (not counting the header) and its size."""
     records = 0
     last = records + _up(16 * n)
     slots = last + _up(16 * n)

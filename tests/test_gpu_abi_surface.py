@@ -269,6 +269,94 @@ def test_episode_slot_carries_into_the_high_dwords(torch_cuda):
     assert np.array_equal(eng2.get_boards().reshape(512, 16), ora2.boards) and np.array_equal(eng2.get_scores(), ora2.score)
 
 
+def test_state_blob_holds_only_the_game(torch_cuda):
+    """Two engines in the same game state write the same blob, whatever statistics were read from one of them: the
+    statistics output, the summary scratch and the graph clock are the engine's work memory, not its state."""
+    torch = torch_cuda
+    from gym2048_amd.batched import Batched2048
+    n, seed, k = 5000, 17, 12
+    read, quiet = Batched2048(n, seed=seed), Batched2048(n, seed=seed)
+    acts = torch.as_tensor(np.random.default_rng(4).integers(0, 4, (k, n)), dtype=torch.uint8).to(read.device)
+    for eng in (read, quiet):
+        eng.reset()
+        for j in range(k):
+            eng.step(acts[j])
+    read.episode_stats()
+    read.episode_stats_device()
+    read.episode_stats_device(returns_only=True)
+    torch.cuda.synchronize()
+    a, b = read.state_dict()["blob"], quiet.state_dict()["blob"]
+    assert a.size == b.size and np.array_equal(a, b)
+    read.close()
+    quiet.close()
+
+
+def test_work_memory_in_a_state_blob_is_ignored(torch_cuda):
+    """g2048_set_state restores boards, terminal records and episode slots only.  A blob whose bytes from the end of
+    the slots to the end of the game region -- statistics output, summary scratch with its "last one out" counters,
+    graph clock -- are all 0xff (a summary launch in flight when it was taken leaves such counters) loads into an engine
+    whose statistics, the one-launch returns summary included, are those of the engine the blob came from."""
+    torch = torch_cuda
+    import episode_slots as es
+    from gym2048_amd.batched import Batched2048, parse_stats
+    n, seed = 5000, 23
+    src = Batched2048(n, seed=seed)
+    src.reset()
+    src.rollout_random(300)
+    want_summary = parse_stats(src.episode_stats_device(returns_only=True))
+    want = src.episode_stats()
+    assert want["episodes"] > 0 and want_summary["return_sum"] == want["return_sum"]
+    state = src.state_dict()
+    blob = state["blob"].copy()
+    off = es.slab_offsets(n)
+    lo = es.HEADER_BYTES + off["slots"] + es._up(es.n_slots(n) * es.SLOT_DWORDS * 4)
+    blob[lo: es.HEADER_BYTES + off["slab_bytes"]] = 0xFF
+    dst = Batched2048(n, seed=seed + 1)
+    dst.load_state_dict(dict(state, blob=blob))
+    out = torch.full((es.STATS_BYTES,), 0xAB, dtype=torch.uint8, device=dst.device)   # (a summary that is not written fails)
+    assert parse_stats(dst.episode_stats_device(out=out, returns_only=True)) == want_summary
+    assert dst.episode_stats() == want
+    src.close()
+    dst.close()
+
+
+def test_engine_teardown_frees_what_it_allocated(torch_cuda, monkeypatch):
+    """g2048_destroy frees everything an engine allocated on the way, lazily or not: device memory after three cycles
+    of creating engines of 2^20 boards (each lazily allocated device buffer several MiB), touching every lazy resource
+    and closing them is within 2 MiB of what it was after the first cycle.  Two chains need the spawn stream, so
+    numpy-RNG mode gets an engine of its own in each cycle."""
+    torch = torch_cuda
+    import gc
+    from gym2048_amd.batched import Batched2048
+    monkeypatch.setenv("G2048_TWO_CHAIN_MIN_STEPS", "2")        # split even a short rollout (read by set_chains)
+    n, k = 1 << 20, 4
+    rew = torch.zeros((k, n), dtype=torch.float32, device="cuda")
+
+    def cycle():
+        eng = Batched2048(n, seed=1)
+        eng.set_chains(2)                                        # the device's side chain, the chain tickets
+        eng.reset()
+        eng.rollout(k, reward=rew)
+        assert eng.chains_used == 2
+        eng.set_strict_actions(True)                             # the pinned report words
+        eng.host_io()["actions"][:] = 2                          # the pinned host-resident I/O block
+        eng.step_host()
+        eng.get_boards()                                         # the host staging buffer
+        num = Batched2048(n, seed=1, rng="numpy")                # the numpy-RNG planes
+        num.reset()
+        num.step(None)
+        eng.close()
+        num.close()
+        del eng, num
+        gc.collect()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()                                 # (the engines' own torch tensors are not the point)
+        return torch.cuda.mem_get_info()[0]
+
+    free = [cycle() for _ in range(3)]
+    assert abs(free[2] - free[0]) <= 2 << 20, free
+
+
 @pytest.mark.parametrize("n", [512, 777, 5000, 65536 + 300])
 def test_two_chain_rollout_is_bit_identical(torch_cuda, n):
     """g2048_set_chains(2): g2048_rollout cuts the batch at a block boundary and runs the halves as two chains of
