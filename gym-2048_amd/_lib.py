@@ -74,6 +74,18 @@ class SearchIO(C.Structure):
     ]
 
 
+class MCIO(C.Structure):
+    """g2048_mc_io (include/g2048.h): playouts per move, playout cap, seed and device output pointers (NULL = not wanted)."""
+    _fields_ = [
+        ("rollouts", C.c_uint32),
+        ("max_steps", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("action", C.c_void_p),
+        ("value", C.c_void_p),
+        ("steps", C.c_void_p),
+    ]
+
+
 class Stats(C.Structure):
     """g2048_stats (include/g2048.h)."""
     _fields_ = [
@@ -129,6 +141,8 @@ SIGNATURES = {
     "g2048_afterstates_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(AfterstateIO), _S]),
     "g2048_expectimax": (C.c_int, [_E, C.POINTER(SearchIO), _S]),
     "g2048_expectimax_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(SearchIO), _S]),
+    "g2048_mc_search": (C.c_int, [_E, C.POINTER(MCIO), _S]),
+    "g2048_mc_search_plain": (C.c_int, [C.c_void_p, _u64, _u32, C.POINTER(MCIO), _S]),
     "g2048_add_tile": (C.c_int, [_E, _u32, _S]),
     "g2048_fill_random_actions": (C.c_int, [_E, _u64, _u32, C.c_void_p, _S]),
     "g2048_onehot": (C.c_int, [_E, C.c_void_p, _i32, _S]),

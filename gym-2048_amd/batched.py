@@ -177,6 +177,61 @@ class _RolloutPlan:
         return self
 
 
+MC_DEFAULT_MAX_STEPS = 65535  # G2048_MC_MAX_STEPS: a playout runs to the end of its game (random play ends within ~10^3 moves)
+
+
+class MCSearch(NamedTuple):
+    """Result of ``mc_search`` (``g2048_mc_search``).  Device tensors; a field that is None was not asked for (``out``)."""
+    action: Optional[torch.Tensor]  # uint8 [n]: the smallest direction of largest value; 0 when no move is legal
+    value: Optional[torch.Tensor]   # int64 [n, 4]: summed scores of the R playouts of direction d, -1 where d is illegal
+    steps: Optional[torch.Tensor]   # int64 [n, 4]: moves those playouts played after the root move, -1 where d is illegal
+
+
+def _mc_io(n, device, rollouts, max_steps, seed, index_offset, out):
+    """(MCIO, MCSearch) for n boards: arguments checked, ``out`` checked field by field or freshly allocated."""
+    for name, v, lo, hi in (("rollouts", rollouts, 1, 65536), ("max_steps", max_steps, 1, 65535), ("seed", seed, 0, (1 << 64) - 1),
+                            ("index_offset", index_offset, 0, (1 << 32) - n)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} must be an int in {lo}..{hi}, not {v!r}")
+    if out is None:
+        out = MCSearch(torch.empty(n, dtype=torch.uint8, device=device), torch.empty((n, 4), dtype=torch.int64, device=device),
+                       torch.empty((n, 4), dtype=torch.int64, device=device))
+    else:
+        out = MCSearch(*out)
+        if out.action is None and out.value is None and out.steps is None:
+            raise ValueError("out requests no output (action, value and steps are all None)")
+    io = _lib.MCIO(int(rollouts), int(max_steps), int(seed))
+    for name, shape, dtype in (("action", (n,), torch.uint8), ("value", (n, 4), torch.int64), ("steps", (n, 4), torch.int64)):
+        t = getattr(out, name)
+        if t is None:
+            continue
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()
+                or t.device != device):
+            raise ValueError(f"out.{name} must be a contiguous {shape} tensor of {dtype} on {device}")
+        setattr(io, name, t.data_ptr())
+    return io, out
+
+
+def mc_search(boards, rollouts=64, max_steps=MC_DEFAULT_MAX_STEPS, seed=0, index_offset=0, out=None) -> MCSearch:
+    """Monte-Carlo rollout search of plain boards (``g2048_mc_search_plain``): for each legal move,
+    ``rollouts`` random playouts of at most ``max_steps`` moves; the action is the move with the largest summed score.
+    ``boards`` is a device ``uint8`` tensor ``[n, 16]`` or ``[n, 4, 4]`` of exponents (taken mod 32); row ``k`` draws
+    the random stream of board index ``index_offset + k`` under ``seed``.  ``max_steps`` defaults to the largest cap,
+    i.e. playouts run to the end of the game.  ``out``: a preallocated :class:`MCSearch` (a field that is None is not
+    written).  One launch, enqueued on the current stream of the boards' device.  Returns ``MCSearch(action [n] uint8,
+    value [n, 4] int64, steps [n, 4] int64)``."""
+    if (not isinstance(boards, torch.Tensor) or boards.dtype != torch.uint8 or boards.device.type != "cuda"
+            or boards.dim() not in (2, 3) or tuple(boards.shape[1:]) not in ((16,), (4, 4)) or not boards.is_contiguous()):
+        raise ValueError("boards must be a contiguous uint8 [n, 16] or [n, 4, 4] tensor on a GPU")
+    n = boards.shape[0]
+    io, out = _mc_io(n, boards.device, rollouts, max_steps, seed, index_offset, out)
+    lib = _lib.load()
+    with torch.cuda.device(boards.device):
+        stream = C.c_void_p(torch.cuda.current_stream(boards.device).cuda_stream)
+        check(lib.g2048_mc_search_plain(boards.data_ptr(), n, int(index_offset), C.byref(io), stream))
+    return out
+
+
 class Batched2048:
     """``n_envs`` boards resident on ``cuda:device``; the batched counterpart of ``Game2048Env``.
 
@@ -805,6 +860,15 @@ class Batched2048:
         record, clock, statistic or randomness; the engine's ``max_tile`` is not modelled."""
         io, out = _search_io(self.n_envs, self.device, depth, weights, out)
         check(self._lib.g2048_expectimax(self._h, C.byref(io), self._stream()))
+        return out
+
+    def mc_search(self, rollouts=64, max_steps=MC_DEFAULT_MAX_STEPS, seed=0, out=None) -> MCSearch:
+        """Monte-Carlo rollout search of the live boards (``g2048_mc_search``): ``MCSearch(action, value, steps)`` on the
+        engine's stream, as :func:`mc_search` with ``index_offset`` = the engine's ``board_offset``, so shards give the
+        results of the unsharded batch.  ``step(result.action)`` plays the chosen move.  The playouts draw from their
+        own stream under ``seed``: no record, clock, statistic or randomness of the engine is touched."""
+        io, out = _mc_io(self.n_envs, self.device, rollouts, max_steps, seed, 0, out)
+        check(self._lib.g2048_mc_search(self._h, C.byref(io), self._stream()))
         return out
 
     def isend_numpy(self) -> np.ndarray:

@@ -1183,6 +1183,61 @@ int g2048_expectimax_plain(const uint8_t *boards, uint64_t n, const g2048_search
     return G2048_OK;
 }
 
+} // extern "C"
+
+// g2048_mc_io -> the kernel's arguments, or G2048_ERR_INVALID (before any HIP call: works without a device)
+static int mc_args(const g2048_mc_io *io, uint64_t n, uint64_t index_offset, g2048::McArgs *a)
+{
+    if (!io)
+        return fail(G2048_ERR_INVALID, "io is NULL");
+    if (!io->action && !io->value && !io->steps)
+        return fail(G2048_ERR_INVALID, "g2048_mc_io requests no output (action, value and steps are all NULL)");
+    if (reinterpret_cast<uintptr_t>(io->value) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: mc value needs 16 bytes");
+    if (reinterpret_cast<uintptr_t>(io->steps) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: mc steps needs 16 bytes");
+    if (io->rollouts < 1 || io->rollouts > G2048_MC_MAX_ROLLOUTS)
+        return fail(G2048_ERR_INVALID, "rollouts=%u: need 1 <= rollouts <= %d", io->rollouts, G2048_MC_MAX_ROLLOUTS);
+    if (io->max_steps < 1 || io->max_steps > G2048_MC_MAX_STEPS)
+        return fail(G2048_ERR_INVALID, "max_steps=%u: need 1 <= max_steps <= %d", io->max_steps, G2048_MC_MAX_STEPS);
+    if (index_offset + n > 0x100000000ull)
+        return fail(G2048_ERR_INVALID, "index_offset=%llu n=%llu: global board indices must fit 32 bits",
+                    (unsigned long long)index_offset, (unsigned long long)n);
+    *a = g2048::McArgs{io->rollouts, io->max_steps, static_cast<uint32_t>(io->seed), static_cast<uint32_t>(io->seed >> 32),
+                       static_cast<uint32_t>(index_offset), io->action, io->value, io->steps};
+    return G2048_OK;
+}
+
+extern "C" {
+
+int g2048_mc_search(const g2048_engine *e, const g2048_mc_io *io, void *stream)
+{
+    if (int rc = usable(e))
+        return rc;
+    g2048::McArgs a;
+    if (int rc = mc_args(io, e->n, e->board_offset, &a))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(g2048::launch_mc_search(e->st.boards, static_cast<uint32_t>(e->n), false, a, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_mc_search_plain(const uint8_t *boards, uint64_t n, uint32_t index_offset, const g2048_mc_io *io, void *stream)
+{
+    if (!boards)
+        return fail(G2048_ERR_INVALID, "boards is NULL");
+    if (reinterpret_cast<uintptr_t>(boards) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: boards need 16 bytes");
+    if (n == 0 || n > 0xffffff00ull) // (32-bit board indices, as g2048_afterstates_plain)
+        return fail(G2048_ERR_INVALID, "n=%llu: need 1 <= n <= 2^32 - 256", (unsigned long long)n);
+    g2048::McArgs a;
+    if (int rc = mc_args(io, n, index_offset, &a))
+        return rc;
+    G2048_HIP(g2048::launch_mc_search(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), true, a,
+                                      static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream)
 {
     if (int rc = usable(e))

@@ -530,6 +530,110 @@ G2048_DEV uint32_t search_root(const Board &cells, const SearchWeights &w, const
     return search_key_action(best_key);
 }
 
+// ------------------------------------------------------------------- Monte-Carlo rollout search
+// g2048_mc_search (include/g2048.h): try each root move, finish the game at random R times, take the
+// move with the largest total score.  Integers only.  For board index i, root direction d, playout r, playout move j:
+//   block(i, d, r, j) = Philox4x32-10(ctr = (j, r, i, d), key = (seed_lo, seed_hi ^ kMcKeyTag))
+//   playout: a = move(b, d) (gain g; an illegal d has no playouts); total = g; then for j = 0, 1, ...: stop when j == L
+//   (before the spawn: a spawn nobody moves on is not drawn); add_tile(a, block[0]); a0 = block[1] >> 30; play the first
+//   of a0, a0 + 1, a0 + 2, a0 + 3 (mod 4) that is legal and add its merge score, or stop when none is (terminal).
+//   value[d] = sum over r < R of total, steps[d] = sum over r of the moves played after the root move (-1: d illegal).
+// A sum of pure functions of (i, d, r): every split of the playouts across lanes, in any order, gives the same bits.
+// The per-move score is shift4's: the true merge score while it stays below 2^31, which holds for every board whose
+// exponents are <= 26 (a move merges at most 8 pairs, each into an exponent <= 27: 8 * 2^27 = 2^30).  Above that it is
+// the sum of 2^(e mod 32) over the merged cells with bit 31 dropped -- not the game's score, but the same on host and
+// device, which share this code.
+//
+// The playout is phrased as a state machine that advances by ONE candidate move per trip (mc_trip), so that the kernel
+// can run the lanes of a wave through one flat loop in which each lane is at its own playout, move and candidate: a
+// lane whose candidate is illegal tries the next direction on its next trip, a lane whose playout ends starts its next
+// playout on its next trip.  mc_playout / mc_root below are the same trips in sequence on one thread.
+constexpr uint32_t kMcKeyTag = 0x4D435332u; // separates this stream from the engine's spawn stream under an equal seed
+constexpr uint32_t kMcMaxRollouts = 65536, kMcMaxSteps = 65535; // = G2048_MC_MAX_* (g2048.h): steps sums fit 32 bits per lane
+
+struct McPlayout {
+    Board a;        // the playout's board: after a move, before the spawn that answers it
+    uint32_t moves; // moves played after the root move = index j of the next Philox block
+    uint32_t tries; // candidates of the current move already found illegal (0: the spawn is still to be drawn)
+};
+
+G2048_DEV McPlayout mc_begin(const Board &after) { return McPlayout{after, 0u, 0u}; }
+
+// One trip: draws the spawn when this is the move's first candidate, tries candidate (a0 + tries) mod 4.  Adds the merge
+// score of a legal move to `total` and 1 to `steps`.  Returns true when the playout has ended (cap or terminal).
+// i, d, r: board index, root direction, playout; max_steps = L >= 1.
+template <class Tables>
+G2048_DEV bool mc_trip(McPlayout &p, uint32_t i, uint32_t d, uint32_t r, uint32_t seed_lo, uint32_t seed_hi,
+                       uint32_t max_steps, const Tables &tb, uint64_t &total, uint32_t &steps)
+{
+    // the block of move j = p.moves; a retry recomputes it (cheaper than keeping four words live per lane)
+    const Words w = philox4x32_10(p.moves, r, i, d, seed_lo, seed_hi ^ kMcKeyTag);
+    add_tile(p.a, w.w[0], lanemask(p.tries == 0u));
+    Board b = p.a;
+    uint32_t gain;
+    const bool legal = move_sel(b, tb.move_sel(((w.w[1] >> 30) + p.tries) & 3u), gain);
+    if (legal) {
+        p.a = b;
+        total += gain;
+        steps += 1u;
+        p.moves += 1u;
+        p.tries = 0u;
+        return p.moves == max_steps; // the cap, before the next spawn
+    }
+    p.tries += 1u;
+    return p.tries == 4u;            // no candidate is legal: terminal
+}
+
+// One whole playout from the root afterstate `after` (gain g already counted by the caller).
+template <class Tables>
+G2048_DEV void mc_playout(const Board &after, uint32_t i, uint32_t d, uint32_t r, uint32_t seed_lo, uint32_t seed_hi,
+                          uint32_t max_steps, const Tables &tb, uint64_t &total, uint32_t &steps)
+{
+    McPlayout p = mc_begin(after);
+    while (!mc_trip(p, i, d, r, seed_lo, seed_hi, max_steps, tb, total, steps)) {
+    }
+}
+
+// The playouts sub, sub + K, ... (< R) of root direction d: what one lane of the kernel sums.  `after`, g: move(b, d).
+template <class Tables>
+G2048_DEV void mc_partial(const Board &after, uint32_t g, uint32_t i, uint32_t d, uint32_t sub, uint32_t K, uint32_t rollouts,
+                          uint32_t seed_lo, uint32_t seed_hi, uint32_t max_steps, const Tables &tb, uint64_t &total, uint64_t &steps)
+{
+    for (uint32_t r = sub; r < rollouts; r += K) {
+        uint32_t s = 0;
+        total += g;
+        mc_playout(after, i, d, r, seed_lo, seed_hi, max_steps, tb, total, s);
+        steps += s;
+    }
+}
+
+// Root choice as one unsigned max over (value + 1, 3 - d): value >= -1 and < 2^62.
+G2048_DEV uint64_t mc_key(int64_t value, uint32_t d) { return (static_cast<uint64_t>(value + 1) << 2) | (3u - d); }
+G2048_DEV uint32_t mc_key_action(uint64_t key) { return 3u - (static_cast<uint32_t>(key) & 3u); }
+
+// The root on one thread: value[4], steps[4] (-1 where d is illegal) and the action (smallest d of largest value, 0
+// when no move is legal).
+template <class Tables>
+G2048_DEV uint32_t mc_root(const Board &cells, uint32_t i, uint32_t rollouts, uint32_t max_steps, uint32_t seed_lo,
+                           uint32_t seed_hi, const Tables &tb, int64_t value[4], int64_t steps[4])
+{
+    uint64_t best = 0;
+    for (uint32_t d = 0; d < 4u; ++d) {
+        Board after = cells;
+        uint32_t g;
+        value[d] = steps[d] = -1;
+        if (move_sel(after, tb.move_sel(d), g)) {
+            uint64_t total = 0, st = 0;
+            mc_partial(after, g, i, d, 0u, 1u, rollouts, seed_lo, seed_hi, max_steps, tb, total, st);
+            value[d] = static_cast<int64_t>(total);
+            steps[d] = static_cast<int64_t>(st);
+        }
+        const uint64_t key = mc_key(value[d], d);
+        best = key > best ? key : best;
+    }
+    return mc_key_action(best);
+}
+
 // ------------------------------------------------------------------- the 16-byte board RECORD
 // What the engine keeps per board in HBM is ONE 16-byte record: bits [4:0] of byte j = exponent of
 // cell j (0..31), and the 24-bit SCORE DEFICIT d in the three spare bits [7:5] of bytes 8..15

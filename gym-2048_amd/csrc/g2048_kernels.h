@@ -104,6 +104,16 @@ struct SearchArgs {
 };
 // depth 1..3; `plain` as in launch_afterstates
 hipError_t launch_expectimax(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const SearchArgs &a, hipStream_t s);
+// g2048_mc_search: parameters and outputs (g2048_mc_io, checked by the caller; NULL = not wanted)
+struct McArgs {
+    uint32_t rollouts, max_steps; // R in 1..65536, L in 1..65535
+    uint32_t seed_lo, seed_hi;
+    uint32_t index_offset;        // board index of row 0 in the Philox counter
+    uint8_t *action;              // [n]
+    int64_t *value;               // [n][4]
+    int64_t *steps;               // [n][4]
+};
+hipError_t launch_mc_search(const uint4 *boards, uint32_t n, bool plain, const McArgs &a, hipStream_t s);
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s);
 // numpy-RNG mode: every board's PCG64 generator, seeded as numpy seeds it, into the DeviceState::rng planes
 hipError_t launch_seed_numpy(uint64_t *planes, uint32_t n, uint64_t first_seed, hipStream_t s);

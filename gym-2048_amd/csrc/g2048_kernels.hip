@@ -1449,6 +1449,71 @@ __global__ void __launch_bounds__(kBlock) expectimax_kernel(const uint4 *__restr
     }
 }
 
+// ---------------------------------------------------------------------------- Monte-Carlo rollout search
+// g2048_mc_search: the rollout search of g2048_device.h ("Monte-Carlo rollout search") for every board.  A board is a
+// group of G lanes, K = G / 4 per root direction d; lane `sub` of direction d runs the playouts sub, sub + K, ... < R of
+// that direction.  Playouts end hundreds of moves apart, so the lanes of a wave do not run them in step: the wave runs
+// ONE flat loop of mc_trip, in which every lane is at its own playout, move and candidate direction -- a lane whose
+// playout ended begins its next one on the following trip -- and leaves it when no lane has a playout left (one ballot).
+// The board stays in registers, the selector rows come from LDS; memory sees one 16-byte load per board and the
+// outputs.  The result is a sum of pure functions of (i, d, r), so this schedule gives the bits of mc_root on the host.
+// G = 64 (one wave per board) when R >= kMcWaveRollouts, else G = 16, which keeps the lanes of a direction busy at small
+// R.  Lanes stride over the boards when n * G exceeds the grid cap (kSearchMaxLanes); PLAIN as in expectimax_kernel.
+constexpr uint32_t kMcWaveRollouts = 32;
+
+template <uint32_t G, bool PLAIN>
+__global__ void __launch_bounds__(kBlock) mc_search_kernel(const uint4 *__restrict__ boards, uint32_t n, const McArgs a)
+{
+    constexpr uint32_t K = G / 4u;
+    __shared__ WaveTables s_tables[kBlock / 64];
+    const LdsTables tb = stage_tables(s_tables, load_tables_piece());
+    const uint32_t j = threadIdx.x % G, d = j / K, sub = j % K;
+    const uint32_t stride = gridDim.x * (kBlock / G);
+    // a group's G lanes hold the same i, so they leave the loop together and every shuffle stays inside live groups
+    for (uint64_t i = (static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x) / G; i < n; i += stride) {
+        const Board in = load_board(boards, static_cast<uint32_t>(i));
+        const Board cells = PLAIN ? Board{{in.r[0] & kCellBits, in.r[1] & kCellBits, in.r[2] & kCellBits, in.r[3] & kCellBits}}
+                                  : record_cells(in);
+        Board after = cells;
+        uint32_t g;
+        const bool legal = move_sel(after, tb.move_sel(d), g);
+        const uint32_t index = a.index_offset + static_cast<uint32_t>(i);
+        uint64_t total = 0;
+        uint32_t steps = 0, r = sub; // a lane plays at most R * L < 2^32 moves
+        bool live = legal && r < a.rollouts;
+        McPlayout p = mc_begin(after);
+        if (live)
+            total = g;
+        while (g2048_any(live)) {
+            if (live && mc_trip(p, index, d, r, a.seed_lo, a.seed_hi, a.max_steps, tb, total, steps)) {
+                r += K;
+                live = r < a.rollouts;
+                if (live) {
+                    p = mc_begin(after);
+                    total += g;
+                }
+            }
+        }
+        uint64_t moved = steps;
+#pragma unroll
+        for (uint32_t o = K / 2u; o > 0u; o >>= 1) {
+            total += __shfl_xor(total, o);
+            moved += __shfl_xor(moved, o);
+        }
+        const int64_t value = legal ? static_cast<int64_t>(total) : -1;
+        uint64_t key = mc_key(value, d), other = __shfl_xor(key, K);
+        key = other > key ? other : key;
+        other = __shfl_xor(key, 2u * K);
+        key = other > key ? other : key;
+        if (sub == 0u && a.value)
+            a.value[i * 4u + d] = value;
+        if (sub == 0u && a.steps)
+            a.steps[i * 4u + d] = legal ? static_cast<int64_t>(moved) : -1;
+        if (j == 0u && a.action)
+            a.action[i] = static_cast<uint8_t>(mc_key_action(key));
+    }
+}
+
 // ---------------------------------------------------------------------------- augmentation
 // training_data.augment() (training_data.py:257-299) for board pairs on the device: the eight
 // symmetries [orig, hflip, rot1(orig), rot1(hflip), rot2(..), rot2(..), rot3(..), rot3(..)] with the
@@ -2020,6 +2085,17 @@ hipError_t launch_expectimax(const uint4 *boards, uint32_t n, uint32_t depth, bo
             return launch_1d(expectimax_kernel<dc, true>, lanes, 0, s, boards, n, a);
         return launch_1d(expectimax_kernel<dc, false>, lanes, 0, s, boards, n, a);
     });
+}
+
+hipError_t launch_mc_search(const uint4 *boards, uint32_t n, bool plain, const McArgs &a, hipStream_t s)
+{
+    auto go = [&](auto gc, auto plain_c) {
+        const uint64_t want = static_cast<uint64_t>(n) * gc, lanes = want < kSearchMaxLanes ? want : kSearchMaxLanes;
+        return launch_1d(mc_search_kernel<gc, plain_c>, lanes, 0, s, boards, n, a);
+    };
+    auto by_form = [&](auto gc) { return plain ? go(gc, std::true_type()) : go(gc, std::false_type()); };
+    return a.rollouts >= kMcWaveRollouts ? by_form(std::integral_constant<uint32_t, 64u>())
+                                         : by_form(std::integral_constant<uint32_t, 16u>());
 }
 
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s)

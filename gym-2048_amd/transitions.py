@@ -33,6 +33,13 @@ def csv_header(add_returns=False):
     return cols
 
 
+def mc_step_seed(seed, clock):
+    """Seed of the Monte-Carlo search at engine clock ``clock`` under the base ``seed``:
+    ``(seed + 0x9E3779B97F4A7C15 * (clock + 1)) mod 2^64``.  The multiplier is odd, so the 2^64 clocks of one base seed
+    give 2^64 different seeds, none equal to the base seed's own use at clock -1."""
+    return (int(seed) + 0x9E3779B97F4A7C15 * (int(clock) + 1)) & ((1 << 64) - 1)
+
+
 class Transitions:
     """(board, action, reward, next_board, done) rows; arrays shaped as ``training_data`` keeps them."""
 
@@ -58,18 +65,30 @@ class Transitions:
         recorder stores, gather_training_data.py:191-196), not the auto-reset board."""
         import torch
         k = n_steps if actions is None else len(actions)
+        if actions is None:
+            given = engine.random_actions(k)
+        else:
+            given = torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions)
+        return cls._record_loop(engine, k, given, None)
+
+    @classmethod
+    def _record_loop(cls, engine, k, actions, choose):
+        """The recording loop of :meth:`record` and :meth:`record_search`: ``k`` steps whose actions are ``actions``
+        (``[k, n]``, copied up front) or, when that is None, written by ``choose(j, row)`` into the recorded action row
+        ``row`` (uint8 ``[n]``, device) from step ``j``'s boards just before the step."""
+        import torch
         n = engine.n_envs
         xs = torch.empty((k, n, 16), dtype=torch.uint8, device=engine.device)
         nxt = torch.empty_like(xs)
         acts = torch.empty((k, n), dtype=torch.uint8, device=engine.device)
         rew = torch.empty((k, n), dtype=torch.float32, device=engine.device)
         done = torch.empty((k, n), dtype=torch.uint8, device=engine.device)
-        if actions is None:
-            acts.copy_(engine.random_actions(k))
-        else:
-            acts.copy_(torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions))
+        if actions is not None:
+            acts.copy_(actions)
         for j in range(k):
             xs[j].copy_(engine.boards().reshape(n, 16))
+            if choose is not None:
+                choose(j, acts[j])
             engine.step(acts[j], auto_reset=True, want_info=True)
             rew[j].copy_(engine.reward)
             done[j].copy_(engine.terminated)
@@ -80,32 +99,28 @@ class Transitions:
                    order(rew).reshape(-1), exp_to_values(order(nxt)).reshape(-1, 4, 4), order(done).reshape(-1))
 
     @classmethod
-    def record_search(cls, engine, n_steps, depth=2, weights=None):
-        """Play ``n_steps`` expectimax moves on a ``Batched2048`` and record every transition: a behaviour-cloning data
+    def record_search(cls, engine, n_steps, depth=2, weights=None, player="expectimax", rollouts=64, max_steps=None, seed=0):
+        """Play ``n_steps`` searched moves on a ``Batched2048`` and record every transition: a behaviour-cloning data
         set in the reference's CSV format (``export_csv``), with a search in place of the person at the keyboard of
-        gather_training_data.py.  Each step's action is ``engine.expectimax(depth, weights).action`` of that step's
-        boards, written straight into the recorded action row.  Rows as in :meth:`record`: env-major, and
+        gather_training_data.py.  ``player="expectimax"`` (the default): each step's action is
+        ``engine.expectimax(depth, weights).action`` of that step's boards.  ``player="mc"``: it is
+        ``engine.mc_search(rollouts, max_steps, seed=mc_step_seed(seed, engine.clock)).action`` (``max_steps`` None = the
+        default of ``mc_search``; ``depth`` and ``weights`` are not used) -- the clock advances with every step, so
+        every step draws fresh playouts, and the same base ``seed`` on the same engine state repeats the recording.
+        The action is written straight into the recorded action row.  Rows as in :meth:`record`: env-major, and
         ``next_board`` of a step that ends an episode is the terminal board."""
-        import torch
+        from .batched import MC_DEFAULT_MAX_STEPS, MCSearch, Search
+        if player == "expectimax":
+            def choose(j, row):
+                engine.expectimax(depth, weights, out=Search(row, None))
+        elif player == "mc":
+            cap = MC_DEFAULT_MAX_STEPS if max_steps is None else max_steps
 
-        from .batched import Search
-        k, n = int(n_steps), engine.n_envs
-        xs = torch.empty((k, n, 16), dtype=torch.uint8, device=engine.device)
-        nxt = torch.empty_like(xs)
-        acts = torch.empty((k, n), dtype=torch.uint8, device=engine.device)
-        rew = torch.empty((k, n), dtype=torch.float32, device=engine.device)
-        done = torch.empty((k, n), dtype=torch.uint8, device=engine.device)
-        for j in range(k):
-            xs[j].copy_(engine.boards().reshape(n, 16))
-            engine.expectimax(depth, weights, out=Search(acts[j], None))
-            engine.step(acts[j], auto_reset=True, want_info=True)
-            rew[j].copy_(engine.reward)
-            done[j].copy_(engine.terminated)
-            nxt[j].copy_(torch.where(engine.terminated.bool().unsqueeze(1), engine.terminal_boards,
-                                     engine.boards().reshape(n, 16)))
-        order = lambda t: t.transpose(0, 1).contiguous().cpu().numpy()  # noqa: E731  env-major
-        return cls(exp_to_values(order(xs)).reshape(-1, 4, 4), order(acts).reshape(-1),
-                   order(rew).reshape(-1), exp_to_values(order(nxt)).reshape(-1, 4, 4), order(done).reshape(-1))
+            def choose(j, row):
+                engine.mc_search(rollouts, cap, seed=mc_step_seed(seed, engine.clock), out=MCSearch(row, None, None))
+        else:
+            raise ValueError(f"player must be 'expectimax' or 'mc', not {player!r}")
+        return cls._record_loop(engine, int(n_steps), None, choose)
 
     # ------------------------------------------------------------------ returns
     def discounted_return(self, gamma=0.9):

@@ -346,6 +346,37 @@ int g2048_expectimax(const g2048_engine *e, const g2048_search_io *io, void *str
  * g2048_afterstates_plain).  Needs no engine; runs on the current device.  1 <= n <= 2^32 - 256. */
 int g2048_expectimax_plain(const uint8_t *boards, uint64_t n, const g2048_search_io *io, void *stream);
 
+/* Monte-Carlo rollout search: the best move of every board by random playouts, with no heuristic.
+ * Directions as in g2048_move; the engine's max_tile is not modelled.  For a board b with global index i, R = rollouts
+ * playouts per move and a cap of L = max_steps moves per playout, in integers only:
+ *   block(i, d, r, j) = Philox4x32-10(ctr = (j, r, i, d), key = (seed_lo, seed_hi ^ 0x4D435332))
+ *   playout(b, i, d, r): a = move(b, d) with merge score g (no playout when d is illegal); total = g; for j = 0, 1, ...:
+ *     stop when j == L (before the spawn); w = block(i, d, r, j); spawn on `a` from w[0] (the engine's rule: position
+ *     floor(u n) among the n empty cells, a 2 when frac(u n) < 0.9); a0 = w[1] >> 30; play the first of a0, a0 + 1,
+ *     a0 + 2, a0 + 3 (mod 4) that is legal and add its merge score to total; stop when none is legal (terminal).
+ *   value[d] = sum over r < R of total, steps[d] = sum over r < R of the moves played after the root move; both -1 where
+ *   d is illegal.  action = the smallest d of largest value, 0 when no move is legal.
+ * Exact: the same bits however the playouts are split.  Merge scores are the game's for exponents <= 26 (g2048_device.h).
+ * All pointers are device pointers; NULL = not wanted, but at least one output must be given. */
+#define G2048_MC_MAX_ROLLOUTS 65536
+#define G2048_MC_MAX_STEPS 65535
+typedef struct g2048_mc_io {
+    uint32_t rollouts, max_steps; /* 1..G2048_MC_MAX_ROLLOUTS, 1..G2048_MC_MAX_STEPS */
+    uint64_t seed;
+    uint8_t *action;              /* [n], or NULL */
+    int64_t *value;               /* [n][4], 16-byte aligned, or NULL */
+    int64_t *steps;               /* [n][4], 16-byte aligned, or NULL */
+} g2048_mc_io;
+
+/* One launch over the engine's live records (the score deficit is ignored), enqueued on `stream`; i = board_offset +
+ * local index, so the shards of a batch give the results of the unsharded batch.  Consumes none of the engine's
+ * randomness, leaves the records, the clock, the episode bookkeeping and cached graphs alone, in either RNG mode. */
+int g2048_mc_search(const g2048_engine *e, const g2048_mc_io *io, void *stream);
+/* The same for n plain boards (uint8[n][16] exponents, device memory, 16-byte aligned; taken mod 32 as in
+ * g2048_expectimax_plain); i = index_offset + row, index_offset + n <= 2^32.  Needs no engine; runs on the current
+ * device.  1 <= n <= 2^32 - 256. */
+int g2048_mc_search_plain(const uint8_t *boards, uint64_t n, uint32_t index_offset, const g2048_mc_io *io, void *stream);
+
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream);
