@@ -1081,6 +1081,18 @@ int g2048_legal_actions(const g2048_engine *e, uint8_t *mask_out, void *stream)
 
 } // extern "C"
 
+// The plain board array of the _plain analysis calls (afterstates, expectimax, mc_search): n rows of 16 exponents
+static int plain_boards(const uint8_t *boards, uint64_t n)
+{
+    if (!boards)
+        return fail(G2048_ERR_INVALID, "boards is NULL");
+    if (reinterpret_cast<uintptr_t>(boards) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: boards need 16 bytes");
+    if (n == 0 || n > 0xffffff00ull) // (32-bit board indices, whole 256-lane blocks: the cap of g2048_create)
+        return fail(G2048_ERR_INVALID, "n=%llu: need 1 <= n <= 2^32 - 256", (unsigned long long)n);
+    return G2048_OK;
+}
+
 // g2048_afterstate_io -> the kernel's outputs, or G2048_ERR_INVALID (before any HIP call: works without a device)
 static int afterstate_out(const g2048_afterstate_io *io, g2048::AfterstateOut *o)
 {
@@ -1113,12 +1125,8 @@ int g2048_afterstates(const g2048_engine *e, const g2048_afterstate_io *io, void
 
 int g2048_afterstates_plain(const uint8_t *boards, uint64_t n, const g2048_afterstate_io *io, void *stream)
 {
-    if (!boards)
-        return fail(G2048_ERR_INVALID, "boards is NULL");
-    if (reinterpret_cast<uintptr_t>(boards) & 15u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: boards need 16 bytes");
-    if (n == 0 || n > 0xffffff00ull) // (32-bit board indices, whole 256-lane blocks: the cap of g2048_create)
-        return fail(G2048_ERR_INVALID, "n=%llu: need 1 <= n <= 2^32 - 256", (unsigned long long)n);
+    if (int rc = plain_boards(boards, n))
+        return rc;
     g2048::AfterstateOut o;
     if (int rc = afterstate_out(io, &o))
         return rc;
@@ -1169,12 +1177,8 @@ int g2048_expectimax(const g2048_engine *e, const g2048_search_io *io, void *str
 
 int g2048_expectimax_plain(const uint8_t *boards, uint64_t n, const g2048_search_io *io, void *stream)
 {
-    if (!boards)
-        return fail(G2048_ERR_INVALID, "boards is NULL");
-    if (reinterpret_cast<uintptr_t>(boards) & 15u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: boards need 16 bytes");
-    if (n == 0 || n > 0xffffff00ull) // (32-bit board indices, as g2048_afterstates_plain)
-        return fail(G2048_ERR_INVALID, "n=%llu: need 1 <= n <= 2^32 - 256", (unsigned long long)n);
+    if (int rc = plain_boards(boards, n))
+        return rc;
     g2048::SearchArgs a;
     if (int rc = search_args(io, &a))
         return rc;
@@ -1224,12 +1228,8 @@ int g2048_mc_search(const g2048_engine *e, const g2048_mc_io *io, void *stream)
 
 int g2048_mc_search_plain(const uint8_t *boards, uint64_t n, uint32_t index_offset, const g2048_mc_io *io, void *stream)
 {
-    if (!boards)
-        return fail(G2048_ERR_INVALID, "boards is NULL");
-    if (reinterpret_cast<uintptr_t>(boards) & 15u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: boards need 16 bytes");
-    if (n == 0 || n > 0xffffff00ull) // (32-bit board indices, as g2048_afterstates_plain)
-        return fail(G2048_ERR_INVALID, "n=%llu: need 1 <= n <= 2^32 - 256", (unsigned long long)n);
+    if (int rc = plain_boards(boards, n))
+        return rc;
     g2048::McArgs a;
     if (int rc = mc_args(io, n, index_offset, &a))
         return rc;

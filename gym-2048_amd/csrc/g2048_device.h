@@ -510,24 +510,32 @@ template <int D, class Tables> G2048_DEV uint32_t search_value(const Board &bd, 
 }
 
 // Root choice as one unsigned max: (value + 1) << 2 orders by value (illegal -1 lowest), 3 - m breaks ties to the
-// smallest m.  value < 2^27, so the key fits 32 bits.
-G2048_DEV uint32_t search_key(int32_t value, uint32_t m) { return (static_cast<uint32_t>(value + 1) << 2) | (3u - m); }
-G2048_DEV uint32_t search_key_action(uint32_t key) { return 3u - (key & 3u); }
+// smallest m.  KEY is as wide as the value: uint32_t for expectimax (value < 2^27), uint64_t for the rollout search
+// (value < 2^62).  best_action: the action of the largest of the four keys, what the kernels find with two shuffles.
+template <class KEY, class V> G2048_DEV KEY root_key(V value, uint32_t m) { return (static_cast<KEY>(value + 1) << 2) | (3u - m); }
+template <class KEY> G2048_DEV uint32_t root_key_action(KEY key) { return 3u - (static_cast<uint32_t>(key) & 3u); }
+
+template <class KEY, class V> G2048_DEV uint32_t best_action(const V value[4])
+{
+    KEY best = 0;
+    for (uint32_t m = 0; m < 4u; ++m) {
+        const KEY key = root_key<KEY>(value[m], m);
+        best = key > best ? key : best;
+    }
+    return root_key_action(best);
+}
 
 // The root: value[m] = C_D(move(b, m)) or -1 when m is illegal, action = the smallest m with the largest value (0 when
 // no move is legal).  One thread; the kernels split the same sums across lanes (chance_partial).
 template <int D, class Tables>
 G2048_DEV uint32_t search_root(const Board &cells, const SearchWeights &w, const Tables &tb, int32_t value[4])
 {
-    uint32_t best_key = 0;
     for (uint32_t m = 0; m < 4u; ++m) {
         Board a = cells;
         uint32_t gain;
         value[m] = move_sel(a, tb.move_sel(m), gain) ? static_cast<int32_t>(chance_value<D>(a, w, tb)) : -1;
-        const uint32_t key = search_key(value[m], m);
-        best_key = key > best_key ? key : best_key;
     }
-    return search_key_action(best_key);
+    return best_action<uint32_t>(value);
 }
 
 // ------------------------------------------------------------------- Monte-Carlo rollout search
@@ -607,17 +615,12 @@ G2048_DEV void mc_partial(const Board &after, uint32_t g, uint32_t i, uint32_t d
     }
 }
 
-// Root choice as one unsigned max over (value + 1, 3 - d): value >= -1 and < 2^62.
-G2048_DEV uint64_t mc_key(int64_t value, uint32_t d) { return (static_cast<uint64_t>(value + 1) << 2) | (3u - d); }
-G2048_DEV uint32_t mc_key_action(uint64_t key) { return 3u - (static_cast<uint32_t>(key) & 3u); }
-
 // The root on one thread: value[4], steps[4] (-1 where d is illegal) and the action (smallest d of largest value, 0
 // when no move is legal).
 template <class Tables>
 G2048_DEV uint32_t mc_root(const Board &cells, uint32_t i, uint32_t rollouts, uint32_t max_steps, uint32_t seed_lo,
                            uint32_t seed_hi, const Tables &tb, int64_t value[4], int64_t steps[4])
 {
-    uint64_t best = 0;
     for (uint32_t d = 0; d < 4u; ++d) {
         Board after = cells;
         uint32_t g;
@@ -628,10 +631,8 @@ G2048_DEV uint32_t mc_root(const Board &cells, uint32_t i, uint32_t rollouts, ui
             value[d] = static_cast<int64_t>(total);
             steps[d] = static_cast<int64_t>(st);
         }
-        const uint64_t key = mc_key(value[d], d);
-        best = key > best ? key : best;
     }
-    return mc_key_action(best);
+    return best_action<uint64_t>(value);
 }
 
 // ------------------------------------------------------------------- the 16-byte board RECORD

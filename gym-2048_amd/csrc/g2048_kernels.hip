@@ -1189,6 +1189,16 @@ __global__ void __launch_bounds__(kBlock) add_tile_kernel(const StepArgs p, uint
     store_board(p.st.boards, i, make_record(bd, record_score(raw)));
 }
 
+// The cells of a loaded 16-byte input row.  PLAIN: plain exponents, taken mod 32; otherwise an engine record, whose
+// deficit bits are dropped.
+template <bool PLAIN> __device__ __forceinline__ Board input_cells(const Board &in)
+{
+    if constexpr (PLAIN)
+        return Board{{in.r[0] & kCellBits, in.r[1] & kCellBits, in.r[2] & kCellBits, in.r[3] & kCellBits}};
+    else
+        return record_cells(in);
+}
+
 // ------------------------------------------------------------- records <-> plain boards / scores
 // get_board / set_board (game2048_env.py:282-288) and self.score for the whole batch.
 __global__ void __launch_bounds__(kBlock) export_boards_kernel(const uint4 *records, uint32_t n, uint4 *cells_out)
@@ -1203,8 +1213,7 @@ __global__ void __launch_bounds__(kBlock) import_boards_kernel(uint4 *records, u
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n)
         return;
-    const Board in = load_board(cells_in, i);
-    const Board cells{{in.r[0] & kCellBits, in.r[1] & kCellBits, in.r[2] & kCellBits, in.r[3] & kCellBits}};
+    const Board cells = input_cells<true>(load_board(cells_in, i));
     store_board(records, i, make_record(cells, record_score(load_board(records, i)))); // score untouched (:286-288)
 }
 
@@ -1352,8 +1361,7 @@ __global__ void __launch_bounds__(kBlock) afterstates_kernel(const uint4 *__rest
     const uint32_t i = valid ? i_raw : n - 1u; // lanes past the end move a copy of the last board and store nothing
     const Board in = load_board_nt(boards, i);
     const LdsTables tb = stage_tables(s_tables, piece);
-    const Board cells = PLAIN ? Board{{in.r[0] & kCellBits, in.r[1] & kCellBits, in.r[2] & kCellBits, in.r[3] & kCellBits}}
-                              : record_cells(in);
+    const Board cells = input_cells<PLAIN>(in);
     Board after[4];
     uint32_t gain[4], mask = 0;
 #pragma unroll
@@ -1414,6 +1422,25 @@ __global__ void __launch_bounds__(kBlock) afterstates_kernel(const uint4 *__rest
 // randomness is touched.  PLAIN: plain exponents (mod 32) instead of engine records.
 constexpr uint64_t kSearchMaxLanes = 1ull << 24;
 
+// Lane j of a board's group of G: lane `sub` of the K = G / 4 that share root direction d.  The groups take the boards
+// first, first + stride, ...; a group's G lanes hold the same board index, so they leave that loop together and every
+// shuffle stays inside live groups.
+template <uint32_t G> struct LaneGroup {
+    static constexpr uint32_t K = G / 4u;
+    const uint32_t j = threadIdx.x % G, d = j / K, sub = j % K;
+    const uint32_t stride = gridDim.x * (kBlock / G);
+    const uint64_t first = (static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x) / G;
+};
+
+// The largest key of the group's four directions, in every lane (the K lanes of a direction hold equal keys)
+template <class KEY> __device__ __forceinline__ KEY group_best_key(KEY key, uint32_t K)
+{
+    KEY other = __shfl_xor(key, K);
+    key = other > key ? other : key;
+    other = __shfl_xor(key, 2u * K);
+    return other > key ? other : key;
+}
+
 template <int D, bool PLAIN>
 __global__ void __launch_bounds__(kBlock) expectimax_kernel(const uint4 *__restrict__ boards, uint32_t n, const SearchArgs a)
 {
@@ -1421,13 +1448,11 @@ __global__ void __launch_bounds__(kBlock) expectimax_kernel(const uint4 *__restr
     __shared__ WaveTables s_tables[kBlock / 64];
     const LdsTables tb = stage_tables(s_tables, load_tables_piece());
     const SearchWeights w{a.base, a.w_empty, a.w_merge, a.w_mono};
-    const uint32_t j = threadIdx.x % G, d = j / K, sub = j % K;
-    const uint32_t stride = gridDim.x * (kBlock / G);
-    // a group's G lanes hold the same i, so they leave the loop together and every shuffle stays inside live groups
-    for (uint64_t i = (static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x) / G; i < n; i += stride) {
+    const LaneGroup<G> grp;
+    const uint32_t j = grp.j, d = grp.d, sub = grp.sub;
+    for (uint64_t i = grp.first; i < n; i += grp.stride) {
         const Board in = load_board(boards, static_cast<uint32_t>(i));
-        const Board cells = PLAIN ? Board{{in.r[0] & kCellBits, in.r[1] & kCellBits, in.r[2] & kCellBits, in.r[3] & kCellBits}}
-                                  : record_cells(in);
+        const Board cells = input_cells<PLAIN>(in);
         Board after = cells;
         uint32_t gain;
         const bool legal = move_sel(after, tb.move_sel(d), gain);
@@ -1438,14 +1463,11 @@ __global__ void __launch_bounds__(kBlock) expectimax_kernel(const uint4 *__restr
         for (uint32_t o = K / 2u; o > 0u; o >>= 1)
             part += __shfl_xor(part, o);
         const int32_t value = legal ? static_cast<int32_t>(part / (10u * count_empty(after))) : -1;
-        uint32_t key = search_key(value, d), other = __shfl_xor(key, K);
-        key = other > key ? other : key;
-        other = __shfl_xor(key, 2u * K);
-        key = other > key ? other : key;
+        const uint32_t key = group_best_key(root_key<uint32_t>(value, d), K);
         if (sub == 0u && a.value)
             a.value[i * 4u + d] = value;
         if (j == 0u && a.action)
-            a.action[i] = static_cast<uint8_t>(search_key_action(key));
+            a.action[i] = static_cast<uint8_t>(root_key_action(key));
     }
 }
 
@@ -1467,13 +1489,11 @@ __global__ void __launch_bounds__(kBlock) mc_search_kernel(const uint4 *__restri
     constexpr uint32_t K = G / 4u;
     __shared__ WaveTables s_tables[kBlock / 64];
     const LdsTables tb = stage_tables(s_tables, load_tables_piece());
-    const uint32_t j = threadIdx.x % G, d = j / K, sub = j % K;
-    const uint32_t stride = gridDim.x * (kBlock / G);
-    // a group's G lanes hold the same i, so they leave the loop together and every shuffle stays inside live groups
-    for (uint64_t i = (static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x) / G; i < n; i += stride) {
+    const LaneGroup<G> grp;
+    const uint32_t j = grp.j, d = grp.d, sub = grp.sub;
+    for (uint64_t i = grp.first; i < n; i += grp.stride) {
         const Board in = load_board(boards, static_cast<uint32_t>(i));
-        const Board cells = PLAIN ? Board{{in.r[0] & kCellBits, in.r[1] & kCellBits, in.r[2] & kCellBits, in.r[3] & kCellBits}}
-                                  : record_cells(in);
+        const Board cells = input_cells<PLAIN>(in);
         Board after = cells;
         uint32_t g;
         const bool legal = move_sel(after, tb.move_sel(d), g);
@@ -1501,16 +1521,13 @@ __global__ void __launch_bounds__(kBlock) mc_search_kernel(const uint4 *__restri
             moved += __shfl_xor(moved, o);
         }
         const int64_t value = legal ? static_cast<int64_t>(total) : -1;
-        uint64_t key = mc_key(value, d), other = __shfl_xor(key, K);
-        key = other > key ? other : key;
-        other = __shfl_xor(key, 2u * K);
-        key = other > key ? other : key;
+        const uint64_t key = group_best_key(root_key<uint64_t>(value, d), K);
         if (sub == 0u && a.value)
             a.value[i * 4u + d] = value;
         if (sub == 0u && a.steps)
             a.steps[i * 4u + d] = legal ? static_cast<int64_t>(moved) : -1;
         if (j == 0u && a.action)
-            a.action[i] = static_cast<uint8_t>(mc_key_action(key));
+            a.action[i] = static_cast<uint8_t>(root_key_action(key));
     }
 }
 
@@ -1974,11 +1991,18 @@ static hipError_t dispatch(int v, F &&f)
         return v == FIRST ? f(std::integral_constant<int, FIRST>()) : dispatch<FIRST + 1, LAST>(v, f);
 }
 
+// f(std::bool_constant<B>()) for the runtime b = B
+template <class F>
+static hipError_t dispatch_bool(bool b, F &&f)
+{
+    return b ? f(std::true_type()) : f(std::false_type());
+}
+
 // f(act, std::bool_constant<FULL>()) for the template arguments <ACT, FULL> of the step kernels
 template <class F>
 static hipError_t dispatch_step(int action_dtype, bool full, F &&f)
 {
-    return dispatch<0, 3>(action_dtype, [&](auto act) { return full ? f(act, std::true_type()) : f(act, std::false_type()); });
+    return dispatch<0, 3>(action_dtype, [&](auto act) { return dispatch_bool(full, [&](auto full_c) { return f(act, full_c); }); });
 }
 
 hipError_t launch_reset(const StepArgs &a, uint32_t first_slot, const uint8_t *mask, hipStream_t s)
@@ -2069,33 +2093,37 @@ hipError_t launch_legal_mask(const uint4 *boards, uint32_t n, uint8_t *mask_out,
 
 hipError_t launch_afterstates(const uint4 *boards, uint32_t n, bool plain, const AfterstateOut &o, hipStream_t s)
 {
-    auto go = [&](auto plain_c) {
+    return dispatch_bool(plain, [&](auto plain_c) {
         if (o.obs)
             return launch_1d(afterstates_kernel<plain_c, true>, n, kAfterstateObsPad, s, boards, n, o);
         return launch_1d(afterstates_kernel<plain_c, false>, n, 0, s, boards, n, o);
-    };
-    return plain ? go(std::true_type()) : go(std::false_type());
+    });
+}
+
+// Lanes of a launch that gives each of n boards a group of G, up to the grid cap (the groups stride beyond it)
+static uint64_t group_lanes(uint32_t n, uint32_t G)
+{
+    const uint64_t want = static_cast<uint64_t>(n) * G;
+    return want < kSearchMaxLanes ? want : kSearchMaxLanes;
 }
 
 hipError_t launch_expectimax(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const SearchArgs &a, hipStream_t s)
 {
     return dispatch<1, 3>(static_cast<int>(depth), [&](auto dc) {
-        const uint64_t want = static_cast<uint64_t>(n) * (dc == 1 ? 4u : 64u), lanes = want < kSearchMaxLanes ? want : kSearchMaxLanes;
-        if (plain)
-            return launch_1d(expectimax_kernel<dc, true>, lanes, 0, s, boards, n, a);
-        return launch_1d(expectimax_kernel<dc, false>, lanes, 0, s, boards, n, a);
+        return dispatch_bool(plain, [&](auto plain_c) {
+            return launch_1d(expectimax_kernel<dc, plain_c>, group_lanes(n, dc == 1 ? 4u : 64u), 0, s, boards, n, a);
+        });
     });
 }
 
 hipError_t launch_mc_search(const uint4 *boards, uint32_t n, bool plain, const McArgs &a, hipStream_t s)
 {
-    auto go = [&](auto gc, auto plain_c) {
-        const uint64_t want = static_cast<uint64_t>(n) * gc, lanes = want < kSearchMaxLanes ? want : kSearchMaxLanes;
-        return launch_1d(mc_search_kernel<gc, plain_c>, lanes, 0, s, boards, n, a);
+    auto go = [&](auto gc) {
+        return dispatch_bool(plain, [&](auto plain_c) {
+            return launch_1d(mc_search_kernel<gc, plain_c>, group_lanes(n, gc), 0, s, boards, n, a);
+        });
     };
-    auto by_form = [&](auto gc) { return plain ? go(gc, std::true_type()) : go(gc, std::false_type()); };
-    return a.rollouts >= kMcWaveRollouts ? by_form(std::integral_constant<uint32_t, 64u>())
-                                         : by_form(std::integral_constant<uint32_t, 16u>());
+    return a.rollouts >= kMcWaveRollouts ? go(std::integral_constant<uint32_t, 64u>()) : go(std::integral_constant<uint32_t, 16u>());
 }
 
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s)

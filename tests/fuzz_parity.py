@@ -12,7 +12,7 @@ reward, max_tile, auto_reset; then 12-40 calls chosen among
   the read-only and board-only calls: legal_actions, query, move (trial, or committed: the afterstate is kept),
   afterstates (a random subset of outputs, a random observation dtype or none) and expectimax (depth 1, 2 at n <= 512),
   each against the oracle's row table (tests/move_lut.py), the plain form or the host build of the search
-  (tests/host_search)
+  (tests/host_check)
 and after every call the boards, scores, last returns, episode counts and the exact return sum (both statistics flavours)
     python tests/fuzz_parity.py [seconds=120] [seed=0]          (G2048_FUZZ_STREAMS=1: every case on its own non-default stream)"""
 import ctypes as C
@@ -30,13 +30,11 @@ import torch
 import __graft_entry__ as ge
 
 ge.build()
-import tempfile
-
+from analysis_helpers import host_search, load_host_lib
 from gym2048_amd import _lib
 from gym2048_amd.batched import Afterstates, Batched2048, afterstates, parse_stats
 from move_lut import build_row_lut, lut_afterstates, onehot_ref
 from oracle import OracleBatch, load as load_oracle
-from test_search_host import build_search_check, host_search
 
 rs = np.random.default_rng(0)
 DT = {0: torch.uint8, 1: torch.float16, 2: torch.float32}
@@ -51,7 +49,7 @@ def refs():
     """(row table, host search build), made on first use."""
     if not _refs:
         _refs["lut"] = build_row_lut(load_oracle())
-        _refs["search"] = build_search_check(tempfile.mkdtemp(prefix="fuzz_search_"))
+        _refs["search"] = load_host_lib()
     return _refs["lut"], _refs["search"]
 
 

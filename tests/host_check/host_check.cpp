@@ -1,7 +1,8 @@
 // host_check.cpp -- TEST HARNESS ONLY: compiles the device header g2048_device.h with g++
 // (-DG2048_HOST_CHECK) so that the exact byte-parallel arithmetic the gfx950 kernels run can be
 // unit-tested against the oracle in a container that has no GPU.  It mirrors the bodies of
-// step_kernel / reset_kernel (g2048_kernels.hip) one board at a time.  Not part of the product.
+// step_kernel / reset_kernel (g2048_kernels.hip) one board at a time; the last two sections do the same for the
+// expectimax and Monte-Carlo search.  Not part of the product.
 #define G2048_HOST_CHECK 1
 #include "../../gym-2048_amd/csrc/g2048_device.h"
 #include "../../gym-2048_amd/csrc/g2048_pcg64.h"
@@ -18,6 +19,11 @@ static Board load_board(const uint8_t *b)
     return bd;
 }
 static void store_board(uint8_t *b, const Board &bd) { std::memcpy(b, bd.r, 16); }
+static Board load_cells(const uint8_t *b) // exponents mod 32, as the plain kernels read them
+{
+    const Board bd = load_board(b);
+    return Board{{bd.r[0] & kCellBits, bd.r[1] & kCellBits, bd.r[2] & kCellBits, bd.r[3] & kCellBits}};
+}
 
 extern "C" {
 
@@ -332,6 +338,208 @@ void hostcheck_step_batch_numpy(g2048o_batch *s, g2048o_pcg64 *rng, uint64_t n, 
         store_board(s->boards + 16 * i, record_cells(rec));
         s->score[i] = (int32_t)record_score(rec);
     }
+}
+
+} // extern "C"
+
+// ---- expectimax search (g2048_expectimax): the search code of g2048_device.h, one board at a time on one thread.
+// tests/test_search_host.py compares it with the pure-Python reference (tests/search_ref.py), the GPU tests compare the
+// kernels with it, and tools/search_probe.py times it as the host baseline.
+namespace {
+
+SearchWeights weights(const int32_t w[4])
+{
+    return SearchWeights{(uint32_t)w[0], (uint32_t)w[1], (uint32_t)w[2], (uint32_t)w[3]};
+}
+
+template <int D> uint32_t root(const Board &b, const SearchWeights &w, int32_t value[4])
+{
+    return search_root<D>(b, w, HostTables(), value);
+}
+
+// the kernels' split: K lanes per direction, each summing its own chance items, then one sum and one divide
+template <int D> void root_split(const Board &b, const SearchWeights &w, uint32_t K, int32_t value[4])
+{
+    for (uint32_t m = 0; m < 4; ++m) {
+        Board a = b;
+        uint32_t gain;
+        if (!move_sel(a, HostTables().move_sel(m), gain)) {
+            value[m] = -1;
+            continue;
+        }
+        uint64_t sum = 0;
+        for (uint32_t sub = 0; sub < K; ++sub)
+            sum += chance_partial<D>(a, sub, K, w, HostTables());
+        value[m] = (int32_t)(sum / (10u * count_empty(a)));
+    }
+}
+
+// number of heuristic evaluations (leaves) of V_D(b), mirroring search_value / chance_partial
+template <int D> uint64_t leaves_value(const Board &b)
+{
+    if constexpr (D == 0) {
+        return 1;
+    } else {
+        uint64_t total = 0;
+        for (uint32_t m = 0; m < 4; ++m) {
+            Board a = b;
+            uint32_t gain;
+            if (move_sel(a, HostTables().move_sel(m), gain))
+                for (uint32_t e = empty_bits(a); e; e &= e - 1)
+                    for (uint32_t v = 1; v <= 2; ++v)
+                        total += leaves_value<D - 1>(place(a, g2048_ctz(e), v));
+        }
+        return total;
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+// total leaves of a depth-`depth` search over n boards (the root is V_depth without its max)
+uint64_t search_check_leaves(const uint8_t *boards, uint64_t n, uint32_t depth)
+{
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const Board b = load_cells(boards + 16 * i);
+        total += depth == 1 ? leaves_value<1>(b) : depth == 2 ? leaves_value<2>(b) : leaves_value<3>(b);
+    }
+    return total;
+}
+
+uint32_t search_check_heuristic(const uint8_t board[16], const int32_t w[4])
+{
+    return heuristic(load_cells(board), weights(w));
+}
+
+// action[n] and value[n][4] of g2048_expectimax_plain; returns 0, or -1 for a depth outside 1..3
+int search_check_boards(const uint8_t *boards, uint64_t n, uint32_t depth, const int32_t w[4], uint8_t *action,
+                        int32_t *value)
+{
+    if (depth < 1 || depth > 3)
+        return -1;
+    const SearchWeights sw = weights(w);
+    for (uint64_t i = 0; i < n; ++i) {
+        const Board b = load_cells(boards + 16 * i);
+        int32_t *v = value + 4 * i;
+        action[i] = (uint8_t)(depth == 1 ? root<1>(b, sw, v) : depth == 2 ? root<2>(b, sw, v) : root<3>(b, sw, v));
+    }
+    return 0;
+}
+
+// the root values through the kernels' lane split with K lanes per direction
+int search_check_split(const uint8_t *boards, uint64_t n, uint32_t depth, const int32_t w[4], uint32_t K, int32_t *value)
+{
+    if (depth < 1 || depth > 3 || K == 0)
+        return -1;
+    const SearchWeights sw = weights(w);
+    for (uint64_t i = 0; i < n; ++i) {
+        const Board b = load_cells(boards + 16 * i);
+        int32_t *v = value + 4 * i;
+        if (depth == 1)
+            root_split<1>(b, sw, K, v);
+        else if (depth == 2)
+            root_split<2>(b, sw, K, v);
+        else
+            root_split<3>(b, sw, K, v);
+    }
+    return 0;
+}
+
+} // extern "C"
+
+// ---- Monte-Carlo rollout search (g2048_mc_search), likewise.  tests/test_mc_host.py compares it with the pure-Python
+// reference (tests/mc_ref.py), the GPU tests compare the kernel with it, and tools/mc_probe.py's games run on it.
+namespace {
+
+bool any_legal(const Board &b)
+{
+    for (uint32_t d = 0; d < 4; ++d) {
+        Board a = b;
+        uint32_t g;
+        if (move_sel(a, HostTables().move_sel(d), g))
+            return true;
+    }
+    return false;
+}
+
+} // namespace
+
+extern "C" {
+
+// action[n], value[n][4], steps[n][4] of g2048_mc_search_plain; returns 0, or -1 for R or L outside their limits
+int mc_check_boards(const uint8_t *boards, uint64_t n, uint32_t index_offset, uint32_t rollouts, uint32_t max_steps, uint64_t seed,
+                    uint8_t *action, int64_t *value, int64_t *steps)
+{
+    if (rollouts < 1 || rollouts > kMcMaxRollouts || max_steps < 1 || max_steps > kMcMaxSteps)
+        return -1;
+    for (uint64_t i = 0; i < n; ++i)
+        action[i] = (uint8_t)mc_root(load_cells(boards + 16 * i), index_offset + (uint32_t)i, rollouts, max_steps, (uint32_t)seed,
+                                     (uint32_t)(seed >> 32), HostTables(), value + 4 * i, steps + 4 * i);
+    return 0;
+}
+
+// the root sums through the kernel's lane split: K lanes per direction, lane sub sums the playouts sub, sub + K, ...
+int mc_check_split(const uint8_t *boards, uint64_t n, uint32_t index_offset, uint32_t rollouts, uint32_t max_steps, uint64_t seed,
+                   uint32_t K, int64_t *value, int64_t *steps)
+{
+    if (rollouts < 1 || rollouts > kMcMaxRollouts || max_steps < 1 || max_steps > kMcMaxSteps || K == 0)
+        return -1;
+    for (uint64_t i = 0; i < n; ++i) {
+        const Board b = load_cells(boards + 16 * i);
+        for (uint32_t d = 0; d < 4; ++d) {
+            Board after = b;
+            uint32_t g;
+            value[4 * i + d] = steps[4 * i + d] = -1;
+            if (!move_sel(after, HostTables().move_sel(d), g))
+                continue;
+            uint64_t total = 0, st = 0;
+            for (uint32_t sub = K; sub-- > 0;) // the lanes in another order than mc_root's r = 0, 1, ...
+                mc_partial(after, g, index_offset + (uint32_t)i, d, sub, K, rollouts, (uint32_t)seed, (uint32_t)(seed >> 32), max_steps,
+                           HostTables(), total, st);
+            value[4 * i + d] = (int64_t)total;
+            steps[4 * i + d] = (int64_t)st;
+        }
+    }
+    return 0;
+}
+
+// Whole games on the CPU: game k starts from fresh_board and is played to its end by the Monte-Carlo player
+// (rollouts > 0; the search of move t is seeded seed + t + 1 and sees board index k) or, with rollouts == 0, by the
+// uniform random policy under the engine's rule that an illegal move ends the episode.  The game's own spawns and the
+// random policy's actions come from Philox blocks keyed by `seed` with counter word 3 = 0xffffffff.  scores[k] = the
+// summed merge scores, moves[k] = the moves played; illegal_picks counts searched moves that were illegal while a legal
+// one existed.  Returns that count.
+uint64_t mc_check_play(uint64_t n_games, uint64_t seed, uint32_t rollouts, uint32_t max_steps, int64_t *scores, int64_t *moves)
+{
+    const HostTables tb;
+    uint64_t illegal_picks = 0;
+    for (uint64_t k = 0; k < n_games; ++k) {
+        const Words w0 = philox4x32_10(0u, 0u, (uint32_t)k, 0xffffffffu, (uint32_t)seed, (uint32_t)(seed >> 32));
+        Board b = fresh_board(w0.w[0], w0.w[1]);
+        int64_t score = 0, t = 0;
+        while (any_legal(b)) {
+            const Words w = philox4x32_10((uint32_t)(t + 1), 0u, (uint32_t)k, 0xffffffffu, (uint32_t)seed, (uint32_t)(seed >> 32));
+            uint32_t action = w.w[3] >> 30;
+            if (rollouts > 0) {
+                int64_t value[4], steps[4];
+                const uint64_t s = seed + (uint64_t)t + 1u;
+                action = mc_root(b, (uint32_t)k, rollouts, max_steps, (uint32_t)s, (uint32_t)(s >> 32), tb, value, steps);
+            }
+            uint32_t g;
+            if (!move_sel(b, tb.move_sel(action), g)) {
+                illegal_picks += rollouts > 0;
+                break; // the engine's rule: an illegal move ends the episode
+            }
+            score += g;
+            ++t;
+            add_tile(b, w.w[0]);
+        }
+        scores[k] = score;
+        moves[k] = t;
+    }
+    return illegal_picks;
 }
 
 } // extern "C"

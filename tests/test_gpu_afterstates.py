@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
-from move_lut import build_row_lut, lut_afterstates
+from analysis_helpers import row_lut  # noqa: F401 (fixture)
+from move_lut import lut_afterstates
 
 DTYPES = ("uint8", "float16", "float32")
 
@@ -18,13 +19,6 @@ def stack_np(boards):
     b = np.asarray(boards)
     oh = (b[..., None, :] == np.arange(16, dtype=b.dtype)[:, None]).astype(np.uint8)
     return oh.reshape(b.shape[:-1] + (16, 4, 4))
-
-
-@pytest.fixture(scope="module")
-def row_lut(oracle_lib):
-    """shift() of every row of exponents 0..17 from the oracle's g2048o_shift, pinned against the reference's fixture
-    (tests/move_lut.py)."""
-    return build_row_lut(oracle_lib)
 
 
 def test_numpy_checkers_pinned(row_lut):

@@ -6,8 +6,8 @@ and every row equals the reference of its base row.  Each test frees what it all
 import numpy as np
 import pytest
 
-from move_lut import build_row_lut, lut_afterstates, onehot_ref
-from test_search_host import build_search_check, host_search, trajectory_boards
+from analysis_helpers import assert_rows_periodic, host_search, hs, row_lut, tiled, trajectory_boards  # noqa: F401 (hs, row_lut: fixtures)
+from move_lut import lut_afterstates, onehot_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -17,19 +17,9 @@ M = 4099  # odd period: rows one power of two apart are different boards
 
 
 @pytest.fixture(scope="module")
-def hs(tmp_path_factory):
-    return build_search_check(tmp_path_factory.mktemp("search_check_large"))
-
-
-@pytest.fixture(scope="module")
 def g_mod(torch_cuda):
     import gym2048_amd
     return gym2048_amd
-
-
-@pytest.fixture(scope="module")
-def row_lut(oracle_lib):
-    return build_row_lut(oracle_lib)
 
 
 @pytest.fixture(scope="module")
@@ -47,28 +37,9 @@ def torch(torch_cuda):
     torch_cuda.cuda.empty_cache()          # the next test allocates its own 4 GiB+
 
 
-def tiled(torch, base, n):
-    """uint8 [n, 16] on the device: row i = base[i % m]."""
-    b = torch.as_tensor(np.ascontiguousarray(base)).cuda()
-    return b.repeat(-(-n // len(b)), 1)[:n]
-
-
 def windows(n, line_row):
     """Row windows: the first rows, the rows across byte 2^32 of an output of 2^32 / line_row bytes per row, the last."""
     return [(0, WIN), (line_row - WIN // 2, line_row + WIN // 2), (n - WIN, n)]
-
-
-def assert_rows_periodic(torch, got, want, chunk):
-    """got[i] == want[i % m] for every row i, compared on the device ``chunk`` rows at a time."""
-    m, n = len(want), len(got)
-    for k in range(0, n, chunk):
-        g = got[k:k + chunk]
-        idx = torch.arange(k, k + len(g), device=got.device) % m
-        eq = (g == want[idx]).reshape(len(g), -1).all(1)
-        if not bool(eq.all()):
-            i = k + int((~eq).nonzero()[0, 0])
-            raise AssertionError(f"row {i} (base row {i % m}) differs: {got[i].flatten()[:16].tolist()} vs "
-                                 f"{want[i % m].flatten()[:16].tolist()}")
 
 
 def test_expectimax_values_past_4_gib(g_mod, torch, hs, base):

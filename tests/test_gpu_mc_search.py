@@ -6,24 +6,10 @@ Figures measured on the MI355X: profiles/r09_mc_probe.txt and the strength test'
 import numpy as np
 import pytest
 
-from test_mc_host import SEED, build_mc_check, host_mc, legal_count
-from test_search_host import high_boards, random_boards, trajectory_boards
+from analysis_helpers import (ONE_LEGAL, SEARCH_MAX_LANES, SEED, TERMINAL, WAVE_ROLLOUTS, g, high_boards, hm, host_mc,  # noqa: F401
+                              legal_count, mixed_boards, play, random_boards, random_policy)  # (g, hm: fixtures)
 
 pytestmark = pytest.mark.gpu
-
-SEARCH_MAX_LANES = 1 << 24  # kSearchMaxLanes (g2048_kernels.hip): the grid cap past which mc_search_kernel strides
-WAVE_ROLLOUTS = 32          # kMcWaveRollouts: R >= this runs 64 lanes per board (16 per direction), below it 16 (4)
-
-
-@pytest.fixture(scope="module")
-def hm(tmp_path_factory):
-    return build_mc_check(tmp_path_factory.mktemp("mc_check_gpu"))
-
-
-@pytest.fixture(scope="module")
-def g(torch_cuda):
-    import gym2048_amd
-    return gym2048_amd
 
 
 def to_np(s):
@@ -40,13 +26,6 @@ def assert_same(dev, host, where=""):
     bad = np.nonzero((dev[0] != host[0]) | (dev[1] != host[1]).any(1) | (dev[2] != host[2]).any(1))[0]
     assert len(bad) == 0, f"{where}: {len(bad)} boards differ, first index {bad[0]}: {[x[bad[0]].tolist() for x in dev]} vs " \
                           f"{[x[bad[0]].tolist() for x in host]}"
-
-
-def mixed_boards(n, seed):
-    boards = random_boards(n, seed)
-    traj = trajectory_boards(every=3)
-    boards[::2] = traj[np.random.default_rng(seed).integers(0, len(traj), len(boards[::2]))]
-    return boards
 
 
 # R below, equal to and above the lanes per direction of the 16-lane form (4); 31 / 32 straddle the switch to the
@@ -72,7 +51,6 @@ def test_high_boards_and_hand_cases(g, torch_cuda, hm):
         host = host_mc(hm, boards, R, L)
         assert host[1].max() >= 1 << 32
         assert_same(device_mc(g, torch_cuda, boards, R, L), host, (R, L))
-    from test_mc_host import ONE_LEGAL, TERMINAL
     hand = np.concatenate([ONE_LEGAL, TERMINAL, ONE_LEGAL, TERMINAL, random_boards(60, 41)])
     assert legal_count(hand[:2]).tolist() == [1, 0]
     for R in (3, 64):
@@ -267,43 +245,15 @@ def test_grid_stride_passes(g, torch_cuda, hm, R, G):
         eng.close()
 
 
-def play(g, torch, n, seed, policy, cap=5000):
-    """Final score of every board's first game (numpy-RNG mode), and whether any searched move was illegal: the loop of
-    tests/test_gpu_search.py with the Monte-Carlo player (R = 64, playouts to the end, a seed per step) as the search."""
-    from gym2048_amd.transitions import mc_step_seed
-    eng = g.Batched2048(n, seed=seed, rng="numpy")
-    gen = torch.Generator(device="cuda").manual_seed(seed)
-    first = torch.full((n,), -1, dtype=torch.int64, device="cuda")
-    illegal = False
-    try:
-        eng.reset()
-        for t in range(cap):
-            if policy == "search":
-                a = eng.mc_search(64, seed=mc_step_seed(seed, t)).action
-            else:
-                a = torch.randint(0, 4, (n,), generator=gen, device="cuda", dtype=torch.uint8)
-            eng.step(a)
-            live = first < 0
-            if policy == "search":
-                illegal |= bool((eng.illegal.bool() & live).any())
-            ended = eng.terminated.bool() & live
-            if bool(ended.any()):
-                first[ended] = eng.last_scores().to(torch.int64)[ended]
-            if not bool((first < 0).any()):
-                break
-        return first.cpu().numpy(), illegal
-    finally:
-        eng.close()
-
-
 def test_mc_plays_well(g, torch_cuda):
     """512 games to the end: never an illegal move while a legal one exists, and a mean final score of at least 10 x the
     random policy's (the bar of test_depth1_plays_well).  On the CPU the definition itself (host build, R = 16, 24 games)
     scores a mean of 16 402 against the random policy's 47.5 (tests/test_mc_host.py); on the MI355X this test measured
     30 550 against 66.4 (profiles/r09_mc_probe.txt)."""
-    n, seed = 512, 2048
-    searched, illegal = play(g, torch_cuda, n, seed, "search")
-    rand, _ = play(g, torch_cuda, n, seed, "random")
+    from gym2048_amd.transitions import mc_step_seed
+    n, seed = 512, 2048   # the Monte-Carlo player: R = 64, playouts to the end, a seed per step
+    searched, illegal, *_ = play(g, torch_cuda, n, seed, lambda eng, t: eng.mc_search(64, seed=mc_step_seed(seed, t)).action)
+    rand, *_ = play(g, torch_cuda, n, seed, random_policy(torch_cuda, n, seed))
     print(f"mc R=64 mean final score {searched.mean():.1f}, random {rand.mean():.1f}")
     assert not illegal, "the search picked an illegal move while a legal one existed"
     assert (searched >= 0).all() and (rand >= 0).all(), "a game outlived the 5 000-move cap"

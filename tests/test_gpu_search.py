@@ -4,24 +4,13 @@ import numpy as np
 import pytest
 
 import search_ref as ref
-from move_lut import build_row_lut, lut_afterstates, onehot_ref
-from test_search_host import afterstate_empties, build_search_check, high_boards, host_search, random_boards, trajectory_boards
+from analysis_helpers import (SEARCH_MAX_LANES, afterstate_empties, assert_rows_periodic, g, high_boards, host_search, hs,  # noqa: F401
+                              mid_game, play, random_boards, random_policy, row_lut, tiled, trajectory_boards)  # (g, hs, row_lut: fixtures)
+from move_lut import lut_afterstates, onehot_ref
 
 pytestmark = pytest.mark.gpu
 
 ODD_W = (12345, 7, 65535, 3)
-SEARCH_MAX_LANES = 1 << 24  # kSearchMaxLanes (g2048_kernels.hip): the grid cap past which expectimax_kernel strides
-
-
-@pytest.fixture(scope="module")
-def hs(tmp_path_factory):
-    return build_search_check(tmp_path_factory.mktemp("search_check_gpu"))
-
-
-@pytest.fixture(scope="module")
-def g(torch_cuda):
-    import gym2048_amd
-    return gym2048_amd
 
 
 def device_search(g, torch, boards, depth, w=None):
@@ -109,37 +98,10 @@ def test_out_reuse_and_stream_order(g, torch_cuda):
     assert torch.equal(only.value, g.expectimax(boards, 2).value)
 
 
-def play(g, torch, n, seed, policy, cap=5000):
-    """Final score of every board's first game (numpy-RNG mode), and whether any searched move was illegal."""
-    eng = g.Batched2048(n, seed=seed, rng="numpy")
-    gen = torch.Generator(device="cuda").manual_seed(seed)
-    first = torch.full((n,), -1, dtype=torch.int64, device="cuda")
-    illegal = False
-    try:
-        eng.reset()
-        for _ in range(cap):
-            if policy == "search":
-                a = eng.expectimax(1).action
-            else:
-                a = torch.randint(0, 4, (n,), generator=gen, device="cuda", dtype=torch.uint8)
-            eng.step(a)
-            live = first < 0
-            if policy == "search":
-                illegal |= bool((eng.illegal.bool() & live).any())
-            ended = eng.terminated.bool() & live
-            if bool(ended.any()):
-                first[ended] = eng.last_scores().to(torch.int64)[ended]
-            if not bool((first < 0).any()):
-                break
-        return first.cpu().numpy(), illegal
-    finally:
-        eng.close()
-
-
 def test_depth1_plays_well(g, torch_cuda):
     n, seed = 512, 2048
-    searched, illegal = play(g, torch_cuda, n, seed, "search")
-    rand, _ = play(g, torch_cuda, n, seed, "random")
+    searched, illegal, *_ = play(g, torch_cuda, n, seed, lambda eng, t: eng.expectimax(1).action)
+    rand, *_ = play(g, torch_cuda, n, seed, random_policy(torch_cuda, n, seed))
     assert not illegal, "the search picked an illegal move while a legal one existed"
     assert (searched >= 0).all() and (rand >= 0).all(), "a game outlived the 5 000-move cap"
     assert searched.mean() >= 10 * rand.mean(), (searched.mean(), rand.mean())
@@ -174,32 +136,6 @@ def test_record_search(g, torch_cuda, tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------- edges of the kernels
-def mid_game(m, seed, max_empty=16):
-    """m distinct boards of the golden trajectories with at most ``max_empty`` empty cells."""
-    traj = trajectory_boards()
-    traj = traj[(traj == 0).sum(1) <= max_empty]
-    return traj[np.random.default_rng(seed).choice(len(traj), m, replace=False)]
-
-
-def periodic(torch, base, n):
-    """uint8 [n, 16] on the device: board i = base[i % m]."""
-    b = torch.as_tensor(np.ascontiguousarray(base, dtype=np.uint8)).cuda()
-    return b.repeat(-(-n // len(b)), 1)[:n]
-
-
-def assert_periodic(torch, s, host, n, chunk=1 << 20):
-    """Every row i of the Search ``s`` equals the host result of base[i % m], compared on the device chunk by chunk."""
-    ha, hv = (torch.as_tensor(np.ascontiguousarray(x)).cuda() for x in host)
-    m = len(ha)
-    for k in range(0, n, chunk):
-        idx = torch.arange(k, min(n, k + chunk), device="cuda") % m
-        bad = (s.action[k:k + chunk] != ha[idx]) | (s.value[k:k + chunk] != hv[idx]).any(1)
-        if bool(bad.any()):
-            i = k + int(bad.nonzero()[0, 0])
-            raise AssertionError(f"board {i} (base row {i % m}) differs: {s.action[i].item()} {s.value[i].tolist()} vs "
-                                 f"{host[0][i % m]} {host[1][i % m].tolist()}")
-
-
 GRID_STRIDE = {1: ((1 << 22) + 4133, 4099), 2: ((1 << 18) + 4133, 4099), 3: ((1 << 18) + 37, 257)}  # depth: (n, period m)
 
 
@@ -217,18 +153,21 @@ def test_grid_stride_passes(g, torch_cuda, hs, depth):
     else:
         base = mid_game(m, 80 + depth, 16 if depth == 2 else 6)
     assert len(np.unique(base, axis=0)) == m and m % 2 == 1
-    boards = periodic(torch, base, n)
+    boards = tiled(torch, base, n)
     eng = g.Batched2048(n)
     try:
         eng.set_boards(boards)
         for w in (None, ODD_W) if depth == 1 else (None,):
             host = host_search(hs, base, depth, ref.DEFAULT_WEIGHTS if w is None else w)
+            host_dev = [torch.as_tensor(x).cuda() for x in host]
             r = np.arange(m)   # a kernel that read or wrote board i +- stride instead of i would not go unnoticed
             assert (host[1] != host[1][(r + stride) % m]).any(1).mean() > 0.5
             for form in ("plain", "engine"):
                 s = g.expectimax(boards, depth, w) if form == "plain" else eng.expectimax(depth, w)
                 torch.cuda.synchronize()
-                assert_periodic(torch, s, host, n)
+                assert len(s.action) == len(s.value) == n
+                assert_rows_periodic(torch, s.action, host_dev[0], 1 << 20)
+                assert_rows_periodic(torch, s.value, host_dev[1], 1 << 20)
                 del s
     finally:
         eng.close()
@@ -253,11 +192,6 @@ def test_wide_sums(g, torch_cuda, hs, depth, n):
         assert_same((s.action.cpu().numpy(), s.value.cpu().numpy()), host)
     finally:
         eng.close()
-
-
-@pytest.fixture(scope="module")
-def row_lut(oracle_lib):
-    return build_row_lut(oracle_lib)
 
 
 def test_engine_forms_with_full_score_deficits(g, torch_cuda, hs, row_lut):

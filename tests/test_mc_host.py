@@ -1,57 +1,14 @@
 """CPU: the Monte-Carlo rollout search of g2048_device.h -- the header the kernel is compiled from -- built for the host
-(tests/host_mc/mc_check.cpp, g++) and compared bit for bit with the pure-Python reference tests/mc_ref.py.  Every test
+(tests/host_check/host_check.cpp, g++) and compared bit for bit with the pure-Python reference tests/mc_ref.py.  Every test
 shows from the reference's own trace (never from the code under test) that its inputs reach the edge it is about."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import mc_ref as ref
-from conftest import ROOT
+from analysis_helpers import (ONE_LEGAL, SEED, TERMINAL, high_boards, hm, host_mc, legal_count,  # noqa: F401 (hm: fixture)
+                              random_boards, trajectory_boards)
+from analysis_helpers import host_mc_split as host_split
 from move_lut import build_row_lut
-from test_search_host import high_boards, random_boards, trajectory_boards
-
-SRC = os.path.join(ROOT, "tests", "host_mc", "mc_check.cpp")
-SEED = 0x0123456789ABCDEF
-
-
-def build_mc_check(out_dir):
-    so = os.path.join(str(out_dir), "libmc_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", so, SRC])
-    lib = C.CDLL(so)
-    lib.mc_check_boards.restype = C.c_int
-    lib.mc_check_boards.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
-                                    C.c_void_p]
-    lib.mc_check_split.restype = C.c_int
-    lib.mc_check_split.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p,
-                                   C.c_void_p]
-    lib.mc_check_play.restype = C.c_uint64
-    lib.mc_check_play.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    return lib
-
-
-@pytest.fixture(scope="module")
-def hm(tmp_path_factory):
-    return build_mc_check(tmp_path_factory.mktemp("mc_check"))
-
-
-def host_mc(lib, boards, R, L, seed=SEED, index_offset=0):
-    b = np.ascontiguousarray(np.asarray(boards, np.uint8).reshape(-1, 16))
-    act = np.zeros(len(b), np.uint8)
-    val = np.zeros((len(b), 4), np.int64)
-    stp = np.zeros((len(b), 4), np.int64)
-    assert lib.mc_check_boards(b.ctypes.data, len(b), index_offset, R, L, seed, act.ctypes.data, val.ctypes.data, stp.ctypes.data) == 0
-    return act, val, stp
-
-
-def host_split(lib, boards, R, L, K, seed=SEED, index_offset=0):
-    b = np.ascontiguousarray(np.asarray(boards, np.uint8).reshape(-1, 16))
-    val = np.zeros((len(b), 4), np.int64)
-    stp = np.zeros((len(b), 4), np.int64)
-    assert lib.mc_check_split(b.ctypes.data, len(b), index_offset, R, L, seed, K, val.ctypes.data, stp.ctypes.data) == 0
-    return val, stp
 
 
 def check(lib, boards, R, L, seed=SEED, index_offset=0):
@@ -63,14 +20,6 @@ def check(lib, boards, R, L, seed=SEED, index_offset=0):
     assert len(bad) == 0, f"{len(bad)} boards differ, first {np.asarray(boards)[bad[0]].tolist()}: " \
                           f"{[x[bad[0]].tolist() for x in got]} vs {[x[bad[0]].tolist() for x in want]}"
     return got, stats
-
-
-def legal_count(boards):
-    return np.array([sum(ref.move(tuple(int(x) % 32 for x in b), d)[2] for d in range(4)) for b in np.asarray(boards).reshape(-1, 16)])
-
-
-ONE_LEGAL = np.array([[1, 2, 3, 4, 2, 3, 4, 5, 3, 4, 5, 6, 0, 0, 0, 0]], np.uint8)    # only "down" moves a tile
-TERMINAL = np.array([[1, 2, 1, 2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 2, 1]], np.uint8)
 
 
 def test_shift_row_is_the_row_table(oracle_lib):

@@ -1,93 +1,11 @@
 """CPU: the expectimax code of g2048_device.h -- the header the search kernels are compiled from -- built for the host
-(tests/host_search/search_check.cpp, g++) and compared bit for bit with the pure-Python reference tests/search_ref.py."""
-import ctypes as C
-import os
-import subprocess
-
+(tests/host_check/host_check.cpp, g++) and compared bit for bit with the pure-Python reference tests/search_ref.py."""
 import numpy as np
 import pytest
 
 import search_ref as ref
-from conftest import ROOT, TRAJECTORIES, load_golden
-
-SRC = os.path.join(ROOT, "tests", "host_search", "search_check.cpp")
-I32x4 = C.c_int32 * 4
-
-
-def build_search_check(out_dir):
-    so = os.path.join(str(out_dir), "libsearch_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", so, SRC])
-    lib = C.CDLL(so)
-    lib.search_check_heuristic.restype = C.c_uint32
-    lib.search_check_heuristic.argtypes = [C.c_void_p, I32x4]
-    lib.search_check_boards.restype = C.c_int
-    lib.search_check_boards.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, I32x4, C.c_void_p, C.c_void_p]
-    lib.search_check_split.restype = C.c_int
-    lib.search_check_split.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, I32x4, C.c_uint32, C.c_void_p]
-    return lib
-
-
-@pytest.fixture(scope="module")
-def hs(tmp_path_factory):
-    return build_search_check(tmp_path_factory.mktemp("search_check"))
-
-
-def host_search(lib, boards, depth, w=ref.DEFAULT_WEIGHTS):
-    b = np.ascontiguousarray(np.asarray(boards, np.uint8).reshape(-1, 16))
-    act = np.zeros(len(b), np.uint8)
-    val = np.zeros((len(b), 4), np.int32)
-    assert lib.search_check_boards(b.ctypes.data, len(b), depth, I32x4(*w), act.ctypes.data, val.ctypes.data) == 0
-    return act, val
-
-
-def host_split(lib, boards, depth, K, w=ref.DEFAULT_WEIGHTS):
-    b = np.ascontiguousarray(np.asarray(boards, np.uint8).reshape(-1, 16))
-    val = np.zeros((len(b), 4), np.int32)
-    assert lib.search_check_split(b.ctypes.data, len(b), depth, I32x4(*w), K, val.ctypes.data) == 0
-    return val
-
-
-def random_boards(n, seed, max_exp=17):
-    """Exponents 0..max_exp at densities from nearly empty to full."""
-    rng = np.random.default_rng(seed)
-    density = rng.uniform(0.05, 1.0, size=(n, 1))
-    b = rng.integers(1, max_exp + 1, size=(n, 16))
-    return np.where(rng.random((n, 16)) < density, b, 0).astype(np.uint8)
-
-
-def high_boards(n, seed, empties, lo=26, hi=31, full_rows=0):
-    """Exponents lo..hi with ``empties`` = (fewest, most) empty cells, a horizontal pair of ``hi`` (a merge makes hi + 1)
-    and a vertical pair of a random exponent in every board; the first ``full_rows`` rows are all ``hi`` (merged twice:
-    hi + 2; two such rows, merged a third time: hi + 3)."""
-    rng = np.random.default_rng(seed)
-    b = rng.integers(lo, hi + 1, size=(n, 16)).astype(np.uint8)
-    for x in b:
-        r, c = rng.integers(full_rows, 4), rng.integers(0, 3)
-        keep = list(range(4 * full_rows)) + [4 * r + c, 4 * r + c + 1]
-        x[keep] = hi
-        r2, c2 = rng.integers(0, 3), rng.integers(0, 4)
-        while 4 * r2 + c2 in keep or 4 * r2 + c2 + 4 in keep:
-            r2, c2 = rng.integers(0, 3), rng.integers(0, 4)
-        x[[4 * r2 + c2, 4 * r2 + c2 + 4]] = rng.integers(lo, hi + 1)
-        keep = set(keep) | {4 * r2 + c2, 4 * r2 + c2 + 4}
-        free = [k for k in range(16) if k not in keep]
-        x[rng.choice(free, int(rng.integers(empties[0], empties[1] + 1)), replace=False)] = 0
-    return b
-
-
-def afterstate_empties(boards):
-    """int [n, 4]: empty cells of move(b, d) by the Python reference, 0 where d is illegal."""
-    out = np.zeros((len(boards), 4), np.int64)
-    for i, b in enumerate(np.asarray(boards).reshape(-1, 16)):
-        for d in range(4):
-            a, legal = ref.move(tuple(int(x) % 32 for x in b), d)
-            out[i, d] = sum(1 for x in a if x == 0) if legal else 0
-    return out
-
-
-def trajectory_boards(every=1):
-    out = [load_golden(t)["boards"].reshape(-1, 16)[::every] for t in TRAJECTORIES]
-    return np.unique(np.concatenate(out), axis=0)
+from analysis_helpers import (I32x4, afterstate_empties, high_boards, host_search, host_split, hs,  # noqa: F401 (hs: fixture)
+                              random_boards, trajectory_boards)
 
 
 def check(lib, boards, depth, w=ref.DEFAULT_WEIGHTS):

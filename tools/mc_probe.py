@@ -20,7 +20,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]  # tests/analysis_helpers.py: play(), random_policy()
 
 COST = [(1 << 12, 64, 65535), (1 << 12, 16, 65535), (1 << 16, 64, 65535), (1 << 16, 16, 65535), (1 << 16, 64, 32),
         (1 << 16, 16, 32), (1 << 16, 256, 65535), (1 << 20, 16, 32)]
@@ -74,29 +74,6 @@ def rollout_random_rate(g, torch):
         eng.close()
 
 
-def play(g, torch, n, seed, choose, cap=20000):
-    """(final scores of every board's first game, moves played by all boards, seconds)."""
-    eng = g.Batched2048(n, seed=seed, rng="numpy")
-    first = torch.full((n,), -1, dtype=torch.int64, device="cuda")
-    moves = 0
-    try:
-        eng.reset()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for t in range(cap):
-            eng.step(choose(eng, t))
-            ended = eng.terminated.bool() & (first < 0)
-            moves += int((first < 0).sum())
-            if bool(ended.any()):
-                first[ended] = eng.last_scores().to(torch.int64)[ended]
-            if not bool((first < 0).any()):
-                break
-        torch.cuda.synchronize()
-        return first.cpu().numpy(), moves, time.perf_counter() - t0
-    finally:
-        eng.close()
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -106,6 +83,7 @@ def main():
     import __graft_entry__ as ge
     ge.build()
     import gym2048_amd as g
+    from analysis_helpers import play, random_policy
     from gym2048_amd.transitions import mc_step_seed
 
     boards_all = midgame_boards(g, torch, 1 << 20)
@@ -128,12 +106,11 @@ def main():
         return
     print(f"\n{GAMES} games to the end (numpy-RNG engine, seed 2048)")
     print("player            mean score   median      max  mean moves  us/move (whole batch)  us/move/board")
-    gen = torch.Generator(device="cuda").manual_seed(2048)
-    players = [("random", lambda e, t: torch.randint(0, 4, (GAMES,), generator=gen, device="cuda", dtype=torch.uint8))]
+    players = [("random", random_policy(torch, GAMES, 2048))]
     players += [(f"expectimax d={d}", lambda e, t, d=d: e.expectimax(d).action) for d in (1, 2, 3)]
     players += [(f"mc R={R}", lambda e, t, R=R: e.mc_search(R, seed=mc_step_seed(2048, t)).action) for R in STRENGTH_R]
     for name, choose in players:
-        score, moves, secs = play(g, torch, GAMES, 2048, choose)
+        score, _, moves, secs = play(g, torch, GAMES, 2048, choose, cap=20000)
         import numpy as np
         done = score >= 0
         print(f"{name:16s} {score[done].mean():11.1f} {np.median(score[done]):8.0f} {score[done].max():8d} {moves / GAMES:11.1f} "

@@ -5,7 +5,7 @@ for n in {2^12, 2^16, 2^20} (depth 3 up to 2^16), on two board sets:
   random    boards of a uniform random-policy rollout (auto-reset; early-game boards with many empty cells).
 
 A leaf is one heuristic evaluation.  Leaves per board are counted exactly on the host over a 1 024-board sample of each
-set and scaled to n.  The host baseline is the same header (tests/host_search/search_check.cpp, g++ -O2) on one
+set and scaled to n.  The host baseline is the same header (tests/host_check/host_check.cpp, g++ -O2) on one
 thread over a sample, scaled to n; the ratio column is host time / kernel time.
 
   python tools/search_probe.py            # full table
@@ -16,32 +16,17 @@ from __future__ import annotations
 import argparse
 import ctypes as C
 import os
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]  # tests/analysis_helpers.py: the host build of the search
 
 SIZES = (1 << 12, 1 << 16, 1 << 20)
 HOST_SAMPLE = {1: 4096, 2: 256, 3: 8}  # boards timed on the host per depth
 LEAF_SAMPLE = 1024
-
-
-def host_lib():
-    out = tempfile.mkdtemp(prefix="search_probe_")
-    so = os.path.join(out, "libsearch_check.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", so,
-                           os.path.join(ROOT, "tests", "host_search", "search_check.cpp")])
-    lib = C.CDLL(so)
-    lib.search_check_boards.restype = C.c_int
-    lib.search_check_boards.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32 * 4, C.c_void_p, C.c_void_p]
-    lib.search_check_leaves.restype = C.c_uint64
-    lib.search_check_leaves.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32]
-    return lib
 
 
 def midgame_boards(g, torch, n_max):
@@ -100,7 +85,8 @@ def main():
     ge.build()
     import gym2048_amd as g
 
-    host = None if args.quick else host_lib()
+    from analysis_helpers import load_host_lib
+    host = None if args.quick else load_host_lib()
     sets = {"mid-game": midgame_boards(g, torch, SIZES[-1]), "random": random_boards(g, torch, SIZES[-1])}
     torch.cuda.synchronize()
     print(f"device: {torch.cuda.get_device_name(0)}; weights: defaults {tuple(g.SearchWeights())}")
