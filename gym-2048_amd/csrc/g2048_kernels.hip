@@ -126,41 +126,36 @@ __device__ __forceinline__ LdsTables stage_tables(WaveTables *all, uint2 piece)
     return LdsTables{all + (threadIdx.x >> 6)};
 }
 
-template <int ACT>
-__device__ __forceinline__ uint32_t load_action(const void *actions, uint32_t i, uint32_t w3)
+// One lane of a one-board-per-lane launch.  Lanes past the end stay active (whole wavefronts for the ballots and the
+// DPP sums): they recompute board n - 1 and write nothing.
+// FULL: the batch is a whole number of blocks, no lane is past the end -- `valid` is a compile-time true.
+struct Lane { uint32_t i_raw, i; bool valid; }; // blockIdx.x * BLOCK + threadIdx.x; the board worked on; i_raw < n
+template <uint32_t BLOCK, bool FULL> __device__ __forceinline__ Lane lane_of(uint32_t n)
 {
-    if constexpr (ACT == 0)
-        return w3 >> 30;
-    else if constexpr (ACT == 1)
-        return __builtin_nontemporal_load(static_cast<const uint8_t *>(actions) + i) & 3u;
-    else if constexpr (ACT == 2)
-        return static_cast<uint32_t>(__builtin_nontemporal_load(static_cast<const int32_t *>(actions) + i)) & 3u;
-    else
-        return static_cast<uint32_t>(__builtin_nontemporal_load(static_cast<const long long *>(actions) + i)) & 3u;
+    const uint32_t i_raw = blockIdx.x * BLOCK + threadIdx.x;
+    const bool valid = FULL || i_raw < n;
+    return Lane{i_raw, valid ? i_raw : n - 1u, valid};
 }
 
-// Strict actions (g2048_set_strict_actions; game2048_env.py:49 declares Discrete(4), :210-212 happens to play 4 as "down" and
-// -1 as "right"): the same load, and whether the RAW value lies outside 0..3.  The move always uses the low two bits.
+// ---- actions.  ACT: 0 = the synthetic policy (no buffer: the top two bits of the step's Philox word 3), 1 / 2 / 3 = a
+// buffer of uint8 / int32 / int64.  A loaded action keeps its memory type until it is consumed: the fused rollout holds
+// its actions in flight for kPrefetch steps, and a conversion next to the load would be a use of its result (the wait
+// would land there instead of kPrefetch steps later).
+template <int ACT> struct RawAction { typedef uint32_t type; };
+template <> struct RawAction<1> { typedef uint8_t type; };
+template <> struct RawAction<2> { typedef int32_t type; };
+template <> struct RawAction<3> { typedef long long type; };
 template <int ACT>
-__device__ __forceinline__ uint32_t load_action_checked(const void *actions, uint32_t i, bool &bad, uint32_t &raw_low)
+__device__ __forceinline__ typename RawAction<ACT>::type load_action_at(const void *__restrict__ actions, size_t idx)
 {
-    if constexpr (ACT == 1) {
-        const uint32_t v = __builtin_nontemporal_load(static_cast<const uint8_t *>(actions) + i);
-        bad = v > 3u;
-        raw_low = v;
-        return v & 3u;
-    } else if constexpr (ACT == 2) {
-        const uint32_t v = static_cast<uint32_t>(__builtin_nontemporal_load(static_cast<const int32_t *>(actions) + i));
-        bad = v > 3u;
-        raw_low = v;
-        return v & 3u;
-    } else {
-        const unsigned long long v = static_cast<unsigned long long>(__builtin_nontemporal_load(static_cast<const long long *>(actions) + i));
-        bad = v > 3ull;
-        raw_low = static_cast<uint32_t>(v);
-        return static_cast<uint32_t>(v) & 3u;
-    }
+    if constexpr (ACT == 0)
+        return 0u;
+    else
+        return __builtin_nontemporal_load(static_cast<const typename RawAction<ACT>::type *>(actions) + idx);
 }
+
+// the move always uses the low two bits
+template <class Raw> __device__ __forceinline__ uint32_t action_bits(Raw raw) { return static_cast<uint32_t>(raw) & 3u; }
 
 // One lane of the wavefront (the first offender) publishes {bit 63, low byte of the action, global board index} to the
 // engine's pinned error word; the host finds it at the entry of its next call on the engine.  Whole wavefronts call this.
@@ -173,6 +168,26 @@ __device__ __forceinline__ void report_bad_action(unsigned long long *action_err
         __hip_atomic_store(action_err, (1ull << 63) | (static_cast<unsigned long long>(raw_low & 0xffu) << 32) | global_index,
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+
+// Strict actions (g2048_set_strict_actions; game2048_env.py:49 declares Discrete(4), :210-212 happens to play 4 as "down" and
+// -1 as "right"): whether an action lay outside 0..3 as the RAW value of its type, and its low bits for the report.
+struct BadAction {
+    bool bad = false; uint32_t raw = 0;
+    template <class Raw> __device__ __forceinline__ static bool outside(Raw v) // THE definition (one inline copy: rollout_fused_numpy_kernel)
+    {
+        typedef typename std::make_unsigned<Raw>::type U;
+        return static_cast<U>(v) > static_cast<U>(3);
+    }
+    // ONE-SHOT, the lane's only action of a per-step launch: OVERWRITES an earlier finding (a loop over k actions needs a
+    // select per action: rollout_fused_kernel).  Returns the move.  Widened first: the value is consumed at once.
+    template <class Raw> __device__ __forceinline__ uint32_t note_only(Raw v)
+    {
+        const auto w = static_cast<typename std::conditional<(sizeof(Raw) > 4), unsigned long long, uint32_t>::type>(v);
+        bad = outside(w);
+        raw = static_cast<uint32_t>(w);
+        return action_bits(w);
+    }
+};
 
 // Episode bookkeeping, shared by every step kernel.  A lane whose episode ended stores the record it
 // ended on (sparse 16-byte store; plain, not nt: L2 merges these into lines) and, if asked, the plain
@@ -501,15 +516,19 @@ struct StepTail {
     unsigned long long *action_err; // !STD kernels only: strict actions (NULL = not checked)
 };
 
-// STD: the standard configuration -- reward and terminated present, no illegal / highest / terminal_boards, no
-// max_tile -- so none of the "is this wanted" branches exists (a taken scalar branch costs a wavefront ~20 cycles).
-// HAS_OBS: the step also returns its observation (game2048_env.py:100 `return stack(self.Matrix), ...`): the
-// one-hot of the record it leaves behind is written by emit_onehot (+256 / 512 / 1 024 B per board; the dtype is a
-// wave-uniform switch, one taken branch against hundreds of store-bound instructions).
-template <int ACT, bool FULL, bool STD, bool HAS_OBS>
-__device__ __forceinline__ void step_body(WaveTables *s_tables, uint4 *s_recs, uint4 *boards, const void *actions,
-                                          unsigned long long *ep_counters, uint32_t board_offset, uint32_t seed_lo, uint32_t seed_hi,
-                                          uint32_t t_lo, uint32_t t_hi, uint32_t n, float *reward, const StepTail &tail)
+// StepArgs -> StepTail (launchers) and back (step_body; obs, boards_out, done_* and action_err are read from the tail
+// itself): a field added to one direction belongs in the other.
+static StepTail step_tail(const StepArgs &a)
+{
+    return StepTail{a.terminated, a.st.last_record, a.illegal, a.highest, a.terminal_boards, a.illegal_reward, a.max_exp,
+                    a.auto_reset, a.obs, a.obs_dtype, a.boards_out, a.done_seq, a.done_value, a.action_err};
+}
+
+// STD: the optional outputs are compile-time NULL and max_exp a compile-time 0 (no max tile), so none of their "is this
+// wanted" branches exists
+template <bool STD> __device__ __forceinline__ StepArgs
+step_args(uint4 *boards, const void *actions, unsigned long long *ep_counters, uint32_t board_offset, uint32_t seed_lo, uint32_t seed_hi,
+          uint32_t t_lo, uint32_t t_hi, uint32_t n, float *reward, const StepTail &tail)
 {
     StepArgs p{};
     p.st.boards = boards;
@@ -528,33 +547,39 @@ __device__ __forceinline__ void step_body(WaveTables *s_tables, uint4 *s_recs, u
     p.t_lo = t_lo;
     p.t_hi = t_hi;
     p.illegal_reward = tail.illegal_reward;
-    p.max_exp = tail.max_exp;
+    p.max_exp = STD ? 0u : tail.max_exp;
     p.auto_reset = tail.auto_reset;
-    // Lanes past the end stay active (whole wavefronts for the ballots): they recompute board n-1
-    // and write nothing.
-    const uint32_t i_raw = blockIdx.x * kBlock + threadIdx.x;
-    const bool valid = FULL || i_raw < p.n;
-    const uint32_t i = valid ? i_raw : p.n - 1u;
-    Board rec = load_board_nt(p.st.boards, i);
-    const uint2 tables_piece = load_tables_piece();
-    const EpisodeCounters counters = load_episode_counters(p, i_raw);
+    return p;
+}
 
-    const Words w = philox4x32_10(p.t_lo, p.t_hi, p.board_offset + i, 0u, p.seed_lo, p.seed_hi);
-    uint32_t action, raw_action = 0;
-    bool bad_action = false;
-    if constexpr (!STD && ACT != 0)
-        action = load_action_checked<ACT>(p.actions, i, bad_action, raw_action);
-    else
-        action = load_action<ACT>(p.actions, i, w.w[3]);
+// STD: the standard configuration -- reward and terminated present, no illegal / highest / terminal_boards, no
+// max_tile -- so none of the "is this wanted" branches exists (a taken scalar branch costs a wavefront ~20 cycles).
+// HAS_OBS: the step also returns its observation (game2048_env.py:100 `return stack(self.Matrix), ...`): the
+// one-hot of the record it leaves behind is written by emit_onehot (+256 / 512 / 1 024 B per board; the dtype is a
+// wave-uniform switch, one taken branch against hundreds of store-bound instructions).
+template <int ACT, bool FULL, bool STD, bool HAS_OBS>
+__device__ __forceinline__ void step_body(WaveTables *s_tables, uint4 *s_recs, uint4 *boards, const void *actions,
+                                          unsigned long long *ep_counters, uint32_t board_offset, uint32_t seed_lo, uint32_t seed_hi,
+                                          uint32_t t_lo, uint32_t t_hi, uint32_t n, float *reward, const StepTail &tail)
+{
+    const StepArgs p = step_args<STD>(boards, actions, ep_counters, board_offset, seed_lo, seed_hi, t_lo, t_hi, n, reward, tail);
+    const Lane ln = lane_of<kBlock, FULL>(p.n);
+    Board rec = load_board_nt(p.st.boards, ln.i);
+    const uint2 tables_piece = load_tables_piece();
+    const EpisodeCounters counters = load_episode_counters(p, ln.i_raw);
+
+    const Words w = philox4x32_10(p.t_lo, p.t_hi, p.board_offset + ln.i, 0u, p.seed_lo, p.seed_hi);
+    BadAction bad; // (reported by the !STD kernels only)
+    const uint32_t action = ACT == 0 ? w.w[3] >> 30 : bad.note_only(load_action_at<ACT>(p.actions, ln.i));
     const LdsTables tb = stage_tables(s_tables, use_after(tables_piece, w.w[0]));
 
-    const StepOut o = play_record(rec, action, w, STD ? 0u : p.max_exp, tb);
+    const StepOut o = play_record(rec, action, w, p.max_exp, tb);
 
     // episode ends first: the terminal record goes out before the reset overwrites it in place
     uint32_t episodes = 0, illegal_ends = 0;
-    const unsigned long long done = record_episode_ends(p, i, o.terminated && valid, !o.legal, rec, episodes, illegal_ends);
+    const unsigned long long done = record_episode_ends(p, ln.i, o.terminated && ln.valid, !o.legal, rec, episodes, illegal_ends);
     // :86 self.score += score -- the wave's 64 gains go to its slot (G of the return accounting; an illegal move gains 0)
-    const uint32_t wave_gain = wave_sum_lane63((FULL || valid) ? o.gain : 0u);
+    const uint32_t wave_gain = wave_sum_lane63(ln.valid ? o.gain : 0u);
     const unsigned long long pending = pending_after_step(done, p.auto_reset);
     uint32_t top = 0;
     if (p.highest)
@@ -562,26 +587,26 @@ __device__ __forceinline__ void step_body(WaveTables *s_tables, uint4 *s_recs, u
     if (o.terminated && p.auto_reset != 0)
         reset_record(rec, o, w, tb);
 
-    if (valid) {
-        store_board_nt(p.st.boards, i, rec);
+    if (ln.valid) {
+        store_board_nt(p.st.boards, ln.i, rec);
         if (STD || p.reward)                                       // :90 / :95
-            __builtin_nontemporal_store(o.legal ? static_cast<float>(o.gain) : p.illegal_reward, p.reward + i);
+            __builtin_nontemporal_store(o.legal ? static_cast<float>(o.gain) : p.illegal_reward, p.reward + ln.i);
         if (STD || p.terminated)
-            __builtin_nontemporal_store(static_cast<uint8_t>(o.terminated ? 1 : 0), p.terminated + i);
+            __builtin_nontemporal_store(static_cast<uint8_t>(o.terminated ? 1 : 0), p.terminated + ln.i);
         if (p.illegal)
-            __builtin_nontemporal_store(static_cast<uint8_t>(o.legal ? 0 : 1), p.illegal + i);
+            __builtin_nontemporal_store(static_cast<uint8_t>(o.legal ? 0 : 1), p.illegal + ln.i);
         if (p.highest)
-            __builtin_nontemporal_store(static_cast<uint8_t>(top), p.highest + i);
+            __builtin_nontemporal_store(static_cast<uint8_t>(top), p.highest + ln.i);
         if (!STD && tail.boards_out)
-            store_board(tail.boards_out, i, record_cells(rec));
+            store_board(tail.boards_out, ln.i, record_cells(rec));
     }
     flush_episode_counts(counters, episodes, illegal_ends, wave_gain, pending);
     if constexpr (!STD && ACT != 0) {
         if (tail.action_err) // (wave-uniform)
-            report_bad_action(tail.action_err, bad_action && valid, raw_action, p.board_offset + i);
+            report_bad_action(tail.action_err, bad.bad && ln.valid, bad.raw, p.board_offset + ln.i);
     }
     if constexpr (HAS_OBS)
-        emit_onehot<FULL>(s_recs + (threadIdx.x & ~63u), rec, tail.obs, tail.obs_dtype, i_raw & ~63u, n);
+        emit_onehot<FULL>(s_recs + (threadIdx.x & ~63u), rec, tail.obs, tail.obs_dtype, ln.i_raw & ~63u, n);
     if (!STD && tail.done_seq)
         signal_done(tail.done_seq, tail.done_value);
 }
@@ -625,12 +650,10 @@ constexpr uint32_t kGainFold = 1024;
 __global__ void __launch_bounds__(kBlock) rollout_random_kernel(const StepArgs p)
 {
     __shared__ WaveTables s_tables[kBlock / 64];
-    const uint32_t i_raw = blockIdx.x * kBlock + threadIdx.x;
-    const bool valid = i_raw < p.n;
-    const uint32_t i = valid ? i_raw : p.n - 1u;
-    Board rec = load_board(p.st.boards, i);
+    const Lane ln = lane_of<kBlock, false>(p.n);
+    Board rec = load_board(p.st.boards, ln.i);
     const LdsTables tb = stage_tables(s_tables, load_tables_piece());
-    const EpisodeCounters counters = load_episode_counters(p, i_raw);
+    const EpisodeCounters counters = load_episode_counters(p, ln.i_raw);
     uint64_t t = (static_cast<uint64_t>(p.t_hi) << 32) | p.t_lo; // transaction of the first step
     uint32_t episodes = 0, illegal_ends = 0;
     // this lane's merge scores over the k steps (reduced over the wave once, at the end): one 32-bit add per step, folded
@@ -640,19 +663,19 @@ __global__ void __launch_bounds__(kBlock) rollout_random_kernel(const StepArgs p
         const uint32_t j1 = p.k_steps - j0 < kGainFold ? p.k_steps : j0 + kGainFold;
         uint32_t gained32 = 0;
         for (uint32_t j = j0; j < j1; ++j, ++t) {
-            const Words w = philox4x32_10(static_cast<uint32_t>(t), static_cast<uint32_t>(t >> 32), p.board_offset + i, 0u,
+            const Words w = philox4x32_10(static_cast<uint32_t>(t), static_cast<uint32_t>(t >> 32), p.board_offset + ln.i, 0u,
                                           p.seed_lo, p.seed_hi);
             const StepOut o = play_record(rec, w.w[3] >> 30, w, p.max_exp, tb);
             gained32 += o.gain;
-            record_episode_ends(p, i, o.terminated && valid, !o.legal, rec, episodes, illegal_ends);
+            record_episode_ends(p, ln.i, o.terminated && ln.valid, !o.legal, rec, episodes, illegal_ends);
             if (o.terminated)
                 reset_record(rec, o, w, tb);
         }
         gained += gained32;
     }
-    if (valid)
-        store_board(p.st.boards, i, rec);
-    flush_episode_counts(counters, episodes, illegal_ends, wave_sum64_lane63(valid ? gained : 0ull), 0ull);
+    if (ln.valid)
+        store_board(p.st.boards, ln.i, rec);
+    flush_episode_counts(counters, episodes, illegal_ends, wave_sum64_lane63(ln.valid ? gained : 0ull), 0ull);
 }
 
 // ---------------------------------------------------------------- fused rollout with per-step I/O
@@ -667,33 +690,15 @@ __global__ void __launch_bounds__(kBlock) rollout_random_kernel(const StepArgs p
 // A -- so every in-flight action has a fixed register whose old value is dead when the new load is issued (rotating
 // registers with moves, or reloading the slot that is being consumed, makes the compiler wait for everything at the
 // loop latch).  Step j then waits with s_waitcnt vmcnt(n > 0) for a load issued kPrefetch steps -- thousands of
-// cycles -- earlier, and the younger loads and stores stay in flight.  The I/O pointers are __restrict__, which
-// lets the compiler issue a step's load ahead of the previous steps' stores.
+// cycles -- earlier, and the younger loads and stores stay in flight (RawAction).  The I/O pointers are __restrict__,
+// which lets the compiler issue a step's load ahead of the previous steps' stores.
 constexpr uint32_t kPrefetch = 4;
-
-// the in-flight actions keep their memory type (a conversion next to the load would be a use of its result: the
-// wait would land there instead of kPrefetch steps later)
-template <int ACT> struct RawAction { typedef uint32_t type; };
-template <> struct RawAction<1> { typedef uint8_t type; };
-template <> struct RawAction<2> { typedef int32_t type; };
-template <> struct RawAction<3> { typedef long long type; };
-
-template <int ACT>
-__device__ __forceinline__ typename RawAction<ACT>::type load_action_at(const void *__restrict__ actions, size_t idx)
-{
-    if constexpr (ACT == 0)
-        return 0u;
-    else
-        return __builtin_nontemporal_load(static_cast<const typename RawAction<ACT>::type *>(actions) + idx);
-}
 
 template <int ACT>
 __global__ void __launch_bounds__(kBlock) rollout_fused_kernel(const StepArgs p, uint64_t stride)
 {
     __shared__ WaveTables s_tables[kBlock / 64];
-    const uint32_t i_raw = blockIdx.x * kBlock + threadIdx.x;
-    const bool valid = i_raw < p.n;
-    const uint32_t i = valid ? i_raw : p.n - 1u;
+    const Lane ln = lane_of<kBlock, false>(p.n);
     const void *__restrict__ actions = p.actions;
     float *__restrict__ reward = p.reward;
     uint8_t *__restrict__ terminated = p.terminated;
@@ -704,31 +709,32 @@ __global__ void __launch_bounds__(kBlock) rollout_fused_kernel(const StepArgs p,
     typename RawAction<ACT>::type ahead[kPrefetch];
 #pragma unroll
     for (uint32_t q = 0; q < kPrefetch; ++q) {
-        ahead[q] = load_action_at<ACT>(actions, static_cast<size_t>(q < k ? q : k - 1u) * stride + i);
+        ahead[q] = load_action_at<ACT>(actions, static_cast<size_t>(q < k ? q : k - 1u) * stride + ln.i);
         asm volatile("" ::: "memory"); // issue order = consumption order (the scheduler reverses them otherwise, and
                                        // the loop's first wait would then have to cover all of them)
     }
-    Board rec = load_board_nt(p.st.boards, i);
+    Board rec = load_board_nt(p.st.boards, ln.i);
     const LdsTables tb = stage_tables(s_tables, load_tables_piece());
-    const EpisodeCounters counters = load_episode_counters(p, i_raw);
+    const EpisodeCounters counters = load_episode_counters(p, ln.i_raw);
     uint64_t t = (static_cast<uint64_t>(p.t_hi) << 32) | p.t_lo;
     uint32_t episodes = 0, illegal_ends = 0;
     unsigned long long gained = 0; // this lane's merge scores over the k steps: 32-bit adds, folded once per double group
     uint32_t gained32 = 0;
     unsigned long long ended_last = 0; // lanes whose episode the LAST step ended (pending marks when auto_reset == 0)
-    // step j with its action; t advances with it
-    bool bad_action = false;   // strict actions: any of this lane's k actions outside 0..3 (checked where they are fetched)
+    // strict actions over k actions: BadAction's fields as two variables (as a struct they change this loop's register allocation)
+    bool bad_action = false;
     uint32_t bad_raw = 0;
+    // step j with its action; t advances with it
     auto one_step = [&](uint32_t j, uint32_t action_in) {
-        const size_t o_idx = static_cast<size_t>(j) * stride + i;
-        const Words w = philox4x32_10(static_cast<uint32_t>(t), static_cast<uint32_t>(t >> 32), p.board_offset + i, 0u,
+        const size_t o_idx = static_cast<size_t>(j) * stride + ln.i;
+        const Words w = philox4x32_10(static_cast<uint32_t>(t), static_cast<uint32_t>(t >> 32), p.board_offset + ln.i, 0u,
                                       p.seed_lo, p.seed_hi);
         ++t;
         const uint32_t action = ACT == 0 ? w.w[3] >> 30 : action_in & 3u;
         const StepOut o = play_record(rec, action, w, p.max_exp, tb);
         gained32 += o.gain;
-        ended_last = record_episode_ends(p, i, o.terminated && valid, !o.legal, rec, episodes, illegal_ends);
-        if (valid) {
+        ended_last = record_episode_ends(p, ln.i, o.terminated && ln.valid, !o.legal, rec, episodes, illegal_ends);
+        if (ln.valid) {
             if (reward)
                 __builtin_nontemporal_store(o.legal ? static_cast<float>(o.gain) : p.illegal_reward, reward + o_idx);
             if (terminated)
@@ -743,12 +749,11 @@ __global__ void __launch_bounds__(kBlock) rollout_fused_kernel(const StepArgs p,
     };
     // past the end the last step's action is fetched again and never used (an unconditional load: a conditional one
     // would be waited for where the branches join)
-    auto fetch = [&](uint32_t j) { return load_action_at<ACT>(actions, static_cast<size_t>(j < k ? j : k - 1u) * stride + i); };
+    auto fetch = [&](uint32_t j) { return load_action_at<ACT>(actions, static_cast<size_t>(j < k ? j : k - 1u) * stride + ln.i); };
     // (every action that is played passes through `check` right before its step)
     auto check = [&](typename RawAction<ACT>::type raw) {
         if constexpr (ACT != 0) {
-            typedef typename std::make_unsigned<typename RawAction<ACT>::type>::type U;
-            if (static_cast<U>(raw) > static_cast<U>(3)) {
+            if (BadAction::outside(raw)) {
                 bad_action = true;
                 bad_raw = static_cast<uint32_t>(raw);
             }
@@ -781,13 +786,13 @@ __global__ void __launch_bounds__(kBlock) rollout_fused_kernel(const StepArgs p,
     for (uint32_t j = j0 + kPrefetch; j < k; ++j)
         one_step(j, check(fetch(j)));
     gained += gained32; // (at most 2 * kPrefetch - 1 tail steps)
-    if (valid)
-        store_board_nt(p.st.boards, i, rec);
-    flush_episode_counts(counters, episodes, illegal_ends, wave_sum64_lane63(valid ? gained : 0ull),
+    if (ln.valid)
+        store_board_nt(p.st.boards, ln.i, rec);
+    flush_episode_counts(counters, episodes, illegal_ends, wave_sum64_lane63(ln.valid ? gained : 0ull),
                          pending_after_step(ended_last, p.auto_reset));
     if constexpr (ACT != 0) {
         if (p.action_err)
-            report_bad_action(p.action_err, bad_action && valid, bad_raw, p.board_offset + i);
+            report_bad_action(p.action_err, bad_action && ln.valid, bad_raw, p.board_offset + ln.i);
     }
 }
 
@@ -804,6 +809,16 @@ __device__ __forceinline__ void store_rng(uint64_t *planes, uint32_t n, uint32_t
     planes[i] = r.state_lo;
     planes[n + i] = r.state_hi;
     planes[4ull * n + i] = r.buf; // inc never changes
+}
+
+// ... except where it is made: seeding
+__device__ __forceinline__ void store_rng_all(uint64_t *planes, uint32_t n, uint32_t i, const Pcg64 &r)
+{
+    planes[i] = r.state_lo;
+    planes[n + i] = r.state_hi;
+    planes[2ull * n + i] = r.inc_lo;
+    planes[3ull * n + i] = r.inc_hi;
+    planes[4ull * n + i] = r.buf;
 }
 
 // Game2048Env.step + the caller's `if terminated: env.reset()` in ONE launch.  A spawn in this mode is ~1 000 VALU
@@ -835,47 +850,44 @@ __global__ void __launch_bounds__(kNumpyBlock) step_numpy_kernel(const StepArgs 
     __shared__ uint32_t s_count;
     if (threadIdx.x == 0u)
         s_count = 0u;
-    const uint32_t i_raw = blockIdx.x * kNumpyBlock + threadIdx.x;
-    const bool valid = i_raw < p.n;
-    const uint32_t i = valid ? i_raw : p.n - 1u;
-    Board rec = load_board(p.st.boards, i);
-    Pcg64 rng = load_rng(p.st.rng, p.n, i);
-    const EpisodeCounters counters = load_episode_counters(p, i_raw);
+    const Lane ln = lane_of<kNumpyBlock, false>(p.n);
+    Board rec = load_board(p.st.boards, ln.i);
+    Pcg64 rng = load_rng(p.st.rng, p.n, ln.i);
+    const EpisodeCounters counters = load_episode_counters(p, ln.i_raw);
     uint32_t action;
     if constexpr (ACT == 0)
-        action = philox4x32_10(p.t_lo, p.t_hi, p.board_offset + i, 0u, p.seed_lo, p.seed_hi).w[3] >> 30;
+        action = philox4x32_10(p.t_lo, p.t_hi, p.board_offset + ln.i, 0u, p.seed_lo, p.seed_hi).w[3] >> 30;
     else {
-        bool bad_action = false;
-        uint32_t raw_action = 0;
-        action = load_action_checked<ACT>(p.actions, i, bad_action, raw_action);
+        BadAction bad;
+        action = bad.note_only(load_action_at<ACT>(p.actions, ln.i));
         if (p.action_err) // strict actions (wave-uniform)
-            report_bad_action(p.action_err, bad_action && valid, raw_action, p.board_offset + i);
+            report_bad_action(p.action_err, bad.bad && ln.valid, bad.raw, p.board_offset + ln.i);
     }
     if (p.auto_reset != 0u)
         __syncthreads(); // s_count = 0 is visible before the first hand-over (placed here: the loads above are in flight)
 
     // rec: the terminal record where the episode ended.  A lane whose move is illegal draws the first tile of its reset here
     const NumpyStepOut o = play_record_numpy(rec, action, rng, p.max_exp, p.auto_reset != 0u);
-    const uint32_t wave_gain = wave_sum_lane63(valid ? o.gain : 0u);         // :86
+    const uint32_t wave_gain = wave_sum_lane63(ln.valid ? o.gain : 0u);         // :86
 
-    const bool fin = o.terminated && valid;
+    const bool fin = o.terminated && ln.valid;
     const bool hand_over = fin && p.auto_reset != 0u;
-    if (valid) {
+    if (ln.valid) {
         if (!hand_over) { // (a board that is reset below is stored there, once)
-            store_board(p.st.boards, i, rec);
-            store_rng(p.st.rng, p.n, i, rng);
+            store_board(p.st.boards, ln.i, rec);
+            store_rng(p.st.rng, p.n, ln.i, rng);
         }
         if (p.reward)
-            p.reward[i] = o.legal ? static_cast<float>(o.gain) : p.illegal_reward;  // :90 / :95
+            p.reward[ln.i] = o.legal ? static_cast<float>(o.gain) : p.illegal_reward;  // :90 / :95
         if (p.terminated)
-            p.terminated[i] = o.terminated ? 1 : 0;
+            p.terminated[ln.i] = o.terminated ? 1 : 0;
         if (p.illegal)
-            p.illegal[i] = o.legal ? 0 : 1;
+            p.illegal[ln.i] = o.legal ? 0 : 1;
         if (p.highest)
-            p.highest[i] = static_cast<uint8_t>(o.top);
+            p.highest[ln.i] = static_cast<uint8_t>(o.top);
     }
     uint32_t episodes = 0, illegal_ends = 0;
-    const unsigned long long ended = record_episode_ends(p, i, fin, !o.legal, rec, episodes, illegal_ends);
+    const unsigned long long ended = record_episode_ends(p, ln.i, fin, !o.legal, rec, episodes, illegal_ends);
     flush_episode_counts(counters, episodes, illegal_ends, wave_gain, pending_after_step(ended, p.auto_reset));
     if (p.auto_reset == 0u) // (kernel-uniform)
         return;
@@ -931,12 +943,10 @@ __global__ void __launch_bounds__(kNumpyBlock) step_numpy_kernel(const StepArgs 
 template <int ACT>
 __global__ void __launch_bounds__(kBlock) rollout_fused_numpy_kernel(const StepArgs p, uint64_t stride)
 {
-    const uint32_t i_raw = blockIdx.x * kBlock + threadIdx.x;
-    const bool valid = i_raw < p.n;
-    const uint32_t i = valid ? i_raw : p.n - 1u;
-    Board rec = load_board(p.st.boards, i);
-    Pcg64 rng = load_rng(p.st.rng, p.n, i);
-    const EpisodeCounters counters = load_episode_counters(p, i_raw);
+    const Lane ln = lane_of<kBlock, false>(p.n);
+    Board rec = load_board(p.st.boards, ln.i);
+    Pcg64 rng = load_rng(p.st.rng, p.n, ln.i);
+    const EpisodeCounters counters = load_episode_counters(p, ln.i_raw);
     const uint64_t t0 = (static_cast<uint64_t>(p.t_hi) << 32) | p.t_lo; // transaction of this lane's step 0
     const uint32_t k = p.k_steps;
     uint32_t j = 0;        // the step this lane plays next
@@ -946,7 +956,7 @@ __global__ void __launch_bounds__(kBlock) rollout_fused_numpy_kernel(const StepA
     uint32_t episodes = 0, illegal_ends = 0, gained32 = 0;
     unsigned long long gained = 0;
     bool last_ended = false; // this lane's step k - 1 ended its episode (the pending mark when auto_reset == 0)
-    bool bad_action = false;
+    bool bad_action = false; // (BadAction spelled out: see rollout_fused_kernel)
     uint32_t bad_raw = 0;
     for (;;) {
         const bool stepping = phase == 0u && j < k;
@@ -956,17 +966,17 @@ __global__ void __launch_bounds__(kBlock) rollout_fused_numpy_kernel(const StepA
         uint32_t gain = 0;
         bool legal = false;
         Board cells = record_cells(rec);
-        const size_t io_idx = static_cast<size_t>(j < k ? j : 0u) * stride + i;
+        const size_t io_idx = static_cast<size_t>(j < k ? j : 0u) * stride + ln.i;
         if (stepping) {
             uint32_t action;
             if constexpr (ACT == 0) {
                 const uint64_t t = t0 + j;
-                action = philox4x32_10(static_cast<uint32_t>(t), static_cast<uint32_t>(t >> 32), p.board_offset + i, 0u, p.seed_lo,
+                action = philox4x32_10(static_cast<uint32_t>(t), static_cast<uint32_t>(t >> 32), p.board_offset + ln.i, 0u, p.seed_lo,
                                        p.seed_hi).w[3] >> 30;
             } else {
                 const typename RawAction<ACT>::type v = load_action_at<ACT>(p.actions, io_idx);
                 typedef typename std::make_unsigned<typename RawAction<ACT>::type>::type U;
-                if (static_cast<U>(v) > static_cast<U>(3)) {
+                if (static_cast<U>(v) > static_cast<U>(3)) { // = BadAction::outside(v), which costs this loop its registers' order
                     bad_action = true;
                     bad_raw = static_cast<uint32_t>(v);
                 }
@@ -992,7 +1002,7 @@ __global__ void __launch_bounds__(kBlock) rollout_fused_numpy_kernel(const StepA
             const bool terminated = legal ? end : true;                         // :89, :94
             record_update(rec, cells, (legal && four) ? 0x80u : 0u);            // a spawned 4: deficit += 4
             gained32 += gain;                                                   // :86
-            if (valid) {
+            if (ln.valid) {
                 if (p.reward)
                     __builtin_nontemporal_store(legal ? static_cast<float>(gain) : p.illegal_reward, p.reward + io_idx);
                 if (p.terminated)
@@ -1002,7 +1012,7 @@ __global__ void __launch_bounds__(kBlock) rollout_fused_numpy_kernel(const StepA
                 if (p.highest)
                     __builtin_nontemporal_store(static_cast<uint8_t>(highest(cells)), p.highest + io_idx);
             }
-            fin = terminated && valid;
+            fin = terminated && ln.valid;
             if (j + 1u == k)
                 last_ended = fin;
             ++j;
@@ -1022,23 +1032,23 @@ __global__ void __launch_bounds__(kBlock) rollout_fused_numpy_kernel(const StepA
             phase = 0u;
         }
         // episode ends of this trip (terminal record first: rec still holds it -- a reset only lands two trips later)
-        (void)record_episode_ends(p, i, fin, !legal, rec, episodes, illegal_ends);
+        (void)record_episode_ends(p, ln.i, fin, !legal, rec, episodes, illegal_ends);
         if ((gained32 >> 30) != 0u) { // (a lane gains < 2^18 per step: folded long before it could wrap)
             gained += gained32;
             gained32 = 0;
         }
     }
     gained += gained32;
-    if (valid) {
-        store_board(p.st.boards, i, rec);
-        store_rng(p.st.rng, p.n, i, rng);
+    if (ln.valid) {
+        store_board(p.st.boards, ln.i, rec);
+        store_rng(p.st.rng, p.n, ln.i, rng);
     }
     const unsigned long long ended_last = __builtin_amdgcn_ballot_w64(last_ended);
-    flush_episode_counts(counters, episodes, illegal_ends, wave_sum64_lane63(valid ? gained : 0ull),
+    flush_episode_counts(counters, episodes, illegal_ends, wave_sum64_lane63(ln.valid ? gained : 0ull),
                          pending_after_step(ended_last, p.auto_reset));
     if constexpr (ACT != 0) {
         if (p.action_err)
-            report_bad_action(p.action_err, bad_action && valid, bad_raw, p.board_offset + i);
+            report_bad_action(p.action_err, bad_action && ln.valid, bad_raw, p.board_offset + ln.i);
     }
 }
 
@@ -1048,12 +1058,7 @@ __global__ void __launch_bounds__(kBlock) seed_numpy_kernel(uint64_t *planes, ui
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n)
         return;
-    const Pcg64 r = pcg64_from_seed(first_seed + i);
-    planes[i] = r.state_lo;
-    planes[n + i] = r.state_hi;
-    planes[2ull * n + i] = r.inc_lo;
-    planes[3ull * n + i] = r.inc_hi;
-    planes[4ull * n + i] = r.buf;
+    store_rng_all(planes, n, i, pcg64_from_seed(first_seed + i));
 }
 
 // Return accounting of an explicit reset (g2048_reset; whole wavefronts): see adjust_slot.
@@ -1068,16 +1073,15 @@ __device__ __forceinline__ void account_reset(const StepArgs &p, uint32_t i_raw,
 
 __global__ void __launch_bounds__(kBlock) reset_numpy_kernel(const StepArgs p, const uint8_t *mask)
 {
-    const uint32_t i_raw = blockIdx.x * kBlock + threadIdx.x;
-    const uint32_t i = i_raw < p.n ? i_raw : p.n - 1u;
-    const bool doit = i_raw < p.n && !(mask && mask[i] == 0);
-    account_reset(p, i_raw, i, doit);
+    const Lane ln = lane_of<kBlock, false>(p.n);
+    const bool doit = ln.valid && !(mask && mask[ln.i] == 0);
+    account_reset(p, ln.i_raw, ln.i, doit);
     if (!doit)
         return;
-    Pcg64 rng = load_rng(p.st.rng, p.n, i);
+    Pcg64 rng = load_rng(p.st.rng, p.n, ln.i);
     const Board fresh = fresh_record_numpy(rng); // game2048_env.py:104-109
-    store_rng(p.st.rng, p.n, i, rng);
-    store_board(p.st.boards, i, fresh);
+    store_rng(p.st.rng, p.n, ln.i, rng);
+    store_board(p.st.boards, ln.i, fresh);
 }
 
 __global__ void __launch_bounds__(kBlock) add_tile_numpy_kernel(const StepArgs p)
@@ -1101,13 +1105,12 @@ __global__ void __launch_bounds__(kBlock) add_tile_numpy_kernel(const StepArgs p
 // Game2048Env.reset for every (masked) board (game2048_env.py:102-111).
 __global__ void __launch_bounds__(kBlock) reset_kernel(const StepArgs p, uint32_t first_slot, const uint8_t *mask)
 {
-    const uint32_t i_raw = blockIdx.x * kBlock + threadIdx.x;
-    const uint32_t i = i_raw < p.n ? i_raw : p.n - 1u;
-    const bool doit = i_raw < p.n && !(mask && mask[i] == 0);
-    account_reset(p, i_raw, i, doit);
+    const Lane ln = lane_of<kBlock, false>(p.n);
+    const bool doit = ln.valid && !(mask && mask[ln.i] == 0);
+    account_reset(p, ln.i_raw, ln.i, doit);
     if (!doit)
         return;
-    const uint32_t b = p.board_offset + i;
+    const uint32_t b = p.board_offset + ln.i;
     const Words w = philox4x32_10(p.t_lo, p.t_hi, b, first_slot >> 2, p.seed_lo, p.seed_hi);
     const uint32_t s = first_slot & 3u;
     const uint32_t w1 = select_word(w, s);
@@ -1116,7 +1119,7 @@ __global__ void __launch_bounds__(kBlock) reset_kernel(const StepArgs p, uint32_
         w2 = philox4x32_10(p.t_lo, p.t_hi, b, (first_slot >> 2) + 1u, p.seed_lo, p.seed_hi).w[0];
     else
         w2 = select_word(w, s + 1u);
-    store_board(p.st.boards, i, fresh_record(w1, w2)); // score 0 (:105) is part of the record
+    store_board(p.st.boards, ln.i, fresh_record(w1, w2)); // score 0 (:105) is part of the record
 }
 
 // ------------------------------------------------------------------------- game primitives
@@ -1131,7 +1134,7 @@ __global__ void __launch_bounds__(kBlock) move_kernel(uint4 *boards, uint32_t n,
     const Board raw = load_board(boards, i);
     Board bd = record_cells(raw);
     uint32_t gain;
-    const bool legal = move(bd, load_action<ACT>(actions, i, 0u), gain);
+    const bool legal = move(bd, action_bits(load_action_at<ACT>(actions, i)), gain);
     if (score_out)
         score_out[i] = legal ? static_cast<int32_t>(gain) : 0;
     if (legal_out)
@@ -1227,17 +1230,15 @@ __global__ void __launch_bounds__(kBlock) export_scores_kernel(const uint4 *reco
 __global__ void __launch_bounds__(kBlock) import_scores_kernel(uint4 *records, uint32_t n, const int32_t *scores_in,
                                                                unsigned long long *ep_counters)
 {
-    const uint32_t i_raw = blockIdx.x * kBlock + threadIdx.x;
-    const bool valid = i_raw < n;
-    const uint32_t i = valid ? i_raw : n - 1u;
-    const Board raw = load_board(records, i);
-    const uint32_t score = static_cast<uint32_t>(scores_in[i]) & kScoreMask;
+    const Lane ln = lane_of<kBlock, false>(n);
+    const Board raw = load_board(records, ln.i);
+    const uint32_t score = static_cast<uint32_t>(scores_in[ln.i]) & kScoreMask;
     // return accounting: the live score of a running episode changes by (new - old); a board whose episode has ended
     // keeps its place among the finished ones
-    const bool live = valid && !is_pending(ep_counters, i_raw);
-    adjust_slot(ep_counters, i_raw, live ? static_cast<int32_t>(score) - static_cast<int32_t>(record_score(raw)) : 0, false);
-    if (valid)
-        store_board(records, i, make_record(record_cells(raw), score));
+    const bool live = ln.valid && !is_pending(ep_counters, ln.i_raw);
+    adjust_slot(ep_counters, ln.i_raw, live ? static_cast<int32_t>(score) - static_cast<int32_t>(record_score(raw)) : 0, false);
+    if (ln.valid)
+        store_board(records, ln.i, make_record(record_cells(raw), score));
 }
 
 // g2048_seed: forget the finished episodes (game2048_env.py:103 restarts the stream).  Every slot restarts with
@@ -2017,12 +2018,6 @@ static bool standard_outputs(const StepArgs &a)
 {
     return a.reward && a.terminated && !a.illegal && !a.highest && !a.terminal_boards && a.max_exp == 0 && !a.boards_out &&
            !a.done_seq;
-}
-
-static StepTail step_tail(const StepArgs &a)
-{
-    return StepTail{a.terminated, a.st.last_record, a.illegal, a.highest, a.terminal_boards, a.illegal_reward, a.max_exp,
-                    a.auto_reset, a.obs, a.obs_dtype, a.boards_out, a.done_seq, a.done_value, a.action_err};
 }
 
 template <int ACT, bool FULL, bool STD, bool OBS>

@@ -200,6 +200,81 @@ def test_strict_actions_report_out_of_range_values(torch_cuda, rng, dtype):
     assert np.array_equal(eng.get_boards().reshape(n, 16), ora.boards)
 
 
+def _strict_fused_rollout(torch, eng, ora_step, acts, tdt, bad_board, low_byte):
+    """One fused [k, n] rollout with strict actions on and one out-of-range action: the next call names the board and the
+    action's low byte, the one after succeeds, and boards, scores, reward and terminated are the oracle's for `action & 3`."""
+    from gym2048_amd.batched import G2048Error
+    k, n = acts.shape
+    rew = torch.full((k, n), -7.0, dtype=torch.float32, device=eng.device)
+    term = torch.full((k, n), 9, dtype=torch.uint8, device=eng.device)
+    eng.prepare_rollout(torch.as_tensor(acts).to(eng.device, tdt), reward=rew, terminated=term, fused=True).run()
+    torch.cuda.synchronize()
+    with pytest.raises(G2048Error, match=r"strict actions.*board %d, low byte 0x%02x" % (bad_board, low_byte)):
+        eng.get_scores()
+    scores = eng.get_scores()                                      # reported once; the engine goes on
+    rew, term = rew.cpu().numpy(), term.cpu().numpy()
+    for j in range(k):
+        ora = ora_step((acts[j] & 3).astype(np.uint8))
+        assert np.array_equal(rew[j], ora.reward), j
+        assert np.array_equal(term[j], ora.terminated), j
+    assert np.array_equal(eng.get_boards().reshape(n, 16), ora.boards)
+    assert np.array_equal(scores, ora.score)
+
+
+@pytest.mark.parametrize("dtype", ["uint8", "int32", "int64"])
+def test_strict_actions_every_fetch_site_of_the_fused_rollout(torch_cuda, dtype):
+    """rollout_fused_kernel consumes its actions at four places: register set A and set B of a double group, a tail step
+    whose action was prefetched and a tail step fetched late.  With k = 13 these are steps 1, 5, 9 and 12; each gets one
+    out-of-range action, on a board of its own (one of them in the ragged second block of n = 300)."""
+    torch = torch_cuda
+    from gym2048_amd.batched import Batched2048
+    from oracle import OracleBatch
+    n, seed, k = 300, 47, 13
+    tdt = getattr(torch, dtype)
+    eng, ora = Batched2048(n, seed=seed, strict_actions=True), OracleBatch(n, seed)
+    eng.reset()
+    ora.reset()
+
+    def ora_step(a):
+        ora.step(a)
+        return ora
+    rs = np.random.default_rng(11)
+    for j, board, value in ((1, 17, 4), (5, 255, 7), (9, 299, 5), (12, 64, 6)):
+        acts = rs.integers(0, 4, (k, n))
+        acts[j, board] = value if dtype == "uint8" else value - 8   # 4..7, or the negative value with the same low bits
+        _strict_fused_rollout(torch, eng, ora_step, acts, tdt, board, int(acts[j, board]) & 0xff)
+
+
+@pytest.mark.parametrize("dtype", ["uint8", "int32", "int64"])
+def test_strict_actions_fused_rollout_numpy_mode_drifted_lanes(torch_cuda, dtype):
+    """The same for rollout_fused_numpy_kernel, whose lanes fetch their own row once resets have made them drift apart
+    (auto_reset on).  Every board repeats one move, so moves soon become illegal and episodes end at different steps INSIDE
+    the rollout; the bad action sits in the last row, on a board whose wavefront has had episodes end before that row."""
+    torch = torch_cuda
+    from gym2048_amd.batched import Batched2048
+    from oracle import OracleBatch
+    n, seed, k, bad_board = 300, 53, 13, 290
+    eng, ora = Batched2048(n, seed=seed, rng="numpy", strict_actions=True), OracleBatch(n, seed)
+    ora.seed_numpy(seed)
+    eng.reset()
+    ora.reset_numpy()
+    ended_before_last_row = np.zeros(n, bool)
+    rows = []
+
+    def ora_step(a):
+        ora.step_numpy(a, auto_reset=True)
+        rows.append(1)
+        if len(rows) < k:
+            ended_before_last_row[:] |= ora.terminated != 0
+        return ora
+    rs = np.random.default_rng(12)
+    acts = np.repeat(rs.integers(0, 4, (1, n)), k, axis=0)
+    acts[k - 1, bad_board] = 200 if dtype == "uint8" else 200 - 256  # low byte 0xc8 either way
+    _strict_fused_rollout(torch, eng, ora_step, acts, getattr(torch, dtype), bad_board, 200)
+    wave = slice(bad_board & ~63, n)
+    assert 0 < ended_before_last_row[wave].sum() < ended_before_last_row[wave].size   # some lanes of that wavefront drifted, not all
+
+
 def test_strict_actions_host_step_is_refused_before_stepping(torch_cuda):
     """g2048_step_host reads its actions from host memory: with strict actions on a value outside 0..3 is refused BEFORE
     anything is stepped (boards and clock unchanged); Game2048Env.step raises ValueError for a Python int outside 0..3."""
