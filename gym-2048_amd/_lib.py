@@ -86,6 +86,28 @@ class MCIO(C.Structure):
     ]
 
 
+class NTupleNetC(C.Structure):
+    """g2048_ntuple_net (include/g2048.h): T tuples of L cells, F fraction bits, the cell lists and the device weights."""
+    _fields_ = [
+        ("n_tuples", C.c_uint32),
+        ("tuple_len", C.c_uint32),
+        ("frac_bits", C.c_uint32),
+        ("cells", (C.c_uint8 * 6) * 8),
+        ("weights", C.c_void_p),
+    ]
+
+
+class NTupleIO(C.Structure):
+    """g2048_ntuple_io (include/g2048.h): device output pointers of evaluate (NULL = not wanted)."""
+    _fields_ = [
+        ("value", C.c_void_p),
+        ("action", C.c_void_p),
+        ("best", C.c_void_p),
+        ("after", C.c_void_p),
+        ("after_value", C.c_void_p),
+    ]
+
+
 class Stats(C.Structure):
     """g2048_stats (include/g2048.h)."""
     _fields_ = [
@@ -143,6 +165,10 @@ SIGNATURES = {
     "g2048_expectimax_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(SearchIO), _S]),
     "g2048_mc_search": (C.c_int, [_E, C.POINTER(MCIO), _S]),
     "g2048_mc_search_plain": (C.c_int, [C.c_void_p, _u64, _u32, C.POINTER(MCIO), _S]),
+    "g2048_ntuple_evaluate": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleIO), _S]),
+    "g2048_ntuple_evaluate_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleIO), _S]),
+    "g2048_ntuple_values_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.c_void_p, _S]),
+    "g2048_ntuple_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, C.POINTER(NTupleNetC), _S]),
     "g2048_add_tile": (C.c_int, [_E, _u32, _S]),
     "g2048_fill_random_actions": (C.c_int, [_E, _u64, _u32, C.c_void_p, _S]),
     "g2048_onehot": (C.c_int, [_E, C.c_void_p, _i32, _S]),

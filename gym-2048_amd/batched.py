@@ -19,6 +19,8 @@ from ._lib import G2048Error, HostIO, StepIO, Stats, check
 # the analysis calls on plain boards, re-exported; Batched2048 has them as methods on its live boards
 from .analysis import (MC_DEFAULT_MAX_STEPS, Afterstates, MCSearch, Search, SearchWeights, afterstates,  # noqa: F401
                        expectimax, mc_search, _OBS_DTYPES, _afterstate_io, _mc_io, _search_io)
+# the n-tuple network value function, re-exported; Batched2048.ntuple_evaluate runs it on the live boards
+from .ntuple import NTupleEval, NTupleNet, TUPLES, td_step, train, _eval_io  # noqa: F401
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}
 
@@ -704,6 +706,18 @@ class Batched2048:
         own stream under ``seed``: no record, clock, statistic or randomness of the engine is touched."""
         io, out = _mc_io(self.n_envs, self.device, rollouts, max_steps, seed, 0, out)
         check(self._lib.g2048_mc_search(self._h, C.byref(io), self._stream()))
+        return out
+
+    def ntuple_evaluate(self, net, out=None) -> NTupleEval:
+        """The greedy player of an n-tuple network on the live boards (``g2048_ntuple_evaluate``):
+        ``NTupleEval(value [n, 4], action [n], best [n], after [n, 16], after_value [n])`` on the engine's stream, as
+        :meth:`NTupleNet.evaluate`.  ``step(result.action)`` plays the chosen move.  ``out``: a preallocated
+        ``NTupleEval`` (fields that are None are not written).  Touches no record, clock, statistic or randomness."""
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        ref = net._ref(self.device)
+        io, out = _eval_io(self.n_envs, self.device, out)
+        check(self._lib.g2048_ntuple_evaluate(self._h, ref, C.byref(io), self._stream()))
         return out
 
     def isend_numpy(self) -> np.ndarray:

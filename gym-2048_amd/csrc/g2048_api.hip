@@ -1238,6 +1238,126 @@ int g2048_mc_search_plain(const uint8_t *boards, uint64_t n, uint32_t index_offs
     return G2048_OK;
 }
 
+} // extern "C"
+
+// g2048_ntuple_net -> the launchers' network, or G2048_ERR_INVALID (before any HIP call: works without a device)
+static int ntuple_net(const g2048_ntuple_net *net, g2048::NtupleNet *out)
+{
+    if (!net)
+        return fail(G2048_ERR_INVALID, "net is NULL");
+    if (net->n_tuples < 1 || net->n_tuples > G2048_NTUPLE_MAX_TUPLES)
+        return fail(G2048_ERR_INVALID, "n_tuples=%u: need 1 <= n_tuples <= %d", net->n_tuples, G2048_NTUPLE_MAX_TUPLES);
+    if (net->tuple_len < 1 || net->tuple_len > G2048_NTUPLE_MAX_LEN)
+        return fail(G2048_ERR_INVALID, "tuple_len=%u: need 1 <= tuple_len <= %d", net->tuple_len, G2048_NTUPLE_MAX_LEN);
+    if (net->frac_bits > G2048_NTUPLE_MAX_FRAC_BITS)
+        return fail(G2048_ERR_INVALID, "frac_bits=%u: need 0 <= frac_bits <= %d", net->frac_bits, G2048_NTUPLE_MAX_FRAC_BITS);
+    for (uint32_t t = 0; t < net->n_tuples; ++t) {
+        uint32_t seen = 0;
+        for (uint32_t k = 0; k < net->tuple_len; ++k) {
+            const uint32_t c = net->cells[t][k];
+            if (c > 15)
+                return fail(G2048_ERR_INVALID, "cells[%u][%u]=%u: a cell index is 0..15", t, k, c);
+            if (seen >> c & 1u)
+                return fail(G2048_ERR_INVALID, "cells[%u][%u]=%u: cell repeated within tuple %u", t, k, c, t);
+            seen |= 1u << c;
+        }
+    }
+    if (!net->weights)
+        return fail(G2048_ERR_INVALID, "net weights is NULL");
+    if (reinterpret_cast<uintptr_t>(net->weights) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple weights need 16 bytes");
+    out->n_tuples = net->n_tuples;
+    out->tuple_len = net->tuple_len;
+    out->frac_bits = net->frac_bits;
+    memcpy(out->cells, net->cells, sizeof(out->cells));
+    out->weights = net->weights;
+    return G2048_OK;
+}
+
+static int ntuple_out(const g2048_ntuple_io *io, g2048::NtupleOut *o)
+{
+    if (!io)
+        return fail(G2048_ERR_INVALID, "io is NULL");
+    if (!io->value && !io->action && !io->best && !io->after && !io->after_value)
+        return fail(G2048_ERR_INVALID, "g2048_ntuple_io requests no output (value, action, best, after and after_value are all NULL)");
+    if (reinterpret_cast<uintptr_t>(io->value) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple value needs 16 bytes");
+    if (reinterpret_cast<uintptr_t>(io->after) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple after needs 16 bytes");
+    if ((reinterpret_cast<uintptr_t>(io->best) | reinterpret_cast<uintptr_t>(io->after_value)) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple best and after_value need 8 bytes");
+    *o = g2048::NtupleOut{io->value, io->action, io->best, reinterpret_cast<uint4 *>(io->after), io->after_value};
+    return G2048_OK;
+}
+
+extern "C" {
+
+int g2048_ntuple_evaluate(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_io *io, void *stream)
+{
+    if (int rc = usable(e))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleOut o;
+    if (int rc = ntuple_out(io, &o))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(g2048::launch_ntuple_eval(e->st.boards, static_cast<uint32_t>(e->n), false, nn, o, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_ntuple_evaluate_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_io *io,
+                                void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleOut o;
+    if (int rc = ntuple_out(io, &o))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_eval(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), true, nn, o,
+                                        static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_ntuple_values_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, int64_t *v, void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (!v)
+        return fail(G2048_ERR_INVALID, "v is NULL");
+    if (reinterpret_cast<uintptr_t>(v) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple v needs 8 bytes");
+    G2048_HIP(g2048::launch_ntuple_values(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), nn, v,
+                                          static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift,
+                              const g2048_ntuple_net *net, void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (!delta)
+        return fail(G2048_ERR_INVALID, "delta is NULL");
+    if (reinterpret_cast<uintptr_t>(delta) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple delta needs 8 bytes");
+    if (lr_shift > G2048_NTUPLE_MAX_LR_SHIFT)
+        return fail(G2048_ERR_INVALID, "lr_shift=%u: need 0 <= lr_shift <= %d", lr_shift, G2048_NTUPLE_MAX_LR_SHIFT);
+    G2048_HIP(g2048::launch_ntuple_update(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), delta, lr_shift, nn,
+                                          static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream)
 {
     if (int rc = usable(e))

@@ -635,6 +635,200 @@ G2048_DEV uint32_t mc_root(const Board &cells, uint32_t i, uint32_t rollouts, ui
     return best_action<uint64_t>(value);
 }
 
+// ------------------------------------------------------------------- n-tuple network value function
+// g2048_ntuple_* (include/g2048.h): a value function that is nothing but table look-ups, learned by
+// afterstate TD(0) (Szubert & Jaskowski 2014).  T tuples of L cells each; tuple t owns a table of 16^L int32 weights, a
+// weight being a score in units of 2^-F.  Integers only:
+//   c(e)     = min(e mod 32, 15)                              (tiles of 2^15 and above share the last table row)
+//   idx_t(b) = sum over k < L of c(b[cells[t][k]]) << 4k
+//   V(b)     = sum over the 8 symmetries s of b, sum over t < T of weights[t][idx_t(s(b))]             (|V| <= 2^37)
+//   evaluate: q[d] = (g_d << F) + V(a_d) for (a_d, g_d) = move(b, d), kNtupleIllegal where d is illegal; action = the
+//             smallest d of largest q (q may be negative), 0 when no move is legal; best = q[action], after = a_action,
+//             after_value = V(after) -- 0, the input board, 0 when no move is legal
+//   update:   step = sat_int32(delta >> lr_shift) (arithmetic shift); weights[t][idx_t(s(a))] += step for every s and t,
+//             a 32-bit add that wraps.  A sum of adds: any order, any split over lanes or launches gives the same weights.
+// The symmetries are applied to the CELL LISTS, once, on the host: s(b)[c] = b[ntuple_sym_cell(s, c)], so
+// idx_t(s(b)) reads b at the cells ntuple_sym_cell(s, cells[t][k]) -- NtupleShape::list holds those 8T lists as six
+// nibbles each.  The lists are wave-uniform kernel arguments (SGPRs), the board is its 16 clamped cells packed into one
+// 64-bit value, and reading a cell is a 64-bit shift by a scalar amount: no per-lane array, nothing in scratch.  The eight
+// maps (transpose, reverse the rows, reverse the columns, in every combination) are the dihedral group of the square, the
+// set training_data.augment() / g2048_augment generate; the sum does not care about their order.
+#if defined(G2048_HOST_CHECK)
+#define G2048_HOST_DEV static inline
+#else
+#define G2048_HOST_DEV __host__ __device__ __forceinline__
+#endif
+constexpr uint32_t kNtupleMaxTuples = 8, kNtupleMaxLen = 6, kNtupleMaxFrac = 16, kNtupleMaxShift = 40; // = G2048_NTUPLE_* (g2048.h)
+constexpr int64_t kNtupleIllegal = INT64_MIN;                                                          // G2048_NTUPLE_ILLEGAL
+
+struct NtupleShape {
+    uint32_t n_tuples, tuple_len;
+    uint32_t list[8 * kNtupleMaxTuples]; // list[8 * s + t]: nibble k = the cell of b that idx_t(s(b)) reads for k
+};
+
+// The cell of b that symmetry s (0..7) puts at cell c: bit 0 transposes, bit 1 reverses the rows, bit 2 the columns.
+G2048_HOST_DEV uint32_t ntuple_sym_cell(uint32_t s, uint32_t c)
+{
+    uint32_t r = c >> 2, q = c & 3u;
+    if (s & 1u) {
+        const uint32_t x = r;
+        r = q;
+        q = x;
+    }
+    if (s & 2u)
+        r = 3u - r;
+    if (s & 4u)
+        q = 3u - q;
+    return 4u * r + q;
+}
+
+G2048_HOST_DEV NtupleShape ntuple_shape(uint32_t n_tuples, uint32_t tuple_len, const uint8_t cells[8][6])
+{
+    NtupleShape sh{};
+    sh.n_tuples = n_tuples;
+    sh.tuple_len = tuple_len;
+    for (uint32_t s = 0; s < 8u; ++s)
+        for (uint32_t t = 0; t < n_tuples; ++t)
+            for (uint32_t k = 0; k < tuple_len; ++k)
+                sh.list[8u * s + t] |= ntuple_sym_cell(s, cells[t][k]) << (4u * k);
+    return sh;
+}
+
+// c(e) for the four cells of a row register: min(byte mod 32, 15)
+G2048_DEV uint32_t ntuple_cell(uint32_t row)
+{
+    const uint32_t e = row & 0x1f1f1f1fu;
+    const uint32_t over = (e >> 4) & 0x01010101u; // 1 where the exponent is 16..31
+    return (e | (over * 15u)) & 0x0f0f0f0fu;
+}
+
+// The 16 clamped cells as nibbles: cell c in bits 4c .. 4c + 3
+G2048_DEV uint64_t ntuple_pack(const Board &b)
+{
+    uint32_t h[4];
+    for (int i = 0; i < 4; ++i) {
+        uint32_t x = ntuple_cell(b.r[i]);
+        x = (x | (x >> 4)) & 0x00ff00ffu;
+        h[i] = (x | (x >> 8)) & 0xffffu;
+    }
+    return (static_cast<uint64_t>(h[2] | (h[3] << 16)) << 32) | (h[0] | (h[1] << 16));
+}
+
+// idx of one cell list (six nibbles, the first L used) on a packed board; < 16^L
+G2048_DEV uint32_t ntuple_index(uint64_t packed, uint32_t list, uint32_t L)
+{
+    uint32_t idx = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kNtupleMaxLen; ++k) {
+        const uint32_t cell = (list >> (4u * k)) & 15u;
+        idx |= (static_cast<uint32_t>(packed >> (4u * cell)) & (k < L ? 15u : 0u)) << (4u * k);
+    }
+    return idx;
+}
+
+// offset of look-up (s, t) in the weight array [T][16^L]; < T * 16^L
+G2048_DEV uint32_t ntuple_offset(uint64_t packed, const NtupleShape &sh, uint32_t s, uint32_t t)
+{
+    return (t << (4u * sh.tuple_len)) + ntuple_index(packed, sh.list[8u * s + t], sh.tuple_len);
+}
+
+// V(b).  T = sh.n_tuples as a template argument: the 8T look-ups are straight-line code, all offsets first, then all
+// loads, then the adds -- the loads do not depend on each other and are in flight together.
+template <uint32_t T> G2048_DEV int64_t ntuple_value(uint64_t packed, const NtupleShape &sh, const int32_t *weights)
+{
+    uint32_t off[8u * T];
+    int32_t w[8u * T];
+#pragma unroll
+    for (uint32_t s = 0; s < 8u; ++s)
+#pragma unroll
+        for (uint32_t t = 0; t < T; ++t)
+            off[s * T + t] = ntuple_offset(packed, sh, s, t);
+#pragma unroll
+    for (uint32_t j = 0; j < 8u * T; ++j)
+        w[j] = weights[off[j]];
+    int64_t v = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 8u * T; ++j)
+        v += w[j];
+    return v;
+}
+
+// One root direction: the afterstate, its value and q.
+struct NtupleMove {
+    Board after;
+    int64_t v, q; // V(after); (gain << F) + v, kNtupleIllegal where the move is illegal
+    bool legal;
+};
+
+template <uint32_t T, class Tables>
+G2048_DEV NtupleMove ntuple_move(const Board &cells, uint32_t d, const NtupleShape &sh, uint32_t F, const int32_t *weights,
+                                 const Tables &tb)
+{
+    NtupleMove m;
+    m.after = cells;
+    uint32_t gain;
+    m.legal = move_sel(m.after, tb.move_sel(d), gain); // illegal: after == cells
+    m.v = ntuple_value<T>(ntuple_pack(m.after), sh, weights);
+    m.q = m.legal ? static_cast<int64_t>(static_cast<uint64_t>(gain) << F) + m.v : kNtupleIllegal;
+    return m;
+}
+
+// Root choice as one unsigned max.  |q| < 2^48 (gain < 2^31, F <= 16, |V| <= 2^37), so q + 2^60 is positive and fits 62
+// bits: a signed-to-unsigned bias (root_key's value + 1 assumes values >= -1).  An illegal direction's key is below
+// every legal one; 3 - d breaks ties to the smallest d and makes the action 0 when no direction is legal.
+G2048_DEV uint64_t ntuple_key(int64_t q, bool legal, uint32_t d)
+{
+    return (legal ? static_cast<uint64_t>(q + (1ll << 60)) << 2 : 0ull) | (3u - d);
+}
+G2048_DEV bool ntuple_key_legal(uint64_t key) { return key >= 4u; }
+
+// The evaluate definition on one thread; the kernel gives each direction a lane and joins the keys with two shuffles.
+struct NtupleRoot {
+    int64_t q[4];
+    uint32_t action;
+    int64_t best;
+    Board after;
+    int64_t after_value;
+};
+
+template <uint32_t T, class Tables>
+G2048_DEV NtupleRoot ntuple_root(const Board &cells, const NtupleShape &sh, uint32_t F, const int32_t *weights, const Tables &tb)
+{
+    NtupleRoot r;
+    NtupleMove m[4];
+    uint64_t best = 0;
+    for (uint32_t d = 0; d < 4u; ++d) {
+        m[d] = ntuple_move<T>(cells, d, sh, F, weights, tb);
+        r.q[d] = m[d].q;
+        const uint64_t key = ntuple_key(m[d].q, m[d].legal, d);
+        best = key > best ? key : best;
+    }
+    r.action = root_key_action(best);
+    const bool any = ntuple_key_legal(best);
+    r.best = any ? r.q[r.action] : 0;
+    r.after = any ? m[r.action].after : cells;
+    r.after_value = any ? m[r.action].v : 0;
+    return r;
+}
+
+// The update's step: sat_int32(delta >> lr_shift), the shift arithmetic (it floors negatives); lr_shift <= 40
+G2048_DEV int32_t ntuple_step(int64_t delta, uint32_t lr_shift)
+{
+    const int64_t x = delta >> lr_shift;
+    return x > INT32_MAX ? INT32_MAX : (x < INT32_MIN ? INT32_MIN : static_cast<int32_t>(x));
+}
+
+// add(offset, step) for each of the 8T look-ups of one board: the device passes a fire-and-forget atomic, the host a
+// wrapping add.
+template <uint32_t T, class Add> G2048_DEV void ntuple_update(uint64_t packed, const NtupleShape &sh, int32_t step, Add add)
+{
+#pragma unroll
+    for (uint32_t s = 0; s < 8u; ++s)
+#pragma unroll
+        for (uint32_t t = 0; t < T; ++t)
+            add(ntuple_offset(packed, sh, s, t), step);
+}
+
 // ------------------------------------------------------------------- the 16-byte board RECORD
 // What the engine keeps per board in HBM is ONE 16-byte record: bits [4:0] of byte j = exponent of
 // cell j (0..31), and the 24-bit SCORE DEFICIT d in the three spare bits [7:5] of bytes 8..15

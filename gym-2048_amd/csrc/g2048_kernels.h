@@ -114,6 +114,23 @@ struct McArgs {
     int64_t *steps;               // [n][4]
 };
 hipError_t launch_mc_search(const uint4 *boards, uint32_t n, bool plain, const McArgs &a, hipStream_t s);
+// g2048_ntuple_*: the network (g2048_ntuple_net) and evaluate's outputs (g2048_ntuple_io), both checked by the caller
+struct NtupleNet {
+    uint32_t n_tuples, tuple_len, frac_bits; // T in 1..8, L in 1..6, F in 0..16
+    uint8_t cells[8][6];                     // < 16, distinct within a tuple
+    int32_t *weights;                        // [T][16^L]
+};
+struct NtupleOut {
+    int64_t *value;       // [n][4]
+    uint8_t *action;      // [n]
+    int64_t *best;        // [n]
+    uint4 *after;         // [n] plain cells of the chosen afterstate
+    int64_t *after_value; // [n]
+};
+hipError_t launch_ntuple_eval(const uint4 *boards, uint32_t n, bool plain, const NtupleNet &net, const NtupleOut &o, hipStream_t s);
+hipError_t launch_ntuple_values(const uint4 *boards, uint32_t n, const NtupleNet &net, int64_t *v, hipStream_t s);
+hipError_t launch_ntuple_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
+                                hipStream_t s);
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s);
 // numpy-RNG mode: every board's PCG64 generator, seeded as numpy seeds it, into the DeviceState::rng planes
 hipError_t launch_seed_numpy(uint64_t *planes, uint32_t n, uint64_t first_seed, hipStream_t s);

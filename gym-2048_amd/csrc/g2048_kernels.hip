@@ -1532,6 +1532,77 @@ __global__ void __launch_bounds__(kBlock) mc_search_kernel(const uint4 *__restri
     }
 }
 
+// ---------------------------------------------------------------------------- n-tuple network
+// g2048_ntuple_evaluate: the evaluate definition of g2048_device.h ("n-tuple network value function") for every board.
+// A board is a group of four lanes, one per root direction d: lane d moves the board, looks up V of its afterstate --
+// 8T gathers whose offsets are all computed before the first load is issued (ntuple_value), so they are in flight
+// together -- and the four keys meet in two shuffles.  The lane of the chosen direction writes best, after and
+// after_value (lane 0 when no move is legal: every lane then holds the input board).  The cell lists are kernel
+// arguments: wave-uniform, so reading a cell of the packed board is a shift by a scalar.  T is a template argument (1..8):
+// the look-ups are straight-line code with no per-lane array left at run time.  Lanes stride over the boards when 4n
+// exceeds the grid cap (kSearchMaxLanes).  Nothing is written back: no record, clock, episode slot or randomness.
+template <uint32_t T, bool PLAIN>
+__global__ void __launch_bounds__(kBlock) ntuple_eval_kernel(const uint4 *__restrict__ boards, uint32_t n, const NtupleShape sh,
+                                                             uint32_t frac_bits, const int32_t *__restrict__ weights,
+                                                             const NtupleOut o)
+{
+    __shared__ WaveTables s_tables[kBlock / 64];
+    const LdsTables tb = stage_tables(s_tables, load_tables_piece());
+    const LaneGroup<4> grp;
+    const uint32_t d = grp.d;
+    for (uint64_t i = grp.first; i < n; i += grp.stride) {
+        const Board in = load_board(boards, static_cast<uint32_t>(i));
+        const Board cells = input_cells<PLAIN>(in);
+        const NtupleMove m = ntuple_move<T>(cells, d, sh, frac_bits, weights, tb);
+        const uint64_t key = group_best_key(ntuple_key(m.q, m.legal, d), 1u);
+        const uint32_t action = root_key_action(key);
+        const bool any = ntuple_key_legal(key);
+        if (o.value)
+            o.value[i * 4u + d] = m.q;
+        if (d == 0u && o.action)
+            o.action[i] = static_cast<uint8_t>(action);
+        if (d == (any ? action : 0u)) {
+            if (o.best)
+                o.best[i] = any ? m.q : 0;
+            if (o.after)
+                store_board(o.after, static_cast<uint32_t>(i), m.after);
+            if (o.after_value)
+                o.after_value[i] = any ? m.v : 0;
+        }
+    }
+}
+
+// g2048_ntuple_values_plain: V of every board, one board per lane, the same gathers.
+template <uint32_t T>
+__global__ void __launch_bounds__(kBlock) ntuple_values_kernel(const uint4 *__restrict__ boards, uint32_t n, const NtupleShape sh,
+                                                               const int32_t *__restrict__ weights, int64_t *__restrict__ v)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    v[i] = ntuple_value<T>(ntuple_pack(load_board(boards, i)), sh, weights);
+}
+
+// g2048_ntuple_update_plain: one board per lane, 8T relaxed agent-scope atomic adds whose result nobody reads (fire and
+// forget); a lane whose step is 0 issues none.  Integer adds commute, so the weights after the launch do not depend on
+// the order the lanes, waves or launches arrive in.
+template <uint32_t T>
+__global__ void __launch_bounds__(kBlock) ntuple_update_kernel(const uint4 *__restrict__ boards, uint32_t n,
+                                                               const int64_t *__restrict__ delta, uint32_t lr_shift,
+                                                               const NtupleShape sh, int32_t *weights)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    const int32_t step = ntuple_step(delta[i], lr_shift);
+    if (step == 0)
+        return;
+    uint32_t *w = reinterpret_cast<uint32_t *>(weights); // unsigned: the add wraps mod 2^32
+    ntuple_update<T>(ntuple_pack(load_board(boards, i)), sh, step, [w](uint32_t off, int32_t st) {
+        __hip_atomic_fetch_add(w + off, static_cast<uint32_t>(st), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    });
+}
+
 // ---------------------------------------------------------------------------- augmentation
 // training_data.augment() (training_data.py:257-299) for board pairs on the device: the eight
 // symmetries [orig, hflip, rot1(orig), rot1(hflip), rot2(..), rot2(..), rot3(..), rot3(..)] with the
@@ -2119,6 +2190,42 @@ hipError_t launch_mc_search(const uint4 *boards, uint32_t n, bool plain, const M
         });
     };
     return a.rollouts >= kMcWaveRollouts ? go(std::integral_constant<uint32_t, 64u>()) : go(std::integral_constant<uint32_t, 16u>());
+}
+
+// f(std::integral_constant<uint32_t, T>()) for the network's tuple count T = 1..8
+template <class F>
+static hipError_t dispatch_tuples(const NtupleNet &net, F &&f)
+{
+    return dispatch<1, 8>(static_cast<int>(net.n_tuples),
+                          [&](auto tc) { return f(std::integral_constant<uint32_t, static_cast<uint32_t>(decltype(tc)::value)>()); });
+}
+
+hipError_t launch_ntuple_eval(const uint4 *boards, uint32_t n, bool plain, const NtupleNet &net, const NtupleOut &o, hipStream_t s)
+{
+    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
+    return dispatch_tuples(net, [&](auto tc) {
+        return dispatch_bool(plain, [&](auto plain_c) {
+            return launch_1d(ntuple_eval_kernel<tc, plain_c>, group_lanes(n, 4u), 0, s, boards, n, sh, net.frac_bits,
+                             static_cast<const int32_t *>(net.weights), o);
+        });
+    });
+}
+
+hipError_t launch_ntuple_values(const uint4 *boards, uint32_t n, const NtupleNet &net, int64_t *v, hipStream_t s)
+{
+    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
+    return dispatch_tuples(net, [&](auto tc) {
+        return launch_1d(ntuple_values_kernel<tc>, n, 0, s, boards, n, sh, static_cast<const int32_t *>(net.weights), v);
+    });
+}
+
+hipError_t launch_ntuple_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
+                                hipStream_t s)
+{
+    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
+    return dispatch_tuples(net, [&](auto tc) {
+        return launch_1d(ntuple_update_kernel<tc>, n, 0, s, boards, n, delta, lr_shift, sh, net.weights);
+    });
 }
 
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s)

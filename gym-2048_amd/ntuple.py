@@ -1,0 +1,209 @@
+"""N-tuple network value function (``g2048_ntuple_*``): table look-ups indexed by cell exponents,
+summed over the eight board symmetries, with int32 fixed-point weights -- evaluated on the afterstates of the four moves
+(a greedy player: one launch for the whole batch) and learned by afterstate TD(0) (Szubert & Jaskowski 2014), one launch
+per update.  Everything is an integer: the same bits however the batch is split over lanes, launches or shards.
+
+``NTupleNet`` owns the weights (a device tensor); ``Batched2048.ntuple_evaluate`` evaluates the engine's live boards;
+``td_step`` / ``train`` chain evaluate, ``g2048_step`` and update on the device with no host synchronisation.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Optional
+
+import torch
+
+from . import _lib
+from ._lib import NTupleIO, NTupleNetC, check
+from .analysis import _bind_out, _int_arg, _plain_boards
+
+MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
+ILLEGAL = -(1 << 63)                                              # G2048_NTUPLE_ILLEGAL: q of an illegal move
+
+# Default shapes, as row-major cell indices (cell 4r + c).  The value sums every tuple over the eight symmetries of the
+# board, so a shape lists each tuple once, not once per placement.
+TUPLES = {
+    # the 4 x 6-tuple network of Szubert & Jaskowski 2014: two 2x3 rectangles and two "axes"
+    "4x6": ((0, 1, 2, 3, 4, 5), (4, 5, 6, 7, 8, 9), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10)),
+    # all 17 straight and square 4-tuples -- 4 rows, 4 columns, 9 2x2 squares -- as the symmetric images of five: the
+    # outer and the inner row, the corner, the edge and the centre square
+    "17x4": ((0, 1, 2, 3), (4, 5, 6, 7), (0, 1, 4, 5), (1, 2, 5, 6), (5, 6, 9, 10)),
+}
+
+
+class NTupleEval(NamedTuple):
+    """Result of evaluate (``g2048_ntuple_evaluate``).  Device tensors; a field that is None was not asked for (``out``)."""
+    value: Optional[torch.Tensor]        # int64 [n, 4]: q[d] = (merge score << F) + V(afterstate d); ILLEGAL where d is illegal
+    action: Optional[torch.Tensor]       # uint8 [n]: the smallest d of largest q among the legal d; 0 when none is legal
+    best: Optional[torch.Tensor]         # int64 [n]: q[action]; 0 when no move is legal
+    after: Optional[torch.Tensor]        # uint8 [n, 16]: the afterstate of `action`; the board itself when no move is legal
+    after_value: Optional[torch.Tensor]  # int64 [n]: V(after); 0 when no move is legal
+
+
+def _eval_io(n, device, out):
+    """(NTupleIO, NTupleEval) for n boards: ``out`` checked field by field, or freshly allocated outputs."""
+    if out is None:
+        i64 = dict(dtype=torch.int64, device=device)
+        out = NTupleEval(torch.empty((n, 4), **i64), torch.empty(n, dtype=torch.uint8, device=device), torch.empty(n, **i64),
+                         torch.empty((n, 16), dtype=torch.uint8, device=device), torch.empty(n, **i64))
+    else:
+        out = NTupleEval(*out)
+        if all(t is None for t in out):
+            raise ValueError("out requests no output (value, action, best, after and after_value are all None)")
+    io = NTupleIO()
+    _bind_out(io, out, {"value": ((n, 4), (torch.int64,)), "action": ((n,), (torch.uint8,)), "best": ((n,), (torch.int64,)),
+                        "after": ((n, 16), (torch.uint8,)), "after_value": ((n,), (torch.int64,))}, device)
+    return io, out
+
+
+class NTupleNet:
+    """T tuples of L cells with a table of 16^L int32 weights each; a weight is a score in units of 2^-``frac_bits``.
+
+    ``tuples``: a name in ``TUPLES`` or a sequence of equally long sequences of distinct cell indices 0..15 (at most 8
+    tuples of at most 6 cells).  ``weights`` is the int32 ``[T, 16^L]`` tensor on ``device``, zero-initialised; the
+    kernels read and update it in place, so it can be shared between engines."""
+
+    def __init__(self, tuples="4x6", frac_bits=10, device="cuda:0"):
+        if isinstance(tuples, str):
+            if tuples not in TUPLES:
+                raise ValueError(f"tuples must be one of {sorted(TUPLES)} or a sequence of cell lists, not {tuples!r}")
+            tuples = TUPLES[tuples]
+        try:
+            tuples = tuple(tuple(t) for t in tuples)
+        except TypeError:
+            raise ValueError("tuples must be a sequence of sequences of cell indices") from None
+        if not 1 <= len(tuples) <= MAX_TUPLES:
+            raise ValueError(f"tuples: need 1..{MAX_TUPLES} tuples, not {len(tuples)}")
+        length = len(tuples[0])
+        if not 1 <= length <= MAX_LEN or any(len(t) != length for t in tuples):
+            raise ValueError(f"tuples: every tuple needs the same length in 1..{MAX_LEN}")
+        for t in tuples:
+            cells = [_int_arg("tuples cell", c, 0, 15) for c in t]
+            if len(set(cells)) != len(cells):
+                raise ValueError(f"tuples: cell repeated within tuple {t}")
+        self.tuples = tuple(tuple(int(c) for c in t) for t in tuples)
+        self.frac_bits = _int_arg("frac_bits", frac_bits, 0, MAX_FRAC_BITS)
+        self.device = torch.device(device)
+        self.weights = torch.zeros((len(tuples), 16 ** length), dtype=torch.int32, device=self.device)
+        self._c = NTupleNetC(len(tuples), length, self.frac_bits)
+        for t, cells in enumerate(self.tuples):
+            for k, c in enumerate(cells):
+                self._c.cells[t][k] = c
+        self._c.weights = self.weights.data_ptr()
+
+    @property
+    def n_tuples(self):
+        return len(self.tuples)
+
+    @property
+    def tuple_len(self):
+        return len(self.tuples[0])
+
+    def _ref(self, device):
+        """The C descriptor, for a launch on ``device``."""
+        if self.device != device:
+            raise ValueError(f"the network's weights are on {self.device}, the boards on {device}")
+        return C.byref(self._c)
+
+    def _launch(self, fn, boards, *args):
+        with torch.cuda.device(boards.device):
+            stream = C.c_void_p(torch.cuda.current_stream(boards.device).cuda_stream)
+            check(fn(boards.data_ptr(), boards.shape[0], *args, stream))
+
+    def values(self, boards, out=None) -> torch.Tensor:
+        """V of plain boards (``g2048_ntuple_values_plain``): ``boards`` a device ``uint8`` ``[n, 16]`` or ``[n, 4, 4]``
+        tensor of exponents; returns int64 ``[n]``."""
+        n, device = _plain_boards(boards)
+        net = self._ref(device)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int64, device=device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n,) or not out.is_contiguous()
+              or out.device != device):
+            raise ValueError(f"out must be a contiguous int64 [{n}] tensor on {device}")
+        self._launch(_lib.load().g2048_ntuple_values_plain, boards, net, out.data_ptr())
+        return out
+
+    def evaluate(self, boards, out=None) -> NTupleEval:
+        """The greedy player on plain boards (``g2048_ntuple_evaluate_plain``): q of the four moves, the best move, its
+        q, its afterstate and the afterstate's value, in one launch on the current stream of the boards' device.
+        ``out``: a preallocated :class:`NTupleEval` (a field that is None is not written)."""
+        n, device = _plain_boards(boards)
+        net = self._ref(device)
+        io, out = _eval_io(n, device, out)
+        self._launch(_lib.load().g2048_ntuple_evaluate_plain, boards, net, C.byref(io))
+        return out
+
+    def update(self, boards, delta, lr_shift):
+        """``weights[t][idx_t(s(board_i))] += sat_int32(delta_i >> lr_shift)`` for every symmetry s and tuple t of every
+        board (``g2048_ntuple_update_plain``): ``boards`` as in :meth:`values`, ``delta`` a device int64 ``[n]`` tensor,
+        ``lr_shift`` 0..40.  One launch of integer atomic adds: the result does not depend on their order."""
+        n, device = _plain_boards(boards)
+        net = self._ref(device)
+        if (not isinstance(delta, torch.Tensor) or delta.dtype != torch.int64 or tuple(delta.shape) != (n,)
+                or not delta.is_contiguous() or delta.device != device):
+            raise ValueError(f"delta must be a contiguous int64 [{n}] tensor on {device}")
+        shift = _int_arg("lr_shift", lr_shift, 0, MAX_LR_SHIFT)
+        self._launch(_lib.load().g2048_ntuple_update_plain, boards, delta.data_ptr(), shift, net)
+
+    def state_dict(self):
+        return {"tuples": self.tuples, "frac_bits": self.frac_bits, "weights": self.weights.clone()}
+
+    def load_state_dict(self, state):
+        """Copy the weights of a ``state_dict()`` of a network of the same shape into this one's tensor (in place)."""
+        if tuple(tuple(t) for t in state["tuples"]) != self.tuples or int(state["frac_bits"]) != self.frac_bits:
+            raise ValueError("state_dict is of a network with other tuples or frac_bits")
+        w = torch.as_tensor(state["weights"])
+        if w.dtype != torch.int32 or w.shape != self.weights.shape:
+            raise ValueError(f"state_dict weights must be int32 {tuple(self.weights.shape)}")
+        self.weights.copy_(w)
+
+
+class TDWork(NamedTuple):
+    """Preallocated buffers of :func:`td_step` for one engine."""
+    before: NTupleEval   # action, after, after_value of the boards before the step
+    after: NTupleEval    # best of the boards after the step
+    delta: torch.Tensor  # int64 [n]
+
+
+def td_work(engine) -> TDWork:
+    n, dev = engine.n_envs, engine.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    return TDWork(NTupleEval(None, torch.empty(n, dtype=torch.uint8, device=dev), None,
+                             torch.empty((n, 16), dtype=torch.uint8, device=dev), torch.empty(n, **i64)),
+                  NTupleEval(None, None, torch.empty(n, **i64), None, None), torch.empty(n, **i64))
+
+
+def td_evaluate(engine, net, work) -> TDWork:
+    """Points 1-3 of the TD(0) step and the delta of point 4, leaving the weights alone: evaluate, play the greedy move
+    (auto-reset on), evaluate the new boards, ``work.delta = (0 if terminated else best') - V(after)``.  Shards that share
+    one weight tensor run this on every shard before :func:`td_update` on any, so that all of them see the same weights."""
+    engine.ntuple_evaluate(net, out=work.before)
+    engine.step(work.before.action, auto_reset=True, want_info=False)
+    engine.ntuple_evaluate(net, out=work.after)
+    work.delta.copy_(work.after.best)
+    work.delta.masked_fill_(engine.terminated.bool(), 0)
+    work.delta.sub_(work.before.after_value)
+    return work
+
+
+def td_update(net, work, lr_shift):
+    """Point 4: ``net.update(after, delta, lr_shift)`` with what :func:`td_evaluate` left in ``work``."""
+    net.update(work.before.after, work.delta, lr_shift)
+
+
+def td_step(engine, net, lr_shift, work=None) -> TDWork:
+    """One afterstate TD(0) step of every board of ``engine`` (a ``Batched2048``) under ``net``, on the engine's stream:
+    evaluate, play the greedy move, evaluate the new boards, and move V of the afterstate just played towards what
+    followed it (:func:`td_evaluate`, then :func:`td_update`).  The weights change only in that last launch.  No host
+    synchronisation; ``work`` (:func:`td_work`) is reused."""
+    work = td_evaluate(engine, net, td_work(engine) if work is None else work)
+    td_update(net, work, lr_shift)
+    return work
+
+
+def train(engine, net, n_steps, lr_shift):
+    """``n_steps`` :func:`td_step` calls with one set of buffers."""
+    work = td_work(engine)
+    for _ in range(int(n_steps)):
+        td_step(engine, net, lr_shift, work)
+    return net

@@ -99,7 +99,8 @@ class Transitions:
                    order(rew).reshape(-1), exp_to_values(order(nxt)).reshape(-1, 4, 4), order(done).reshape(-1))
 
     @classmethod
-    def record_search(cls, engine, n_steps, depth=2, weights=None, player="expectimax", rollouts=64, max_steps=None, seed=0):
+    def record_search(cls, engine, n_steps, depth=2, weights=None, player="expectimax", rollouts=64, max_steps=None, seed=0,
+                      net=None):
         """Play ``n_steps`` searched moves on a ``Batched2048`` and record every transition: a behaviour-cloning data
         set in the reference's CSV format (``export_csv``), with a search in place of the person at the keyboard of
         gather_training_data.py.  ``player="expectimax"`` (the default): each step's action is
@@ -107,7 +108,8 @@ class Transitions:
         ``engine.mc_search(rollouts, max_steps, seed=mc_step_seed(seed, engine.clock)).action`` (``max_steps`` None = the
         default of ``mc_search``; ``depth`` and ``weights`` are not used) -- the clock advances with every step, so
         every step draws fresh playouts, and the same base ``seed`` on the same engine state repeats the recording.
-        The action is written straight into the recorded action row.  Rows as in :meth:`record`: env-major, and
+        ``player="ntuple"``: it is ``engine.ntuple_evaluate(net).action``, the greedy move of the :class:`NTupleNet`
+        ``net`` (nothing else is used).  The action is written straight into the recorded action row.  Rows as in :meth:`record`: env-major, and
         ``next_board`` of a step that ends an episode is the terminal board."""
         from .batched import MC_DEFAULT_MAX_STEPS, MCSearch, Search
         if player == "expectimax":
@@ -118,8 +120,15 @@ class Transitions:
 
             def choose(j, row):
                 engine.mc_search(rollouts, cap, seed=mc_step_seed(seed, engine.clock), out=MCSearch(row, None, None))
+        elif player == "ntuple":
+            from .ntuple import NTupleEval, NTupleNet
+            if not isinstance(net, NTupleNet):
+                raise ValueError("player='ntuple' needs net=an NTupleNet")
+
+            def choose(j, row):
+                engine.ntuple_evaluate(net, out=NTupleEval(None, row, None, None, None))
         else:
-            raise ValueError(f"player must be 'expectimax' or 'mc', not {player!r}")
+            raise ValueError(f"player must be 'expectimax', 'mc' or 'ntuple', not {player!r}")
         return cls._record_loop(engine, int(n_steps), None, choose)
 
     # ------------------------------------------------------------------ returns

@@ -377,6 +377,62 @@ int g2048_mc_search(const g2048_engine *e, const g2048_mc_io *io, void *stream);
  * device.  1 <= n <= 2^32 - 256. */
 int g2048_mc_search_plain(const uint8_t *boards, uint64_t n, uint32_t index_offset, const g2048_mc_io *io, void *stream);
 
+/* N-tuple network value function: batched evaluation (a greedy player) and the TD(0) weight update, in integers
+ * (Szubert & Jaskowski 2014).  The caller owns the weights.  A network is T tuples of L cells each;
+ * tuple t has a table of 16^L int32 weights, a weight being a score in units of 2^-F.
+ *   cell value  c(e) = min(e mod 32, 15): exponents are taken mod 32 as in g2048_set_boards, tiles of 2^15 and above share
+ *               the last table row; for engine records the cell is byte & 0x1f (the score-deficit bits are ignored).
+ *   index       idx_t(b) = sum over k < L of c(b[cells[t][k]]) << 4k
+ *   value       V(b) = sum over the 8 symmetries s of b, sum over t < T of weights[t][idx_t(s(b))]
+ *               The symmetries are those of g2048_augment / training_data.augment(); the order is irrelevant (a sum).
+ *               V is int64, |V| <= 64 * 2^31.  A table entry reached by two symmetries of a symmetric board counts twice.
+ *   evaluate    (per board b) for d = 0..3: (a_d, g_d) = move(b, d), q[d] = (g_d << F) + V(a_d), or G2048_NTUPLE_ILLEGAL
+ *               where d is illegal.  action = the smallest d of largest q among the legal d (q may be negative), 0 when
+ *               none is legal; best = q[action], after = a_action, after_value = V(after) -- or 0, the input board and 0
+ *               when no move is legal.
+ *   update      for plain boards a_i and int64 delta_i, i < n, and a shift lr_shift in 0..40:
+ *               step_i = sat_int32(delta_i >> lr_shift) (an arithmetic shift: it floors negatives); for every symmetry s
+ *               and tuple t: weights[t][idx_t(s(a_i))] += step_i, a 32-bit add that wraps mod 2^32 (the caller's lr_shift
+ *               keeps weights away from the wrap).  step_i == 0 touches nothing.  Exact: the final weights are the same
+ *               bits whatever the order, however the batch is split over lanes, launches or shards.
+ *   TD(0) step of an engine under weights W (unchanged until 4):  1. E = evaluate(boards);  2. g2048_step with E.action,
+ *               keep terminated;  3. E' = evaluate(boards after the step; with auto-reset a finished board is already its
+ *               fresh board);  4. delta_i = (terminated_i ? 0 : E'.best_i) - E.after_value_i, update(E.after, delta,
+ *               lr_shift).  All on one stream, no host synchronisation (gym2048_amd.ntuple.td_step). */
+#define G2048_NTUPLE_MAX_TUPLES 8
+#define G2048_NTUPLE_MAX_LEN 6
+#define G2048_NTUPLE_MAX_FRAC_BITS 16
+#define G2048_NTUPLE_MAX_LR_SHIFT 40
+#define G2048_NTUPLE_ILLEGAL INT64_MIN
+typedef struct g2048_ntuple_net {
+    uint32_t n_tuples;      /* T, 1..8 */
+    uint32_t tuple_len;     /* L, 1..6: every tuple has L cells, its table 16^L entries */
+    uint32_t frac_bits;     /* F, 0..16: a weight is a score in units of 2^-F */
+    uint8_t cells[8][6];    /* cells[t][k] in 0..15 (row-major cell index), distinct within a tuple */
+    int32_t *weights;       /* device, [T][16^L], 16-byte aligned */
+} g2048_ntuple_net;
+/* Outputs of evaluate: device pointers, NULL = not wanted, but at least one must be given. */
+typedef struct g2048_ntuple_io {
+    int64_t *value;         /* [n][4] q, G2048_NTUPLE_ILLEGAL where the move is illegal; 16-byte aligned */
+    uint8_t *action;        /* [n] */
+    int64_t *best;          /* [n] */
+    uint8_t *after;         /* [n][16] plain cells of the chosen afterstate; 16-byte aligned */
+    int64_t *after_value;   /* [n] */
+} g2048_ntuple_io;
+
+/* Evaluate the engine's live records in one launch, enqueued on `stream`: consumes no randomness, leaves the records,
+ * the clock, the episode bookkeeping and cached graphs alone, in either RNG mode (like g2048_expectimax). */
+int g2048_ntuple_evaluate(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_io *io, void *stream);
+/* The same for n plain boards (uint8[n][16] exponents, device memory, 16-byte aligned).  Needs no engine; runs on the
+ * current device.  1 <= n <= 2^32 - 256. */
+int g2048_ntuple_evaluate_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_io *io,
+                                void *stream);
+/* v[i] = V(boards[i]) for n plain boards, one board per lane. */
+int g2048_ntuple_values_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, int64_t *v, void *stream);
+/* The update above in one launch: n plain boards, delta int64[n] (device), lr_shift 0..40. */
+int g2048_ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift,
+                              const g2048_ntuple_net *net, void *stream);
+
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream);
