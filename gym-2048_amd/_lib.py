@@ -108,6 +108,15 @@ class NTupleIO(C.Structure):
     ]
 
 
+class NTupleSearchIO(C.Structure):
+    """g2048_ntuple_search_io (include/g2048.h): depth and device output pointers (NULL = not wanted)."""
+    _fields_ = [
+        ("depth", C.c_uint32),
+        ("action", C.c_void_p),
+        ("value", C.c_void_p),
+    ]
+
+
 class Stats(C.Structure):
     """g2048_stats (include/g2048.h)."""
     _fields_ = [
@@ -167,6 +176,8 @@ SIGNATURES = {
     "g2048_mc_search_plain": (C.c_int, [C.c_void_p, _u64, _u32, C.POINTER(MCIO), _S]),
     "g2048_ntuple_evaluate": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleIO), _S]),
     "g2048_ntuple_evaluate_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleIO), _S]),
+    "g2048_ntuple_search": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), _S]),
+    "g2048_ntuple_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), _S]),
     "g2048_ntuple_values_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.c_void_p, _S]),
     "g2048_ntuple_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, C.POINTER(NTupleNetC), _S]),
     "g2048_add_tile": (C.c_int, [_E, _u32, _S]),

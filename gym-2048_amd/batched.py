@@ -20,7 +20,8 @@ from ._lib import G2048Error, HostIO, StepIO, Stats, check
 from .analysis import (MC_DEFAULT_MAX_STEPS, Afterstates, MCSearch, Search, SearchWeights, afterstates,  # noqa: F401
                        expectimax, mc_search, _OBS_DTYPES, _afterstate_io, _mc_io, _search_io)
 # the n-tuple network value function, re-exported; Batched2048.ntuple_evaluate runs it on the live boards
-from .ntuple import NTupleEval, NTupleNet, TUPLES, td_step, train, _eval_io  # noqa: F401
+from .ntuple import NTupleEval, NTupleNet, NTupleSearch, TUPLES, td_step, train, _eval_io  # noqa: F401
+from .ntuple import _search_io as _ntuple_search_io
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}
 
@@ -718,6 +719,18 @@ class Batched2048:
         ref = net._ref(self.device)
         io, out = _eval_io(self.n_envs, self.device, out)
         check(self._lib.g2048_ntuple_evaluate(self._h, ref, C.byref(io), self._stream()))
+        return out
+
+    def ntuple_search(self, net, depth=1, out=None) -> NTupleSearch:
+        """Expectimax over an n-tuple network's afterstate values on the live boards (``g2048_ntuple_search``,
+        INTEGRATION.md §10): ``NTupleSearch(action [n], value [n, 4])`` on the engine's stream, as
+        :meth:`NTupleNet.search`.  ``depth`` 1..2; ``step(result.action)`` plays the chosen move.  ``out``: a preallocated
+        ``NTupleSearch`` (fields that are None are not written).  Touches no record, clock, statistic or randomness."""
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        ref = net._ref(self.device)
+        io, out = _ntuple_search_io(self.n_envs, self.device, depth, out)
+        check(self._lib.g2048_ntuple_search(self._h, ref, C.byref(io), self._stream()))
         return out
 
     def isend_numpy(self) -> np.ndarray:

@@ -1323,6 +1323,57 @@ int g2048_ntuple_evaluate_plain(const uint8_t *boards, uint64_t n, const g2048_n
     return G2048_OK;
 }
 
+} // extern "C"
+
+// g2048_ntuple_search_io -> the kernel's outputs, or G2048_ERR_INVALID (before any HIP call: works without a device)
+static int ntuple_search_out(const g2048_ntuple_search_io *io, g2048::NtupleSearchOut *o)
+{
+    if (!io)
+        return fail(G2048_ERR_INVALID, "io is NULL");
+    if (!io->action && !io->value)
+        return fail(G2048_ERR_INVALID, "g2048_ntuple_search_io requests no output (action and value are both NULL)");
+    if (reinterpret_cast<uintptr_t>(io->value) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple search value needs 16 bytes");
+    if (io->depth < 1 || io->depth > G2048_NTUPLE_SEARCH_MAX_DEPTH)
+        return fail(G2048_ERR_INVALID, "depth=%u: need 1 <= depth <= %d", io->depth, G2048_NTUPLE_SEARCH_MAX_DEPTH);
+    *o = g2048::NtupleSearchOut{io->action, io->value};
+    return G2048_OK;
+}
+
+extern "C" {
+
+int g2048_ntuple_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io, void *stream)
+{
+    if (int rc = usable(e))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleSearchOut o;
+    if (int rc = ntuple_search_out(io, &o))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(g2048::launch_ntuple_search(e->st.boards, static_cast<uint32_t>(e->n), io->depth, false, nn, o,
+                                          static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_ntuple_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io,
+                              void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleSearchOut o;
+    if (int rc = ntuple_search_out(io, &o))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_search(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), io->depth, true, nn, o,
+                                          static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 int g2048_ntuple_values_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, int64_t *v, void *stream)
 {
     if (int rc = plain_boards(boards, n))

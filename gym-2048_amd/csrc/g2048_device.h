@@ -463,22 +463,31 @@ G2048_DEV Board place(const Board &bd, uint32_t p, uint32_t v)
 
 template <int D, class Tables> G2048_DEV uint32_t search_value(const Board &bd, const SearchWeights &w, const Tables &tb);
 
-// Part of the chance-node sum of afterstate `a`: the items t = sub, sub + K, ... of the 2E items (item t = empty cell
-// t / 2 in bit order, spawn exponent 1 + t % 2 with weight 9 / 1).  K lanes with sub = 0 .. K-1 cover the whole sum.
-template <int D, class Tables>
-G2048_DEV uint64_t chance_partial(const Board &a, uint32_t sub, uint32_t K, const SearchWeights &w, const Tables &tb)
+// The chance items t = sub, sub + K, ... of the 2E items of afterstate `a` (item t = empty cell t / 2 in bit order, spawn
+// exponent 1 + t % 2 with weight 9 / 1): f(child board, weight) for each.  K lanes with sub = 0 .. K-1 cover all items.
+// The one item walk of both searches (chance_partial here, ntuple_chance_partial below).
+template <class F> G2048_DEV void chance_items(const Board &a, uint32_t sub, uint32_t K, F &&f)
 {
     uint32_t m = empty_bits(a), skipped = 0;
     const uint32_t items = 2u * g2048_popc(m);
-    uint64_t sum = 0;
 #pragma unroll 1
     for (uint32_t t = sub; t < items; t += K) {
 #pragma unroll 1
         for (; skipped < (t >> 1); ++skipped)
             m &= m - 1u;
         const uint32_t v = 1u + (t & 1u);
-        sum += static_cast<uint64_t>(v == 1u ? 9u : 1u) * search_value<D - 1>(place(a, g2048_ctz(m), v), w, tb);
+        f(place(a, g2048_ctz(m), v), v == 1u ? 9u : 1u);
     }
+}
+
+// Part of the chance-node sum of afterstate `a`: the items sub, sub + K, ... (chance_items).
+template <int D, class Tables>
+G2048_DEV uint64_t chance_partial(const Board &a, uint32_t sub, uint32_t K, const SearchWeights &w, const Tables &tb)
+{
+    uint64_t sum = 0;
+    chance_items(a, sub, K, [&](const Board &child, uint32_t weight) {
+        sum += static_cast<uint64_t>(weight) * search_value<D - 1>(child, w, tb);
+    });
     return sum;
 }
 
@@ -827,6 +836,93 @@ template <uint32_t T, class Add> G2048_DEV void ntuple_update(uint64_t packed, c
 #pragma unroll
         for (uint32_t t = 0; t < T; ++t)
             add(ntuple_offset(packed, sh, s, t), step);
+}
+
+// ------------------------------------------------------------------- n-tuple expectimax
+// g2048_ntuple_search (include/g2048.h): the expectimax of above with the network at the leaves.
+// Integers only, so every split of the tree across lanes gives the same bits.  With V, move(b, d) = (a_d, g_d, legal)
+// as in the n-tuple block, a cell empty when it equals 0 and E(a) the number of empty cells:
+//   A_0(a) = V(a)
+//   S_k(b) = max over legal d of ((g_d << F) + A_k(a_d));   0 when no move is legal           (S_0 = evaluate's best)
+//   A_k(a) = floor(sum over empty c of (9 S_{k-1}(a, 2 in c) + S_{k-1}(a, 4 in c)) / (10 E(a)))   for k >= 1
+//   value[d] = (g_d << F) + A_D(a_d), kNtupleIllegal where d is illegal; action = the smallest d of largest value among
+//   the legal d, 0 when none is legal.  D = 1..2 (kNtupleSearchMaxDepth).
+// floor rounds toward minus infinity (weights are signed: the sum may be negative); an afterstate of a legal move has
+// E >= 1.  Bounds: |V| <= 2^37 and g < 2^31, so |(g << F) + V| < 2^48 and every level adds at most one more g << F:
+// |value| < 2^50.  A chance sum has weights that add up to 10 E <= 150: it stays below 150 * 2^50 < 2^58, an int64 in
+// every lane, and the 2^60 bias of ntuple_key still makes every legal key positive.
+constexpr uint32_t kNtupleSearchMaxDepth = 2; // = G2048_NTUPLE_SEARCH_MAX_DEPTH (g2048.h)
+
+// floor(a / b) for b > 0: C++ '/' truncates toward zero, one too high for a negative inexact quotient
+G2048_DEV int64_t floor_div(int64_t a, int64_t b)
+{
+    const int64_t q = a / b;
+    return q - (a - q * b < 0 ? 1 : 0);
+}
+
+template <int D, uint32_t T, class Tables>
+G2048_DEV int64_t ntuple_search_state(const Board &b, const NtupleShape &sh, uint32_t F, const int32_t *weights, const Tables &tb);
+
+// Part of the chance-node sum of afterstate `a`: the items sub, sub + K, ... of chance_items, each weight * S_{D-1}.
+template <int D, uint32_t T, class Tables>
+G2048_DEV int64_t ntuple_chance_partial(const Board &a, uint32_t sub, uint32_t K, const NtupleShape &sh, uint32_t F,
+                                        const int32_t *weights, const Tables &tb)
+{
+    int64_t sum = 0;
+    chance_items(a, sub, K, [&](const Board &child, uint32_t weight) {
+        sum += static_cast<int64_t>(weight) * ntuple_search_state<D - 1, T>(child, sh, F, weights, tb);
+    });
+    return sum;
+}
+
+// A_D(a); for D >= 1 a must have an empty cell
+template <int D, uint32_t T, class Tables>
+G2048_DEV int64_t ntuple_after_value(const Board &a, const NtupleShape &sh, uint32_t F, const int32_t *weights, const Tables &tb)
+{
+    if constexpr (D == 0)
+        return ntuple_value<T>(ntuple_pack(a), sh, weights);
+    else
+        return floor_div(ntuple_chance_partial<D, T>(a, 0u, 1u, sh, F, weights, tb), 10 * static_cast<int64_t>(count_empty(a)));
+}
+
+// S_D(b).  As in search_value the four moves are one loop body with a run-time selector row and the depths D .. 0 one
+// inlined body each: no recursion and no per-lane array at run time.  A leaf (D = 0) looks up its moves one after the
+// other, 8T gathers in flight at a time, which keeps the registers of T = 8 out of scratch.
+template <int D, uint32_t T, class Tables>
+G2048_DEV int64_t ntuple_search_state(const Board &b, const NtupleShape &sh, uint32_t F, const int32_t *weights, const Tables &tb)
+{
+    int64_t best = 0;
+    bool any = false;
+#pragma unroll 1
+    for (uint32_t m = 0; m < 4u; ++m) {
+        Board a = b;
+        uint32_t gain;
+        if (move_sel(a, tb.move_sel(m), gain)) {
+            const int64_t q = static_cast<int64_t>(static_cast<uint64_t>(gain) << F) + ntuple_after_value<D, T>(a, sh, F, weights, tb);
+            best = !any || q > best ? q : best;
+            any = true;
+        }
+    }
+    return best;
+}
+
+// The root on one thread: value[4] and the action.  The kernel splits the same chance sums across lanes
+// (ntuple_chance_partial) and joins the four keys with shuffles.
+template <int D, uint32_t T, class Tables>
+G2048_DEV uint32_t ntuple_search_root(const Board &cells, const NtupleShape &sh, uint32_t F, const int32_t *weights,
+                                      const Tables &tb, int64_t value[4])
+{
+    uint64_t best = 0;
+    for (uint32_t d = 0; d < 4u; ++d) {
+        Board a = cells;
+        uint32_t gain;
+        const bool legal = move_sel(a, tb.move_sel(d), gain);
+        value[d] = legal ? static_cast<int64_t>(static_cast<uint64_t>(gain) << F) + ntuple_after_value<D, T>(a, sh, F, weights, tb)
+                         : kNtupleIllegal;
+        const uint64_t key = ntuple_key(value[d], legal, d);
+        best = key > best ? key : best;
+    }
+    return root_key_action(best);
 }
 
 // ------------------------------------------------------------------- the 16-byte board RECORD

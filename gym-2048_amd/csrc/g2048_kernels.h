@@ -128,6 +128,13 @@ struct NtupleOut {
     int64_t *after_value; // [n]
 };
 hipError_t launch_ntuple_eval(const uint4 *boards, uint32_t n, bool plain, const NtupleNet &net, const NtupleOut &o, hipStream_t s);
+// g2048_ntuple_search's outputs (g2048_ntuple_search_io), checked by the caller; depth in 1..2
+struct NtupleSearchOut {
+    uint8_t *action; // [n]
+    int64_t *value;  // [n][4]
+};
+hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
+                                const NtupleSearchOut &o, hipStream_t s);
 hipError_t launch_ntuple_values(const uint4 *boards, uint32_t n, const NtupleNet &net, int64_t *v, hipStream_t s);
 hipError_t launch_ntuple_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
                                 hipStream_t s);

@@ -1572,6 +1572,53 @@ __global__ void __launch_bounds__(kBlock) ntuple_eval_kernel(const uint4 *__rest
     }
 }
 
+// g2048_ntuple_search: the depth-D search of g2048_device.h ("n-tuple expectimax") for every board.  A board is a
+// LaneGroup<G>, K = G / 4 lanes per root direction d; lane `sub` of direction d takes the chance items sub, sub + K, ...
+// of that direction's afterstate (ntuple_chance_partial), the K int64 partial sums meet in an xor-shuffle tree, the floor
+// division happens once per direction and the four keys meet in group_best_key.  The kernel is gather-latency bound: a
+// leaf is four moves of 8T independent loads each, and the only thing that hides their latency is other waves.
+// G per depth (kNtupleSearchGroup): 16 at depth 1, where a direction has at most 30 items and K = 4 lanes leave each lane a
+// few leaves in a row, and 64 at depth 2, as in expectimax_kernel, where an item is a whole depth-1 tree.  These are the
+// starting values: G = 4, 16, 64 at depth 1 and 16, 32, 64 at depth 2 have NOT been timed against each other yet
+// (tools/ntuple_search_probe.py --lib times a build with other values; profiles/r12_ntuple_search_probe.txt says what
+// was and was not measured).  The weights are read with plain loads and nothing but the outputs is
+// written: no record, clock, episode slot or randomness is touched.  Lanes stride over the boards when n * G exceeds the
+// grid cap (kSearchMaxLanes); PLAIN as in expectimax_kernel.
+template <int D> constexpr uint32_t kNtupleSearchGroup = D == 1 ? 16u : 64u;
+
+template <int D, uint32_t T, bool PLAIN>
+__global__ void __launch_bounds__(kBlock) ntuple_search_kernel(const uint4 *__restrict__ boards, uint32_t n, const NtupleShape sh,
+                                                               uint32_t frac_bits, const int32_t *__restrict__ weights,
+                                                               const NtupleSearchOut o)
+{
+    constexpr uint32_t G = kNtupleSearchGroup<D>, K = G / 4u;
+    __shared__ WaveTables s_tables[kBlock / 64];
+    const LdsTables tb = stage_tables(s_tables, load_tables_piece());
+    const LaneGroup<G> grp;
+    const uint32_t j = grp.j, d = grp.d, sub = grp.sub;
+    for (uint64_t i = grp.first; i < n; i += grp.stride) {
+        const Board in = load_board(boards, static_cast<uint32_t>(i));
+        const Board cells = input_cells<PLAIN>(in);
+        Board after = cells;
+        uint32_t gain;
+        const bool legal = move_sel(after, tb.move_sel(d), gain);
+        long long part = 0;
+        if (legal)
+            part = ntuple_chance_partial<D, T>(after, sub, K, sh, frac_bits, weights, tb);
+#pragma unroll
+        for (uint32_t x = K / 2u; x > 0u; x >>= 1)
+            part += __shfl_xor(part, x);
+        // (an illegal direction divides its 0 by 1: its afterstate may have no empty cell)
+        const int64_t chance = floor_div(part, legal ? 10 * static_cast<int64_t>(count_empty(after)) : 1);
+        const int64_t value = legal ? static_cast<int64_t>(static_cast<uint64_t>(gain) << frac_bits) + chance : kNtupleIllegal;
+        const uint64_t key = group_best_key(ntuple_key(value, legal, d), K);
+        if (sub == 0u && o.value)
+            o.value[i * 4u + d] = value;
+        if (j == 0u && o.action)
+            o.action[i] = static_cast<uint8_t>(root_key_action(key));
+    }
+}
+
 // g2048_ntuple_values_plain: V of every board, one board per lane, the same gathers.
 template <uint32_t T>
 __global__ void __launch_bounds__(kBlock) ntuple_values_kernel(const uint4 *__restrict__ boards, uint32_t n, const NtupleShape sh,
@@ -2207,6 +2254,20 @@ hipError_t launch_ntuple_eval(const uint4 *boards, uint32_t n, bool plain, const
         return dispatch_bool(plain, [&](auto plain_c) {
             return launch_1d(ntuple_eval_kernel<tc, plain_c>, group_lanes(n, 4u), 0, s, boards, n, sh, net.frac_bits,
                              static_cast<const int32_t *>(net.weights), o);
+        });
+    });
+}
+
+hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
+                                const NtupleSearchOut &o, hipStream_t s)
+{
+    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
+    return dispatch<1, static_cast<int>(kNtupleSearchMaxDepth)>(static_cast<int>(depth), [&](auto dc) {
+        return dispatch_tuples(net, [&](auto tc) {
+            return dispatch_bool(plain, [&](auto plain_c) {
+                return launch_1d(ntuple_search_kernel<dc, tc, plain_c>, group_lanes(n, kNtupleSearchGroup<dc>), 0, s, boards, n, sh,
+                                 net.frac_bits, static_cast<const int32_t *>(net.weights), o);
+            });
         });
     });
 }

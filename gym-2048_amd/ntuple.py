@@ -5,6 +5,8 @@ per update.  Everything is an integer: the same bits however the batch is split 
 
 ``NTupleNet`` owns the weights (a device tensor); ``Batched2048.ntuple_evaluate`` evaluates the engine's live boards;
 ``td_step`` / ``train`` chain evaluate, ``g2048_step`` and update on the device with no host synchronisation.
+``NTupleNet.search`` / ``Batched2048.ntuple_search`` play the network through a depth-1..2 expectimax
+(``g2048_ntuple_search``), one launch for the whole batch.
 """
 from __future__ import annotations
 
@@ -14,11 +16,12 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import NTupleIO, NTupleNetC, check
+from ._lib import NTupleIO, NTupleNetC, NTupleSearchIO, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
 ILLEGAL = -(1 << 63)                                              # G2048_NTUPLE_ILLEGAL: q of an illegal move
+SEARCH_MAX_DEPTH = 2                                              # G2048_NTUPLE_SEARCH_MAX_DEPTH
 
 # Default shapes, as row-major cell indices (cell 4r + c).  The value sums every tuple over the eight symmetries of the
 # board, so a shape lists each tuple once, not once per placement.
@@ -53,6 +56,26 @@ def _eval_io(n, device, out):
     io = NTupleIO()
     _bind_out(io, out, {"value": ((n, 4), (torch.int64,)), "action": ((n,), (torch.uint8,)), "best": ((n,), (torch.int64,)),
                         "after": ((n, 16), (torch.uint8,)), "after_value": ((n,), (torch.int64,))}, device)
+    return io, out
+
+
+class NTupleSearch(NamedTuple):
+    """Result of search (``g2048_ntuple_search``).  Device tensors; a field that is None was not asked for (``out``)."""
+    action: Optional[torch.Tensor]       # uint8 [n]: the smallest d of largest value among the legal d; 0 when none is legal
+    value: Optional[torch.Tensor]        # int64 [n, 4]: (merge score << F) + A_depth(afterstate d); ILLEGAL where d is illegal
+
+
+def _search_io(n, device, depth, out):
+    """(NTupleSearchIO, NTupleSearch) for n boards: ``depth`` checked, ``out`` checked field by field or freshly allocated."""
+    depth = _int_arg("depth", depth, 1, SEARCH_MAX_DEPTH)
+    if out is None:
+        out = NTupleSearch(torch.empty(n, dtype=torch.uint8, device=device), torch.empty((n, 4), dtype=torch.int64, device=device))
+    else:
+        out = NTupleSearch(*out)
+        if out.action is None and out.value is None:
+            raise ValueError("out requests no output (action and value are both None)")
+    io = NTupleSearchIO(depth)
+    _bind_out(io, out, {"action": ((n,), (torch.uint8,)), "value": ((n, 4), (torch.int64,))}, device)
     return io, out
 
 
@@ -131,6 +154,17 @@ class NTupleNet:
         net = self._ref(device)
         io, out = _eval_io(n, device, out)
         self._launch(_lib.load().g2048_ntuple_evaluate_plain, boards, net, C.byref(io))
+        return out
+
+    def search(self, boards, depth=1, out=None) -> NTupleSearch:
+        """Expectimax over the network's afterstate values on plain boards (``g2048_ntuple_search_plain``, INTEGRATION.md
+        §10): ``depth`` 1..2 chance levels below the root move, :meth:`evaluate`'s ``best`` at the leaves (depth 0 is
+        :meth:`evaluate`).  One launch on the current stream of the boards' device.  ``out``: a preallocated
+        :class:`NTupleSearch` (a field that is None is not written)."""
+        n, device = _plain_boards(boards)
+        net = self._ref(device)
+        io, out = _search_io(n, device, depth, out)
+        self._launch(_lib.load().g2048_ntuple_search_plain, boards, net, C.byref(io))
         return out
 
     def update(self, boards, delta, lr_shift):

@@ -100,7 +100,7 @@ class Transitions:
 
     @classmethod
     def record_search(cls, engine, n_steps, depth=2, weights=None, player="expectimax", rollouts=64, max_steps=None, seed=0,
-                      net=None):
+                      net=None, net_depth=0):
         """Play ``n_steps`` searched moves on a ``Batched2048`` and record every transition: a behaviour-cloning data
         set in the reference's CSV format (``export_csv``), with a search in place of the person at the keyboard of
         gather_training_data.py.  ``player="expectimax"`` (the default): each step's action is
@@ -109,7 +109,9 @@ class Transitions:
         default of ``mc_search``; ``depth`` and ``weights`` are not used) -- the clock advances with every step, so
         every step draws fresh playouts, and the same base ``seed`` on the same engine state repeats the recording.
         ``player="ntuple"``: it is ``engine.ntuple_evaluate(net).action``, the greedy move of the :class:`NTupleNet`
-        ``net`` (nothing else is used).  The action is written straight into the recorded action row.  Rows as in :meth:`record`: env-major, and
+        ``net`` -- or, with ``net_depth`` 1..2, ``engine.ntuple_search(net, net_depth).action``, the network played through
+        that many levels of expectimax (``depth`` belongs to the expectimax player and is not used).  The action is
+        written straight into the recorded action row.  Rows as in :meth:`record`: env-major, and
         ``next_board`` of a step that ends an episode is the terminal board."""
         from .batched import MC_DEFAULT_MAX_STEPS, MCSearch, Search
         if player == "expectimax":
@@ -121,12 +123,17 @@ class Transitions:
             def choose(j, row):
                 engine.mc_search(rollouts, cap, seed=mc_step_seed(seed, engine.clock), out=MCSearch(row, None, None))
         elif player == "ntuple":
-            from .ntuple import NTupleEval, NTupleNet
+            from .analysis import _int_arg
+            from .ntuple import SEARCH_MAX_DEPTH, NTupleEval, NTupleNet, NTupleSearch
             if not isinstance(net, NTupleNet):
                 raise ValueError("player='ntuple' needs net=an NTupleNet")
+            net_depth = _int_arg("net_depth", net_depth, 0, SEARCH_MAX_DEPTH)
 
             def choose(j, row):
-                engine.ntuple_evaluate(net, out=NTupleEval(None, row, None, None, None))
+                if net_depth == 0:
+                    engine.ntuple_evaluate(net, out=NTupleEval(None, row, None, None, None))
+                else:
+                    engine.ntuple_search(net, net_depth, out=NTupleSearch(row, None))
         else:
             raise ValueError(f"player must be 'expectimax', 'mc' or 'ntuple', not {player!r}")
         return cls._record_loop(engine, int(n_steps), None, choose)

@@ -433,6 +433,36 @@ int g2048_ntuple_values_plain(const uint8_t *boards, uint64_t n, const g2048_ntu
 int g2048_ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift,
                               const g2048_ntuple_net *net, void *stream);
 
+/* N-tuple expectimax: a depth-1..2 search of every board with the network at the leaves, in one launch (INTEGRATION.md
+ * §10) -- the player the n-tuple literature plays with.  Notation of the block above: net (T, L, F, cells, weights),
+ * V(a) the sum over the 8 symmetries and T tuples, move(b, d) = (a_d, g_d, legal); cells are exponents, a cell is empty
+ * when it equals 0, E(a) is the number of empty cells.  All values are integers, exact, and independent of how the work
+ * is split:
+ *   A_0(a) = V(a)
+ *   S_k(b) = max over legal d of ((g_d << F) + A_k(a_d));   0 when no move is legal
+ *   A_k(a) = floor( sum over empty c of (9 * S_{k-1}(a, 2 in c) + S_{k-1}(a, 4 in c)) / (10 * E(a)) )   for k >= 1
+ * floor rounds toward minus infinity (weights are signed, the sum may be negative); an afterstate of a legal move always
+ * has E >= 1; S_0(b) is `best` of g2048_ntuple_evaluate.  Outputs for depth = D in 1..2:
+ *   value[d] = (g_d << F) + A_D(a_d), or G2048_NTUPLE_ILLEGAL where d is illegal;
+ *   action   = the smallest d of largest value among the legal d, or 0 when none is legal.
+ * Depth 0 is g2048_ntuple_evaluate.  Bounds: |V| <= 2^37 and g < 2^31, so |value| < 2^50; a chance sum is below
+ * 150 * 2^50 < 2^58, so int64 partial sums are safe in any split.  Boards are read exactly as g2048_ntuple_evaluate reads
+ * them: the engine form uses byte & 0x1f, the plain form exponents mod 32, the index c(e) = min(e mod 32, 15). */
+#define G2048_NTUPLE_SEARCH_MAX_DEPTH 2
+typedef struct g2048_ntuple_search_io {
+    uint32_t depth;      /* 1..G2048_NTUPLE_SEARCH_MAX_DEPTH */
+    uint8_t *action;     /* [n], or NULL */
+    int64_t *value;      /* [n][4], 16-byte aligned, or NULL */
+} g2048_ntuple_search_io;
+/* Search the engine's live records in one launch, enqueued on `stream`: consumes no randomness, leaves the records, the
+ * clock, the episode bookkeeping and cached graphs alone, in either RNG mode (like g2048_ntuple_evaluate).  At least one
+ * of action and value must be given. */
+int g2048_ntuple_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io, void *stream);
+/* The same for n plain boards (uint8[n][16] exponents, device memory, 16-byte aligned).  Needs no engine; runs on the
+ * current device.  1 <= n <= 2^32 - 256. */
+int g2048_ntuple_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io,
+                              void *stream);
+
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream);
