@@ -117,6 +117,14 @@ class NTupleSearchIO(C.Structure):
     ]
 
 
+class NTupleTCC(C.Structure):
+    """g2048_ntuple_tc (include/g2048.h): the device accumulators of temporal-coherence learning, int64 [T][16^L] each."""
+    _fields_ = [
+        ("err", C.c_void_p),
+        ("mag", C.c_void_p),
+    ]
+
+
 class Stats(C.Structure):
     """g2048_stats (include/g2048.h)."""
     _fields_ = [
@@ -180,6 +188,8 @@ SIGNATURES = {
     "g2048_ntuple_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), _S]),
     "g2048_ntuple_values_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.c_void_p, _S]),
     "g2048_ntuple_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, C.POINTER(NTupleNetC), _S]),
+    "g2048_ntuple_tc_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleNetC),
+                                              C.POINTER(NTupleTCC), _S]),
     "g2048_add_tile": (C.c_int, [_E, _u32, _S]),
     "g2048_fill_random_actions": (C.c_int, [_E, _u64, _u32, C.c_void_p, _S]),
     "g2048_onehot": (C.c_int, [_E, C.c_void_p, _i32, _S]),

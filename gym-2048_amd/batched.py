@@ -21,6 +21,7 @@ from .analysis import (MC_DEFAULT_MAX_STEPS, Afterstates, MCSearch, Search, Sear
                        expectimax, mc_search, _OBS_DTYPES, _afterstate_io, _mc_io, _search_io)
 # the n-tuple network value function, re-exported; Batched2048.ntuple_evaluate runs it on the live boards
 from .ntuple import NTupleEval, NTupleNet, NTupleSearch, TUPLES, td_step, train, _eval_io  # noqa: F401
+from .ntuple import NTupleTC, tc_step, tc_train, tc_update  # noqa: F401
 from .ntuple import _search_io as _ntuple_search_io
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}

@@ -1409,6 +1409,35 @@ int g2048_ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t *
     return G2048_OK;
 }
 
+int g2048_ntuple_tc_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                 const g2048_ntuple_net *net, const g2048_ntuple_tc *tc, void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (!delta)
+        return fail(G2048_ERR_INVALID, "delta is NULL");
+    if (reinterpret_cast<uintptr_t>(delta) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple delta needs 8 bytes");
+    if (lr_shift > G2048_NTUPLE_MAX_LR_SHIFT)
+        return fail(G2048_ERR_INVALID, "lr_shift=%u: need 0 <= lr_shift <= %d", lr_shift, G2048_NTUPLE_MAX_LR_SHIFT);
+    if (phases < 1 || phases > (G2048_NTUPLE_TC_WEIGHTS | G2048_NTUPLE_TC_ACCUM))
+        return fail(G2048_ERR_INVALID, "phases=%u: need G2048_NTUPLE_TC_WEIGHTS (1), G2048_NTUPLE_TC_ACCUM (2) or both (3)", phases);
+    if (!tc)
+        return fail(G2048_ERR_INVALID, "tc is NULL");
+    if (!tc->err)
+        return fail(G2048_ERR_INVALID, "tc err is NULL");
+    if (!tc->mag)
+        return fail(G2048_ERR_INVALID, "tc mag is NULL");
+    if ((reinterpret_cast<uintptr_t>(tc->err) | reinterpret_cast<uintptr_t>(tc->mag)) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple tc err and mag need 8 bytes");
+    G2048_HIP(g2048::launch_ntuple_tc_update(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), delta, lr_shift,
+                                             phases, nn, tc->err, tc->mag, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream)
 {
     if (int rc = usable(e))

@@ -45,6 +45,7 @@ static inline uint32_t g2048_funnel_shr(uint32_t hi, uint32_t lo, uint32_t k) //
     return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (k & 31u));
 }
 static inline uint32_t g2048_ctz(uint32_t x) { return (uint32_t)__builtin_ctz(x); }   // x != 0
+static inline float g2048_rcp(float x) { return 1.0f / x; }
 static inline uint32_t g2048_opaque(uint32_t x) { return x; }
 static inline uint32_t g2048_bfi(uint32_t m, uint32_t a, uint32_t b) { return (m & a) | (~m & b); }
 static inline bool g2048_any(bool x) { return x; }
@@ -60,6 +61,7 @@ G2048_DEV uint32_t g2048_clz(uint32_t x) { return (uint32_t)__builtin_clz(x); } 
 // low word of (hi:lo) >> k, 0 <= k <= 31: v_alignbit_b32
 G2048_DEV uint32_t g2048_funnel_shr(uint32_t hi, uint32_t lo, uint32_t k) { return __builtin_amdgcn_alignbit(hi, lo, k); }
 G2048_DEV uint32_t g2048_ctz(uint32_t x) { return (uint32_t)__builtin_ctz(x); }   // x != 0: v_ffbl_b32
+G2048_DEV float g2048_rcp(float x) { return __builtin_amdgcn_rcpf(x); }               // x normal: v_rcp_f32, 1 ulp
 // Hides a value's origin from the optimizer.  Used on lane-wide select masks: without it LLVM turns
 // "(m & a) | (~m & b)" with m = -(cond) back into v_cndmask_b32_e64 (4 issue cycles) instead of one
 // v_bitop3_b32 (2 cycles).
@@ -836,6 +838,94 @@ template <uint32_t T, class Add> G2048_DEV void ntuple_update(uint64_t packed, c
 #pragma unroll
         for (uint32_t t = 0; t < T; ++t)
             add(ntuple_offset(packed, sh, s, t), step);
+}
+
+// Temporal-coherence learning (g2048_ntuple_tc_update_plain, include/g2048.h; Beal & Smith 1999,
+// Jaskowski 2017): every weight has two int64 accumulators, err = E (the signed sum of the deltas it has seen) and
+// mag = A (the sum of their magnitudes, an unsigned 64-bit number), and learns at its own rate |E| / A.  Integers only:
+//   rate(E, A)  A == 0 -> 65536 (1.0 in Q16); else m = min(|E| as uint64, A), k = max(0, bitlen(A) - 32),
+//               r = floor(((m >> k) << 16) / (A >> k)), 0..65536
+//   d           = clamp(delta, -2^40, +2^40)
+//   step(d, r)  = sat_int32((d * r) >> (16 + lr_shift)), the shift arithmetic; |d * r| <= 2^56
+//   phase W: weights[j] += step(d_i, rate(err[j], mag[j])) for each of the 8T look-ups j of board i, err and mag as they
+//            were BEFORE the call;   phase A: err[j] += d_i, mag[j] += |d_i|.   d_i == 0 touches nothing.
+// Phase W only reads the accumulators and phase A only adds to them, each in a launch of its own: sums of integer adds,
+// the same bits in any lane order.  rate is total: any bit pattern of E and A gives a result in 0..65536.
+constexpr int64_t kNtupleTcMaxDelta = 1ll << 40; // the clamp of d
+constexpr uint32_t kNtupleTcOne = 1u << 16;      // rate 1.0
+
+// floor((m << 16) / a) for m <= a, 1 <= a < 2^32: at most 65536.  The float estimate is off by less than 2^-6 -- two
+// conversions and a product of half an ulp each, a reciprocal of at most 2.5 ulp, on a quotient of at most 2^16 -- so its
+// floor is the quotient or a neighbour of it, and one step either way on the exact remainder lands on it.
+G2048_DEV uint32_t ntuple_tc_quotient(uint32_t m, uint32_t a)
+{
+    const uint64_t num = static_cast<uint64_t>(m) << 16;
+    uint32_t q = static_cast<uint32_t>(static_cast<float>(m) * 65536.0f * g2048_rcp(static_cast<float>(a)));
+    const int64_t rem = static_cast<int64_t>(num - static_cast<uint64_t>(q) * a);
+    q -= rem < 0 ? 1u : 0u;
+    q += rem >= static_cast<int64_t>(a) ? 1u : 0u;
+    return q;
+}
+
+G2048_DEV uint32_t ntuple_tc_rate(int64_t err, uint64_t mag)
+{
+    if (mag == 0)
+        return kNtupleTcOne;
+    const uint64_t e = err < 0 ? 0ull - static_cast<uint64_t>(err) : static_cast<uint64_t>(err); // INT64_MIN -> 2^63
+    const uint64_t m = e < mag ? e : mag;
+    const uint32_t hi = static_cast<uint32_t>(mag >> 32);
+    const uint32_t k = hi ? 32u - g2048_clz(hi) : 0u; // bitlen(A) - 32 where that is positive
+    return ntuple_tc_quotient(static_cast<uint32_t>(m >> k), static_cast<uint32_t>(mag >> k));
+}
+
+G2048_DEV int64_t ntuple_tc_delta(int64_t delta)
+{
+    return delta > kNtupleTcMaxDelta ? kNtupleTcMaxDelta : (delta < -kNtupleTcMaxDelta ? -kNtupleTcMaxDelta : delta);
+}
+
+// d as ntuple_tc_delta returns it, rate 0..65536, lr_shift <= 40
+G2048_DEV int32_t ntuple_tc_step(int64_t d, uint32_t rate, uint32_t lr_shift)
+{
+    const int64_t x = (d * static_cast<int64_t>(rate)) >> (16u + lr_shift);
+    return x > INT32_MAX ? INT32_MAX : (x < INT32_MIN ? INT32_MIN : static_cast<int32_t>(x));
+}
+
+// Phase W of one board, d != 0: all 8T offsets, then all 16T accumulator loads (independent: in flight together, as in
+// ntuple_value), then the rates and steps, then add(offset, step) for every step that is not 0.
+template <uint32_t T, class Add>
+G2048_DEV void ntuple_tc_weights(uint64_t packed, const NtupleShape &sh, int64_t d, uint32_t lr_shift, const int64_t *err,
+                                 const int64_t *mag, Add add)
+{
+    uint32_t off[8u * T];
+    int64_t e[8u * T];
+    uint64_t a[8u * T];
+#pragma unroll
+    for (uint32_t s = 0; s < 8u; ++s)
+#pragma unroll
+        for (uint32_t t = 0; t < T; ++t)
+            off[s * T + t] = ntuple_offset(packed, sh, s, t);
+#pragma unroll
+    for (uint32_t j = 0; j < 8u * T; ++j) {
+        e[j] = err[off[j]];
+        a[j] = static_cast<uint64_t>(mag[off[j]]);
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 8u * T; ++j) {
+        const int32_t step = ntuple_tc_step(d, ntuple_tc_rate(e[j], a[j]), lr_shift);
+        if (step != 0)
+            add(off[j], step);
+    }
+}
+
+// Phase A of one board, d != 0: add(offset, d, |d|) for each of the 8T look-ups.
+template <uint32_t T, class Add> G2048_DEV void ntuple_tc_accum(uint64_t packed, const NtupleShape &sh, int64_t d, Add add)
+{
+    const uint64_t m = static_cast<uint64_t>(d < 0 ? -d : d);
+#pragma unroll
+    for (uint32_t s = 0; s < 8u; ++s)
+#pragma unroll
+        for (uint32_t t = 0; t < T; ++t)
+            add(ntuple_offset(packed, sh, s, t), d, m);
 }
 
 // ------------------------------------------------------------------- n-tuple expectimax

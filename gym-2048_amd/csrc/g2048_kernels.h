@@ -138,6 +138,11 @@ hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth,
 hipError_t launch_ntuple_values(const uint4 *boards, uint32_t n, const NtupleNet &net, int64_t *v, hipStream_t s);
 hipError_t launch_ntuple_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
                                 hipStream_t s);
+// g2048_ntuple_tc_update_plain: phase W (kNtupleTcWeights = G2048_NTUPLE_TC_WEIGHTS), then phase A (kNtupleTcAccum =
+// G2048_NTUPLE_TC_ACCUM), a launch each; phases in 1..3, err and mag [T][16^L], checked by the caller
+constexpr uint32_t kNtupleTcWeights = 1u, kNtupleTcAccum = 2u;
+hipError_t launch_ntuple_tc_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                   const NtupleNet &net, int64_t *err, int64_t *mag, hipStream_t s);
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s);
 // numpy-RNG mode: every board's PCG64 generator, seeded as numpy seeds it, into the DeviceState::rng planes
 hipError_t launch_seed_numpy(uint64_t *planes, uint32_t n, uint64_t first_seed, hipStream_t s);

@@ -1650,6 +1650,50 @@ __global__ void __launch_bounds__(kBlock) ntuple_update_kernel(const uint4 *__re
     });
 }
 
+// g2048_ntuple_tc_update_plain, phase W (the definition of g2048_device.h, "Temporal-coherence learning"): one board per
+// lane; the 8T offsets, then the 16T 8-byte loads of err and mag in flight together, then the rates and steps, then up to
+// 8T relaxed agent-scope 32-bit atomic adds whose result nobody reads.  err and mag are only read here: phase A adds to
+// them in a launch of its own, so every lane sees the accumulators of before the call.  A lane whose d is 0 loads and adds
+// nothing.  Lanes stride over the boards when n exceeds the grid cap (kSearchMaxLanes).
+template <uint32_t T>
+__global__ void __launch_bounds__(kBlock) ntuple_tc_weights_kernel(const uint4 *__restrict__ boards, uint32_t n,
+                                                                   const int64_t *__restrict__ delta, uint32_t lr_shift,
+                                                                   const NtupleShape sh, int32_t *weights,
+                                                                   const int64_t *__restrict__ err, const int64_t *__restrict__ mag)
+{
+    uint32_t *w = reinterpret_cast<uint32_t *>(weights); // unsigned: the add wraps mod 2^32
+    const uint32_t stride = gridDim.x * kBlock;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
+        const int64_t d = ntuple_tc_delta(delta[i]);
+        if (d == 0)
+            continue;
+        ntuple_tc_weights<T>(ntuple_pack(load_board(boards, static_cast<uint32_t>(i))), sh, d, lr_shift, err, mag,
+                             [w](uint32_t off, int32_t st) {
+                                 __hip_atomic_fetch_add(w + off, static_cast<uint32_t>(st), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                             });
+    }
+}
+
+// Phase A: err[j] += d, mag[j] += |d| for the 8T look-ups of every board with d != 0 -- 16T relaxed agent-scope 64-bit
+// atomic adds, fire and forget, wrapping mod 2^64.  The same lanes and stride as phase W.
+template <uint32_t T>
+__global__ void __launch_bounds__(kBlock) ntuple_tc_accum_kernel(const uint4 *__restrict__ boards, uint32_t n,
+                                                                 const int64_t *__restrict__ delta, const NtupleShape sh,
+                                                                 int64_t *err, int64_t *mag)
+{
+    unsigned long long *e = reinterpret_cast<unsigned long long *>(err), *a = reinterpret_cast<unsigned long long *>(mag);
+    const uint32_t stride = gridDim.x * kBlock;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
+        const int64_t d = ntuple_tc_delta(delta[i]);
+        if (d == 0)
+            continue;
+        ntuple_tc_accum<T>(ntuple_pack(load_board(boards, static_cast<uint32_t>(i))), sh, d, [e, a](uint32_t off, int64_t dd, uint64_t m) {
+            __hip_atomic_fetch_add(e + off, static_cast<unsigned long long>(dd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(a + off, static_cast<unsigned long long>(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        });
+    }
+}
+
 // ---------------------------------------------------------------------------- augmentation
 // training_data.augment() (training_data.py:257-299) for board pairs on the device: the eight
 // symmetries [orig, hflip, rot1(orig), rot1(hflip), rot2(..), rot2(..), rot3(..), rot3(..)] with the
@@ -2286,6 +2330,23 @@ hipError_t launch_ntuple_update(const uint4 *boards, uint32_t n, const int64_t *
     const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
     return dispatch_tuples(net, [&](auto tc) {
         return launch_1d(ntuple_update_kernel<tc>, n, 0, s, boards, n, delta, lr_shift, sh, net.weights);
+    });
+}
+
+hipError_t launch_ntuple_tc_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                   const NtupleNet &net, int64_t *err, int64_t *mag, hipStream_t s)
+{
+    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
+    return dispatch_tuples(net, [&](auto tc) {
+        if (phases & kNtupleTcWeights) {
+            const hipError_t rc = launch_1d(ntuple_tc_weights_kernel<tc>, group_lanes(n, 1u), 0, s, boards, n, delta, lr_shift, sh,
+                                            net.weights, static_cast<const int64_t *>(err), static_cast<const int64_t *>(mag));
+            if (rc != hipSuccess)
+                return rc;
+        }
+        if (phases & kNtupleTcAccum)
+            return launch_1d(ntuple_tc_accum_kernel<tc>, group_lanes(n, 1u), 0, s, boards, n, delta, sh, err, mag);
+        return hipSuccess;
     });
 }
 

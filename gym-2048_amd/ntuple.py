@@ -4,7 +4,9 @@ summed over the eight board symmetries, with int32 fixed-point weights -- evalua
 per update.  Everything is an integer: the same bits however the batch is split over lanes, launches or shards.
 
 ``NTupleNet`` owns the weights (a device tensor); ``Batched2048.ntuple_evaluate`` evaluates the engine's live boards;
-``td_step`` / ``train`` chain evaluate, ``g2048_step`` and update on the device with no host synchronisation.
+``td_step`` / ``train`` chain evaluate, ``g2048_step`` and update on the device with no host synchronisation;
+``NTupleTC`` and ``tc_step`` / ``tc_train`` do the same with temporal-coherence learning, a learning rate per weight
+(``g2048_ntuple_tc_update_plain``).
 ``NTupleNet.search`` / ``Batched2048.ntuple_search`` play the network through a depth-1..2 expectimax
 (``g2048_ntuple_search``), one launch for the whole batch.
 """
@@ -16,12 +18,13 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import NTupleIO, NTupleNetC, NTupleSearchIO, check
+from ._lib import NTupleIO, NTupleNetC, NTupleSearchIO, NTupleTCC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
 ILLEGAL = -(1 << 63)                                              # G2048_NTUPLE_ILLEGAL: q of an illegal move
 SEARCH_MAX_DEPTH = 2                                              # G2048_NTUPLE_SEARCH_MAX_DEPTH
+TC_WEIGHTS, TC_ACCUM = 1, 2                                       # G2048_NTUPLE_TC_WEIGHTS, G2048_NTUPLE_TC_ACCUM
 
 # Default shapes, as row-major cell indices (cell 4r + c).  The value sums every tuple over the eight symmetries of the
 # board, so a shape lists each tuple once, not once per placement.
@@ -179,6 +182,24 @@ class NTupleNet:
         shift = _int_arg("lr_shift", lr_shift, 0, MAX_LR_SHIFT)
         self._launch(_lib.load().g2048_ntuple_update_plain, boards, delta.data_ptr(), shift, net)
 
+    def tc_update(self, boards, delta, lr_shift, tc, phases=3):
+        """The temporal-coherence update (``g2048_ntuple_tc_update_plain``) with the accumulators of
+        ``tc`` (an :class:`NTupleTC` of this network): phase W (``phases`` bit 1) adds
+        ``sat_int32((d_i * rate(err, mag)) >> (16 + lr_shift))`` to every weight a board reaches, with the accumulators of
+        before the call; phase A (bit 2) adds ``d_i`` to ``err`` and ``|d_i|`` to ``mag``.  ``boards``, ``delta`` and
+        ``lr_shift`` as in :meth:`update`.  ``phases=3`` is two launches, W then A; shards that share the network run
+        W on every shard, then A on every shard."""
+        n, device = _plain_boards(boards)
+        net = self._ref(device)
+        if (not isinstance(delta, torch.Tensor) or delta.dtype != torch.int64 or tuple(delta.shape) != (n,)
+                or not delta.is_contiguous() or delta.device != device):
+            raise ValueError(f"delta must be a contiguous int64 [{n}] tensor on {device}")
+        shift = _int_arg("lr_shift", lr_shift, 0, MAX_LR_SHIFT)
+        phases = _int_arg("phases", phases, TC_WEIGHTS, TC_WEIGHTS | TC_ACCUM)
+        if not isinstance(tc, NTupleTC) or tc.net is not self:
+            raise ValueError("tc must be the NTupleTC of this network")
+        self._launch(_lib.load().g2048_ntuple_tc_update_plain, boards, delta.data_ptr(), shift, phases, net, C.byref(tc._c))
+
     def state_dict(self):
         return {"tuples": self.tuples, "frac_bits": self.frac_bits, "weights": self.weights.clone()}
 
@@ -190,6 +211,35 @@ class NTupleNet:
         if w.dtype != torch.int32 or w.shape != self.weights.shape:
             raise ValueError(f"state_dict weights must be int32 {tuple(self.weights.shape)}")
         self.weights.copy_(w)
+
+
+class NTupleTC:
+    """The accumulators of temporal-coherence learning for ``net`` (``g2048_ntuple_tc``): ``err``, the
+    signed sum of the deltas every weight has seen, and ``mag``, the sum of their magnitudes (read as unsigned), both
+    int64 ``[T, 16^L]`` tensors on the network's device, zero-initialised; a weight learns at rate ``|err| / mag``.
+
+    Memory: 16 bytes per weight on top of the weight's own 4 -- 1 GiB per table for the 4x6 network (4 GiB in all), 5 MiB
+    in all for the 17x4 network."""
+
+    def __init__(self, net):
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        self.net = net
+        self.err = torch.zeros(tuple(net.weights.shape), dtype=torch.int64, device=net.device)
+        self.mag = torch.zeros(tuple(net.weights.shape), dtype=torch.int64, device=net.device)
+        self._c = NTupleTCC(self.err.data_ptr(), self.mag.data_ptr())
+
+    def state_dict(self):
+        return {"err": self.err.clone(), "mag": self.mag.clone()}
+
+    def load_state_dict(self, state):
+        """Copy the accumulators of a ``state_dict()`` of the same shape into this one's tensors (in place)."""
+        err, mag = torch.as_tensor(state["err"]), torch.as_tensor(state["mag"])
+        for name, t in (("err", err), ("mag", mag)):
+            if t.dtype != torch.int64 or t.shape != self.err.shape:
+                raise ValueError(f"state_dict {name} must be int64 {tuple(self.err.shape)}")
+        self.err.copy_(err)
+        self.mag.copy_(mag)
 
 
 class TDWork(NamedTuple):
@@ -240,4 +290,27 @@ def train(engine, net, n_steps, lr_shift):
     work = td_work(engine)
     for _ in range(int(n_steps)):
         td_step(engine, net, lr_shift, work)
+    return net
+
+
+def tc_update(net, tc, work, lr_shift, phases=3):
+    """``net.tc_update(after, delta, lr_shift, tc, phases)`` with what :func:`td_evaluate` left in ``work``.  Shards that
+    share one network and one :class:`NTupleTC` run :func:`td_evaluate` on every shard, then this with ``phases=1`` on
+    every shard, then with ``phases=2`` on every shard: the bits of the unsharded step."""
+    net.tc_update(work.before.after, work.delta, lr_shift, tc, phases)
+
+
+def tc_step(engine, net, tc, lr_shift, work=None) -> TDWork:
+    """:func:`td_step` with the temporal-coherence update in place of the TD(0) one: :func:`td_evaluate`, then
+    :func:`tc_update` (two launches).  No host synchronisation; ``work`` (:func:`td_work`) is reused."""
+    work = td_evaluate(engine, net, td_work(engine) if work is None else work)
+    tc_update(net, tc, work, lr_shift)
+    return work
+
+
+def tc_train(engine, net, tc, n_steps, lr_shift):
+    """``n_steps`` :func:`tc_step` calls with one set of buffers."""
+    work = td_work(engine)
+    for _ in range(int(n_steps)):
+        tc_step(engine, net, tc, lr_shift, work)
     return net

@@ -433,6 +433,34 @@ int g2048_ntuple_values_plain(const uint8_t *boards, uint64_t n, const g2048_ntu
 int g2048_ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift,
                               const g2048_ntuple_net *net, void *stream);
 
+/* Temporal-coherence (TC) learning for the network above (Beal & Smith 1999, Jaskowski 2017): every
+ * weight learns at a rate of its own, |E| / A, from two caller-owned accumulators -- E, the signed sum of the deltas the
+ * weight has seen, and A, the sum of their magnitudes.  A weight whose deltas agree keeps rate 1; one whose deltas
+ * alternate in sign (the overshoot of a large batch) slows itself down.  In integers, with off(a, s, t) the offset
+ * t * 16^L + idx_t(s(a)) into [T][16^L]:
+ *   state       err, mag: int64 [T][16^L] each, device memory, 8-byte aligned, zero-initialised by the caller.  err is E;
+ *               mag is A, read as an unsigned 64-bit number.  Both wrap mod 2^64 on overflow.
+ *   rate(E, A)  A == 0 -> 65536 (1.0 in Q16: a weight never updated learns at full rate); else
+ *               m = min(|E| as uint64, A), k = max(0, bitlen(A) - 32), r = floor(((m >> k) << 16) / (A >> k)), 0..65536.
+ *               Total: any bit pattern of E and A gives a defined result (|E| > A gives 65536, |INT64_MIN| is 2^63).
+ *   d_i         = clamp(delta_i, -2^40, +2^40)
+ *   step(d, r)  = sat_int32((d * r) >> (16 + lr_shift)), an arithmetic shift (it floors negatives); lr_shift 0..40
+ *   phase W     for every board i, symmetry s, tuple t, j = off(a_i, s, t): weights[j] += step(d_i, rate(err[j], mag[j])),
+ *               a 32-bit add that wraps, with err and mag AS THEY WERE BEFORE THE CALL.  d_i == 0 touches nothing.
+ *   phase A     for the same (i, s, t): err[j] += d_i, mag[j] += |d_i|.  d_i == 0 touches nothing.
+ * An entry that two symmetries of a symmetric board reach counts twice, in both phases.  Phase W only reads the
+ * accumulators and both phases are sums of integer adds, so the result of a call does not depend on lane, wave or block
+ * order.  Unlike the TD(0) update it DOES depend on how a batch is split over calls: a second call sees the accumulators
+ * the first one left.  Shards that share one network therefore run phase W on every shard, then phase A on every shard
+ * (`phases`); that reproduces the bits of the unsharded call. */
+#define G2048_NTUPLE_TC_WEIGHTS 1u
+#define G2048_NTUPLE_TC_ACCUM   2u
+typedef struct g2048_ntuple_tc { int64_t *err; int64_t *mag; } g2048_ntuple_tc;   /* [T][16^L] each */
+/* n plain boards, delta int64[n] (device), lr_shift 0..40, as in g2048_ntuple_update_plain; phases = 1 (W), 2 (A) or 3:
+ * two launches on `stream`, W then A (never one kernel: no lane reads an accumulator another lane of its launch adds to). */
+int g2048_ntuple_tc_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift,
+                                 uint32_t phases, const g2048_ntuple_net *net, const g2048_ntuple_tc *tc, void *stream);
+
 /* N-tuple expectimax: a depth-1..2 search of every board with the network at the leaves, in one launch (INTEGRATION.md
  * §10) -- the player the n-tuple literature plays with.  Notation of the block above: net (T, L, F, cells, weights),
  * V(a) the sum over the 8 symmetries and T tuples, move(b, d) = (a_d, g_d, legal); cells are exponents, a cell is empty

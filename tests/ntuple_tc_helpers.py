@@ -1,0 +1,80 @@
+"""Shared by the temporal-coherence tests: the host build of the header's TC code (tests/host_ntuple_tc/ntuple_tc_check.cpp,
+g++) behind ctypes, and accumulators pre-loaded so that a batch reaches the edges of the rate.  A plain module, like
+ntuple_helpers."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import ntuple_tc_ref as tcref
+from ntuple_helpers import ROOT, _cells, _rows, _w32
+
+HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple_tc")
+
+
+def build_host_ntuple_tc(force=False):
+    """g++ build of tests/host_ntuple_tc (the device header's TC code compiled for the host; tests only)."""
+    so, src = os.path.join(HOST_DIR, "libntuple_tc_check.so"), os.path.join(HOST_DIR, "ntuple_tc_check.cpp")
+    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
+    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
+    return so
+
+
+def load_host_ntuple_tc():
+    lib = C.CDLL(build_host_ntuple_tc())
+    P, u32, u64, i64 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int64
+    lib.ntuple_tc_check_rate.restype, lib.ntuple_tc_check_rate.argtypes = u32, [i64, u64]
+    lib.ntuple_tc_check_step.restype, lib.ntuple_tc_check_step.argtypes = C.c_int32, [i64, u32, u32]
+    lib.ntuple_tc_check_update.restype, lib.ntuple_tc_check_update.argtypes = C.c_int, [P, u64, P, u32, u32, u32, u32, P, P, P, P]
+    return lib
+
+
+def host_tc_update(lib, boards, deltas, lr_shift, phases, net, tc):
+    """(weights, err, mag) after the update, as int64 arrays (``net`` and ``tc`` are not modified)."""
+    b, c, w = _rows(boards), _cells(net), _w32(net)
+    d = np.ascontiguousarray(np.asarray(deltas, np.int64))
+    err, mag = np.ascontiguousarray(tc.err.copy()), np.ascontiguousarray(tc.mag_i64().copy())
+    assert lib.ntuple_tc_check_update(b.ctypes.data, len(b), d.ctypes.data, lr_shift, phases, len(net.tuples), len(net.tuples[0]),
+                                      c.ctypes.data, w.ctypes.data, err.ctypes.data, mag.ctypes.data) == 0
+    return w.astype(np.int64), err, mag
+
+
+# (E, A) pairs that reach every branch of the rate: never updated; E = 0; |E| = A; |E| = A - 1; A at and around 2^32, 2^63
+# and 2^64 - 1 (k > 0); |E| > A (not reachable by updates, defined all the same); E = INT64_MIN
+EDGE_PAIRS = [(0, 0), (5, 0), (0, 7), (9, 9), (-9, 9), (8, 9), (-1, 1 << 20), (1 << 31, (1 << 32) - 1), (-(1 << 31), 1 << 32),
+              ((1 << 32), (1 << 32) + 1), (-(1 << 62), 1 << 63), ((1 << 63) - 1, (1 << 64) - 1), (-(1 << 63), (1 << 64) - 1),
+              (10, 3), (-(1 << 40), 1 << 33), (-(1 << 63), 5), (-(1 << 63), 1 << 63), (1, (1 << 64) - 1), (3, 1 << 17)]
+
+
+def preload(net, seed, boards=None):
+    """A reference TC for ``net`` whose accumulators are random with bitlen(A) uniform in 0..64 and |E| <= A; the entries
+    the ``boards`` reach cycle through EDGE_PAIRS so that a small batch meets every edge."""
+    rng = np.random.default_rng(seed)
+    shape = net.weights.shape
+    bits = rng.integers(0, 65, size=shape)
+    top = rng.integers(0, 1 << 64, size=shape, dtype=np.uint64) | np.uint64(1 << 63)
+    mag = top >> (64 - np.maximum(bits, 1)).astype(np.uint64)       # bitlen(mag) == bits
+    mag[bits == 0] = 0
+    half = mag >> np.uint64(1)
+    kind = rng.integers(0, 4, size=shape)                           # |E| = A (where it fits), E = 0, or somewhere below A / 2
+    mask = rng.integers(0, 1 << 64, size=shape, dtype=np.uint64)
+    err = np.where(kind == 0, np.where(bits < 64, mag, half), np.where(kind == 1, np.uint64(0), half & mask)).astype(np.int64)
+    err = err * rng.choice(np.array([-1, 1], np.int64), size=shape)
+    tc = tcref.TC(net, err.astype(np.int64), mag)
+    if boards is not None:
+        k = 0
+        for b in np.asarray(boards).reshape(-1, 16):
+            for t, i in tcref.hits_of(b, net):
+                e, a = EDGE_PAIRS[k % len(EDGE_PAIRS)]
+                tc.err[t, i], tc.mag[t, i] = e, a
+                k += 1
+    return tc
+
+
+def assert_tables_equal(got, want, names=("weights", "err", "mag")):
+    for name, g, w in zip(names, got, want):
+        g, w = np.asarray(g), np.asarray(w)
+        bad = np.argwhere(g != w)
+        assert len(bad) == 0, f"{len(bad)} entries of {name} differ, first {bad[0].tolist()}: {g[tuple(bad[0])]} vs {w[tuple(bad[0])]}"
