@@ -17,6 +17,22 @@ TUPLES_2x6 = TUPLES_4x6[:2]
 # T = 8, L = 6: every count and length at its limit
 TUPLES_8x6 = TUPLES_4x6 + ((0, 4, 8, 12, 13, 9), (3, 2, 1, 5, 9, 13), (15, 14, 10, 11, 7, 6), (12, 8, 9, 5, 6, 2))
 
+# T = 1..8 at L = 4: network T is the first T lists.  Pairwise different and none a symmetry image of another (as a set of
+# cells or as a list), so a look-up that reads the table of another tuple reads other entries: the five of TUPLES_17x4, an
+# L, an S and a T shape
+TUPLES_8x4 = TUPLES_17x4 + ((0, 1, 2, 4), (0, 1, 5, 6), (0, 1, 2, 5))
+# L = 1..6 at T = 3: prefixes of the first three 6-cell lists
+TUPLES_3xL = {L: tuple(t[:L] for t in TUPLES_4x6[:3]) for L in range(1, 7)}
+
+
+def symmetry_images(cells):
+    """The eight images of a cell list under the board's symmetries, by the reference's own permutations."""
+    out = []
+    for perm in ref._sym_perms():
+        where = {c: k for k, c in enumerate(perm)}      # perm[k] = the cell that lands on k
+        out.append(tuple(where[c] for c in cells))
+    return out
+
 
 def build_host_ntuple(force=False):
     """g++ build of tests/host_ntuple (the device header's n-tuple code compiled for the host; tests only)."""

@@ -18,6 +18,22 @@ SEARCH_GROUP = {1: 16, 2: 64}   # kNtupleSearchGroup<D> (g2048_kernels.hip): lan
 PAIR_ONLY = np.array([[1, 1, 3, 2, 5, 6, 7, 4, 1, 2, 3, 5, 4, 5, 6, 7]], np.uint8)
 
 
+def _sparse(cells, exponents):
+    b = np.zeros(16, np.uint8)
+    b[list(cells)] = exponents
+    return b
+
+
+# Boards whose afterstates have E = 15, 14, 12, 9, 8 and 7 empty cells: 30, 28, 24, 18, 16 and 14 chance items in a
+# direction.  On the 16 lanes a direction has at depth 2, 16 items are one full pass, 18 a second pass on two lanes, 24
+# on eight, 30 on all but two (tests assert the counts from the reference's trace).  One- and two-tile boards give E = 15.
+WIDE_FANS = np.array([
+    _sparse([5], [3]), _sparse([0], [1]), _sparse([0, 1], [1, 1]), _sparse([6, 9], [2, 5]),
+    _sparse([0, 2, 5, 7], [1, 2, 1, 2]), _sparse([0, 5, 10, 15], [3, 1, 2, 4]),
+    _sparse(range(7), [1, 2, 3, 4, 2, 3, 1]), _sparse(range(8), [1, 2, 3, 4, 2, 3, 4, 5]),
+    _sparse(range(9), [1, 2, 3, 4, 2, 3, 4, 5, 1]), _sparse([0, 2, 5, 7, 8, 10, 13], [1, 2, 3, 1, 2, 3, 1])], np.uint8)
+
+
 def build_host_ntuple_search(force=False):
     """g++ build of tests/host_ntuple_search (the device header's n-tuple expectimax compiled for the host; tests only)."""
     so, src = os.path.join(HOST_DIR, "libntuple_search_check.so"), os.path.join(HOST_DIR, "ntuple_search_check.cpp")

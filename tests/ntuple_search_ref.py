@@ -23,10 +23,12 @@ ILLEGAL = ref.ILLEGAL
 
 class Trace:
     """chance: chance nodes; negative_inexact: those whose sum was negative and not divisible by 10E; terminal_children:
-    children of a chance node with no legal move (S = 0); root_ties: boards whose largest root value two moves share."""
+    children of a chance node with no legal move (S = 0); root_ties: boards whose largest root value two moves share;
+    root_items: {number of chance items 2E of a root direction's afterstate: how many legal root directions had it}."""
 
     def __init__(self):
         self.chance = self.negative_inexact = self.terminal_children = self.root_ties = 0
+        self.root_items = {}
 
     def __repr__(self):
         return (f"Trace(chance={self.chance}, negative_inexact={self.negative_inexact}, "
@@ -72,6 +74,9 @@ def search(board, depth, net, trace=None):
         a, g, legal = ref.move(b, d)
         if legal:
             value[d] = (g << net.frac_bits) + after_value(a, depth, net, trace)
+            if trace is not None:
+                items = 2 * sum(1 for x in a if x == 0)
+                trace.root_items[items] = trace.root_items.get(items, 0) + 1
     legal = [d for d in range(4) if value[d] != ILLEGAL]
     if not legal:
         return value, 0

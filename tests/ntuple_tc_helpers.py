@@ -73,6 +73,16 @@ def preload(net, seed, boards=None):
     return tc
 
 
+def edge_deltas(n, seed):
+    """Mixed-sign deltas of every size up to beyond the clamp, with zeros."""
+    rng = np.random.default_rng(seed)
+    d = rng.integers(-(1 << 20), 1 << 20, n) << rng.integers(0, 24, n)
+    d[::9] = 0
+    special = [(1 << 40) + 1, -(1 << 40) - 1, tcref.INT64_MAX, tcref.INT64_MIN, 1 << 40, -(1 << 40), 1, -1, 1 << 31, -(1 << 31) - 1]
+    d[1::13][:len(special)] = special[:len(d[1::13])]
+    return d
+
+
 def assert_tables_equal(got, want, names=("weights", "err", "mag")):
     for name, g, w in zip(names, got, want):
         g, w = np.asarray(g), np.asarray(w)

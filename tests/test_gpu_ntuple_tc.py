@@ -12,11 +12,9 @@ import ntuple_ref as ref
 import ntuple_tc_ref as tcref
 from analysis_helpers import SEARCH_MAX_LANES, g, mixed_boards, random_boards, tiled  # noqa: F401 (g: fixture)
 from ntuple_helpers import TUPLES_17x4, random_net
-from ntuple_tc_helpers import EDGE_PAIRS, assert_tables_equal, preload
+from ntuple_tc_helpers import EDGE_PAIRS, assert_tables_equal, edge_deltas, preload
 
 pytestmark = pytest.mark.gpu
-
-INT64_MAX, INT64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
 def dev(torch, a):
@@ -39,16 +37,6 @@ def tables(net, tc):
 
 def want_tables(rnet, rtc):
     return rnet.weights, rtc.err, rtc.mag_i64()
-
-
-def edge_deltas(n, seed):
-    """Mixed-sign deltas of every size up to beyond the clamp, with zeros."""
-    rng = np.random.default_rng(seed)
-    d = rng.integers(-(1 << 20), 1 << 20, n) << rng.integers(0, 24, n)
-    d[::9] = 0
-    special = [(1 << 40) + 1, -(1 << 40) - 1, INT64_MAX, INT64_MIN, 1 << 40, -(1 << 40), 1, -1, 1 << 31, -(1 << 31) - 1]
-    d[1::13][:len(special)] = special[:len(d[1::13])]
-    return d
 
 
 @pytest.mark.parametrize("phases", [3, 1, 2])

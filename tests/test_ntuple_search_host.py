@@ -8,8 +8,8 @@ import pytest
 import ntuple_ref as ref
 import ntuple_search_ref as sref
 from analysis_helpers import ONE_LEGAL, TERMINAL, mid_game, mixed_boards, random_boards
-from ntuple_helpers import TUPLES_2x6, TUPLES_8x6, TUPLES_17x4, random_net
-from ntuple_search_helpers import PAIR_ONLY, assert_search_equal, host_search, host_split, load_host_ntuple_search
+from ntuple_helpers import TUPLES_2x6, TUPLES_8x4, TUPLES_8x6, TUPLES_17x4, random_net
+from ntuple_search_helpers import PAIR_ONLY, WIDE_FANS, assert_search_equal, host_search, host_split, load_host_ntuple_search
 
 @pytest.fixture(scope="module")
 def hs():
@@ -50,13 +50,21 @@ def test_depth_2_near_full_boards(hs):
     assert trace.chance > 1000 and trace.negative_inexact > 100 and trace.terminal_children > 0
 
 
-@pytest.mark.parametrize("depth, boards", [(1, mixed_boards(60, 23)), (2, mid_game(8, 23, max_empty=3))], ids=["depth1", "depth2"])
-def test_lane_split_sums_to_the_one_thread_sum(hs, depth, boards):
-    """The kernel's split: the parts of K lanes add up to the whole chance sum, for K lanes per direction in {1, 4, 16}."""
-    net = random_net(TUPLES_17x4, 23)
+@pytest.mark.parametrize("depth, boards, tuples", [(1, mixed_boards(60, 23), TUPLES_17x4), (2, mid_game(8, 23, max_empty=3), TUPLES_17x4),
+                                                   (2, WIDE_FANS, TUPLES_8x4[:1])], ids=["depth1", "depth2", "depth2-wide"])
+def test_lane_split_sums_to_the_one_thread_sum(hs, depth, boards, tuples):
+    """The kernel's split: the parts of K lanes add up to the whole chance sum, for K lanes per direction in {1, 4, 16}.
+    The wide boards give a direction up to 30 items: with K = 16 lanes take a second item, with K = 4 up to eight (the
+    one-tuple network keeps the reference at about 9 s)."""
+    net = random_net(tuples, 23)
     whole = host_split(hs, boards, depth, net, 1)
-    _, val = sref.search_batch(boards, depth, net)
+    trace = sref.Trace()
+    _, val = sref.search_batch(boards, depth, net, trace)
     legal = val != sref.ILLEGAL
+    if boards is WIDE_FANS:
+        assert max(trace.root_items) == 30 and {16, 18, 24, 30} <= set(trace.root_items)
+    else:
+        assert depth == 1 or max(trace.root_items) < 16      # (the near-full boards never give a lane a second item)
     # the whole sum is the reference's: floor(sum / 10E) + (gain << F) = value
     for i, b in enumerate(boards):
         for d in range(4):
