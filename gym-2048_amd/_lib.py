@@ -125,6 +125,16 @@ class NTupleTCC(C.Structure):
     ]
 
 
+class NTupleTraceC(C.Structure):
+    """g2048_ntuple_trace (include/g2048.h): depth H, lambda in Q16 and the device history of the n-tuple traces."""
+    _fields_ = [
+        ("depth", C.c_uint32),
+        ("lambda_", C.c_uint32),
+        ("hist", C.c_void_p),
+        ("len", C.c_void_p),
+    ]
+
+
 class Stats(C.Structure):
     """g2048_stats (include/g2048.h)."""
     _fields_ = [
@@ -190,6 +200,11 @@ SIGNATURES = {
     "g2048_ntuple_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, C.POINTER(NTupleNetC), _S]),
     "g2048_ntuple_tc_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleNetC),
                                               C.POINTER(NTupleTCC), _S]),
+    "g2048_ntuple_trace_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64, C.POINTER(NTupleTraceC), _u32,
+                                         C.c_void_p, _S]),
+    "g2048_ntuple_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, C.POINTER(NTupleNetC), C.POINTER(NTupleTraceC), _u32, _S]),
+    "g2048_ntuple_tc_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleNetC), C.POINTER(NTupleTCC),
+                                              C.POINTER(NTupleTraceC), _u32, _S]),
     "g2048_add_tile": (C.c_int, [_E, _u32, _S]),
     "g2048_fill_random_actions": (C.c_int, [_E, _u64, _u32, C.c_void_p, _S]),
     "g2048_onehot": (C.c_int, [_E, C.c_void_p, _i32, _S]),

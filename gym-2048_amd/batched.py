@@ -22,6 +22,7 @@ from .analysis import (MC_DEFAULT_MAX_STEPS, Afterstates, MCSearch, Search, Sear
 # the n-tuple network value function, re-exported; Batched2048.ntuple_evaluate runs it on the live boards
 from .ntuple import NTupleEval, NTupleNet, NTupleSearch, TUPLES, td_step, train, _eval_io  # noqa: F401
 from .ntuple import NTupleTC, tc_step, tc_train, tc_update  # noqa: F401
+from .ntuple import NTupleTrace, tcl_step, tcl_train, tdl_evaluate, tdl_step, tdl_train  # noqa: F401
 from .ntuple import _search_io as _ntuple_search_io
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}

@@ -1438,6 +1438,124 @@ int g2048_ntuple_tc_update_plain(const uint8_t *boards, uint64_t n, const int64_
     return G2048_OK;
 }
 
+} // extern "C"
+
+// the board count of a trace call (the cap of plain_boards: 32-bit board indices)
+static int trace_boards(uint64_t n)
+{
+    if (n == 0 || n > 0xffffff00ull)
+        return fail(G2048_ERR_INVALID, "n=%llu: need 1 <= n <= 2^32 - 256", (unsigned long long)n);
+    return G2048_OK;
+}
+
+// g2048_ntuple_trace and a slot -> the launchers' history, or G2048_ERR_INVALID (before any HIP call: works without a device)
+static int ntuple_trace(const g2048_ntuple_trace *tr, uint32_t slot, g2048::NtupleTrace *out)
+{
+    if (!tr)
+        return fail(G2048_ERR_INVALID, "tr is NULL");
+    if (!tr->hist)
+        return fail(G2048_ERR_INVALID, "trace hist is NULL");
+    if (!tr->len)
+        return fail(G2048_ERR_INVALID, "trace len is NULL");
+    if (tr->depth < 1 || tr->depth > G2048_NTUPLE_TRACE_MAX)
+        return fail(G2048_ERR_INVALID, "depth=%u: need 1 <= depth <= %d", tr->depth, G2048_NTUPLE_TRACE_MAX);
+    if (tr->lambda > 65536u)
+        return fail(G2048_ERR_INVALID, "lambda=%u: need 0 <= lambda <= 65536 (Q16)", tr->lambda);
+    if (slot >= tr->depth)
+        return fail(G2048_ERR_INVALID, "slot=%u: need slot < depth=%u", slot, tr->depth);
+    if (reinterpret_cast<uintptr_t>(tr->hist) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: trace hist needs 16 bytes");
+    *out = g2048::NtupleTrace{tr->depth, tr->lambda, reinterpret_cast<uint4 *>(tr->hist), tr->len};
+    return G2048_OK;
+}
+
+// delta and lr_shift of an update, as g2048_ntuple_update_plain checks them
+static int ntuple_delta(const int64_t *delta, uint32_t lr_shift)
+{
+    if (!delta)
+        return fail(G2048_ERR_INVALID, "delta is NULL");
+    if (reinterpret_cast<uintptr_t>(delta) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple delta needs 8 bytes");
+    if (lr_shift > G2048_NTUPLE_MAX_LR_SHIFT)
+        return fail(G2048_ERR_INVALID, "lr_shift=%u: need 0 <= lr_shift <= %d", lr_shift, G2048_NTUPLE_MAX_LR_SHIFT);
+    return G2048_OK;
+}
+
+extern "C" {
+
+int g2048_ntuple_trace_push(const uint8_t *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,
+                            uint64_t n, const g2048_ntuple_trace *tr, uint32_t slot, int64_t *delta, void *stream)
+{
+    if (!after)
+        return fail(G2048_ERR_INVALID, "after is NULL");
+    if (!after_value)
+        return fail(G2048_ERR_INVALID, "after_value is NULL");
+    if (!best_next)
+        return fail(G2048_ERR_INVALID, "best_next is NULL");
+    if (!terminated)
+        return fail(G2048_ERR_INVALID, "terminated is NULL");
+    if (!delta)
+        return fail(G2048_ERR_INVALID, "delta is NULL");
+    if (int rc = trace_boards(n))
+        return rc;
+    g2048::NtupleTrace t;
+    if (int rc = ntuple_trace(tr, slot, &t))
+        return rc;
+    if (reinterpret_cast<uintptr_t>(after) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: trace after needs 16 bytes");
+    if ((reinterpret_cast<uintptr_t>(after_value) | reinterpret_cast<uintptr_t>(best_next) | reinterpret_cast<uintptr_t>(delta)) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: trace after_value, best_next and delta need 8 bytes");
+    G2048_HIP(g2048::launch_ntuple_trace_push(reinterpret_cast<const uint4 *>(after), after_value, best_next, terminated,
+                                              static_cast<uint32_t>(n), t, slot, delta, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_ntuple_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, const g2048_ntuple_net *net,
+                              const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (int rc = trace_boards(n))
+        return rc;
+    if (int rc = ntuple_delta(delta, lr_shift))
+        return rc;
+    g2048::NtupleTrace t;
+    if (int rc = ntuple_trace(tr, slot, &t))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_trace_update(static_cast<uint32_t>(n), delta, lr_shift, nn, t, slot,
+                                                static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_ntuple_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const g2048_ntuple_net *net,
+                                 const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (int rc = trace_boards(n))
+        return rc;
+    if (int rc = ntuple_delta(delta, lr_shift))
+        return rc;
+    if (phases < 1 || phases > (G2048_NTUPLE_TC_WEIGHTS | G2048_NTUPLE_TC_ACCUM))
+        return fail(G2048_ERR_INVALID, "phases=%u: need G2048_NTUPLE_TC_WEIGHTS (1), G2048_NTUPLE_TC_ACCUM (2) or both (3)", phases);
+    if (!tc)
+        return fail(G2048_ERR_INVALID, "tc is NULL");
+    if (!tc->err)
+        return fail(G2048_ERR_INVALID, "tc err is NULL");
+    if (!tc->mag)
+        return fail(G2048_ERR_INVALID, "tc mag is NULL");
+    if ((reinterpret_cast<uintptr_t>(tc->err) | reinterpret_cast<uintptr_t>(tc->mag)) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple tc err and mag need 8 bytes");
+    g2048::NtupleTrace t;
+    if (int rc = ntuple_trace(tr, slot, &t))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_tc_trace_update(static_cast<uint32_t>(n), delta, lr_shift, phases, nn, tc->err, tc->mag, t, slot,
+                                                   static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream)
 {
     if (int rc = usable(e))

@@ -928,6 +928,99 @@ template <uint32_t T, class Add> G2048_DEV void ntuple_tc_accum(uint64_t packed,
             add(ntuple_offset(packed, sh, s, t), d, m);
 }
 
+// n-tuple traces (g2048_ntuple_trace_push / g2048_ntuple_trace_update / g2048_ntuple_tc_trace_update, include/g2048.h,
+// INTEGRATION.md §12; Sutton 1988, the TC(lambda) of Jaskowski 2017): the error of step t also moves, decayed, the last
+// few afterstates of the same board.  The history is caller-owned device memory, zero-initialised, one per engine or shard:
+//   H     1..kNtupleTraceMax (= 8) slots
+//   lam   lambda in Q16, 0..65536
+//   hist  uint8 [H][n][16]   slot-major, 16-byte aligned: slot k of board i is the 16 exponents at hist + (k*n + i)*16
+//   len   uint8 [n]          bits 0..6: number of valid slots; bit 7: the episode ended at the last push
+// push(slot), for every board i, slot in 0..H-1 (the caller advances slot by one mod H before each push):
+//   old      = len[i];   l = (old & 0x80) ? 0 : min(old & 0x7f, H)
+//   hist[slot][i] = after[i]                                                   (16 bytes)
+//   delta[i] = (terminated[i] ? 0 : best_next[i]) - after_value[i]             (int64, wraps; exactly td_evaluate's delta)
+//   len[i]   = min(l + 1, H) | (terminated[i] ? 0x80 : 0)
+// push is total: any byte in len gives a defined result.
+// trace update(slot), slot the slot of the last push, for every board i:
+//   L   = min(len[i] & 0x7f, H);   d = clamp(delta[i], -2^40, +2^40)           (ntuple_tc_delta)
+//   p_0 = 65536;  p_k = (p_{k-1} * lam) >> 16                                  (uint64 arithmetic; 0..65536)
+//   for k in 0..L-1:   a   = hist[(slot + H - k) mod H][i]
+//                      d_k = (d * p_k) >> 16                                   (arithmetic shift: floors negatives; |d*p_k| <= 2^56)
+//     TD:    step = ntuple_step(d_k, lr_shift);  weights[off(a,s,t)] += step for all s, t;  a zero step touches nothing
+//     TC W:  weights[j] += ntuple_tc_step(d_k, rate(err[j], mag[j]), lr_shift)  with err, mag as they were before the call
+//     TC A:  err[j] += d_k;  mag[j] += |d_k|                                    d_k == 0 touches nothing
+// The same weight entry reached from two slots, or from two symmetries, counts once per reach.  Phase W and phase A are
+// separate launches, as above and for the same reason.  The shifts floor: a negative d_k decays to -1 and not to 0, while
+// its positive twin reaches 0 -- the rule ntuple_step and ntuple_tc_step follow.  With H = 1 or lam = 0 (p_k = 0 for
+// k > 0) the TD form is the plain update whenever |delta| <= 2^40, and the TC form is the plain TC update always.
+constexpr uint32_t kNtupleTraceMax = 8;        // = G2048_NTUPLE_TRACE_MAX (g2048.h)
+constexpr uint32_t kNtupleTraceEnded = 0x80u;  // bit 7 of a len byte
+
+// l of push: the valid slots an old len byte stands for -- none once the episode has ended
+G2048_DEV uint32_t ntuple_trace_kept(uint32_t old, uint32_t H)
+{
+    const uint32_t l = old & 0x7fu;
+    return (old & kNtupleTraceEnded) ? 0u : (l < H ? l : H);
+}
+
+// the len byte push writes
+G2048_DEV uint32_t ntuple_trace_push_len(uint32_t old, uint32_t H, bool terminated)
+{
+    const uint32_t l = ntuple_trace_kept(old, H) + 1u;
+    return (l < H ? l : H) | (terminated ? kNtupleTraceEnded : 0u);
+}
+
+// the delta push writes; the subtraction wraps mod 2^64
+G2048_DEV int64_t ntuple_trace_delta(int64_t best_next, int64_t after_value, bool terminated)
+{
+    return static_cast<int64_t>((terminated ? 0ull : static_cast<uint64_t>(best_next)) - static_cast<uint64_t>(after_value));
+}
+
+// L of the update: min(len & 0x7f, H)
+G2048_DEV uint32_t ntuple_trace_len(uint32_t len, uint32_t H)
+{
+    const uint32_t l = len & 0x7fu;
+    return l < H ? l : H;
+}
+
+// p_k, k < kNtupleTraceMax, lam <= 65536: at most 65536, and never increasing in k
+G2048_DEV uint32_t ntuple_trace_decay(uint32_t lam, uint32_t k)
+{
+    uint64_t p = kNtupleTcOne;
+    for (uint32_t j = 0; j < k; ++j)
+        p = (p * lam) >> 16;
+    return static_cast<uint32_t>(p);
+}
+
+// d_k for d as ntuple_tc_delta returns it and p = p_k
+G2048_DEV int64_t ntuple_trace_dk(int64_t d, uint32_t p) { return (d * static_cast<int64_t>(p)) >> 16; }
+
+// the slot that holds the afterstate k pushes before the one in `slot`; k < H, slot < H
+G2048_DEV uint32_t ntuple_trace_slot(uint32_t slot, uint32_t k, uint32_t H)
+{
+    const uint32_t s = slot + H - k;
+    return s >= H ? s - H : s;
+}
+
+// Work item `item` < H * n of a trace update, k-major: item = k * n + i.  H <= 8, so k is a count of compares, not a
+// 64-bit division.
+G2048_DEV void ntuple_trace_split(uint64_t item, uint32_t n, uint32_t H, uint32_t &k, uint32_t &i)
+{
+    k = 0;
+    for (uint32_t j = 1; j < H; ++j)
+        k += item >= static_cast<uint64_t>(j) * n ? 1u : 0u;
+    i = static_cast<uint32_t>(item - static_cast<uint64_t>(k) * n);
+}
+
+// One work item (k, i) of a trace update up to the point where it needs its board: d_k, or 0 when the item has nothing
+// to do (k >= L, or d_k == 0).  len_i and delta_i are the item's only loads so far.
+G2048_DEV int64_t ntuple_trace_item(uint32_t len_i, int64_t delta_i, uint32_t k, uint32_t H, uint32_t lam)
+{
+    if (k >= ntuple_trace_len(len_i, H))
+        return 0;
+    return ntuple_trace_dk(ntuple_tc_delta(delta_i), ntuple_trace_decay(lam, k));
+}
+
 // ------------------------------------------------------------------- n-tuple expectimax
 // g2048_ntuple_search (include/g2048.h): the expectimax of above with the network at the leaves.
 // Integers only, so every split of the tree across lanes gives the same bits.  With V, move(b, d) = (a_d, g_d, legal)

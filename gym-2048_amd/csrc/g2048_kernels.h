@@ -143,6 +143,20 @@ hipError_t launch_ntuple_update(const uint4 *boards, uint32_t n, const int64_t *
 constexpr uint32_t kNtupleTcWeights = 1u, kNtupleTcAccum = 2u;
 hipError_t launch_ntuple_tc_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
                                    const NtupleNet &net, int64_t *err, int64_t *mag, hipStream_t s);
+// g2048_ntuple_trace_*: the history (g2048_ntuple_trace), checked by the caller: depth in 1..8, lambda <= 65536, slot < depth
+struct NtupleTrace {
+    uint32_t depth, lambda;
+    uint4 *hist;  // [depth][n] plain boards
+    uint8_t *len; // [n]
+};
+hipError_t launch_ntuple_trace_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next,
+                                    const uint8_t *terminated, uint32_t n, const NtupleTrace &tr, uint32_t slot, int64_t *delta,
+                                    hipStream_t s);
+hipError_t launch_ntuple_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
+                                      const NtupleTrace &tr, uint32_t slot, hipStream_t s);
+// phases as in launch_ntuple_tc_update: W, then A, a launch each
+hipError_t launch_ntuple_tc_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const NtupleNet &net,
+                                         int64_t *err, int64_t *mag, const NtupleTrace &tr, uint32_t slot, hipStream_t s);
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s);
 // numpy-RNG mode: every board's PCG64 generator, seeded as numpy seeds it, into the DeviceState::rng planes
 hipError_t launch_seed_numpy(uint64_t *planes, uint32_t n, uint64_t first_seed, hipStream_t s);

@@ -1694,6 +1694,99 @@ __global__ void __launch_bounds__(kBlock) ntuple_tc_accum_kernel(const uint4 *__
     }
 }
 
+// g2048_ntuple_trace_push (the definition of g2048_device.h, "n-tuple traces"): one board per lane -- one 16-byte load of
+// the afterstate and one 16-byte store into the slot, the len byte, and delta formed in the same pass (what td_evaluate
+// forms with three element-wise launches).  `slot_boards` is the slot's base, hist + slot * n, formed in 64 bits by the
+// launcher.  Lanes stride over the boards when n exceeds the grid cap (kSearchMaxLanes).
+__global__ void __launch_bounds__(kBlock) ntuple_trace_push_kernel(const uint4 *__restrict__ after,
+                                                                   const int64_t *__restrict__ after_value,
+                                                                   const int64_t *__restrict__ best_next,
+                                                                   const uint8_t *__restrict__ terminated, uint32_t n, uint32_t H,
+                                                                   uint4 *__restrict__ slot_boards, uint8_t *__restrict__ len,
+                                                                   int64_t *__restrict__ delta)
+{
+    const uint32_t stride = gridDim.x * kBlock;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
+        const bool term = terminated[i] != 0;
+        store_board(slot_boards, static_cast<uint32_t>(i), load_board(after, static_cast<uint32_t>(i)));
+        delta[i] = ntuple_trace_delta(best_next[i], after_value[i], term);
+        len[i] = static_cast<uint8_t>(ntuple_trace_push_len(len[i], H, term));
+    }
+}
+
+// The three trace updates: one work item per (k, i), k-major (ntuple_trace_split), so a wave reads 64 consecutive boards
+// of one slot; 64-bit item index and slot base (H * n * 16 bytes exceeds 2^32); the items stride past the grid cap.  A lane
+// reads len[i] and delta[i] first and leaves before loading its board when k >= L or d_k == 0 (ntuple_trace_item); the
+// body is that of the one-step kernel with d_k for the delta.
+struct TraceArgs {
+    const uint4 *hist;  // [H][n] boards
+    const uint8_t *len; // [n]
+    uint32_t n, H, lam, slot;
+};
+
+// f(board index, d_k, packed board) for every work item of this lane that `keep(d_k)` lets through
+template <class Keep, class F> __device__ __forceinline__ void trace_items(const TraceArgs &tr, const int64_t *delta, Keep keep, F f)
+{
+    const uint64_t items = static_cast<uint64_t>(tr.H) * tr.n, stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    for (uint64_t item = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; item < items; item += stride) {
+        uint32_t k, i;
+        ntuple_trace_split(item, tr.n, tr.H, k, i);
+        const int64_t dk = ntuple_trace_item(tr.len[i], delta[i], k, tr.H, tr.lam);
+        if (dk == 0 || !keep(dk))
+            continue;
+        const uint4 *boards = tr.hist + static_cast<uint64_t>(ntuple_trace_slot(tr.slot, k, tr.H)) * tr.n;
+        f(dk, ntuple_pack(load_board(boards, i)));
+    }
+}
+
+// g2048_ntuple_trace_update: ntuple_update_kernel's 8T fire-and-forget adds with step(d_k); a zero step issues none.
+template <uint32_t T>
+__global__ void __launch_bounds__(kBlock) ntuple_trace_update_kernel(const TraceArgs tr, const int64_t *__restrict__ delta,
+                                                                     uint32_t lr_shift, const NtupleShape sh, int32_t *weights)
+{
+    uint32_t *w = reinterpret_cast<uint32_t *>(weights); // unsigned: the add wraps mod 2^32
+    trace_items(
+        tr, delta, [lr_shift](int64_t dk) { return ntuple_step(dk, lr_shift) != 0; },
+        [&](int64_t dk, uint64_t packed) {
+            ntuple_update<T>(packed, sh, ntuple_step(dk, lr_shift), [w](uint32_t off, int32_t st) {
+                __hip_atomic_fetch_add(w + off, static_cast<uint32_t>(st), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            });
+        });
+}
+
+// g2048_ntuple_tc_trace_update, phase W: ntuple_tc_weights_kernel's body per item.  err and mag are only read.
+template <uint32_t T>
+__global__ void __launch_bounds__(kBlock) ntuple_tc_trace_weights_kernel(const TraceArgs tr, const int64_t *__restrict__ delta,
+                                                                         uint32_t lr_shift, const NtupleShape sh, int32_t *weights,
+                                                                         const int64_t *__restrict__ err,
+                                                                         const int64_t *__restrict__ mag)
+{
+    uint32_t *w = reinterpret_cast<uint32_t *>(weights); // unsigned: the add wraps mod 2^32
+    trace_items(
+        tr, delta, [](int64_t) { return true; },
+        [&](int64_t dk, uint64_t packed) {
+            ntuple_tc_weights<T>(packed, sh, dk, lr_shift, err, mag, [w](uint32_t off, int32_t st) {
+                __hip_atomic_fetch_add(w + off, static_cast<uint32_t>(st), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            });
+        });
+}
+
+// Phase A: ntuple_tc_accum_kernel's body per item, the same items as phase W.
+template <uint32_t T>
+__global__ void __launch_bounds__(kBlock) ntuple_tc_trace_accum_kernel(const TraceArgs tr, const int64_t *__restrict__ delta,
+                                                                       const NtupleShape sh, int64_t *err, int64_t *mag)
+{
+    unsigned long long *e = reinterpret_cast<unsigned long long *>(err), *a = reinterpret_cast<unsigned long long *>(mag);
+    trace_items(
+        tr, delta, [](int64_t) { return true; },
+        [&](int64_t dk, uint64_t packed) {
+            ntuple_tc_accum<T>(packed, sh, dk, [e, a](uint32_t off, int64_t dd, uint64_t m) {
+                __hip_atomic_fetch_add(e + off, static_cast<unsigned long long>(dd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(a + off, static_cast<unsigned long long>(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            });
+        });
+}
+
 // ---------------------------------------------------------------------------- augmentation
 // training_data.augment() (training_data.py:257-299) for board pairs on the device: the eight
 // symmetries [orig, hflip, rot1(orig), rot1(hflip), rot2(..), rot2(..), rot3(..), rot3(..)] with the
@@ -2346,6 +2439,49 @@ hipError_t launch_ntuple_tc_update(const uint4 *boards, uint32_t n, const int64_
         }
         if (phases & kNtupleTcAccum)
             return launch_1d(ntuple_tc_accum_kernel<tc>, group_lanes(n, 1u), 0, s, boards, n, delta, sh, err, mag);
+        return hipSuccess;
+    });
+}
+
+hipError_t launch_ntuple_trace_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next,
+                                    const uint8_t *terminated, uint32_t n, const NtupleTrace &tr, uint32_t slot, int64_t *delta,
+                                    hipStream_t s)
+{
+    return launch_1d(ntuple_trace_push_kernel, group_lanes(n, 1u), 0, s, after, after_value, best_next, terminated, n, tr.depth,
+                     tr.hist + static_cast<uint64_t>(slot) * n, tr.len, delta);
+}
+
+// Lanes of a trace update: one per (k, i) item, up to the grid cap
+static uint64_t trace_lanes(uint32_t n, const NtupleTrace &tr)
+{
+    const uint64_t want = static_cast<uint64_t>(n) * tr.depth;
+    return want < kSearchMaxLanes ? want : kSearchMaxLanes;
+}
+
+hipError_t launch_ntuple_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
+                                      const NtupleTrace &tr, uint32_t slot, hipStream_t s)
+{
+    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
+    const TraceArgs ta{tr.hist, tr.len, n, tr.depth, tr.lambda, slot};
+    return dispatch_tuples(net, [&](auto tc) {
+        return launch_1d(ntuple_trace_update_kernel<tc>, trace_lanes(n, tr), 0, s, ta, delta, lr_shift, sh, net.weights);
+    });
+}
+
+hipError_t launch_ntuple_tc_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const NtupleNet &net,
+                                         int64_t *err, int64_t *mag, const NtupleTrace &tr, uint32_t slot, hipStream_t s)
+{
+    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
+    const TraceArgs ta{tr.hist, tr.len, n, tr.depth, tr.lambda, slot};
+    return dispatch_tuples(net, [&](auto tc) {
+        if (phases & kNtupleTcWeights) {
+            const hipError_t rc = launch_1d(ntuple_tc_trace_weights_kernel<tc>, trace_lanes(n, tr), 0, s, ta, delta, lr_shift, sh,
+                                            net.weights, static_cast<const int64_t *>(err), static_cast<const int64_t *>(mag));
+            if (rc != hipSuccess)
+                return rc;
+        }
+        if (phases & kNtupleTcAccum)
+            return launch_1d(ntuple_tc_trace_accum_kernel<tc>, trace_lanes(n, tr), 0, s, ta, delta, sh, err, mag);
         return hipSuccess;
     });
 }

@@ -6,7 +6,9 @@ per update.  Everything is an integer: the same bits however the batch is split 
 ``NTupleNet`` owns the weights (a device tensor); ``Batched2048.ntuple_evaluate`` evaluates the engine's live boards;
 ``td_step`` / ``train`` chain evaluate, ``g2048_step`` and update on the device with no host synchronisation;
 ``NTupleTC`` and ``tc_step`` / ``tc_train`` do the same with temporal-coherence learning, a learning rate per weight
-(``g2048_ntuple_tc_update_plain``).
+(``g2048_ntuple_tc_update_plain``).  ``NTupleTrace`` and ``tdl_step`` / ``tdl_train`` / ``tcl_step`` /
+``tcl_train`` are the multi-step forms, TD(lambda) and TC(lambda): the error of a step also moves, decayed, the last few
+afterstates of the same board (``g2048_ntuple_trace_*``).
 ``NTupleNet.search`` / ``Batched2048.ntuple_search`` play the network through a depth-1..2 expectimax
 (``g2048_ntuple_search``), one launch for the whole batch.
 """
@@ -18,13 +20,14 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import NTupleIO, NTupleNetC, NTupleSearchIO, NTupleTCC, check
+from ._lib import NTupleIO, NTupleNetC, NTupleSearchIO, NTupleTCC, NTupleTraceC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
 ILLEGAL = -(1 << 63)                                              # G2048_NTUPLE_ILLEGAL: q of an illegal move
 SEARCH_MAX_DEPTH = 2                                              # G2048_NTUPLE_SEARCH_MAX_DEPTH
 TC_WEIGHTS, TC_ACCUM = 1, 2                                       # G2048_NTUPLE_TC_WEIGHTS, G2048_NTUPLE_TC_ACCUM
+TRACE_MAX = 8                                                     # G2048_NTUPLE_TRACE_MAX
 
 # Default shapes, as row-major cell indices (cell 4r + c).  The value sums every tuple over the eight symmetries of the
 # board, so a shape lists each tuple once, not once per placement.
@@ -200,6 +203,39 @@ class NTupleNet:
             raise ValueError("tc must be the NTupleTC of this network")
         self._launch(_lib.load().g2048_ntuple_tc_update_plain, boards, delta.data_ptr(), shift, phases, net, C.byref(tc._c))
 
+    def _trace_args(self, trace, delta, lr_shift):
+        """(net, lr_shift) for a trace update: ``trace`` and ``delta`` checked as :meth:`update` checks its arguments."""
+        if not isinstance(trace, NTupleTrace):
+            raise ValueError("trace must be an NTupleTrace")
+        net = self._ref(trace.device)
+        if (not isinstance(delta, torch.Tensor) or delta.dtype != torch.int64 or tuple(delta.shape) != (trace.n,)
+                or not delta.is_contiguous() or delta.device != trace.device):
+            raise ValueError(f"delta must be a contiguous int64 [{trace.n}] tensor on {trace.device}")
+        return net, _int_arg("lr_shift", lr_shift, 0, MAX_LR_SHIFT)
+
+    def trace_update(self, trace, delta, lr_shift):
+        """The TD(lambda) update (``g2048_ntuple_trace_update``): for the k-th last afterstate pushed
+        into ``trace`` (an :class:`NTupleTrace`), k below the board's history length, :meth:`update` with
+        ``d_k = (clamp(delta) * lam^k) >> 16``.  ``delta`` a device int64 ``[trace.n]`` tensor, ``lr_shift`` 0..40.  One
+        launch of integer atomic adds."""
+        net, shift = self._trace_args(trace, delta, lr_shift)
+        with torch.cuda.device(trace.device):
+            stream = C.c_void_p(torch.cuda.current_stream(trace.device).cuda_stream)
+            check(_lib.load().g2048_ntuple_trace_update(trace.n, delta.data_ptr(), shift, net, C.byref(trace._c), trace.slot, stream))
+
+    def tc_trace_update(self, trace, delta, lr_shift, tc, phases=3):
+        """The TC(lambda) update (``g2048_ntuple_tc_trace_update``): :meth:`tc_update` with ``d_k`` for
+        the k-th last afterstate of ``trace``.  ``phases=3`` is two launches, W then A; shards that share the network run W
+        on every shard, then A on every shard."""
+        net, shift = self._trace_args(trace, delta, lr_shift)
+        phases = _int_arg("phases", phases, TC_WEIGHTS, TC_WEIGHTS | TC_ACCUM)
+        if not isinstance(tc, NTupleTC) or tc.net is not self:
+            raise ValueError("tc must be the NTupleTC of this network")
+        with torch.cuda.device(trace.device):
+            stream = C.c_void_p(torch.cuda.current_stream(trace.device).cuda_stream)
+            check(_lib.load().g2048_ntuple_tc_trace_update(trace.n, delta.data_ptr(), shift, phases, net, C.byref(tc._c),
+                                                           C.byref(trace._c), trace.slot, stream))
+
     def state_dict(self):
         return {"tuples": self.tuples, "frac_bits": self.frac_bits, "weights": self.weights.clone()}
 
@@ -240,6 +276,67 @@ class NTupleTC:
                 raise ValueError(f"state_dict {name} must be int64 {tuple(self.err.shape)}")
         self.err.copy_(err)
         self.mag.copy_(mag)
+
+
+class NTupleTrace:
+    """The history of the n-tuple traces for ``n`` boards (``g2048_ntuple_trace``): ``hist``, the last
+    ``depth`` (H, 1..8) afterstates of every board as a uint8 ``[H, n, 16]`` ring, ``len``, uint8 ``[n]`` (bits 0..6 the
+    number of valid slots, bit 7 "the episode ended at the last push"), and the slot of the last push.  ``lam`` is a float in
+    0..1, stored as ``lam_q16 = round(lam * 65536)``.  One per engine or shard; call :meth:`reset` after ``engine.reset()``.
+
+    Memory: 16 H + 1 bytes per board."""
+
+    def __init__(self, n, depth=4, lam=0.5, device="cuda:0"):
+        self.n = _int_arg("n", n, 1, 0xffffff00)
+        self.depth = _int_arg("depth", depth, 1, TRACE_MAX)
+        if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0.0 <= lam <= 1.0:
+            raise ValueError(f"lam must be a number in 0..1, not {lam!r}")
+        self.lam_q16 = int(round(lam * 65536))
+        self.device = torch.device(device)
+        self.hist = torch.zeros((self.depth, self.n, 16), dtype=torch.uint8, device=self.device)
+        self.len = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        self.slot = self.depth - 1                      # the slot of the last push: the first push goes into slot 0
+        self._c = NTupleTraceC(self.depth, self.lam_q16, self.hist.data_ptr(), self.len.data_ptr())
+
+    def reset(self):
+        """Forget every board's history (``len`` = 0); the slot counter keeps running."""
+        self.len.zero_()
+
+    def push(self, after, after_value, best_next, terminated, out):
+        """Advance the slot and push (``g2048_ntuple_trace_push``), one launch on the current stream: store ``after`` (uint8
+        ``[n, 16]``) into the slot, update ``len`` with ``terminated`` (uint8 or bool ``[n]``), and write
+        ``out = (0 if terminated else best_next) - after_value`` (int64 ``[n]`` each).  Returns ``out``."""
+        n, dev = self.n, self.device
+        for name, t, shape, dtypes in (("after", after, (n, 16), (torch.uint8,)), ("after_value", after_value, (n,), (torch.int64,)),
+                                       ("best_next", best_next, (n,), (torch.int64,)),
+                                       ("terminated", terminated, (n,), (torch.uint8, torch.bool)), ("out", out, (n,), (torch.int64,))):
+            if (not isinstance(t, torch.Tensor) or t.dtype not in dtypes or tuple(t.shape) != shape or not t.is_contiguous()
+                    or t.device != dev):
+                raise ValueError(f"{name} must be a contiguous {str(dtypes[0]).replace('torch.', '')} {list(shape)} tensor on {dev}")
+        slot = (self.slot + 1) % self.depth
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            check(_lib.load().g2048_ntuple_trace_push(after.data_ptr(), after_value.data_ptr(), best_next.data_ptr(),
+                                                      terminated.data_ptr(), n, C.byref(self._c), slot, out.data_ptr(), stream))
+        self.slot = slot
+        return out
+
+    def state_dict(self):
+        return {"depth": self.depth, "lam_q16": self.lam_q16, "slot": self.slot, "hist": self.hist.clone(), "len": self.len.clone()}
+
+    def load_state_dict(self, state):
+        """Copy the history and the slot counter of a ``state_dict()`` of a trace of the same shape into this one (in place)."""
+        if int(state["depth"]) != self.depth or int(state["lam_q16"]) != self.lam_q16:
+            raise ValueError("state_dict is of a trace with another depth or lam")
+        hist, ln = torch.as_tensor(state["hist"]), torch.as_tensor(state["len"])
+        if hist.dtype != torch.uint8 or hist.shape != self.hist.shape:
+            raise ValueError(f"state_dict hist must be uint8 {tuple(self.hist.shape)}")
+        if ln.dtype != torch.uint8 or ln.shape != self.len.shape:
+            raise ValueError(f"state_dict len must be uint8 {tuple(self.len.shape)}")
+        slot = _int_arg("state_dict slot", state["slot"], 0, self.depth - 1)
+        self.hist.copy_(hist)
+        self.len.copy_(ln)
+        self.slot = slot
 
 
 class TDWork(NamedTuple):
@@ -313,4 +410,53 @@ def tc_train(engine, net, tc, n_steps, lr_shift):
     work = td_work(engine)
     for _ in range(int(n_steps)):
         tc_step(engine, net, tc, lr_shift, work)
+    return net
+
+
+def tdl_evaluate(engine, net, trace, work) -> TDWork:
+    """:func:`td_evaluate` for the trace learners: evaluate, play the greedy move, evaluate the new boards, then one
+    ``trace.push`` that stores the afterstate just played and forms ``work.delta`` in the same launch (in place of
+    td_evaluate's three element-wise ones).  Shards that share one network run this on every shard before an update on any."""
+    engine.ntuple_evaluate(net, out=work.before)
+    engine.step(work.before.action, auto_reset=True, want_info=False)
+    engine.ntuple_evaluate(net, out=work.after)
+    trace.push(work.before.after, work.before.after_value, work.after.best, engine.terminated, work.delta)
+    return work
+
+
+def _trace_of(engine, trace):
+    if not isinstance(trace, NTupleTrace) or trace.n != engine.n_envs or trace.device != engine.device:
+        raise ValueError(f"trace must be an NTupleTrace of {engine.n_envs} boards on {engine.device}")
+    return trace
+
+
+def tdl_step(engine, net, trace, lr_shift, work=None) -> TDWork:
+    """One afterstate TD(lambda) step of every board of ``engine`` under ``net``: :func:`tdl_evaluate`, then
+    ``net.trace_update``.  No host synchronisation; ``work`` (:func:`td_work`) is reused."""
+    work = tdl_evaluate(engine, net, _trace_of(engine, trace), td_work(engine) if work is None else work)
+    net.trace_update(trace, work.delta, lr_shift)
+    return work
+
+
+def tdl_train(engine, net, trace, n_steps, lr_shift):
+    """``n_steps`` :func:`tdl_step` calls with one set of buffers."""
+    work = td_work(engine)
+    for _ in range(int(n_steps)):
+        tdl_step(engine, net, trace, lr_shift, work)
+    return net
+
+
+def tcl_step(engine, net, tc, trace, lr_shift, work=None) -> TDWork:
+    """:func:`tdl_step` with the temporal-coherence trace update: :func:`tdl_evaluate`, then ``net.tc_trace_update`` (two
+    launches, W then A)."""
+    work = tdl_evaluate(engine, net, _trace_of(engine, trace), td_work(engine) if work is None else work)
+    net.tc_trace_update(trace, work.delta, lr_shift, tc)
+    return work
+
+
+def tcl_train(engine, net, tc, trace, n_steps, lr_shift):
+    """``n_steps`` :func:`tcl_step` calls with one set of buffers."""
+    work = td_work(engine)
+    for _ in range(int(n_steps)):
+        tcl_step(engine, net, tc, trace, lr_shift, work)
     return net

@@ -461,6 +461,48 @@ typedef struct g2048_ntuple_tc { int64_t *err; int64_t *mag; } g2048_ntuple_tc; 
 int g2048_ntuple_tc_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift,
                                  uint32_t phases, const g2048_ntuple_net *net, const g2048_ntuple_tc *tc, void *stream);
 
+/* N-tuple traces: TD(lambda) and TC(lambda) for the network above (Sutton 1988, Jaskowski 2017).  The
+ * error of step t also moves, decayed, the last few afterstates of the same board, so a terminal error travels H moves back
+ * per game and not one.  Notation of the two blocks above.  The history is caller-owned device memory, zero-initialised,
+ * one per engine or shard:
+ *   H     1..G2048_NTUPLE_TRACE_MAX (= 8) slots
+ *   lam   lambda in Q16, 0..65536
+ *   hist  uint8 [H][n][16]   slot-major, 16-byte aligned: slot k of board i is the 16 exponents at hist + (k*n + i)*16
+ *   len   uint8 [n]          bits 0..6: number of valid slots; bit 7: the episode ended at the last push
+ * push(slot), for every board i with `slot` in 0..H-1.  The caller advances `slot` by one mod H before each push:
+ *   old      = len[i];   l = (old & 0x80) ? 0 : min(old & 0x7f, H)
+ *   hist[slot][i] = after[i]                                                   (16 bytes)
+ *   delta[i] = (terminated[i] ? 0 : best_next[i]) - after_value[i]             (int64, wraps; exactly td_evaluate's delta)
+ *   len[i]   = min(l + 1, H) | (terminated[i] ? 0x80 : 0)
+ * `terminated` is uint8, non-zero meaning true.  push is total: any byte in len gives a defined result.
+ * trace update(slot), where `slot` is the slot of the last push, for every board i:
+ *   L   = min(len[i] & 0x7f, H);   d = clamp(delta[i], -2^40, +2^40)
+ *   p_0 = 65536;  p_k = (p_{k-1} * lam) >> 16                                  (uint64 arithmetic; 0..65536)
+ *   for k in 0..L-1:   a   = hist[(slot + H - k) mod H][i]
+ *                      d_k = (d * p_k) >> 16                                   (arithmetic shift: floors negatives; |d*p_k| <= 2^56)
+ *     TD:    step = sat_int32(d_k >> lr_shift);  weights[off(a,s,t)] += step for all s, t;  a zero step touches nothing
+ *     TC W:  weights[j] += step(d_k, rate(err[j], mag[j]))  with err, mag as they were before the call
+ *     TC A:  err[j] += d_k;  mag[j] += |d_k|                                    d_k == 0 touches nothing
+ * The same weight entry reached from two slots, or from two symmetries, counts once per reach.  Phase W and phase A are
+ * separate launches, as in the TC block and for the same reason; every update is a sum of integer adds, so its result does
+ * not depend on lane, wave or block order.  The shifts floor: a negative d_k decays to -1 and not to 0, while its positive
+ * twin reaches 0 -- the rule of the two step functions above, kept on purpose.  Consequence: with H = 1, or with lam = 0, the
+ * TD form equals g2048_ntuple_update_plain whenever |delta| <= 2^40, and the TC form equals g2048_ntuple_tc_update_plain
+ * always.  Shards that share a network each own a history and run push everywhere, then update everywhere (for TC: W
+ * everywhere, then A everywhere). */
+#define G2048_NTUPLE_TRACE_MAX 8
+typedef struct g2048_ntuple_trace { uint32_t depth; uint32_t lambda; uint8_t *hist; uint8_t *len; } g2048_ntuple_trace;
+/* One launch: n boards, `after` uint8[n][16] (16-byte aligned), after_value / best_next / delta int64[n], terminated
+ * uint8[n], all device memory; delta is written.  1 <= n <= 2^32 - 256. */
+int g2048_ntuple_trace_push(const uint8_t *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,
+                            uint64_t n, const g2048_ntuple_trace *tr, uint32_t slot, int64_t *delta, void *stream);
+/* The TD trace update in one launch: delta int64[n] (device), lr_shift 0..40. */
+int g2048_ntuple_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, const g2048_ntuple_net *net,
+                              const g2048_ntuple_trace *tr, uint32_t slot, void *stream);
+/* The TC trace update: phases = 1 (W), 2 (A) or 3, one launch per phase, W then A. */
+int g2048_ntuple_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const g2048_ntuple_net *net,
+                                 const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr, uint32_t slot, void *stream);
+
 /* N-tuple expectimax: a depth-1..2 search of every board with the network at the leaves, in one launch (INTEGRATION.md
  * §10) -- the player the n-tuple literature plays with.  Notation of the block above: net (T, L, F, cells, weights),
  * V(a) the sum over the 8 symmetries and T tuples, move(b, d) = (a_d, g_d, legal); cells are exponents, a cell is empty
