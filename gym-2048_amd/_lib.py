@@ -97,6 +97,15 @@ class NTupleNetC(C.Structure):
     ]
 
 
+class NTupleStagedNetC(C.Structure):
+    """g2048_ntuple_staged_net (include/g2048.h): the network with weights [S][T][16^L], S and the S - 1 stage thresholds."""
+    _fields_ = [
+        ("net", NTupleNetC),
+        ("n_stages", C.c_uint32),
+        ("thresholds", C.c_uint16 * 7),
+    ]
+
+
 class NTupleIO(C.Structure):
     """g2048_ntuple_io (include/g2048.h): device output pointers of evaluate (NULL = not wanted)."""
     _fields_ = [
@@ -205,6 +214,19 @@ SIGNATURES = {
     "g2048_ntuple_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, C.POINTER(NTupleNetC), C.POINTER(NTupleTraceC), _u32, _S]),
     "g2048_ntuple_tc_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleNetC), C.POINTER(NTupleTCC),
                                               C.POINTER(NTupleTraceC), _u32, _S]),
+    "g2048_ntuple_staged_evaluate": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleIO), _S]),
+    "g2048_ntuple_staged_evaluate_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleIO), _S]),
+    "g2048_ntuple_staged_search": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleSearchIO), _S]),
+    "g2048_ntuple_staged_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleSearchIO), _S]),
+    "g2048_ntuple_staged_values_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.c_void_p, _S]),
+    "g2048_ntuple_staged_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, C.POINTER(NTupleStagedNetC), _S]),
+    "g2048_ntuple_staged_tc_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleStagedNetC),
+                                                     C.POINTER(NTupleTCC), _S]),
+    "g2048_ntuple_staged_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleTraceC),
+                                                  _u32, _S]),
+    "g2048_ntuple_staged_tc_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleStagedNetC),
+                                                     C.POINTER(NTupleTCC), C.POINTER(NTupleTraceC), _u32, _S]),
+    "g2048_ntuple_stage_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.c_void_p, _S]),
     "g2048_add_tile": (C.c_int, [_E, _u32, _S]),
     "g2048_fill_random_actions": (C.c_int, [_E, _u64, _u32, C.c_void_p, _S]),
     "g2048_onehot": (C.c_int, [_E, C.c_void_p, _i32, _S]),

@@ -20,7 +20,7 @@ from ._lib import G2048Error, HostIO, StepIO, Stats, check
 from .analysis import (MC_DEFAULT_MAX_STEPS, Afterstates, MCSearch, Search, SearchWeights, afterstates,  # noqa: F401
                        expectimax, mc_search, _OBS_DTYPES, _afterstate_io, _mc_io, _search_io)
 # the n-tuple network value function, re-exported; Batched2048.ntuple_evaluate runs it on the live boards
-from .ntuple import NTupleEval, NTupleNet, NTupleSearch, TUPLES, td_step, train, _eval_io  # noqa: F401
+from .ntuple import NTupleEval, NTupleNet, NTupleSearch, TUPLES, stage_mask, td_step, train, _eval_io  # noqa: F401
 from .ntuple import NTupleTC, tc_step, tc_train, tc_update  # noqa: F401
 from .ntuple import NTupleTrace, tcl_step, tcl_train, tdl_evaluate, tdl_step, tdl_train  # noqa: F401
 from .ntuple import _search_io as _ntuple_search_io
@@ -720,7 +720,7 @@ class Batched2048:
             raise ValueError("net must be an NTupleNet")
         ref = net._ref(self.device)
         io, out = _eval_io(self.n_envs, self.device, out)
-        check(self._lib.g2048_ntuple_evaluate(self._h, ref, C.byref(io), self._stream()))
+        check(net._fn("evaluate")(self._h, ref, C.byref(io), self._stream()))
         return out
 
     def ntuple_search(self, net, depth=1, out=None) -> NTupleSearch:
@@ -732,7 +732,7 @@ class Batched2048:
             raise ValueError("net must be an NTupleNet")
         ref = net._ref(self.device)
         io, out = _ntuple_search_io(self.n_envs, self.device, depth, out)
-        check(self._lib.g2048_ntuple_search(self._h, ref, C.byref(io), self._stream()))
+        check(net._fn("search")(self._h, ref, C.byref(io), self._stream()))
         return out
 
     def isend_numpy(self) -> np.ndarray:

@@ -1240,8 +1240,9 @@ int g2048_mc_search_plain(const uint8_t *boards, uint64_t n, uint32_t index_offs
 
 } // extern "C"
 
-// g2048_ntuple_net -> the launchers' network, or G2048_ERR_INVALID (before any HIP call: works without a device)
-static int ntuple_net(const g2048_ntuple_net *net, g2048::NtupleNet *out)
+// g2048_ntuple_net -> the launchers' network, or G2048_ERR_INVALID (before any HIP call: works without a device).
+// need_weights = false for the one call that reads no table (g2048_ntuple_stage_plain).
+static int ntuple_net(const g2048_ntuple_net *net, g2048::NtupleNet *out, bool need_weights = true)
 {
     if (!net)
         return fail(G2048_ERR_INVALID, "net is NULL");
@@ -1262,15 +1263,39 @@ static int ntuple_net(const g2048_ntuple_net *net, g2048::NtupleNet *out)
             seen |= 1u << c;
         }
     }
-    if (!net->weights)
+    if (need_weights && !net->weights)
         return fail(G2048_ERR_INVALID, "net weights is NULL");
-    if (reinterpret_cast<uintptr_t>(net->weights) & 15u)
+    if (need_weights && reinterpret_cast<uintptr_t>(net->weights) & 15u)
         return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple weights need 16 bytes");
+    *out = g2048::NtupleNet{};
     out->n_tuples = net->n_tuples;
     out->tuple_len = net->tuple_len;
     out->frac_bits = net->frac_bits;
     memcpy(out->cells, net->cells, sizeof(out->cells));
     out->weights = net->weights;
+    return G2048_OK;
+}
+
+// g2048_ntuple_staged_net -> the same network with its stages: every ntuple entry point below is written once, for either
+// descriptor, and reaches the same launchers and kernels (S = 1 is the unstaged network).
+static int ntuple_net(const g2048_ntuple_staged_net *net, g2048::NtupleNet *out, bool need_weights = true)
+{
+    if (!net)
+        return fail(G2048_ERR_INVALID, "net is NULL");
+    if (net->n_stages < 1 || net->n_stages > G2048_NTUPLE_MAX_STAGES)
+        return fail(G2048_ERR_INVALID, "n_stages=%u: need 1 <= n_stages <= %d", net->n_stages, G2048_NTUPLE_MAX_STAGES);
+    for (uint32_t j = 0; j + 1 < net->n_stages; ++j) {
+        if (net->thresholds[j] == 0)
+            return fail(G2048_ERR_INVALID, "thresholds[%u]=0: a stage threshold is 1..65535", j);
+        if (j > 0 && net->thresholds[j] <= net->thresholds[j - 1])
+            return fail(G2048_ERR_INVALID, "thresholds[%u]=%u: thresholds must be strictly ascending (thresholds[%u]=%u)", j,
+                        net->thresholds[j], j - 1, net->thresholds[j - 1]);
+    }
+    if (int rc = ntuple_net(&net->net, out, need_weights))
+        return rc;
+    out->n_stages = net->n_stages;
+    for (uint32_t j = 0; j + 1 < net->n_stages; ++j)
+        out->thresholds[j] = net->thresholds[j];
     return G2048_OK;
 }
 
@@ -1290,41 +1315,6 @@ static int ntuple_out(const g2048_ntuple_io *io, g2048::NtupleOut *o)
     return G2048_OK;
 }
 
-extern "C" {
-
-int g2048_ntuple_evaluate(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_io *io, void *stream)
-{
-    if (int rc = usable(e))
-        return rc;
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    g2048::NtupleOut o;
-    if (int rc = ntuple_out(io, &o))
-        return rc;
-    G2048_HIP(hipSetDevice(e->device));
-    G2048_HIP(g2048::launch_ntuple_eval(e->st.boards, static_cast<uint32_t>(e->n), false, nn, o, static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-int g2048_ntuple_evaluate_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_io *io,
-                                void *stream)
-{
-    if (int rc = plain_boards(boards, n))
-        return rc;
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    g2048::NtupleOut o;
-    if (int rc = ntuple_out(io, &o))
-        return rc;
-    G2048_HIP(g2048::launch_ntuple_eval(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), true, nn, o,
-                                        static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-} // extern "C"
-
 // g2048_ntuple_search_io -> the kernel's outputs, or G2048_ERR_INVALID (before any HIP call: works without a device)
 static int ntuple_search_out(const g2048_ntuple_search_io *io, g2048::NtupleSearchOut *o)
 {
@@ -1339,106 +1329,6 @@ static int ntuple_search_out(const g2048_ntuple_search_io *io, g2048::NtupleSear
     *o = g2048::NtupleSearchOut{io->action, io->value};
     return G2048_OK;
 }
-
-extern "C" {
-
-int g2048_ntuple_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io, void *stream)
-{
-    if (int rc = usable(e))
-        return rc;
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    g2048::NtupleSearchOut o;
-    if (int rc = ntuple_search_out(io, &o))
-        return rc;
-    G2048_HIP(hipSetDevice(e->device));
-    G2048_HIP(g2048::launch_ntuple_search(e->st.boards, static_cast<uint32_t>(e->n), io->depth, false, nn, o,
-                                          static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-int g2048_ntuple_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io,
-                              void *stream)
-{
-    if (int rc = plain_boards(boards, n))
-        return rc;
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    g2048::NtupleSearchOut o;
-    if (int rc = ntuple_search_out(io, &o))
-        return rc;
-    G2048_HIP(g2048::launch_ntuple_search(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), io->depth, true, nn, o,
-                                          static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-int g2048_ntuple_values_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, int64_t *v, void *stream)
-{
-    if (int rc = plain_boards(boards, n))
-        return rc;
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    if (!v)
-        return fail(G2048_ERR_INVALID, "v is NULL");
-    if (reinterpret_cast<uintptr_t>(v) & 7u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple v needs 8 bytes");
-    G2048_HIP(g2048::launch_ntuple_values(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), nn, v,
-                                          static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-int g2048_ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift,
-                              const g2048_ntuple_net *net, void *stream)
-{
-    if (int rc = plain_boards(boards, n))
-        return rc;
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    if (!delta)
-        return fail(G2048_ERR_INVALID, "delta is NULL");
-    if (reinterpret_cast<uintptr_t>(delta) & 7u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple delta needs 8 bytes");
-    if (lr_shift > G2048_NTUPLE_MAX_LR_SHIFT)
-        return fail(G2048_ERR_INVALID, "lr_shift=%u: need 0 <= lr_shift <= %d", lr_shift, G2048_NTUPLE_MAX_LR_SHIFT);
-    G2048_HIP(g2048::launch_ntuple_update(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), delta, lr_shift, nn,
-                                          static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-int g2048_ntuple_tc_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
-                                 const g2048_ntuple_net *net, const g2048_ntuple_tc *tc, void *stream)
-{
-    if (int rc = plain_boards(boards, n))
-        return rc;
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    if (!delta)
-        return fail(G2048_ERR_INVALID, "delta is NULL");
-    if (reinterpret_cast<uintptr_t>(delta) & 7u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple delta needs 8 bytes");
-    if (lr_shift > G2048_NTUPLE_MAX_LR_SHIFT)
-        return fail(G2048_ERR_INVALID, "lr_shift=%u: need 0 <= lr_shift <= %d", lr_shift, G2048_NTUPLE_MAX_LR_SHIFT);
-    if (phases < 1 || phases > (G2048_NTUPLE_TC_WEIGHTS | G2048_NTUPLE_TC_ACCUM))
-        return fail(G2048_ERR_INVALID, "phases=%u: need G2048_NTUPLE_TC_WEIGHTS (1), G2048_NTUPLE_TC_ACCUM (2) or both (3)", phases);
-    if (!tc)
-        return fail(G2048_ERR_INVALID, "tc is NULL");
-    if (!tc->err)
-        return fail(G2048_ERR_INVALID, "tc err is NULL");
-    if (!tc->mag)
-        return fail(G2048_ERR_INVALID, "tc mag is NULL");
-    if ((reinterpret_cast<uintptr_t>(tc->err) | reinterpret_cast<uintptr_t>(tc->mag)) & 7u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple tc err and mag need 8 bytes");
-    G2048_HIP(g2048::launch_ntuple_tc_update(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), delta, lr_shift,
-                                             phases, nn, tc->err, tc->mag, static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-} // extern "C"
 
 // the board count of a trace call (the cap of plain_boards: 32-bit board indices)
 static int trace_boards(uint64_t n)
@@ -1481,7 +1371,270 @@ static int ntuple_delta(const int64_t *delta, uint32_t lr_shift)
     return G2048_OK;
 }
 
+// phases and the accumulators of a TC update
+static int ntuple_tc(uint32_t phases, const g2048_ntuple_tc *tc)
+{
+    if (phases < 1 || phases > (G2048_NTUPLE_TC_WEIGHTS | G2048_NTUPLE_TC_ACCUM))
+        return fail(G2048_ERR_INVALID, "phases=%u: need G2048_NTUPLE_TC_WEIGHTS (1), G2048_NTUPLE_TC_ACCUM (2) or both (3)", phases);
+    if (!tc)
+        return fail(G2048_ERR_INVALID, "tc is NULL");
+    if (!tc->err)
+        return fail(G2048_ERR_INVALID, "tc err is NULL");
+    if (!tc->mag)
+        return fail(G2048_ERR_INVALID, "tc mag is NULL");
+    if ((reinterpret_cast<uintptr_t>(tc->err) | reinterpret_cast<uintptr_t>(tc->mag)) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple tc err and mag need 8 bytes");
+    return G2048_OK;
+}
+
+// The entry points that take a network, once each for Net = g2048_ntuple_net and g2048_ntuple_staged_net (the extern "C"
+// wrappers below): only ntuple_net() differs.
+template <class Net> static int ntuple_evaluate(const g2048_engine *e, const Net *net, const g2048_ntuple_io *io, void *stream)
+{
+    if (int rc = usable(e))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleOut o;
+    if (int rc = ntuple_out(io, &o))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(g2048::launch_ntuple_eval(e->st.boards, static_cast<uint32_t>(e->n), false, nn, o, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+template <class Net>
+static int ntuple_evaluate_plain(const uint8_t *boards, uint64_t n, const Net *net, const g2048_ntuple_io *io, void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleOut o;
+    if (int rc = ntuple_out(io, &o))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_eval(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), true, nn, o,
+                                        static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+template <class Net> static int ntuple_search(const g2048_engine *e, const Net *net, const g2048_ntuple_search_io *io, void *stream)
+{
+    if (int rc = usable(e))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleSearchOut o;
+    if (int rc = ntuple_search_out(io, &o))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(g2048::launch_ntuple_search(e->st.boards, static_cast<uint32_t>(e->n), io->depth, false, nn, o,
+                                          static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+template <class Net>
+static int ntuple_search_plain(const uint8_t *boards, uint64_t n, const Net *net, const g2048_ntuple_search_io *io, void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleSearchOut o;
+    if (int rc = ntuple_search_out(io, &o))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_search(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), io->depth, true, nn, o,
+                                          static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+template <class Net> static int ntuple_values_plain(const uint8_t *boards, uint64_t n, const Net *net, int64_t *v, void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (!v)
+        return fail(G2048_ERR_INVALID, "v is NULL");
+    if (reinterpret_cast<uintptr_t>(v) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple v needs 8 bytes");
+    G2048_HIP(g2048::launch_ntuple_values(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), nn, v,
+                                          static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+template <class Net>
+static int ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, const Net *net, void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (int rc = ntuple_delta(delta, lr_shift))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_update(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), delta, lr_shift, nn,
+                                          static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+template <class Net>
+static int ntuple_tc_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                  const Net *net, const g2048_ntuple_tc *tc, void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (int rc = ntuple_delta(delta, lr_shift))
+        return rc;
+    if (int rc = ntuple_tc(phases, tc))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_tc_update(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), delta, lr_shift,
+                                             phases, nn, tc->err, tc->mag, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+template <class Net>
+static int ntuple_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, const Net *net, const g2048_ntuple_trace *tr,
+                               uint32_t slot, void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (int rc = trace_boards(n))
+        return rc;
+    if (int rc = ntuple_delta(delta, lr_shift))
+        return rc;
+    g2048::NtupleTrace t;
+    if (int rc = ntuple_trace(tr, slot, &t))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_trace_update(static_cast<uint32_t>(n), delta, lr_shift, nn, t, slot,
+                                                static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+template <class Net>
+static int ntuple_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const Net *net,
+                                  const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (int rc = trace_boards(n))
+        return rc;
+    if (int rc = ntuple_delta(delta, lr_shift))
+        return rc;
+    if (int rc = ntuple_tc(phases, tc))
+        return rc;
+    g2048::NtupleTrace t;
+    if (int rc = ntuple_trace(tr, slot, &t))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_tc_trace_update(static_cast<uint32_t>(n), delta, lr_shift, phases, nn, tc->err, tc->mag, t, slot,
+                                                   static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 extern "C" {
+
+int g2048_ntuple_evaluate(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_io *io, void *stream)
+{
+    return ntuple_evaluate(e, net, io, stream);
+}
+
+int g2048_ntuple_staged_evaluate(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_io *io, void *stream)
+{
+    return ntuple_evaluate(e, net, io, stream);
+}
+
+int g2048_ntuple_evaluate_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_io *io,
+                                void *stream)
+{
+    return ntuple_evaluate_plain(boards, n, net, io, stream);
+}
+
+int g2048_ntuple_staged_evaluate_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
+                                       const g2048_ntuple_io *io, void *stream)
+{
+    return ntuple_evaluate_plain(boards, n, net, io, stream);
+}
+
+int g2048_ntuple_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io, void *stream)
+{
+    return ntuple_search(e, net, io, stream);
+}
+
+int g2048_ntuple_staged_search(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_search_io *io,
+                               void *stream)
+{
+    return ntuple_search(e, net, io, stream);
+}
+
+int g2048_ntuple_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io,
+                              void *stream)
+{
+    return ntuple_search_plain(boards, n, net, io, stream);
+}
+
+int g2048_ntuple_staged_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
+                                     const g2048_ntuple_search_io *io, void *stream)
+{
+    return ntuple_search_plain(boards, n, net, io, stream);
+}
+
+int g2048_ntuple_values_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, int64_t *v, void *stream)
+{
+    return ntuple_values_plain(boards, n, net, v, stream);
+}
+
+int g2048_ntuple_staged_values_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net, int64_t *v, void *stream)
+{
+    return ntuple_values_plain(boards, n, net, v, stream);
+}
+
+int g2048_ntuple_stage_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net, uint8_t *stage, void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn, false))
+        return rc;
+    if (!stage)
+        return fail(G2048_ERR_INVALID, "stage is NULL");
+    G2048_HIP(g2048::launch_ntuple_stage(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), nn, stage,
+                                         static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift,
+                              const g2048_ntuple_net *net, void *stream)
+{
+    return ntuple_update_plain(boards, n, delta, lr_shift, net, stream);
+}
+
+int g2048_ntuple_staged_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift,
+                                     const g2048_ntuple_staged_net *net, void *stream)
+{
+    return ntuple_update_plain(boards, n, delta, lr_shift, net, stream);
+}
+
+int g2048_ntuple_tc_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                 const g2048_ntuple_net *net, const g2048_ntuple_tc *tc, void *stream)
+{
+    return ntuple_tc_update_plain(boards, n, delta, lr_shift, phases, net, tc, stream);
+}
+
+int g2048_ntuple_staged_tc_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                        const g2048_ntuple_staged_net *net, const g2048_ntuple_tc *tc, void *stream)
+{
+    return ntuple_tc_update_plain(boards, n, delta, lr_shift, phases, net, tc, stream);
+}
 
 int g2048_ntuple_trace_push(const uint8_t *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,
                             uint64_t n, const g2048_ntuple_trace *tr, uint32_t slot, int64_t *delta, void *stream)
@@ -1513,47 +1666,26 @@ int g2048_ntuple_trace_push(const uint8_t *after, const int64_t *after_value, co
 int g2048_ntuple_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, const g2048_ntuple_net *net,
                               const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
 {
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    if (int rc = trace_boards(n))
-        return rc;
-    if (int rc = ntuple_delta(delta, lr_shift))
-        return rc;
-    g2048::NtupleTrace t;
-    if (int rc = ntuple_trace(tr, slot, &t))
-        return rc;
-    G2048_HIP(g2048::launch_ntuple_trace_update(static_cast<uint32_t>(n), delta, lr_shift, nn, t, slot,
-                                                static_cast<hipStream_t>(stream)));
-    return G2048_OK;
+    return ntuple_trace_update(n, delta, lr_shift, net, tr, slot, stream);
+}
+
+int g2048_ntuple_staged_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, const g2048_ntuple_staged_net *net,
+                                     const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
+{
+    return ntuple_trace_update(n, delta, lr_shift, net, tr, slot, stream);
 }
 
 int g2048_ntuple_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const g2048_ntuple_net *net,
                                  const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
 {
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    if (int rc = trace_boards(n))
-        return rc;
-    if (int rc = ntuple_delta(delta, lr_shift))
-        return rc;
-    if (phases < 1 || phases > (G2048_NTUPLE_TC_WEIGHTS | G2048_NTUPLE_TC_ACCUM))
-        return fail(G2048_ERR_INVALID, "phases=%u: need G2048_NTUPLE_TC_WEIGHTS (1), G2048_NTUPLE_TC_ACCUM (2) or both (3)", phases);
-    if (!tc)
-        return fail(G2048_ERR_INVALID, "tc is NULL");
-    if (!tc->err)
-        return fail(G2048_ERR_INVALID, "tc err is NULL");
-    if (!tc->mag)
-        return fail(G2048_ERR_INVALID, "tc mag is NULL");
-    if ((reinterpret_cast<uintptr_t>(tc->err) | reinterpret_cast<uintptr_t>(tc->mag)) & 7u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple tc err and mag need 8 bytes");
-    g2048::NtupleTrace t;
-    if (int rc = ntuple_trace(tr, slot, &t))
-        return rc;
-    G2048_HIP(g2048::launch_ntuple_tc_trace_update(static_cast<uint32_t>(n), delta, lr_shift, phases, nn, tc->err, tc->mag, t, slot,
-                                                   static_cast<hipStream_t>(stream)));
-    return G2048_OK;
+    return ntuple_tc_trace_update(n, delta, lr_shift, phases, net, tc, tr, slot, stream);
+}
+
+int g2048_ntuple_staged_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                        const g2048_ntuple_staged_net *net, const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr,
+                                        uint32_t slot, void *stream)
+{
+    return ntuple_tc_trace_update(n, delta, lr_shift, phases, net, tc, tr, slot, stream);
 }
 
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream)

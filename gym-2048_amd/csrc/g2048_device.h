@@ -672,9 +672,27 @@ G2048_DEV uint32_t mc_root(const Board &cells, uint32_t i, uint32_t rollouts, ui
 constexpr uint32_t kNtupleMaxTuples = 8, kNtupleMaxLen = 6, kNtupleMaxFrac = 16, kNtupleMaxShift = 40; // = G2048_NTUPLE_* (g2048.h)
 constexpr int64_t kNtupleIllegal = INT64_MIN;                                                          // G2048_NTUPLE_ILLEGAL
 
+// Multi-stage networks (g2048_ntuple_staged_*, include/g2048.h; Yeh et al. 2016, Jaskowski 2017): S
+// weight sets [S][T][16^L], the set of a board chosen by the tiles it holds.  Integers only, a function of the board alone:
+//   mask(b)  = OR over the 16 cells of 1 << c(b[cell])        (16 bits; bit 0 = "has an empty cell"; the same for all 8 symmetries)
+//   stage(b) = the number of j < S - 1 with mask(b) >= thr[j]  (thr strictly ascending, 1..65535; compared as integers)
+//   off(b, s, t) = (stage(b) * T + t) * 16^L + idx_t(s(b))     (an element index below 2^30; the BYTE offset needs 64 bits)
+// Every definition of this header reads and writes the tables of stage(board it looks up): the four afterstates of a board,
+// the leaves below a chance node and the slots of a trace history may all sit in different stages, and stage(b) is not
+// monotone over a game (16k + 8k + 8k -> 16k + 16k leaves the stage of 0x6000).  S = 1 is the network of above, bit for bit.
+// The stages are a compile-time property of a kernel: the unstaged entry points pass an NtupleShape, exactly the kernel
+// argument they had before stages existed, and compute no mask; a network with S > 1 passes an NtupleStagedShape.  Every
+// per-board function below is a template on the shape type (deduced), and ntuple_stage_base is the one place that differs.
+// NtupleStagedShape::thr holds kNtupleNoStage, which no mask reaches, from entry S - 1 on: stage() needs no S.
+constexpr uint32_t kNtupleMaxStages = 8;          // = G2048_NTUPLE_MAX_STAGES (g2048.h)
+constexpr uint32_t kNtupleNoStage = 0x10000u;     // above every 16-bit mask
+
 struct NtupleShape {
     uint32_t n_tuples, tuple_len;
     uint32_t list[8 * kNtupleMaxTuples]; // list[8 * s + t]: nibble k = the cell of b that idx_t(s(b)) reads for k
+};
+struct NtupleStagedShape : NtupleShape {
+    uint32_t thr[kNtupleMaxStages - 1];  // thr[j], j < S - 1; kNtupleNoStage from there on
 };
 
 // The cell of b that symmetry s (0..7) puts at cell c: bit 0 transposes, bit 1 reverses the rows, bit 2 the columns.
@@ -703,6 +721,34 @@ G2048_HOST_DEV NtupleShape ntuple_shape(uint32_t n_tuples, uint32_t tuple_len, c
             for (uint32_t k = 0; k < tuple_len; ++k)
                 sh.list[8u * s + t] |= ntuple_sym_cell(s, cells[t][k]) << (4u * k);
     return sh;
+}
+
+// thresholds: the n_stages - 1 ascending thresholds of a staged network
+G2048_HOST_DEV NtupleStagedShape ntuple_staged_shape(const NtupleShape &shape, uint32_t n_stages, const uint16_t *thresholds)
+{
+    NtupleStagedShape sh{};
+    static_cast<NtupleShape &>(sh) = shape;
+    for (uint32_t j = 0; j < kNtupleMaxStages - 1u; ++j)
+        sh.thr[j] = j + 1u < n_stages ? thresholds[j] : kNtupleNoStage;
+    return sh;
+}
+
+// mask(b) of a packed board (ntuple_pack: the 16 clamped cells as nibbles)
+G2048_HOST_DEV uint32_t ntuple_stage_mask(uint64_t packed)
+{
+    uint32_t mask = 0;
+    for (uint32_t c = 0; c < 16u; ++c)
+        mask |= 1u << (static_cast<uint32_t>(packed >> (4u * c)) & 15u);
+    return mask;
+}
+
+// stage(b) for mask = mask(b): 0..S-1
+G2048_HOST_DEV uint32_t ntuple_stage(uint32_t mask, const NtupleStagedShape &sh)
+{
+    uint32_t stage = 0;
+    for (uint32_t j = 0; j < kNtupleMaxStages - 1u; ++j)
+        stage += mask >= sh.thr[j] ? 1u : 0u;
+    return stage;
 }
 
 // c(e) for the four cells of a row register: min(byte mod 32, 15)
@@ -737,23 +783,35 @@ G2048_DEV uint32_t ntuple_index(uint64_t packed, uint32_t list, uint32_t L)
     return idx;
 }
 
-// offset of look-up (s, t) in the weight array [T][16^L]; < T * 16^L
-G2048_DEV uint32_t ntuple_offset(uint64_t packed, const NtupleShape &sh, uint32_t s, uint32_t t)
+// stage(b) * T * 16^L, the element offset of the board's weight set in [S][T][16^L]: once per packed board, before its 8T
+// offsets.  At most 7 * 8 * 16^6 < 2^30.  The unstaged shape has one set: a constant 0 that folds away.
+G2048_DEV uint32_t ntuple_stage_base(uint64_t, const NtupleShape &) { return 0u; }
+G2048_DEV uint32_t ntuple_stage_base(uint64_t packed, const NtupleStagedShape &sh)
 {
-    return (t << (4u * sh.tuple_len)) + ntuple_index(packed, sh.list[8u * s + t], sh.tuple_len);
+    return (ntuple_stage(ntuple_stage_mask(packed), sh) * sh.n_tuples) << (4u * sh.tuple_len);
 }
 
-// V(b).  T = sh.n_tuples as a template argument: the 8T look-ups are straight-line code, all offsets first, then all
-// loads, then the adds -- the loads do not depend on each other and are in flight together.
-template <uint32_t T> G2048_DEV int64_t ntuple_value(uint64_t packed, const NtupleShape &sh, const int32_t *weights)
+// offset of look-up (s, t) of a board whose weight set starts at element `base` (ntuple_stage_base) in the weight array
+// [S][T][16^L]; < S * T * 16^L <= 2^30: an ELEMENT index that fits uint32.  Every user adds it to a 64-bit pointer (the
+// byte offset of S = 8, T = 8, L = 6 reaches 4 GiB in the weights and 8 GiB in a TC accumulator).
+G2048_DEV uint32_t ntuple_offset(uint64_t packed, const NtupleShape &sh, uint32_t s, uint32_t t, uint32_t base)
+{
+    return base + (t << (4u * sh.tuple_len)) + ntuple_index(packed, sh.list[8u * s + t], sh.tuple_len);
+}
+
+// V(b), read from the tables of stage(b).  T = sh.n_tuples as a template argument: the 8T look-ups are straight-line code,
+// the stage base and all offsets first, then all loads, then the adds -- the loads do not depend on each other and are in
+// flight together.
+template <uint32_t T, class Shape> G2048_DEV int64_t ntuple_value(uint64_t packed, const Shape &sh, const int32_t *weights)
 {
     uint32_t off[8u * T];
     int32_t w[8u * T];
+    const uint32_t base = ntuple_stage_base(packed, sh);
 #pragma unroll
     for (uint32_t s = 0; s < 8u; ++s)
 #pragma unroll
         for (uint32_t t = 0; t < T; ++t)
-            off[s * T + t] = ntuple_offset(packed, sh, s, t);
+            off[s * T + t] = ntuple_offset(packed, sh, s, t, base);
 #pragma unroll
     for (uint32_t j = 0; j < 8u * T; ++j)
         w[j] = weights[off[j]];
@@ -771,8 +829,8 @@ struct NtupleMove {
     bool legal;
 };
 
-template <uint32_t T, class Tables>
-G2048_DEV NtupleMove ntuple_move(const Board &cells, uint32_t d, const NtupleShape &sh, uint32_t F, const int32_t *weights,
+template <uint32_t T, class Shape, class Tables>
+G2048_DEV NtupleMove ntuple_move(const Board &cells, uint32_t d, const Shape &sh, uint32_t F, const int32_t *weights,
                                  const Tables &tb)
 {
     NtupleMove m;
@@ -802,8 +860,8 @@ struct NtupleRoot {
     int64_t after_value;
 };
 
-template <uint32_t T, class Tables>
-G2048_DEV NtupleRoot ntuple_root(const Board &cells, const NtupleShape &sh, uint32_t F, const int32_t *weights, const Tables &tb)
+template <uint32_t T, class Shape, class Tables>
+G2048_DEV NtupleRoot ntuple_root(const Board &cells, const Shape &sh, uint32_t F, const int32_t *weights, const Tables &tb)
 {
     NtupleRoot r;
     NtupleMove m[4];
@@ -831,13 +889,14 @@ G2048_DEV int32_t ntuple_step(int64_t delta, uint32_t lr_shift)
 
 // add(offset, step) for each of the 8T look-ups of one board: the device passes a fire-and-forget atomic, the host a
 // wrapping add.
-template <uint32_t T, class Add> G2048_DEV void ntuple_update(uint64_t packed, const NtupleShape &sh, int32_t step, Add add)
+template <uint32_t T, class Shape, class Add> G2048_DEV void ntuple_update(uint64_t packed, const Shape &sh, int32_t step, Add add)
 {
+    const uint32_t base = ntuple_stage_base(packed, sh);
 #pragma unroll
     for (uint32_t s = 0; s < 8u; ++s)
 #pragma unroll
         for (uint32_t t = 0; t < T; ++t)
-            add(ntuple_offset(packed, sh, s, t), step);
+            add(ntuple_offset(packed, sh, s, t, base), step);
 }
 
 // Temporal-coherence learning (g2048_ntuple_tc_update_plain, include/g2048.h; Beal & Smith 1999,
@@ -892,18 +951,19 @@ G2048_DEV int32_t ntuple_tc_step(int64_t d, uint32_t rate, uint32_t lr_shift)
 
 // Phase W of one board, d != 0: all 8T offsets, then all 16T accumulator loads (independent: in flight together, as in
 // ntuple_value), then the rates and steps, then add(offset, step) for every step that is not 0.
-template <uint32_t T, class Add>
-G2048_DEV void ntuple_tc_weights(uint64_t packed, const NtupleShape &sh, int64_t d, uint32_t lr_shift, const int64_t *err,
+template <uint32_t T, class Shape, class Add>
+G2048_DEV void ntuple_tc_weights(uint64_t packed, const Shape &sh, int64_t d, uint32_t lr_shift, const int64_t *err,
                                  const int64_t *mag, Add add)
 {
     uint32_t off[8u * T];
     int64_t e[8u * T];
     uint64_t a[8u * T];
+    const uint32_t base = ntuple_stage_base(packed, sh);
 #pragma unroll
     for (uint32_t s = 0; s < 8u; ++s)
 #pragma unroll
         for (uint32_t t = 0; t < T; ++t)
-            off[s * T + t] = ntuple_offset(packed, sh, s, t);
+            off[s * T + t] = ntuple_offset(packed, sh, s, t, base);
 #pragma unroll
     for (uint32_t j = 0; j < 8u * T; ++j) {
         e[j] = err[off[j]];
@@ -918,14 +978,15 @@ G2048_DEV void ntuple_tc_weights(uint64_t packed, const NtupleShape &sh, int64_t
 }
 
 // Phase A of one board, d != 0: add(offset, d, |d|) for each of the 8T look-ups.
-template <uint32_t T, class Add> G2048_DEV void ntuple_tc_accum(uint64_t packed, const NtupleShape &sh, int64_t d, Add add)
+template <uint32_t T, class Shape, class Add> G2048_DEV void ntuple_tc_accum(uint64_t packed, const Shape &sh, int64_t d, Add add)
 {
     const uint64_t m = static_cast<uint64_t>(d < 0 ? -d : d);
+    const uint32_t base = ntuple_stage_base(packed, sh);
 #pragma unroll
     for (uint32_t s = 0; s < 8u; ++s)
 #pragma unroll
         for (uint32_t t = 0; t < T; ++t)
-            add(ntuple_offset(packed, sh, s, t), d, m);
+            add(ntuple_offset(packed, sh, s, t, base), d, m);
 }
 
 // n-tuple traces (g2048_ntuple_trace_push / g2048_ntuple_trace_update / g2048_ntuple_tc_trace_update, include/g2048.h,
@@ -1043,12 +1104,12 @@ G2048_DEV int64_t floor_div(int64_t a, int64_t b)
     return q - (a - q * b < 0 ? 1 : 0);
 }
 
-template <int D, uint32_t T, class Tables>
-G2048_DEV int64_t ntuple_search_state(const Board &b, const NtupleShape &sh, uint32_t F, const int32_t *weights, const Tables &tb);
+template <int D, uint32_t T, class Shape, class Tables>
+G2048_DEV int64_t ntuple_search_state(const Board &b, const Shape &sh, uint32_t F, const int32_t *weights, const Tables &tb);
 
 // Part of the chance-node sum of afterstate `a`: the items sub, sub + K, ... of chance_items, each weight * S_{D-1}.
-template <int D, uint32_t T, class Tables>
-G2048_DEV int64_t ntuple_chance_partial(const Board &a, uint32_t sub, uint32_t K, const NtupleShape &sh, uint32_t F,
+template <int D, uint32_t T, class Shape, class Tables>
+G2048_DEV int64_t ntuple_chance_partial(const Board &a, uint32_t sub, uint32_t K, const Shape &sh, uint32_t F,
                                         const int32_t *weights, const Tables &tb)
 {
     int64_t sum = 0;
@@ -1059,8 +1120,8 @@ G2048_DEV int64_t ntuple_chance_partial(const Board &a, uint32_t sub, uint32_t K
 }
 
 // A_D(a); for D >= 1 a must have an empty cell
-template <int D, uint32_t T, class Tables>
-G2048_DEV int64_t ntuple_after_value(const Board &a, const NtupleShape &sh, uint32_t F, const int32_t *weights, const Tables &tb)
+template <int D, uint32_t T, class Shape, class Tables>
+G2048_DEV int64_t ntuple_after_value(const Board &a, const Shape &sh, uint32_t F, const int32_t *weights, const Tables &tb)
 {
     if constexpr (D == 0)
         return ntuple_value<T>(ntuple_pack(a), sh, weights);
@@ -1071,8 +1132,8 @@ G2048_DEV int64_t ntuple_after_value(const Board &a, const NtupleShape &sh, uint
 // S_D(b).  As in search_value the four moves are one loop body with a run-time selector row and the depths D .. 0 one
 // inlined body each: no recursion and no per-lane array at run time.  A leaf (D = 0) looks up its moves one after the
 // other, 8T gathers in flight at a time, which keeps the registers of T = 8 out of scratch.
-template <int D, uint32_t T, class Tables>
-G2048_DEV int64_t ntuple_search_state(const Board &b, const NtupleShape &sh, uint32_t F, const int32_t *weights, const Tables &tb)
+template <int D, uint32_t T, class Shape, class Tables>
+G2048_DEV int64_t ntuple_search_state(const Board &b, const Shape &sh, uint32_t F, const int32_t *weights, const Tables &tb)
 {
     int64_t best = 0;
     bool any = false;
@@ -1091,8 +1152,8 @@ G2048_DEV int64_t ntuple_search_state(const Board &b, const NtupleShape &sh, uin
 
 // The root on one thread: value[4] and the action.  The kernel splits the same chance sums across lanes
 // (ntuple_chance_partial) and joins the four keys with shuffles.
-template <int D, uint32_t T, class Tables>
-G2048_DEV uint32_t ntuple_search_root(const Board &cells, const NtupleShape &sh, uint32_t F, const int32_t *weights,
+template <int D, uint32_t T, class Shape, class Tables>
+G2048_DEV uint32_t ntuple_search_root(const Board &cells, const Shape &sh, uint32_t F, const int32_t *weights,
                                       const Tables &tb, int64_t value[4])
 {
     uint64_t best = 0;

@@ -118,7 +118,9 @@ hipError_t launch_mc_search(const uint4 *boards, uint32_t n, bool plain, const M
 struct NtupleNet {
     uint32_t n_tuples, tuple_len, frac_bits; // T in 1..8, L in 1..6, F in 0..16
     uint8_t cells[8][6];                     // < 16, distinct within a tuple
-    int32_t *weights;                        // [T][16^L]
+    int32_t *weights;                        // [S][T][16^L]
+    uint32_t n_stages = 1;                   // S in 1..8 (g2048_ntuple_staged_net); 1 = the unstaged network
+    uint16_t thresholds[7] = {};             // the first S - 1: strictly ascending, >= 1
 };
 struct NtupleOut {
     int64_t *value;       // [n][4]
@@ -136,6 +138,8 @@ struct NtupleSearchOut {
 hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
                                 const NtupleSearchOut &o, hipStream_t s);
 hipError_t launch_ntuple_values(const uint4 *boards, uint32_t n, const NtupleNet &net, int64_t *v, hipStream_t s);
+// g2048_ntuple_stage_plain: stage[i] of n plain boards; reads the network's shape and thresholds, not its weights
+hipError_t launch_ntuple_stage(const uint4 *boards, uint32_t n, const NtupleNet &net, uint8_t *stage, hipStream_t s);
 hipError_t launch_ntuple_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
                                 hipStream_t s);
 // g2048_ntuple_tc_update_plain: phase W (kNtupleTcWeights = G2048_NTUPLE_TC_WEIGHTS), then phase A (kNtupleTcAccum =

@@ -1541,8 +1541,8 @@ __global__ void __launch_bounds__(kBlock) mc_search_kernel(const uint4 *__restri
 // arguments: wave-uniform, so reading a cell of the packed board is a shift by a scalar.  T is a template argument (1..8):
 // the look-ups are straight-line code with no per-lane array left at run time.  Lanes stride over the boards when 4n
 // exceeds the grid cap (kSearchMaxLanes).  Nothing is written back: no record, clock, episode slot or randomness.
-template <uint32_t T, bool PLAIN>
-__global__ void __launch_bounds__(kBlock) ntuple_eval_kernel(const uint4 *__restrict__ boards, uint32_t n, const NtupleShape sh,
+template <uint32_t T, bool PLAIN, class Shape>
+__global__ void __launch_bounds__(kBlock) ntuple_eval_kernel(const uint4 *__restrict__ boards, uint32_t n, const Shape sh,
                                                              uint32_t frac_bits, const int32_t *__restrict__ weights,
                                                              const NtupleOut o)
 {
@@ -1586,8 +1586,8 @@ __global__ void __launch_bounds__(kBlock) ntuple_eval_kernel(const uint4 *__rest
 // grid cap (kSearchMaxLanes); PLAIN as in expectimax_kernel.
 template <int D> constexpr uint32_t kNtupleSearchGroup = D == 1 ? 16u : 64u;
 
-template <int D, uint32_t T, bool PLAIN>
-__global__ void __launch_bounds__(kBlock) ntuple_search_kernel(const uint4 *__restrict__ boards, uint32_t n, const NtupleShape sh,
+template <int D, uint32_t T, bool PLAIN, class Shape>
+__global__ void __launch_bounds__(kBlock) ntuple_search_kernel(const uint4 *__restrict__ boards, uint32_t n, const Shape sh,
                                                                uint32_t frac_bits, const int32_t *__restrict__ weights,
                                                                const NtupleSearchOut o)
 {
@@ -1620,8 +1620,8 @@ __global__ void __launch_bounds__(kBlock) ntuple_search_kernel(const uint4 *__re
 }
 
 // g2048_ntuple_values_plain: V of every board, one board per lane, the same gathers.
-template <uint32_t T>
-__global__ void __launch_bounds__(kBlock) ntuple_values_kernel(const uint4 *__restrict__ boards, uint32_t n, const NtupleShape sh,
+template <uint32_t T, class Shape>
+__global__ void __launch_bounds__(kBlock) ntuple_values_kernel(const uint4 *__restrict__ boards, uint32_t n, const Shape sh,
                                                                const int32_t *__restrict__ weights, int64_t *__restrict__ v)
 {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -1630,13 +1630,23 @@ __global__ void __launch_bounds__(kBlock) ntuple_values_kernel(const uint4 *__re
     v[i] = ntuple_value<T>(ntuple_pack(load_board(boards, i)), sh, weights);
 }
 
+// g2048_ntuple_stage_plain: stage(b) of every board, one board per lane; no table is read.
+__global__ void __launch_bounds__(kBlock) ntuple_stage_kernel(const uint4 *__restrict__ boards, uint32_t n, const NtupleStagedShape sh,
+                                                              uint8_t *__restrict__ stage)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    stage[i] = static_cast<uint8_t>(ntuple_stage(ntuple_stage_mask(ntuple_pack(load_board(boards, i))), sh));
+}
+
 // g2048_ntuple_update_plain: one board per lane, 8T relaxed agent-scope atomic adds whose result nobody reads (fire and
 // forget); a lane whose step is 0 issues none.  Integer adds commute, so the weights after the launch do not depend on
 // the order the lanes, waves or launches arrive in.
-template <uint32_t T>
+template <uint32_t T, class Shape>
 __global__ void __launch_bounds__(kBlock) ntuple_update_kernel(const uint4 *__restrict__ boards, uint32_t n,
                                                                const int64_t *__restrict__ delta, uint32_t lr_shift,
-                                                               const NtupleShape sh, int32_t *weights)
+                                                               const Shape sh, int32_t *weights)
 {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n)
@@ -1655,10 +1665,10 @@ __global__ void __launch_bounds__(kBlock) ntuple_update_kernel(const uint4 *__re
 // 8T relaxed agent-scope 32-bit atomic adds whose result nobody reads.  err and mag are only read here: phase A adds to
 // them in a launch of its own, so every lane sees the accumulators of before the call.  A lane whose d is 0 loads and adds
 // nothing.  Lanes stride over the boards when n exceeds the grid cap (kSearchMaxLanes).
-template <uint32_t T>
+template <uint32_t T, class Shape>
 __global__ void __launch_bounds__(kBlock) ntuple_tc_weights_kernel(const uint4 *__restrict__ boards, uint32_t n,
                                                                    const int64_t *__restrict__ delta, uint32_t lr_shift,
-                                                                   const NtupleShape sh, int32_t *weights,
+                                                                   const Shape sh, int32_t *weights,
                                                                    const int64_t *__restrict__ err, const int64_t *__restrict__ mag)
 {
     uint32_t *w = reinterpret_cast<uint32_t *>(weights); // unsigned: the add wraps mod 2^32
@@ -1676,9 +1686,9 @@ __global__ void __launch_bounds__(kBlock) ntuple_tc_weights_kernel(const uint4 *
 
 // Phase A: err[j] += d, mag[j] += |d| for the 8T look-ups of every board with d != 0 -- 16T relaxed agent-scope 64-bit
 // atomic adds, fire and forget, wrapping mod 2^64.  The same lanes and stride as phase W.
-template <uint32_t T>
+template <uint32_t T, class Shape>
 __global__ void __launch_bounds__(kBlock) ntuple_tc_accum_kernel(const uint4 *__restrict__ boards, uint32_t n,
-                                                                 const int64_t *__restrict__ delta, const NtupleShape sh,
+                                                                 const int64_t *__restrict__ delta, const Shape sh,
                                                                  int64_t *err, int64_t *mag)
 {
     unsigned long long *e = reinterpret_cast<unsigned long long *>(err), *a = reinterpret_cast<unsigned long long *>(mag);
@@ -1740,9 +1750,9 @@ template <class Keep, class F> __device__ __forceinline__ void trace_items(const
 }
 
 // g2048_ntuple_trace_update: ntuple_update_kernel's 8T fire-and-forget adds with step(d_k); a zero step issues none.
-template <uint32_t T>
+template <uint32_t T, class Shape>
 __global__ void __launch_bounds__(kBlock) ntuple_trace_update_kernel(const TraceArgs tr, const int64_t *__restrict__ delta,
-                                                                     uint32_t lr_shift, const NtupleShape sh, int32_t *weights)
+                                                                     uint32_t lr_shift, const Shape sh, int32_t *weights)
 {
     uint32_t *w = reinterpret_cast<uint32_t *>(weights); // unsigned: the add wraps mod 2^32
     trace_items(
@@ -1755,9 +1765,9 @@ __global__ void __launch_bounds__(kBlock) ntuple_trace_update_kernel(const Trace
 }
 
 // g2048_ntuple_tc_trace_update, phase W: ntuple_tc_weights_kernel's body per item.  err and mag are only read.
-template <uint32_t T>
+template <uint32_t T, class Shape>
 __global__ void __launch_bounds__(kBlock) ntuple_tc_trace_weights_kernel(const TraceArgs tr, const int64_t *__restrict__ delta,
-                                                                         uint32_t lr_shift, const NtupleShape sh, int32_t *weights,
+                                                                         uint32_t lr_shift, const Shape sh, int32_t *weights,
                                                                          const int64_t *__restrict__ err,
                                                                          const int64_t *__restrict__ mag)
 {
@@ -1772,9 +1782,9 @@ __global__ void __launch_bounds__(kBlock) ntuple_tc_trace_weights_kernel(const T
 }
 
 // Phase A: ntuple_tc_accum_kernel's body per item, the same items as phase W.
-template <uint32_t T>
+template <uint32_t T, class Shape>
 __global__ void __launch_bounds__(kBlock) ntuple_tc_trace_accum_kernel(const TraceArgs tr, const int64_t *__restrict__ delta,
-                                                                       const NtupleShape sh, int64_t *err, int64_t *mag)
+                                                                       const Shape sh, int64_t *err, int64_t *mag)
 {
     unsigned long long *e = reinterpret_cast<unsigned long long *>(err), *a = reinterpret_cast<unsigned long long *>(mag);
     trace_items(
@@ -2376,20 +2386,23 @@ hipError_t launch_mc_search(const uint4 *boards, uint32_t n, bool plain, const M
     return a.rollouts >= kMcWaveRollouts ? go(std::integral_constant<uint32_t, 64u>()) : go(std::integral_constant<uint32_t, 16u>());
 }
 
-// f(std::integral_constant<uint32_t, T>()) for the network's tuple count T = 1..8
+// f(std::integral_constant<uint32_t, T>(), shape) for the network's tuple count T = 1..8 and its shape: an NtupleShape for
+// one weight set -- the kernels of the unstaged network, whichever descriptor it came in -- an NtupleStagedShape for S > 1
 template <class F>
 static hipError_t dispatch_tuples(const NtupleNet &net, F &&f)
 {
-    return dispatch<1, 8>(static_cast<int>(net.n_tuples),
-                          [&](auto tc) { return f(std::integral_constant<uint32_t, static_cast<uint32_t>(decltype(tc)::value)>()); });
+    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
+    return dispatch<1, 8>(static_cast<int>(net.n_tuples), [&](auto tc) {
+        const std::integral_constant<uint32_t, static_cast<uint32_t>(decltype(tc)::value)> t;
+        return net.n_stages > 1 ? f(t, ntuple_staged_shape(sh, net.n_stages, net.thresholds)) : f(t, sh);
+    });
 }
 
 hipError_t launch_ntuple_eval(const uint4 *boards, uint32_t n, bool plain, const NtupleNet &net, const NtupleOut &o, hipStream_t s)
 {
-    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
-    return dispatch_tuples(net, [&](auto tc) {
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
         return dispatch_bool(plain, [&](auto plain_c) {
-            return launch_1d(ntuple_eval_kernel<tc, plain_c>, group_lanes(n, 4u), 0, s, boards, n, sh, net.frac_bits,
+            return launch_1d(ntuple_eval_kernel<tc, plain_c, decltype(sh)>, group_lanes(n, 4u), 0, s, boards, n, sh, net.frac_bits,
                              static_cast<const int32_t *>(net.weights), o);
         });
     });
@@ -2398,11 +2411,10 @@ hipError_t launch_ntuple_eval(const uint4 *boards, uint32_t n, bool plain, const
 hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
                                 const NtupleSearchOut &o, hipStream_t s)
 {
-    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
     return dispatch<1, static_cast<int>(kNtupleSearchMaxDepth)>(static_cast<int>(depth), [&](auto dc) {
-        return dispatch_tuples(net, [&](auto tc) {
+        return dispatch_tuples(net, [&](auto tc, auto sh) {
             return dispatch_bool(plain, [&](auto plain_c) {
-                return launch_1d(ntuple_search_kernel<dc, tc, plain_c>, group_lanes(n, kNtupleSearchGroup<dc>), 0, s, boards, n, sh,
+                return launch_1d(ntuple_search_kernel<dc, tc, plain_c, decltype(sh)>, group_lanes(n, kNtupleSearchGroup<dc>), 0, s, boards, n, sh,
                                  net.frac_bits, static_cast<const int32_t *>(net.weights), o);
             });
         });
@@ -2411,34 +2423,37 @@ hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth,
 
 hipError_t launch_ntuple_values(const uint4 *boards, uint32_t n, const NtupleNet &net, int64_t *v, hipStream_t s)
 {
-    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
-    return dispatch_tuples(net, [&](auto tc) {
-        return launch_1d(ntuple_values_kernel<tc>, n, 0, s, boards, n, sh, static_cast<const int32_t *>(net.weights), v);
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        return launch_1d(ntuple_values_kernel<tc, decltype(sh)>, n, 0, s, boards, n, sh, static_cast<const int32_t *>(net.weights), v);
     });
+}
+
+hipError_t launch_ntuple_stage(const uint4 *boards, uint32_t n, const NtupleNet &net, uint8_t *stage, hipStream_t s)
+{
+    const NtupleStagedShape sh = ntuple_staged_shape(ntuple_shape(net.n_tuples, net.tuple_len, net.cells), net.n_stages, net.thresholds);
+    return launch_1d(ntuple_stage_kernel, n, 0, s, boards, n, sh, stage);
 }
 
 hipError_t launch_ntuple_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
                                 hipStream_t s)
 {
-    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
-    return dispatch_tuples(net, [&](auto tc) {
-        return launch_1d(ntuple_update_kernel<tc>, n, 0, s, boards, n, delta, lr_shift, sh, net.weights);
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        return launch_1d(ntuple_update_kernel<tc, decltype(sh)>, n, 0, s, boards, n, delta, lr_shift, sh, net.weights);
     });
 }
 
 hipError_t launch_ntuple_tc_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
                                    const NtupleNet &net, int64_t *err, int64_t *mag, hipStream_t s)
 {
-    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
-    return dispatch_tuples(net, [&](auto tc) {
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
         if (phases & kNtupleTcWeights) {
-            const hipError_t rc = launch_1d(ntuple_tc_weights_kernel<tc>, group_lanes(n, 1u), 0, s, boards, n, delta, lr_shift, sh,
+            const hipError_t rc = launch_1d(ntuple_tc_weights_kernel<tc, decltype(sh)>, group_lanes(n, 1u), 0, s, boards, n, delta, lr_shift, sh,
                                             net.weights, static_cast<const int64_t *>(err), static_cast<const int64_t *>(mag));
             if (rc != hipSuccess)
                 return rc;
         }
         if (phases & kNtupleTcAccum)
-            return launch_1d(ntuple_tc_accum_kernel<tc>, group_lanes(n, 1u), 0, s, boards, n, delta, sh, err, mag);
+            return launch_1d(ntuple_tc_accum_kernel<tc, decltype(sh)>, group_lanes(n, 1u), 0, s, boards, n, delta, sh, err, mag);
         return hipSuccess;
     });
 }
@@ -2461,27 +2476,25 @@ static uint64_t trace_lanes(uint32_t n, const NtupleTrace &tr)
 hipError_t launch_ntuple_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
                                       const NtupleTrace &tr, uint32_t slot, hipStream_t s)
 {
-    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
     const TraceArgs ta{tr.hist, tr.len, n, tr.depth, tr.lambda, slot};
-    return dispatch_tuples(net, [&](auto tc) {
-        return launch_1d(ntuple_trace_update_kernel<tc>, trace_lanes(n, tr), 0, s, ta, delta, lr_shift, sh, net.weights);
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        return launch_1d(ntuple_trace_update_kernel<tc, decltype(sh)>, trace_lanes(n, tr), 0, s, ta, delta, lr_shift, sh, net.weights);
     });
 }
 
 hipError_t launch_ntuple_tc_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const NtupleNet &net,
                                          int64_t *err, int64_t *mag, const NtupleTrace &tr, uint32_t slot, hipStream_t s)
 {
-    const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
     const TraceArgs ta{tr.hist, tr.len, n, tr.depth, tr.lambda, slot};
-    return dispatch_tuples(net, [&](auto tc) {
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
         if (phases & kNtupleTcWeights) {
-            const hipError_t rc = launch_1d(ntuple_tc_trace_weights_kernel<tc>, trace_lanes(n, tr), 0, s, ta, delta, lr_shift, sh,
+            const hipError_t rc = launch_1d(ntuple_tc_trace_weights_kernel<tc, decltype(sh)>, trace_lanes(n, tr), 0, s, ta, delta, lr_shift, sh,
                                             net.weights, static_cast<const int64_t *>(err), static_cast<const int64_t *>(mag));
             if (rc != hipSuccess)
                 return rc;
         }
         if (phases & kNtupleTcAccum)
-            return launch_1d(ntuple_tc_trace_accum_kernel<tc>, trace_lanes(n, tr), 0, s, ta, delta, sh, err, mag);
+            return launch_1d(ntuple_tc_trace_accum_kernel<tc, decltype(sh)>, trace_lanes(n, tr), 0, s, ta, delta, sh, err, mag);
         return hipSuccess;
     });
 }

@@ -11,6 +11,8 @@ per update.  Everything is an integer: the same bits however the batch is split 
 afterstates of the same board (``g2048_ntuple_trace_*``).
 ``NTupleNet.search`` / ``Batched2048.ntuple_search`` play the network through a depth-1..2 expectimax
 (``g2048_ntuple_search``), one launch for the whole batch.
+``NTupleNet(..., stages=...)`` is the multi-stage network: a weight set per game stage, chosen per board by the tiles it
+holds (``g2048_ntuple_staged_*``); every method and trainer above works on it unchanged.
 """
 from __future__ import annotations
 
@@ -20,7 +22,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import NTupleIO, NTupleNetC, NTupleSearchIO, NTupleTCC, NTupleTraceC, check
+from ._lib import NTupleIO, NTupleNetC, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTraceC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
@@ -28,6 +30,7 @@ ILLEGAL = -(1 << 63)                                              # G2048_NTUPLE
 SEARCH_MAX_DEPTH = 2                                              # G2048_NTUPLE_SEARCH_MAX_DEPTH
 TC_WEIGHTS, TC_ACCUM = 1, 2                                       # G2048_NTUPLE_TC_WEIGHTS, G2048_NTUPLE_TC_ACCUM
 TRACE_MAX = 8                                                     # G2048_NTUPLE_TRACE_MAX
+MAX_STAGES = 8                                                    # G2048_NTUPLE_MAX_STAGES
 
 # Default shapes, as row-major cell indices (cell 4r + c).  The value sums every tuple over the eight symmetries of the
 # board, so a shape lists each tuple once, not once per placement.
@@ -38,6 +41,36 @@ TUPLES = {
     # outer and the inner row, the corner, the edge and the centre square
     "17x4": ((0, 1, 2, 3), (4, 5, 6, 7), (0, 1, 4, 5), (1, 2, 5, 6), (5, 6, 9, 10)),
 }
+
+
+def stage_mask(*tiles) -> int:
+    """The stage threshold "the board holds all of these tiles": the OR of ``1 << min(log2(tile), 15)`` over ``tiles`` (tile
+    values, powers of two from 2 on), e.g. ``stage_mask(16384, 8192) == 0x6000``.  A board's mask has one bit per distinct
+    cell value (bit 0: an empty cell), and its stage is the number of thresholds its mask is not below -- so a threshold is
+    reached by every board that holds these tiles or any larger one."""
+    if not tiles:
+        raise ValueError("stage_mask needs at least one tile value")
+    mask = 0
+    for tile in tiles:
+        tile = _int_arg("tile", tile, 2, 1 << 31)
+        if tile & (tile - 1):
+            raise ValueError(f"tile must be a power of two, not {tile}")
+        mask |= 1 << min(tile.bit_length() - 1, 15)
+    return mask
+
+
+def _stage_thresholds(stages):
+    """``stages`` of NTupleNet as a tuple of ints: at most 7, each 1..65535, strictly ascending."""
+    try:
+        stages = tuple(stages)
+    except TypeError:
+        raise ValueError("stages must be a sequence of thresholds (ints in 1..65535)") from None
+    if len(stages) > MAX_STAGES - 1:
+        raise ValueError(f"stages: at most {MAX_STAGES - 1} thresholds ({MAX_STAGES} stages), not {len(stages)}")
+    stages = tuple(_int_arg("stages threshold", t, 1, 65535) for t in stages)
+    if any(b <= a for a, b in zip(stages, stages[1:])):
+        raise ValueError(f"stages: thresholds must be strictly ascending, not {stages}")
+    return stages
 
 
 class NTupleEval(NamedTuple):
@@ -90,9 +123,16 @@ class NTupleNet:
 
     ``tuples``: a name in ``TUPLES`` or a sequence of equally long sequences of distinct cell indices 0..15 (at most 8
     tuples of at most 6 cells).  ``weights`` is the int32 ``[T, 16^L]`` tensor on ``device``, zero-initialised; the
-    kernels read and update it in place, so it can be shared between engines."""
+    kernels read and update it in place, so it can be shared between engines.
 
-    def __init__(self, tuples="4x6", frac_bits=10, device="cuda:0"):
+    ``stages``: None, or a sequence of at most 7 strictly ascending thresholds in 1..65535 (:func:`stage_mask`) for a
+    multi-stage network of ``S = len(stages) + 1`` weight sets: ``weights`` is then ``[S, T, 16^L]``,
+    a board reads and updates the set ``stage(board)`` = the number of thresholds its tile mask is not below, and every
+    method goes to its ``g2048_ntuple_staged_`` symbol.  The stage is a function of the board alone: the afterstates of one
+    board, the leaves of a search and the slots of a trace may all be in different stages.  Memory: S times the unstaged
+    network's."""
+
+    def __init__(self, tuples="4x6", frac_bits=10, device="cuda:0", stages=None):
         if isinstance(tuples, str):
             if tuples not in TUPLES:
                 raise ValueError(f"tuples must be one of {sorted(TUPLES)} or a sequence of cell lists, not {tuples!r}")
@@ -113,12 +153,20 @@ class NTupleNet:
         self.tuples = tuple(tuple(int(c) for c in t) for t in tuples)
         self.frac_bits = _int_arg("frac_bits", frac_bits, 0, MAX_FRAC_BITS)
         self.device = torch.device(device)
-        self.weights = torch.zeros((len(tuples), 16 ** length), dtype=torch.int32, device=self.device)
-        self._c = NTupleNetC(len(tuples), length, self.frac_bits)
+        self.stages = None if stages is None else _stage_thresholds(stages)
+        shape = (len(tuples), 16 ** length)
+        if self.stages is None:
+            self.weights = torch.zeros(shape, dtype=torch.int32, device=self.device)
+            self._c = c_net = NTupleNetC(len(tuples), length, self.frac_bits)
+        else:
+            self.weights = torch.zeros((len(self.stages) + 1,) + shape, dtype=torch.int32, device=self.device)
+            self._c = NTupleStagedNetC(NTupleNetC(len(tuples), length, self.frac_bits), len(self.stages) + 1)
+            self._c.thresholds[:len(self.stages)] = self.stages
+            c_net = self._c.net
         for t, cells in enumerate(self.tuples):
             for k, c in enumerate(cells):
-                self._c.cells[t][k] = c
-        self._c.weights = self.weights.data_ptr()
+                c_net.cells[t][k] = c
+        c_net.weights = self.weights.data_ptr()
 
     @property
     def n_tuples(self):
@@ -128,11 +176,19 @@ class NTupleNet:
     def tuple_len(self):
         return len(self.tuples[0])
 
+    @property
+    def n_stages(self):
+        return 1 if self.stages is None else len(self.stages) + 1
+
     def _ref(self, device):
         """The C descriptor, for a launch on ``device``."""
         if self.device != device:
             raise ValueError(f"the network's weights are on {self.device}, the boards on {device}")
         return C.byref(self._c)
+
+    def _fn(self, name):
+        """The library's ``g2048_ntuple_<name>``, or its ``g2048_ntuple_staged_<name>`` sibling for a staged network."""
+        return getattr(_lib.load(), ("g2048_ntuple_" if self.stages is None else "g2048_ntuple_staged_") + name)
 
     def _launch(self, fn, boards, *args):
         with torch.cuda.device(boards.device):
@@ -149,8 +205,42 @@ class NTupleNet:
         elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n,) or not out.is_contiguous()
               or out.device != device):
             raise ValueError(f"out must be a contiguous int64 [{n}] tensor on {device}")
-        self._launch(_lib.load().g2048_ntuple_values_plain, boards, net, out.data_ptr())
+        self._launch(self._fn("values_plain"), boards, net, out.data_ptr())
         return out
+
+    def stage(self, boards, out=None) -> torch.Tensor:
+        """The stage of plain boards (``g2048_ntuple_stage_plain``): ``boards`` as in :meth:`values`; returns uint8 ``[n]``,
+        the index of the weight set each board reads.  A staged network only."""
+        if self.stages is None:
+            raise ValueError("stage() needs a staged network (NTupleNet(..., stages=...))")
+        n, device = _plain_boards(boards)
+        net = self._ref(device)
+        if out is None:
+            out = torch.empty(n, dtype=torch.uint8, device=device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n,) or not out.is_contiguous()
+              or out.device != device):
+            raise ValueError(f"out must be a contiguous uint8 [{n}] tensor on {device}")
+        self._launch(_lib.load().g2048_ntuple_stage_plain, boards, net, out.data_ptr())
+        return out
+
+    def promote(self, src, dst, tc=None):
+        """Whole-stage weight promotion (Yeh et al. 2016): ``weights[dst] = weights[src]`` on the current stream -- a stage
+        that is first reached starts from what an earlier stage has learned.  With ``tc`` (the :class:`NTupleTC` of this
+        network) ``err[dst]`` and ``mag[dst]`` are zeroed, so the promoted stage learns at full rate again.  A staged
+        network only; ``src != dst``.  (Lazy per-weight promotion is not offered: it would read weights that other lanes
+        of the same launch update, and the result would depend on their order.)"""
+        if self.stages is None:
+            raise ValueError("promote() needs a staged network (NTupleNet(..., stages=...))")
+        src = _int_arg("src", src, 0, self.n_stages - 1)
+        dst = _int_arg("dst", dst, 0, self.n_stages - 1)
+        if src == dst:
+            raise ValueError(f"promote: src and dst are both stage {src}")
+        if tc is not None and (not isinstance(tc, NTupleTC) or tc.net is not self):
+            raise ValueError("tc must be the NTupleTC of this network")
+        self.weights[dst].copy_(self.weights[src])          # torch: the current stream of the tensors' device
+        if tc is not None:
+            tc.err[dst].zero_()
+            tc.mag[dst].zero_()
 
     def evaluate(self, boards, out=None) -> NTupleEval:
         """The greedy player on plain boards (``g2048_ntuple_evaluate_plain``): q of the four moves, the best move, its
@@ -159,7 +249,7 @@ class NTupleNet:
         n, device = _plain_boards(boards)
         net = self._ref(device)
         io, out = _eval_io(n, device, out)
-        self._launch(_lib.load().g2048_ntuple_evaluate_plain, boards, net, C.byref(io))
+        self._launch(self._fn("evaluate_plain"), boards, net, C.byref(io))
         return out
 
     def search(self, boards, depth=1, out=None) -> NTupleSearch:
@@ -170,7 +260,7 @@ class NTupleNet:
         n, device = _plain_boards(boards)
         net = self._ref(device)
         io, out = _search_io(n, device, depth, out)
-        self._launch(_lib.load().g2048_ntuple_search_plain, boards, net, C.byref(io))
+        self._launch(self._fn("search_plain"), boards, net, C.byref(io))
         return out
 
     def update(self, boards, delta, lr_shift):
@@ -183,7 +273,7 @@ class NTupleNet:
                 or not delta.is_contiguous() or delta.device != device):
             raise ValueError(f"delta must be a contiguous int64 [{n}] tensor on {device}")
         shift = _int_arg("lr_shift", lr_shift, 0, MAX_LR_SHIFT)
-        self._launch(_lib.load().g2048_ntuple_update_plain, boards, delta.data_ptr(), shift, net)
+        self._launch(self._fn("update_plain"), boards, delta.data_ptr(), shift, net)
 
     def tc_update(self, boards, delta, lr_shift, tc, phases=3):
         """The temporal-coherence update (``g2048_ntuple_tc_update_plain``) with the accumulators of
@@ -201,7 +291,7 @@ class NTupleNet:
         phases = _int_arg("phases", phases, TC_WEIGHTS, TC_WEIGHTS | TC_ACCUM)
         if not isinstance(tc, NTupleTC) or tc.net is not self:
             raise ValueError("tc must be the NTupleTC of this network")
-        self._launch(_lib.load().g2048_ntuple_tc_update_plain, boards, delta.data_ptr(), shift, phases, net, C.byref(tc._c))
+        self._launch(self._fn("tc_update_plain"), boards, delta.data_ptr(), shift, phases, net, C.byref(tc._c))
 
     def _trace_args(self, trace, delta, lr_shift):
         """(net, lr_shift) for a trace update: ``trace`` and ``delta`` checked as :meth:`update` checks its arguments."""
@@ -221,7 +311,7 @@ class NTupleNet:
         net, shift = self._trace_args(trace, delta, lr_shift)
         with torch.cuda.device(trace.device):
             stream = C.c_void_p(torch.cuda.current_stream(trace.device).cuda_stream)
-            check(_lib.load().g2048_ntuple_trace_update(trace.n, delta.data_ptr(), shift, net, C.byref(trace._c), trace.slot, stream))
+            check(self._fn("trace_update")(trace.n, delta.data_ptr(), shift, net, C.byref(trace._c), trace.slot, stream))
 
     def tc_trace_update(self, trace, delta, lr_shift, tc, phases=3):
         """The TC(lambda) update (``g2048_ntuple_tc_trace_update``): :meth:`tc_update` with ``d_k`` for
@@ -233,16 +323,19 @@ class NTupleNet:
             raise ValueError("tc must be the NTupleTC of this network")
         with torch.cuda.device(trace.device):
             stream = C.c_void_p(torch.cuda.current_stream(trace.device).cuda_stream)
-            check(_lib.load().g2048_ntuple_tc_trace_update(trace.n, delta.data_ptr(), shift, phases, net, C.byref(tc._c),
+            check(self._fn("tc_trace_update")(trace.n, delta.data_ptr(), shift, phases, net, C.byref(tc._c),
                                                            C.byref(trace._c), trace.slot, stream))
 
     def state_dict(self):
-        return {"tuples": self.tuples, "frac_bits": self.frac_bits, "weights": self.weights.clone()}
+        return {"tuples": self.tuples, "frac_bits": self.frac_bits, "stages": self.stages, "weights": self.weights.clone()}
 
     def load_state_dict(self, state):
         """Copy the weights of a ``state_dict()`` of a network of the same shape into this one's tensor (in place)."""
         if tuple(tuple(t) for t in state["tuples"]) != self.tuples or int(state["frac_bits"]) != self.frac_bits:
             raise ValueError("state_dict is of a network with other tuples or frac_bits")
+        stages = state.get("stages")                       # absent in the state of a network saved before stages existed
+        if (None if stages is None else tuple(int(t) for t in stages)) != self.stages:
+            raise ValueError(f"state_dict is of a network with stages {stages}, this one has {self.stages}")
         w = torch.as_tensor(state["weights"])
         if w.dtype != torch.int32 or w.shape != self.weights.shape:
             raise ValueError(f"state_dict weights must be int32 {tuple(self.weights.shape)}")
@@ -252,10 +345,11 @@ class NTupleNet:
 class NTupleTC:
     """The accumulators of temporal-coherence learning for ``net`` (``g2048_ntuple_tc``): ``err``, the
     signed sum of the deltas every weight has seen, and ``mag``, the sum of their magnitudes (read as unsigned), both
-    int64 ``[T, 16^L]`` tensors on the network's device, zero-initialised; a weight learns at rate ``|err| / mag``.
+    int64 tensors of the shape of ``net.weights`` (``[T, 16^L]``, or ``[S, T, 16^L]`` for a staged network) on the network's
+    device, zero-initialised; a weight learns at rate ``|err| / mag``.
 
     Memory: 16 bytes per weight on top of the weight's own 4 -- 1 GiB per table for the 4x6 network (4 GiB in all), 5 MiB
-    in all for the 17x4 network."""
+    in all for the 17x4 network; a staged network takes S times that."""
 
     def __init__(self, net):
         if not isinstance(net, NTupleNet):

@@ -533,6 +533,59 @@ int g2048_ntuple_search(const g2048_engine *e, const g2048_ntuple_net *net, cons
 int g2048_ntuple_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io,
                               void *stream);
 
+/* Multi-stage n-tuple networks: a weight set per game stage (Yeh et al. 2016, Jaskowski 2017).  One
+ * table set cannot fit both the opening and the positions after a 16k or 32k tile, so a staged network holds S of them
+ * and every board reads and writes the set that the large tiles on it select.  Notation of the four blocks above:
+ *   cell value  c(e) = min(e mod 32, 15), exactly as for the table index; engine records use byte & 0x1f.
+ *   mask        mask(b) = OR over the 16 cells of 1 << c(b[cell]): a 16-bit number, bit 0 is "has an empty cell".  It is
+ *               the same for the eight symmetries of b, so it is formed once per board and not once per symmetry.
+ *   stages      S in 1..G2048_NTUPLE_MAX_STAGES (= 8), with S - 1 thresholds thr[0] < thr[1] < ... < thr[S-2], each in
+ *               1..65535.
+ *   stage       stage(b) = the number of j with mask(b) >= thr[j], compared as integers: 0..S-1.  "has a 16k" is 0x4000,
+ *               "has a 16k and an 8k" 0x6000, "has a 32k" 0x8000, "a 32k and a 16k" 0xC000, and so on.
+ *   weights     int32 [S][T][16^L];  off(b, s, t) = (stage(b) * T + t) * 16^L + idx_t(s(b)).  The element index stays
+ *               below 2^30; the byte offset does not fit 32 bits (S = 8, T = 8, L = 6 is 4 GiB of weights and 8 GiB per
+ *               TC accumulator) and is formed in 64 bits everywhere.
+ *   everything else is unchanged with this off, V(b) being read from the tables of stage(b): evaluate, search, update,
+ *               TC rate / phase W / phase A, trace push and trace update.  TC accumulators are [S][T][16^L] as well.
+ * stage(b) is a function of the board alone -- nothing about lanes, launches or shards enters it, so every exactness and
+ * shard rule above holds as it stands.  It is NOT monotone over a game: 16k + 8k + 8k (stage of 0x6000) becomes 16k + 16k
+ * (below 0x6000).  Consequences:
+ *   - the four afterstates of one board may sit in different stages;
+ *   - the leaves below a chance node may be in other stages than the root;
+ *   - the slots of one board's trace history may be in different stages;
+ *   - a TD error is V_stage(next)(...) - V_stage(after)(after), across the boundary: the usual multi-stage rule.
+ * S = 1 (no thresholds) is, bit for bit, the network of above.  Every call validates the descriptor before any HIP call:
+ * S in range, the first S - 1 thresholds non-zero and strictly ascending, then `net` as its unstaged sibling does. */
+#define G2048_NTUPLE_MAX_STAGES 8
+typedef struct g2048_ntuple_staged_net {
+    g2048_ntuple_net net;          /* weights: [S][T][16^L] */
+    uint32_t n_stages;             /* S, 1..8 */
+    uint16_t thresholds[7];        /* first S-1 used, strictly ascending, >= 1; the rest ignored */
+} g2048_ntuple_staged_net;
+/* The staged sibling of every entry point that takes a g2048_ntuple_net: the same arguments, outputs, launches and
+ * rules.  g2048_ntuple_trace_push never touches the tables and serves both.  tc->err and tc->mag are [S][T][16^L]. */
+int g2048_ntuple_staged_evaluate(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_io *io, void *stream);
+int g2048_ntuple_staged_evaluate_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
+                                       const g2048_ntuple_io *io, void *stream);
+int g2048_ntuple_staged_search(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_search_io *io,
+                               void *stream);
+int g2048_ntuple_staged_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
+                                     const g2048_ntuple_search_io *io, void *stream);
+int g2048_ntuple_staged_values_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net, int64_t *v, void *stream);
+int g2048_ntuple_staged_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift,
+                                     const g2048_ntuple_staged_net *net, void *stream);
+int g2048_ntuple_staged_tc_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                        const g2048_ntuple_staged_net *net, const g2048_ntuple_tc *tc, void *stream);
+int g2048_ntuple_staged_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, const g2048_ntuple_staged_net *net,
+                                     const g2048_ntuple_trace *tr, uint32_t slot, void *stream);
+int g2048_ntuple_staged_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                        const g2048_ntuple_staged_net *net, const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr,
+                                        uint32_t slot, void *stream);
+/* stage[i] = stage(boards[i]) for n plain boards (as g2048_ntuple_values_plain takes them), one launch; reads the shape
+ * and the thresholds only: net->net.weights may be NULL. */
+int g2048_ntuple_stage_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net, uint8_t *stage, void *stream);
+
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream);
