@@ -100,6 +100,25 @@ struct Board {
     uint32_t r[4];
 };
 
+// Board i of an array of 16-byte boards: one global_load_dwordx4 per lane
+#if defined(G2048_HOST_CHECK)
+struct uint4 {
+    uint32_t x, y, z, w;
+};
+G2048_DEV Board load_board(const uint4 *boards, uint32_t i)
+{
+    Board b;
+    __builtin_memcpy(b.r, boards + i, 16); // the tests' arrays are bytes
+    return b;
+}
+#else
+G2048_DEV Board load_board(const uint4 *boards, uint32_t i)
+{
+    const uint4 v = boards[i];
+    return Board{{v.x, v.y, v.z, v.w}};
+}
+#endif
+
 // ------------------------------------------------------------------------------------ Philox
 // Philox4x32-10, constants as in rocrand_philox4x32_10.h:62-65.  The spawn stream:
 //   word(seed, t, board, slot) = Philox(ctr = (t_lo, t_hi, board, slot >> 2), key = seed)[slot & 3]
@@ -666,8 +685,10 @@ G2048_DEV uint32_t mc_root(const Board &cells, uint32_t i, uint32_t rollouts, ui
 // set training_data.augment() / g2048_augment generate; the sum does not care about their order.
 #if defined(G2048_HOST_CHECK)
 #define G2048_HOST_DEV static inline
+#define G2048_MEMBER inline // a member function, for device code and for the launcher
 #else
 #define G2048_HOST_DEV __host__ __device__ __forceinline__
+#define G2048_MEMBER __host__ __device__ __forceinline__
 #endif
 constexpr uint32_t kNtupleMaxTuples = 8, kNtupleMaxLen = 6, kNtupleMaxFrac = 16, kNtupleMaxShift = 40; // = G2048_NTUPLE_* (g2048.h)
 constexpr int64_t kNtupleIllegal = INT64_MIN;                                                          // G2048_NTUPLE_ILLEGAL
@@ -1080,6 +1101,90 @@ G2048_DEV int64_t ntuple_trace_item(uint32_t len_i, int64_t delta_i, uint32_t k,
     if (k >= ntuple_trace_len(len_i, H))
         return 0;
     return ntuple_trace_dk(ntuple_tc_delta(delta_i), ntuple_trace_decay(lam, k));
+}
+
+// The work items of an update.  All six updates -- TD, TC phase W, TC phase A, each over plain boards or over a trace
+// history -- are one loop over the items of a source (ntuple_for_items) and one per-item operation; the update kernels
+// run exactly this with atomic adds, the host check of the tests with wrapping adds.  A source is a compile-time type, as
+// the shape is: it says how many items there are, which delta an item sees -- without touching its board, so an item
+// with nothing to do leaves before the 16-byte load -- and, on demand, the item's packed board.  `delta` is the int64 [n]
+// array of the call, one entry per board; it is passed alongside the source so that a kernel can take it as a __restrict__
+// argument of its own.
+//   td_delta: what the TD step shifts.  Plain boards: delta[i] as it is (the one form that does not clamp); trace: d_k.
+//   tc_delta: d of phase W and phase A.  Plain boards: clamp(delta[i]) (ntuple_tc_delta); trace: d_k.
+struct NtupleBoardItems { // item i = board i
+    const uint4 *boards;
+    uint32_t n;
+    using Item = uint32_t;
+    G2048_MEMBER uint64_t size() const { return n; }
+    G2048_MEMBER Item at(uint64_t index) const { return static_cast<uint32_t>(index); }
+    G2048_MEMBER int64_t td_delta(const int64_t *delta, Item i) const { return delta[i]; }
+    G2048_MEMBER int64_t tc_delta(const int64_t *delta, Item i) const { return ntuple_tc_delta(delta[i]); }
+    G2048_MEMBER uint64_t packed(Item i) const { return ntuple_pack(load_board(boards, i)); }
+};
+
+// item k * n + i = the afterstate of board i that is k pushes old (ntuple_trace_split): k-major, so a wave reads 64
+// consecutive boards of one slot.  The item index and the slot base are 64-bit: H * n * 16 bytes exceeds 2^32.
+struct NtupleTraceItems {
+    const uint4 *hist;  // [H][n] boards
+    const uint8_t *len; // [n]
+    uint32_t n, H, lam, slot; // slot: that of the last push
+    struct Item {
+        uint32_t k, i;
+    };
+    G2048_MEMBER uint64_t size() const { return static_cast<uint64_t>(H) * n; }
+    G2048_MEMBER Item at(uint64_t index) const
+    {
+        Item it;
+        ntuple_trace_split(index, n, H, it.k, it.i);
+        return it;
+    }
+    G2048_MEMBER int64_t td_delta(const int64_t *delta, Item it) const
+    {
+        return ntuple_trace_item(len[it.i], delta[it.i], it.k, H, lam);
+    }
+    G2048_MEMBER int64_t tc_delta(const int64_t *delta, Item it) const { return td_delta(delta, it); }
+    G2048_MEMBER uint64_t packed(Item it) const
+    {
+        return ntuple_pack(load_board(hist + static_cast<uint64_t>(ntuple_trace_slot(slot, it.k, H)) * n, it.i));
+    }
+};
+
+// f(item) for the items first, first + stride, ... of a source: a lane of a kernel strides by the grid, the host by 1
+template <class Items, class F> G2048_DEV void ntuple_for_items(const Items &items, uint64_t first, uint64_t stride, F f)
+{
+    const uint64_t size = items.size();
+    for (uint64_t index = first; index < size; index += stride)
+        f(items.at(index));
+}
+
+// One item of the TD update: a zero step touches nothing.  add as ntuple_update takes it.
+template <uint32_t T, class Items, class Shape, class Add>
+G2048_DEV void ntuple_item_update(const Items &items, const int64_t *delta, typename Items::Item it, uint32_t lr_shift, const Shape &sh,
+                                  Add add)
+{
+    const int32_t step = ntuple_step(items.td_delta(delta, it), lr_shift);
+    if (step != 0)
+        ntuple_update<T>(items.packed(it), sh, step, add);
+}
+
+// One item of TC phase W: d == 0 touches nothing.  add as ntuple_tc_weights takes it.
+template <uint32_t T, class Items, class Shape, class Add>
+G2048_DEV void ntuple_item_tc_weights(const Items &items, const int64_t *delta, typename Items::Item it, uint32_t lr_shift,
+                                      const Shape &sh, const int64_t *err, const int64_t *mag, Add add)
+{
+    const int64_t d = items.tc_delta(delta, it);
+    if (d != 0)
+        ntuple_tc_weights<T>(items.packed(it), sh, d, lr_shift, err, mag, add);
+}
+
+// One item of TC phase A, the same items as phase W.  add as ntuple_tc_accum takes it.
+template <uint32_t T, class Items, class Shape, class Add>
+G2048_DEV void ntuple_item_tc_accum(const Items &items, const int64_t *delta, typename Items::Item it, const Shape &sh, Add add)
+{
+    const int64_t d = items.tc_delta(delta, it);
+    if (d != 0)
+        ntuple_tc_accum<T>(items.packed(it), sh, d, add);
 }
 
 // ------------------------------------------------------------------- n-tuple expectimax

@@ -52,12 +52,6 @@ __device__ __forceinline__ void store_chunk_nt(uint4 *out, uint64_t g, uint32_t 
     __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(out) + g);
 }
 
-__device__ __forceinline__ Board load_board(const uint4 *boards, uint32_t i)
-{
-    const uint4 v = boards[i];
-    return Board{{v.x, v.y, v.z, v.w}};
-}
-
 __device__ __forceinline__ void store_board(uint4 *boards, uint32_t i, const Board &b)
 {
     boards[i] = make_uint4(b.r[0], b.r[1], b.r[2], b.r[3]);
@@ -1640,68 +1634,71 @@ __global__ void __launch_bounds__(kBlock) ntuple_stage_kernel(const uint4 *__res
     stage[i] = static_cast<uint8_t>(ntuple_stage(ntuple_stage_mask(ntuple_pack(load_board(boards, i))), sh));
 }
 
-// g2048_ntuple_update_plain: one board per lane, 8T relaxed agent-scope atomic adds whose result nobody reads (fire and
-// forget); a lane whose step is 0 issues none.  Integer adds commute, so the weights after the launch do not depend on
-// the order the lanes, waves or launches arrive in.
-template <uint32_t T, class Shape>
-__global__ void __launch_bounds__(kBlock) ntuple_update_kernel(const uint4 *__restrict__ boards, uint32_t n,
-                                                               const int64_t *__restrict__ delta, uint32_t lr_shift,
-                                                               const Shape sh, int32_t *weights)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n)
-        return;
-    const int32_t step = ntuple_step(delta[i], lr_shift);
-    if (step == 0)
-        return;
-    uint32_t *w = reinterpret_cast<uint32_t *>(weights); // unsigned: the add wraps mod 2^32
-    ntuple_update<T>(ntuple_pack(load_board(boards, i)), sh, step, [w](uint32_t off, int32_t st) {
-        __hip_atomic_fetch_add(w + off, static_cast<uint32_t>(st), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    });
-}
-
-// g2048_ntuple_tc_update_plain, phase W (the definition of g2048_device.h, "Temporal-coherence learning"): one board per
-// lane; the 8T offsets, then the 16T 8-byte loads of err and mag in flight together, then the rates and steps, then up to
-// 8T relaxed agent-scope 32-bit atomic adds whose result nobody reads.  err and mag are only read here: phase A adds to
-// them in a launch of its own, so every lane sees the accumulators of before the call.  A lane whose d is 0 loads and adds
-// nothing.  Lanes stride over the boards when n exceeds the grid cap (kSearchMaxLanes).
-template <uint32_t T, class Shape>
-__global__ void __launch_bounds__(kBlock) ntuple_tc_weights_kernel(const uint4 *__restrict__ boards, uint32_t n,
-                                                                   const int64_t *__restrict__ delta, uint32_t lr_shift,
-                                                                   const Shape sh, int32_t *weights,
-                                                                   const int64_t *__restrict__ err, const int64_t *__restrict__ mag)
-{
-    uint32_t *w = reinterpret_cast<uint32_t *>(weights); // unsigned: the add wraps mod 2^32
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
-        const int64_t d = ntuple_tc_delta(delta[i]);
-        if (d == 0)
-            continue;
-        ntuple_tc_weights<T>(ntuple_pack(load_board(boards, static_cast<uint32_t>(i))), sh, d, lr_shift, err, mag,
-                             [w](uint32_t off, int32_t st) {
-                                 __hip_atomic_fetch_add(w + off, static_cast<uint32_t>(st), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                             });
+// The six updates (g2048_ntuple_update_plain, g2048_ntuple_tc_update_plain, g2048_ntuple_trace_update,
+// g2048_ntuple_tc_trace_update; the definitions of g2048_device.h, "n-tuple network value function", "Temporal-coherence
+// learning" and "n-tuple traces") are three kernels, each over either item source of g2048_device.h ("The work items of an
+// update"): NtupleBoardItems, one board per item, or NtupleTraceItems, one (k, i) per item.  A kernel is the header's item
+// loop and per-item operation with an atomic add: relaxed, agent scope, its result read by nobody (fire and forget).
+// Integer adds commute, so the tables after a launch do not depend on the order the lanes, waves or launches arrive in.
+// A lane takes the items lane, lane + grid, ...: the grid is capped at kSearchMaxLanes.  delta is an argument of its own, and
+// __restrict__: as a member of the source, phase W over a trace took 24 and 40 more VGPRs at T = 2 and 3 and lost a wave
+// (profiles/r16_ntuple_items_resource_usage.txt).
+struct AtomicAddWeights { // weights[off] += step, wrapping mod 2^32
+    uint32_t *w;
+    __device__ void operator()(uint32_t off, int32_t step) const
+    {
+        __hip_atomic_fetch_add(w + off, static_cast<uint32_t>(step), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+};
+struct AtomicAddAccum { // err[off] += d, mag[off] += |d|, wrapping mod 2^64
+    unsigned long long *e, *a;
+    __device__ void operator()(uint32_t off, int64_t d, uint64_t m) const
+    {
+        __hip_atomic_fetch_add(e + off, static_cast<unsigned long long>(d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(a + off, static_cast<unsigned long long>(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// f(item) for every item of this lane
+template <class Items, class F> __device__ __forceinline__ void lane_items(const Items &items, F f)
+{
+    ntuple_for_items(items, static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x, static_cast<uint64_t>(gridDim.x) * kBlock, f);
 }
 
-// Phase A: err[j] += d, mag[j] += |d| for the 8T look-ups of every board with d != 0 -- 16T relaxed agent-scope 64-bit
-// atomic adds, fire and forget, wrapping mod 2^64.  The same lanes and stride as phase W.
-template <uint32_t T, class Shape>
-__global__ void __launch_bounds__(kBlock) ntuple_tc_accum_kernel(const uint4 *__restrict__ boards, uint32_t n,
-                                                                 const int64_t *__restrict__ delta, const Shape sh,
+// TD: 8T adds per item; an item whose step is 0 loads no board and issues none.  Over plain boards this kernel had no loop
+// once and ran 8 waves/SIMD.  The loop keeps the 8T cell lists live across its back edge; left alone the allocator takes
+// 106 SGPRs for them, which is 7 waves.  kUpdateMinWaves holds that form to the 8 it had -- the lists beyond 78 SGPRs go to
+// VGPR lanes -- and leaves the trace form, which had the loop and 7 waves, as it was
+// (profiles/r16_ntuple_items_resource_usage.txt).
+template <class Items> constexpr uint32_t kUpdateMinWaves = std::is_same<Items, NtupleBoardItems>::value ? 8u : 1u;
+
+template <uint32_t T, class Shape, class Items>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kUpdateMinWaves<Items>)))
+ntuple_update_kernel(const Items items, const int64_t *__restrict__ delta, uint32_t lr_shift, const Shape sh, int32_t *weights)
+{
+    const AtomicAddWeights add{reinterpret_cast<uint32_t *>(weights)};
+    lane_items(items, [&](typename Items::Item it) { ntuple_item_update<T>(items, delta, it, lr_shift, sh, add); });
+}
+
+// TC phase W: the 8T offsets, then the 16T 8-byte loads of err and mag in flight together, then the rates and steps, then up
+// to 8T adds.  err and mag are only read here: phase A adds to them in a launch of its own, so every lane sees the
+// accumulators of before the call.  An item whose d is 0 loads and adds nothing.
+template <uint32_t T, class Shape, class Items>
+__global__ void __launch_bounds__(kBlock) ntuple_tc_weights_kernel(const Items items, const int64_t *__restrict__ delta, uint32_t lr_shift,
+                                                                   const Shape sh, int32_t *weights, const int64_t *__restrict__ err,
+                                                                   const int64_t *__restrict__ mag)
+{
+    const AtomicAddWeights add{reinterpret_cast<uint32_t *>(weights)};
+    lane_items(items, [&](typename Items::Item it) { ntuple_item_tc_weights<T>(items, delta, it, lr_shift, sh, err, mag, add); });
+}
+
+// TC phase A: 16T 64-bit adds for every item with d != 0, the same items as phase W.
+template <uint32_t T, class Shape, class Items>
+__global__ void __launch_bounds__(kBlock) ntuple_tc_accum_kernel(const Items items, const int64_t *__restrict__ delta, const Shape sh,
                                                                  int64_t *err, int64_t *mag)
 {
-    unsigned long long *e = reinterpret_cast<unsigned long long *>(err), *a = reinterpret_cast<unsigned long long *>(mag);
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
-        const int64_t d = ntuple_tc_delta(delta[i]);
-        if (d == 0)
-            continue;
-        ntuple_tc_accum<T>(ntuple_pack(load_board(boards, static_cast<uint32_t>(i))), sh, d, [e, a](uint32_t off, int64_t dd, uint64_t m) {
-            __hip_atomic_fetch_add(e + off, static_cast<unsigned long long>(dd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(a + off, static_cast<unsigned long long>(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        });
-    }
+    const AtomicAddAccum add{reinterpret_cast<unsigned long long *>(err), reinterpret_cast<unsigned long long *>(mag)};
+    lane_items(items, [&](typename Items::Item it) { ntuple_item_tc_accum<T>(items, delta, it, sh, add); });
 }
 
 // g2048_ntuple_trace_push (the definition of g2048_device.h, "n-tuple traces"): one board per lane -- one 16-byte load of
@@ -1722,79 +1719,6 @@ __global__ void __launch_bounds__(kBlock) ntuple_trace_push_kernel(const uint4 *
         delta[i] = ntuple_trace_delta(best_next[i], after_value[i], term);
         len[i] = static_cast<uint8_t>(ntuple_trace_push_len(len[i], H, term));
     }
-}
-
-// The three trace updates: one work item per (k, i), k-major (ntuple_trace_split), so a wave reads 64 consecutive boards
-// of one slot; 64-bit item index and slot base (H * n * 16 bytes exceeds 2^32); the items stride past the grid cap.  A lane
-// reads len[i] and delta[i] first and leaves before loading its board when k >= L or d_k == 0 (ntuple_trace_item); the
-// body is that of the one-step kernel with d_k for the delta.
-struct TraceArgs {
-    const uint4 *hist;  // [H][n] boards
-    const uint8_t *len; // [n]
-    uint32_t n, H, lam, slot;
-};
-
-// f(board index, d_k, packed board) for every work item of this lane that `keep(d_k)` lets through
-template <class Keep, class F> __device__ __forceinline__ void trace_items(const TraceArgs &tr, const int64_t *delta, Keep keep, F f)
-{
-    const uint64_t items = static_cast<uint64_t>(tr.H) * tr.n, stride = static_cast<uint64_t>(gridDim.x) * kBlock;
-    for (uint64_t item = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; item < items; item += stride) {
-        uint32_t k, i;
-        ntuple_trace_split(item, tr.n, tr.H, k, i);
-        const int64_t dk = ntuple_trace_item(tr.len[i], delta[i], k, tr.H, tr.lam);
-        if (dk == 0 || !keep(dk))
-            continue;
-        const uint4 *boards = tr.hist + static_cast<uint64_t>(ntuple_trace_slot(tr.slot, k, tr.H)) * tr.n;
-        f(dk, ntuple_pack(load_board(boards, i)));
-    }
-}
-
-// g2048_ntuple_trace_update: ntuple_update_kernel's 8T fire-and-forget adds with step(d_k); a zero step issues none.
-template <uint32_t T, class Shape>
-__global__ void __launch_bounds__(kBlock) ntuple_trace_update_kernel(const TraceArgs tr, const int64_t *__restrict__ delta,
-                                                                     uint32_t lr_shift, const Shape sh, int32_t *weights)
-{
-    uint32_t *w = reinterpret_cast<uint32_t *>(weights); // unsigned: the add wraps mod 2^32
-    trace_items(
-        tr, delta, [lr_shift](int64_t dk) { return ntuple_step(dk, lr_shift) != 0; },
-        [&](int64_t dk, uint64_t packed) {
-            ntuple_update<T>(packed, sh, ntuple_step(dk, lr_shift), [w](uint32_t off, int32_t st) {
-                __hip_atomic_fetch_add(w + off, static_cast<uint32_t>(st), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            });
-        });
-}
-
-// g2048_ntuple_tc_trace_update, phase W: ntuple_tc_weights_kernel's body per item.  err and mag are only read.
-template <uint32_t T, class Shape>
-__global__ void __launch_bounds__(kBlock) ntuple_tc_trace_weights_kernel(const TraceArgs tr, const int64_t *__restrict__ delta,
-                                                                         uint32_t lr_shift, const Shape sh, int32_t *weights,
-                                                                         const int64_t *__restrict__ err,
-                                                                         const int64_t *__restrict__ mag)
-{
-    uint32_t *w = reinterpret_cast<uint32_t *>(weights); // unsigned: the add wraps mod 2^32
-    trace_items(
-        tr, delta, [](int64_t) { return true; },
-        [&](int64_t dk, uint64_t packed) {
-            ntuple_tc_weights<T>(packed, sh, dk, lr_shift, err, mag, [w](uint32_t off, int32_t st) {
-                __hip_atomic_fetch_add(w + off, static_cast<uint32_t>(st), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            });
-        });
-}
-
-// Phase A: ntuple_tc_accum_kernel's body per item, the same items as phase W.
-template <uint32_t T, class Shape>
-__global__ void __launch_bounds__(kBlock) ntuple_tc_trace_accum_kernel(const TraceArgs tr, const int64_t *__restrict__ delta,
-                                                                       const Shape sh, int64_t *err, int64_t *mag)
-{
-    unsigned long long *e = reinterpret_cast<unsigned long long *>(err), *a = reinterpret_cast<unsigned long long *>(mag);
-    trace_items(
-        tr, delta, [](int64_t) { return true; },
-        [&](int64_t dk, uint64_t packed) {
-            ntuple_tc_accum<T>(packed, sh, dk, [e, a](uint32_t off, int64_t dd, uint64_t m) {
-                __hip_atomic_fetch_add(e + off, static_cast<unsigned long long>(dd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_fetch_add(a + off, static_cast<unsigned long long>(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            });
-        });
 }
 
 // ---------------------------------------------------------------------------- augmentation
@@ -2434,28 +2358,48 @@ hipError_t launch_ntuple_stage(const uint4 *boards, uint32_t n, const NtupleNet 
     return launch_1d(ntuple_stage_kernel, n, 0, s, boards, n, sh, stage);
 }
 
+// One lane per item of the source, up to the grid cap
+template <class Items> static uint64_t item_lanes(const Items &items)
+{
+    return items.size() < kSearchMaxLanes ? items.size() : kSearchMaxLanes;
+}
+
+template <class Items>
+static hipError_t launch_items_update(const Items &items, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net, hipStream_t s)
+{
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        return launch_1d(ntuple_update_kernel<tc, decltype(sh), Items>, item_lanes(items), 0, s, items, delta, lr_shift, sh, net.weights);
+    });
+}
+
+// phase W, then phase A, a launch each
+template <class Items>
+static hipError_t launch_items_tc_update(const Items &items, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const NtupleNet &net,
+                                         int64_t *err, int64_t *mag, hipStream_t s)
+{
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        if (phases & kNtupleTcWeights) {
+            const hipError_t rc = launch_1d(ntuple_tc_weights_kernel<tc, decltype(sh), Items>, item_lanes(items), 0, s, items, delta, lr_shift,
+                                            sh, net.weights, static_cast<const int64_t *>(err), static_cast<const int64_t *>(mag));
+            if (rc != hipSuccess)
+                return rc;
+        }
+        if (phases & kNtupleTcAccum)
+            return launch_1d(ntuple_tc_accum_kernel<tc, decltype(sh), Items>, item_lanes(items), 0, s, items, delta, sh, err, mag);
+        return hipSuccess;
+    });
+}
+
 hipError_t launch_ntuple_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
                                 hipStream_t s)
 {
-    return dispatch_tuples(net, [&](auto tc, auto sh) {
-        return launch_1d(ntuple_update_kernel<tc, decltype(sh)>, n, 0, s, boards, n, delta, lr_shift, sh, net.weights);
-    });
+    return launch_items_update(NtupleBoardItems{boards, n}, delta, lr_shift, net, s);
 }
 
 hipError_t launch_ntuple_tc_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
                                    const NtupleNet &net, int64_t *err, int64_t *mag, hipStream_t s)
 {
-    return dispatch_tuples(net, [&](auto tc, auto sh) {
-        if (phases & kNtupleTcWeights) {
-            const hipError_t rc = launch_1d(ntuple_tc_weights_kernel<tc, decltype(sh)>, group_lanes(n, 1u), 0, s, boards, n, delta, lr_shift, sh,
-                                            net.weights, static_cast<const int64_t *>(err), static_cast<const int64_t *>(mag));
-            if (rc != hipSuccess)
-                return rc;
-        }
-        if (phases & kNtupleTcAccum)
-            return launch_1d(ntuple_tc_accum_kernel<tc, decltype(sh)>, group_lanes(n, 1u), 0, s, boards, n, delta, sh, err, mag);
-        return hipSuccess;
-    });
+    return launch_items_tc_update(NtupleBoardItems{boards, n}, delta, lr_shift, phases, net, err, mag, s);
 }
 
 hipError_t launch_ntuple_trace_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next,
@@ -2466,37 +2410,17 @@ hipError_t launch_ntuple_trace_push(const uint4 *after, const int64_t *after_val
                      tr.hist + static_cast<uint64_t>(slot) * n, tr.len, delta);
 }
 
-// Lanes of a trace update: one per (k, i) item, up to the grid cap
-static uint64_t trace_lanes(uint32_t n, const NtupleTrace &tr)
-{
-    const uint64_t want = static_cast<uint64_t>(n) * tr.depth;
-    return want < kSearchMaxLanes ? want : kSearchMaxLanes;
-}
-
 hipError_t launch_ntuple_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
                                       const NtupleTrace &tr, uint32_t slot, hipStream_t s)
 {
-    const TraceArgs ta{tr.hist, tr.len, n, tr.depth, tr.lambda, slot};
-    return dispatch_tuples(net, [&](auto tc, auto sh) {
-        return launch_1d(ntuple_trace_update_kernel<tc, decltype(sh)>, trace_lanes(n, tr), 0, s, ta, delta, lr_shift, sh, net.weights);
-    });
+    return launch_items_update(NtupleTraceItems{tr.hist, tr.len, n, tr.depth, tr.lambda, slot}, delta, lr_shift, net, s);
 }
 
 hipError_t launch_ntuple_tc_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const NtupleNet &net,
                                          int64_t *err, int64_t *mag, const NtupleTrace &tr, uint32_t slot, hipStream_t s)
 {
-    const TraceArgs ta{tr.hist, tr.len, n, tr.depth, tr.lambda, slot};
-    return dispatch_tuples(net, [&](auto tc, auto sh) {
-        if (phases & kNtupleTcWeights) {
-            const hipError_t rc = launch_1d(ntuple_tc_trace_weights_kernel<tc, decltype(sh)>, trace_lanes(n, tr), 0, s, ta, delta, lr_shift, sh,
-                                            net.weights, static_cast<const int64_t *>(err), static_cast<const int64_t *>(mag));
-            if (rc != hipSuccess)
-                return rc;
-        }
-        if (phases & kNtupleTcAccum)
-            return launch_1d(ntuple_tc_trace_accum_kernel<tc, decltype(sh)>, trace_lanes(n, tr), 0, s, ta, delta, sh, err, mag);
-        return hipSuccess;
-    });
+    return launch_items_tc_update(NtupleTraceItems{tr.hist, tr.len, n, tr.depth, tr.lambda, slot}, delta, lr_shift, phases, net, err,
+                                  mag, s);
 }
 
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s)

@@ -82,6 +82,19 @@ class NTupleEval(NamedTuple):
     after_value: Optional[torch.Tensor]  # int64 [n]: V(after); 0 when no move is legal
 
 
+def _check_tensor(name, t, dtypes, shape, device):
+    """``t`` is a contiguous tensor of one of ``dtypes`` and of ``shape`` on ``device``, or ValueError."""
+    if (not isinstance(t, torch.Tensor) or t.dtype not in dtypes or tuple(t.shape) != tuple(shape) or not t.is_contiguous()
+            or t.device != device):
+        raise ValueError(f"{name} must be a contiguous {str(dtypes[0]).replace('torch.', '')} {list(shape)} tensor on {device}")
+
+
+def _on_stream(fn, device, *args):
+    """One library call on the current stream of ``device``."""
+    with torch.cuda.device(device):
+        check(fn(*args, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+
+
 def _eval_io(n, device, out):
     """(NTupleIO, NTupleEval) for n boards: ``out`` checked field by field, or freshly allocated outputs."""
     if out is None:
@@ -191,9 +204,11 @@ class NTupleNet:
         return getattr(_lib.load(), ("g2048_ntuple_" if self.stages is None else "g2048_ntuple_staged_") + name)
 
     def _launch(self, fn, boards, *args):
-        with torch.cuda.device(boards.device):
-            stream = C.c_void_p(torch.cuda.current_stream(boards.device).cuda_stream)
-            check(fn(boards.data_ptr(), boards.shape[0], *args, stream))
+        _on_stream(fn, boards.device, boards.data_ptr(), boards.shape[0], *args)
+
+    def _own_tc(self, tc):
+        if not isinstance(tc, NTupleTC) or tc.net is not self:
+            raise ValueError("tc must be the NTupleTC of this network")
 
     def values(self, boards, out=None) -> torch.Tensor:
         """V of plain boards (``g2048_ntuple_values_plain``): ``boards`` a device ``uint8`` ``[n, 16]`` or ``[n, 4, 4]``
@@ -202,9 +217,8 @@ class NTupleNet:
         net = self._ref(device)
         if out is None:
             out = torch.empty(n, dtype=torch.int64, device=device)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n,) or not out.is_contiguous()
-              or out.device != device):
-            raise ValueError(f"out must be a contiguous int64 [{n}] tensor on {device}")
+        else:
+            _check_tensor("out", out, (torch.int64,), (n,), device)
         self._launch(self._fn("values_plain"), boards, net, out.data_ptr())
         return out
 
@@ -217,9 +231,8 @@ class NTupleNet:
         net = self._ref(device)
         if out is None:
             out = torch.empty(n, dtype=torch.uint8, device=device)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n,) or not out.is_contiguous()
-              or out.device != device):
-            raise ValueError(f"out must be a contiguous uint8 [{n}] tensor on {device}")
+        else:
+            _check_tensor("out", out, (torch.uint8,), (n,), device)
         self._launch(_lib.load().g2048_ntuple_stage_plain, boards, net, out.data_ptr())
         return out
 
@@ -235,8 +248,8 @@ class NTupleNet:
         dst = _int_arg("dst", dst, 0, self.n_stages - 1)
         if src == dst:
             raise ValueError(f"promote: src and dst are both stage {src}")
-        if tc is not None and (not isinstance(tc, NTupleTC) or tc.net is not self):
-            raise ValueError("tc must be the NTupleTC of this network")
+        if tc is not None:
+            self._own_tc(tc)
         self.weights[dst].copy_(self.weights[src])          # torch: the current stream of the tensors' device
         if tc is not None:
             tc.err[dst].zero_()
@@ -269,9 +282,7 @@ class NTupleNet:
         ``lr_shift`` 0..40.  One launch of integer atomic adds: the result does not depend on their order."""
         n, device = _plain_boards(boards)
         net = self._ref(device)
-        if (not isinstance(delta, torch.Tensor) or delta.dtype != torch.int64 or tuple(delta.shape) != (n,)
-                or not delta.is_contiguous() or delta.device != device):
-            raise ValueError(f"delta must be a contiguous int64 [{n}] tensor on {device}")
+        _check_tensor("delta", delta, (torch.int64,), (n,), device)
         shift = _int_arg("lr_shift", lr_shift, 0, MAX_LR_SHIFT)
         self._launch(self._fn("update_plain"), boards, delta.data_ptr(), shift, net)
 
@@ -284,13 +295,10 @@ class NTupleNet:
         W on every shard, then A on every shard."""
         n, device = _plain_boards(boards)
         net = self._ref(device)
-        if (not isinstance(delta, torch.Tensor) or delta.dtype != torch.int64 or tuple(delta.shape) != (n,)
-                or not delta.is_contiguous() or delta.device != device):
-            raise ValueError(f"delta must be a contiguous int64 [{n}] tensor on {device}")
+        _check_tensor("delta", delta, (torch.int64,), (n,), device)
         shift = _int_arg("lr_shift", lr_shift, 0, MAX_LR_SHIFT)
         phases = _int_arg("phases", phases, TC_WEIGHTS, TC_WEIGHTS | TC_ACCUM)
-        if not isinstance(tc, NTupleTC) or tc.net is not self:
-            raise ValueError("tc must be the NTupleTC of this network")
+        self._own_tc(tc)
         self._launch(self._fn("tc_update_plain"), boards, delta.data_ptr(), shift, phases, net, C.byref(tc._c))
 
     def _trace_args(self, trace, delta, lr_shift):
@@ -298,9 +306,7 @@ class NTupleNet:
         if not isinstance(trace, NTupleTrace):
             raise ValueError("trace must be an NTupleTrace")
         net = self._ref(trace.device)
-        if (not isinstance(delta, torch.Tensor) or delta.dtype != torch.int64 or tuple(delta.shape) != (trace.n,)
-                or not delta.is_contiguous() or delta.device != trace.device):
-            raise ValueError(f"delta must be a contiguous int64 [{trace.n}] tensor on {trace.device}")
+        _check_tensor("delta", delta, (torch.int64,), (trace.n,), trace.device)
         return net, _int_arg("lr_shift", lr_shift, 0, MAX_LR_SHIFT)
 
     def trace_update(self, trace, delta, lr_shift):
@@ -309,9 +315,7 @@ class NTupleNet:
         ``d_k = (clamp(delta) * lam^k) >> 16``.  ``delta`` a device int64 ``[trace.n]`` tensor, ``lr_shift`` 0..40.  One
         launch of integer atomic adds."""
         net, shift = self._trace_args(trace, delta, lr_shift)
-        with torch.cuda.device(trace.device):
-            stream = C.c_void_p(torch.cuda.current_stream(trace.device).cuda_stream)
-            check(self._fn("trace_update")(trace.n, delta.data_ptr(), shift, net, C.byref(trace._c), trace.slot, stream))
+        _on_stream(self._fn("trace_update"), trace.device, trace.n, delta.data_ptr(), shift, net, C.byref(trace._c), trace.slot)
 
     def tc_trace_update(self, trace, delta, lr_shift, tc, phases=3):
         """The TC(lambda) update (``g2048_ntuple_tc_trace_update``): :meth:`tc_update` with ``d_k`` for
@@ -319,12 +323,9 @@ class NTupleNet:
         on every shard, then A on every shard."""
         net, shift = self._trace_args(trace, delta, lr_shift)
         phases = _int_arg("phases", phases, TC_WEIGHTS, TC_WEIGHTS | TC_ACCUM)
-        if not isinstance(tc, NTupleTC) or tc.net is not self:
-            raise ValueError("tc must be the NTupleTC of this network")
-        with torch.cuda.device(trace.device):
-            stream = C.c_void_p(torch.cuda.current_stream(trace.device).cuda_stream)
-            check(self._fn("tc_trace_update")(trace.n, delta.data_ptr(), shift, phases, net, C.byref(tc._c),
-                                                           C.byref(trace._c), trace.slot, stream))
+        self._own_tc(tc)
+        _on_stream(self._fn("tc_trace_update"), trace.device, trace.n, delta.data_ptr(), shift, phases, net, C.byref(tc._c),
+                   C.byref(trace._c), trace.slot)
 
     def state_dict(self):
         return {"tuples": self.tuples, "frac_bits": self.frac_bits, "stages": self.stages, "weights": self.weights.clone()}
@@ -404,14 +405,10 @@ class NTupleTrace:
         for name, t, shape, dtypes in (("after", after, (n, 16), (torch.uint8,)), ("after_value", after_value, (n,), (torch.int64,)),
                                        ("best_next", best_next, (n,), (torch.int64,)),
                                        ("terminated", terminated, (n,), (torch.uint8, torch.bool)), ("out", out, (n,), (torch.int64,))):
-            if (not isinstance(t, torch.Tensor) or t.dtype not in dtypes or tuple(t.shape) != shape or not t.is_contiguous()
-                    or t.device != dev):
-                raise ValueError(f"{name} must be a contiguous {str(dtypes[0]).replace('torch.', '')} {list(shape)} tensor on {dev}")
+            _check_tensor(name, t, dtypes, shape, dev)
         slot = (self.slot + 1) % self.depth
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            check(_lib.load().g2048_ntuple_trace_push(after.data_ptr(), after_value.data_ptr(), best_next.data_ptr(),
-                                                      terminated.data_ptr(), n, C.byref(self._c), slot, out.data_ptr(), stream))
+        _on_stream(_lib.load().g2048_ntuple_trace_push, dev, after.data_ptr(), after_value.data_ptr(), best_next.data_ptr(),
+                   terminated.data_ptr(), n, C.byref(self._c), slot, out.data_ptr())
         self.slot = slot
         return out
 

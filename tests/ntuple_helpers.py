@@ -1,5 +1,6 @@
-"""Shared by the n-tuple network tests: the host build of the header's n-tuple code (tests/host_ntuple/ntuple_check.cpp,
-g++) behind ctypes, the network shapes the tests use, and random weights.  A plain module, like analysis_helpers."""
+"""Shared by the n-tuple tests: the one host build of the header's n-tuple code (tests/host_ntuple/ntuple_check.cpp, g++)
+behind ctypes -- network, search, TD, TC and trace updates, stages -- the network shapes the tests use, and random weights.
+A plain module, like analysis_helpers."""
 import ctypes as C
 import os
 import subprocess
@@ -34,6 +35,29 @@ def symmetry_images(cells):
     return out
 
 
+class Desc(C.Structure):
+    """struct Desc of ntuple_check.cpp: the network of a call, and the shape type the call instantiates."""
+    _fields_ = [("T", C.c_uint32), ("L", C.c_uint32), ("F", C.c_uint32), ("S", C.c_uint32), ("staged", C.c_uint32),
+                ("thr", C.c_uint16 * 8), ("cells", (C.c_uint8 * 6) * 8)]
+
+
+def desc_of(net):
+    """The description of an ntuple_ref.Net (the NtupleShape code) or an ntuple_staged_ref.StagedNet (the NtupleStagedShape
+    code, S = 1 included)."""
+    thr = getattr(net, "thr", None)
+    d = Desc(len(net.tuples), len(net.tuples[0]), net.frac_bits, 1 if thr is None else len(thr) + 1, 0 if thr is None else 1)
+    d.thr[:len(thr or ())] = thr or ()
+    for t, cells in enumerate(net.tuples):
+        for k, c in enumerate(cells):
+            d.cells[t][k] = c
+    return C.byref(d)
+
+
+def raw_desc(T, L, F=10, S=1, staged=0):
+    """A description by its numbers alone, in or out of range (no cells: for calls that must be refused)."""
+    return C.byref(Desc(T, L, F, S, staged))
+
+
 def build_host_ntuple(force=False):
     """g++ build of tests/host_ntuple (the device header's n-tuple code compiled for the host; tests only)."""
     so, src = os.path.join(HOST_DIR, "libntuple_check.so"), os.path.join(HOST_DIR, "ntuple_check.cpp")
@@ -45,12 +69,20 @@ def build_host_ntuple(force=False):
 
 def load_host_ntuple():
     lib = C.CDLL(build_host_ntuple())
-    P, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
-    lib.ntuple_check_evaluate.restype, lib.ntuple_check_evaluate.argtypes = C.c_int, [P, u64, u32, u32, u32, P, P, P, P, P, P, P]
-    lib.ntuple_check_values.restype, lib.ntuple_check_values.argtypes = C.c_int, [P, u64, u32, u32, P, P, P]
-    lib.ntuple_check_update.restype, lib.ntuple_check_update.argtypes = C.c_int, [P, u64, P, u32, u32, u32, P, P]
-    lib.ntuple_check_step.restype, lib.ntuple_check_step.argtypes = C.c_int32, [C.c_int64, u32]
-    lib.ntuple_check_sym_cells.restype, lib.ntuple_check_sym_cells.argtypes = None, [P]
+    P, u32, u64, i64, D = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int64, C.POINTER(Desc)
+    for name, restype, argtypes in (
+            ("step", C.c_int32, [i64, u32]), ("sym_cells", None, [P]), ("floor_div", i64, [i64, i64]),
+            ("tc_rate", u32, [i64, u64]), ("tc_step", C.c_int32, [i64, u32, u32]),
+            ("decay", u32, [u32, u32]), ("dk", i64, [i64, u32, u32]), ("push_len", u32, [u32, u32, u32]), ("len", u32, [u32, u32]),
+            ("split", u64, [u64, u32, u32]),
+            ("mask", None, [P, u64, P]), ("stage", C.c_int, [P, u64, D, P]), ("base", C.c_int, [P, u64, D, P]),
+            ("evaluate", C.c_int, [P, u64, D, P, P, P, P, P, P]), ("values", C.c_int, [P, u64, D, P, P]),
+            ("search", C.c_int, [P, u64, u32, D, P, P, P]), ("chance_split", C.c_int, [P, u64, u32, D, P, u32, P]),
+            ("update", C.c_int, [P, u64, P, u32, u32, D, P, P, P]), ("tc_update", C.c_int, [P, u64, P, u32, u32, D, P, P, P]),
+            ("push", C.c_int, [P, P, P, P, u64, u32, P, P, u32, P]),
+            ("trace_update", C.c_int, [u64, P, u32, u32, D, P, P, P, u32, u32, P, P, u32])):
+        f = getattr(lib, "ntuple_check_" + name)
+        f.restype, f.argtypes = restype, argtypes
     return lib
 
 
@@ -58,43 +90,99 @@ def _rows(boards):
     return np.ascontiguousarray(np.asarray(boards, np.uint8).reshape(-1, 16))
 
 
-def _cells(net):
-    c = np.zeros((8, 6), np.uint8)
-    for t, cells in enumerate(net.tuples):
-        c[t, :len(cells)] = cells
-    return c
-
-
 def _w32(net):
     return np.ascontiguousarray(net.weights.astype(np.int32))
 
 
+def _tables(net, tc):
+    w = _w32(net)
+    err = np.zeros(1, np.int64) if tc is None else np.ascontiguousarray(tc.err.copy())
+    mag = np.zeros(1, np.int64) if tc is None else np.ascontiguousarray(tc.mag_i64().copy())
+    return w, err, mag
+
+
+def host_mask(lib, raw):
+    b = _rows(raw)
+    out = np.zeros(len(b), np.uint32)
+    lib.ntuple_check_mask(b.ctypes.data, len(b), out.ctypes.data)
+    return out
+
+
+def host_stage(lib, raw, net):
+    b, out = _rows(raw), np.zeros(len(_rows(raw)), np.uint8)
+    assert lib.ntuple_check_stage(b.ctypes.data, len(b), desc_of(net), out.ctypes.data) == 0
+    return out
+
+
+def host_base(lib, boards, net):
+    b, out = _rows(boards), np.zeros(len(_rows(boards)), np.uint32)
+    assert lib.ntuple_check_base(b.ctypes.data, len(b), desc_of(net), out.ctypes.data) == 0
+    return out
+
+
 def host_evaluate(lib, boards, net):
-    b, c, w = _rows(boards), _cells(net), _w32(net)
+    b, w = _rows(boards), _w32(net)
     n = len(b)
     val, act = np.zeros((n, 4), np.int64), np.zeros(n, np.uint8)
     best, after, av = np.zeros(n, np.int64), np.zeros((n, 16), np.uint8), np.zeros(n, np.int64)
-    assert lib.ntuple_check_evaluate(b.ctypes.data, n, len(net.tuples), len(net.tuples[0]), net.frac_bits, c.ctypes.data,
-                                     w.ctypes.data, val.ctypes.data, act.ctypes.data, best.ctypes.data, after.ctypes.data,
-                                     av.ctypes.data) == 0
+    assert lib.ntuple_check_evaluate(b.ctypes.data, n, desc_of(net), w.ctypes.data, val.ctypes.data, act.ctypes.data,
+                                     best.ctypes.data, after.ctypes.data, av.ctypes.data) == 0
     return val, act, best, after, av
 
 
 def host_values(lib, boards, net):
-    b, c, w = _rows(boards), _cells(net), _w32(net)
+    b, w = _rows(boards), _w32(net)
     v = np.zeros(len(b), np.int64)
-    assert lib.ntuple_check_values(b.ctypes.data, len(b), len(net.tuples), len(net.tuples[0]), c.ctypes.data, w.ctypes.data,
-                                   v.ctypes.data) == 0
+    assert lib.ntuple_check_values(b.ctypes.data, len(b), desc_of(net), w.ctypes.data, v.ctypes.data) == 0
     return v
 
 
-def host_update(lib, boards, deltas, lr_shift, net):
-    """The weights after the update, as int64 [T, 16^L] (``net`` is not modified)."""
-    b, c, w = _rows(boards), _cells(net), _w32(net)
+def host_search(lib, boards, depth, net):
+    """(action uint8 [n], value int64 [n, 4]) of ntuple_search_root on the host."""
+    b, w = _rows(boards), _w32(net)
+    act, val = np.zeros(len(b), np.uint8), np.zeros((len(b), 4), np.int64)
+    assert lib.ntuple_check_search(b.ctypes.data, len(b), depth, desc_of(net), w.ctypes.data, act.ctypes.data, val.ctypes.data) == 0
+    return act, val
+
+
+def host_split(lib, boards, depth, net, K):
+    """int64 [n, 4]: the chance sums of the four afterstates, summed over K lanes' parts (0 where the move is illegal)."""
+    b, w = _rows(boards), _w32(net)
+    out = np.zeros((len(b), 4), np.int64)
+    assert lib.ntuple_check_chance_split(b.ctypes.data, len(b), depth, desc_of(net), w.ctypes.data, K, out.ctypes.data) == 0
+    return out
+
+
+def host_update(lib, boards, deltas, lr_shift, mode, net, tc=None):
+    """(weights, err, mag) after the one-step update by the host build, as int64 arrays; mode 0 is the TD(0) update, 1..3 the
+    TC update with those phases (``net`` and ``tc`` are not modified)."""
+    b, d = _rows(boards), np.ascontiguousarray(np.asarray(deltas, np.int64))
+    w, err, mag = _tables(net, tc)
+    assert lib.ntuple_check_update(b.ctypes.data, len(b), d.ctypes.data, lr_shift, mode, desc_of(net), w.ctypes.data,
+                                   err.ctypes.data, mag.ctypes.data) == 0
+    return w.astype(np.int64), err, mag
+
+
+def host_push(lib, tr, after, after_value, best_next, terminated):
+    """Push into a copy of the reference trace ``tr`` by the host build: (the new trace, delta)."""
+    out = tr.copy()
+    out.slot = (tr.slot + 1) % tr.depth
+    a = np.ascontiguousarray(np.asarray(after, np.uint8).reshape(tr.n, 16))
+    av, bn = np.ascontiguousarray(after_value, np.int64), np.ascontiguousarray(best_next, np.int64)
+    term, delta = np.ascontiguousarray(terminated, np.uint8), np.zeros(tr.n, np.int64)
+    assert lib.ntuple_check_push(a.ctypes.data, av.ctypes.data, bn.ctypes.data, term.ctypes.data, tr.n, tr.depth,
+                                 out.hist.ctypes.data, out.len.ctypes.data, out.slot, delta.ctypes.data) == 0
+    return out, delta
+
+
+def host_trace_update(lib, tr, deltas, lr_shift, mode, net, tc=None):
+    """(weights, err, mag) after the trace update by the host build, as int64 arrays; mode as in host_update."""
     d = np.ascontiguousarray(np.asarray(deltas, np.int64))
-    assert lib.ntuple_check_update(b.ctypes.data, len(b), d.ctypes.data, lr_shift, len(net.tuples), len(net.tuples[0]),
-                                   c.ctypes.data, w.ctypes.data) == 0
-    return w.astype(np.int64)
+    w, err, mag = _tables(net, tc)
+    hist, ln = np.ascontiguousarray(tr.hist), np.ascontiguousarray(tr.len)
+    assert lib.ntuple_check_trace_update(tr.n, d.ctypes.data, lr_shift, mode, desc_of(net), w.ctypes.data, err.ctypes.data,
+                                         mag.ctypes.data, tr.depth, tr.lam, hist.ctypes.data, ln.ctypes.data, tr.slot) == 0
+    return w.astype(np.int64), err, mag
 
 
 def random_net(tuples, seed, frac_bits=10, lo=-(1 << 31), hi=1 << 31):

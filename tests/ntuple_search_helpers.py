@@ -1,15 +1,7 @@
-"""Shared by the n-tuple expectimax tests: the host build of the header's search code
-(tests/host_ntuple_search/ntuple_search_check.cpp, g++) behind ctypes, and the boards the tests use.  A plain module,
-like ntuple_helpers."""
-import ctypes as C
-import os
-import subprocess
-
+"""Shared by the n-tuple expectimax tests: the boards the tests use and the comparison of two search results (the host build
+is ntuple_helpers').  A plain module, like ntuple_helpers."""
 import numpy as np
 
-from ntuple_helpers import ROOT, _cells, _rows, _w32
-
-HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple_search")
 SEARCH_NAMES = ("action", "value")
 SEARCH_GROUP = {1: 16, 2: 64}   # kNtupleSearchGroup<D> (g2048_kernels.hip): lanes per board at depth D
 
@@ -32,42 +24,6 @@ WIDE_FANS = np.array([
     _sparse([0, 2, 5, 7], [1, 2, 1, 2]), _sparse([0, 5, 10, 15], [3, 1, 2, 4]),
     _sparse(range(7), [1, 2, 3, 4, 2, 3, 1]), _sparse(range(8), [1, 2, 3, 4, 2, 3, 4, 5]),
     _sparse(range(9), [1, 2, 3, 4, 2, 3, 4, 5, 1]), _sparse([0, 2, 5, 7, 8, 10, 13], [1, 2, 3, 1, 2, 3, 1])], np.uint8)
-
-
-def build_host_ntuple_search(force=False):
-    """g++ build of tests/host_ntuple_search (the device header's n-tuple expectimax compiled for the host; tests only)."""
-    so, src = os.path.join(HOST_DIR, "libntuple_search_check.so"), os.path.join(HOST_DIR, "ntuple_search_check.cpp")
-    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
-    return so
-
-
-def load_host_ntuple_search():
-    lib = C.CDLL(build_host_ntuple_search())
-    P, u32, u64, i64 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int64
-    lib.ntuple_search_check_boards.restype, lib.ntuple_search_check_boards.argtypes = C.c_int, [P, u64, u32, u32, u32, u32, P, P, P, P]
-    lib.ntuple_search_check_split.restype, lib.ntuple_search_check_split.argtypes = C.c_int, [P, u64, u32, u32, u32, u32, P, P, u32, P]
-    lib.ntuple_search_check_floor_div.restype, lib.ntuple_search_check_floor_div.argtypes = i64, [i64, i64]
-    return lib
-
-
-def host_search(lib, boards, depth, net):
-    """(action uint8 [n], value int64 [n, 4]) of ntuple_search_root on the host."""
-    b, c, w = _rows(boards), _cells(net), _w32(net)
-    act, val = np.zeros(len(b), np.uint8), np.zeros((len(b), 4), np.int64)
-    assert lib.ntuple_search_check_boards(b.ctypes.data, len(b), depth, len(net.tuples), len(net.tuples[0]), net.frac_bits,
-                                          c.ctypes.data, w.ctypes.data, act.ctypes.data, val.ctypes.data) == 0
-    return act, val
-
-
-def host_split(lib, boards, depth, net, K):
-    """int64 [n, 4]: the chance sums of the four afterstates, summed over K lanes' parts (0 where the move is illegal)."""
-    b, c, w = _rows(boards), _cells(net), _w32(net)
-    out = np.zeros((len(b), 4), np.int64)
-    assert lib.ntuple_search_check_split(b.ctypes.data, len(b), depth, len(net.tuples), len(net.tuples[0]), net.frac_bits,
-                                         c.ctypes.data, w.ctypes.data, K, out.ctypes.data) == 0
-    return out
 
 
 def assert_search_equal(got, want, boards=None, where=""):

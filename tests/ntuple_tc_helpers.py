@@ -1,44 +1,8 @@
-"""Shared by the temporal-coherence tests: the host build of the header's TC code (tests/host_ntuple_tc/ntuple_tc_check.cpp,
-g++) behind ctypes, and accumulators pre-loaded so that a batch reaches the edges of the rate.  A plain module, like
-ntuple_helpers."""
-import ctypes as C
-import os
-import subprocess
-
+"""Shared by the temporal-coherence tests: accumulators pre-loaded so that a batch reaches the edges of the rate, deltas, and
+the comparison of the three tables (the host build is ntuple_helpers').  A plain module, like ntuple_helpers."""
 import numpy as np
 
 import ntuple_tc_ref as tcref
-from ntuple_helpers import ROOT, _cells, _rows, _w32
-
-HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple_tc")
-
-
-def build_host_ntuple_tc(force=False):
-    """g++ build of tests/host_ntuple_tc (the device header's TC code compiled for the host; tests only)."""
-    so, src = os.path.join(HOST_DIR, "libntuple_tc_check.so"), os.path.join(HOST_DIR, "ntuple_tc_check.cpp")
-    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
-    return so
-
-
-def load_host_ntuple_tc():
-    lib = C.CDLL(build_host_ntuple_tc())
-    P, u32, u64, i64 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int64
-    lib.ntuple_tc_check_rate.restype, lib.ntuple_tc_check_rate.argtypes = u32, [i64, u64]
-    lib.ntuple_tc_check_step.restype, lib.ntuple_tc_check_step.argtypes = C.c_int32, [i64, u32, u32]
-    lib.ntuple_tc_check_update.restype, lib.ntuple_tc_check_update.argtypes = C.c_int, [P, u64, P, u32, u32, u32, u32, P, P, P, P]
-    return lib
-
-
-def host_tc_update(lib, boards, deltas, lr_shift, phases, net, tc):
-    """(weights, err, mag) after the update, as int64 arrays (``net`` and ``tc`` are not modified)."""
-    b, c, w = _rows(boards), _cells(net), _w32(net)
-    d = np.ascontiguousarray(np.asarray(deltas, np.int64))
-    err, mag = np.ascontiguousarray(tc.err.copy()), np.ascontiguousarray(tc.mag_i64().copy())
-    assert lib.ntuple_tc_check_update(b.ctypes.data, len(b), d.ctypes.data, lr_shift, phases, len(net.tuples), len(net.tuples[0]),
-                                      c.ctypes.data, w.ctypes.data, err.ctypes.data, mag.ctypes.data) == 0
-    return w.astype(np.int64), err, mag
 
 
 # (E, A) pairs that reach every branch of the rate: never updated; E = 0; |E| = A; |E| = A - 1; A at and around 2^32, 2^63

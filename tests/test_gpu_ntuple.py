@@ -198,6 +198,29 @@ def test_update_same_address_contention_and_split_launches(g, torch_cuda):
     assert np.array_equal(net.weights.cpu().numpy().astype(np.int64), want)
 
 
+def test_update_grid_stride_passes(g, torch_cuda):
+    """n lanes past the grid cap: the boards after the first pass are reached by the kernel's stride loop.  Only the last
+    pass and one board of the first have a delta, so the reference stays small."""
+    torch = torch_cuda
+    n, m = SEARCH_MAX_LANES + 1027, 509
+    assert n > SEARCH_MAX_LANES and n % m != 0
+    base = mixed_boards(m, 111)
+    live = np.concatenate([[5], np.arange(SEARCH_MAX_LANES, n)])
+    values = np.random.default_rng(112).integers(-(1 << 24), 1 << 24, len(live))
+    values[values == 0] = 1
+    rnet = random_net(TUPLES_17x4, 113, lo=-(1 << 20), hi=1 << 20)
+    net = device_net(g, rnet)
+    trace = {}
+    ref.update(rnet, base[live % m], values, 2, trace)
+    assert len(live) == 1028 and trace.get("zero", 0) < len(live) // 2
+    deltas = torch.zeros(n, dtype=torch.int64, device="cuda")
+    deltas[dev(torch, live)] = dev(torch, values)
+    net.update(tiled(torch, base, n).contiguous(), deltas, 2)
+    got = net.weights.cpu().numpy().astype(np.int64)
+    bad = np.argwhere(got != rnet.weights)
+    assert len(bad) == 0, f"{len(bad)} weights differ, first {bad[0].tolist()}: {got[tuple(bad[0])]} vs {rnet.weights[tuple(bad[0])]}"
+
+
 # lr_shift 4: of the shifts 0, 2, 4, 6, 8, 12 the one at which the reference trainer finishes episodes within the 40 steps
 # (the large steps drive weights to the int32 ends and the play turns erratic); the test asserts it from the reference
 TRAIN = dict(n=64, steps=40, seed=42, lr_shift=4)

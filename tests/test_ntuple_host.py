@@ -9,7 +9,7 @@ import ntuple_ref as ref
 from analysis_helpers import ONE_LEGAL, TERMINAL, random_boards, trajectory_boards
 from move_lut import build_row_lut
 from ntuple_helpers import (TUPLES_2x6, TUPLES_8x6, TUPLES_17x4, assert_eval_equal, host_evaluate, host_update, host_values,
-                            load_host_ntuple, random_net)
+                            load_host_ntuple, random_net, raw_desc)
 
 INT32_MAX, INT32_MIN = (1 << 31) - 1, -(1 << 31)
 
@@ -31,7 +31,7 @@ def check_update(lib, boards, deltas, lr_shift, net):
     """host == reference for one update; returns (the new weights, the reference's trace)."""
     after, trace = net.copy(), {}
     ref.update(after, boards, deltas, lr_shift, trace)
-    got = host_update(lib, boards, deltas, lr_shift, net)
+    got = host_update(lib, boards, deltas, lr_shift, 0, net)[0]
     bad = np.argwhere(got != after.weights)
     assert len(bad) == 0, f"{len(bad)} weights differ, first {bad[0].tolist()}: {got[tuple(bad[0])]} vs {after.weights[tuple(bad[0])]}"
     return after.weights, trace
@@ -194,5 +194,5 @@ def test_shapes_out_of_range_are_refused(hn):
     z = np.zeros(64, np.int64)
     p = z.ctypes.data
     for T, L, F in ((0, 4, 10), (9, 4, 10), (4, 0, 10), (4, 7, 10), (4, 4, 17)):
-        assert hn.ntuple_check_evaluate(p, 1, T, L, F, p, p, p, p, p, p, p) == -1
-    assert hn.ntuple_check_update(p, 1, p, 41, 4, 4, p, p) == -1
+        assert hn.ntuple_check_evaluate(p, 1, raw_desc(T, L, F), p, p, p, p, p, p) == -1
+    assert hn.ntuple_check_update(p, 1, p, 41, 0, raw_desc(4, 4), p, p, p) == -1

@@ -1,5 +1,5 @@
 """CPU: the n-tuple expectimax of g2048_device.h -- the header the kernels are compiled from -- built for the host
-(tests/host_ntuple_search/ntuple_search_check.cpp, g++) and compared bit for bit with the pure-Python reference
+(tests/host_ntuple/ntuple_check.cpp, g++) and compared bit for bit with the pure-Python reference
 tests/ntuple_search_ref.py.  Every named case shows from the reference's own trace (never from the code under test) that
 its input reaches the edge it names."""
 import numpy as np
@@ -8,12 +8,13 @@ import pytest
 import ntuple_ref as ref
 import ntuple_search_ref as sref
 from analysis_helpers import ONE_LEGAL, TERMINAL, mid_game, mixed_boards, random_boards
-from ntuple_helpers import TUPLES_2x6, TUPLES_8x4, TUPLES_8x6, TUPLES_17x4, random_net
-from ntuple_search_helpers import PAIR_ONLY, WIDE_FANS, assert_search_equal, host_search, host_split, load_host_ntuple_search
+from ntuple_helpers import (TUPLES_2x6, TUPLES_8x4, TUPLES_8x6, TUPLES_17x4, host_search, host_split, load_host_ntuple, random_net,
+                            raw_desc)
+from ntuple_search_helpers import PAIR_ONLY, WIDE_FANS, assert_search_equal
 
 @pytest.fixture(scope="module")
 def hs():
-    return load_host_ntuple_search()
+    return load_host_ntuple()
 
 
 def check(lib, boards, depth, net):
@@ -27,7 +28,7 @@ def check(lib, boards, depth, net):
 def test_floor_div(hs):
     """The one named helper: floors where C++ truncates."""
     for a, b in ((-7, 10), (-10, 10), (-11, 10), (7, 10), (0, 150), (-1, 150), (-(1 << 57) - 1, 150), ((1 << 57) + 1, 150), (-149, 150)):
-        assert hs.ntuple_search_check_floor_div(a, b) == a // b, (a, b)
+        assert hs.ntuple_check_floor_div(a, b) == a // b, (a, b)
 
 
 @pytest.mark.parametrize("tuples", [TUPLES_17x4, TUPLES_2x6], ids=["17x4", "2x6"])
@@ -164,4 +165,4 @@ def test_arguments_out_of_range_are_refused(hs):
     z = np.zeros(64, np.int64)
     p = z.ctypes.data
     for depth, T, L, F in ((0, 4, 4, 10), (3, 4, 4, 10), (1, 0, 4, 10), (1, 9, 4, 10), (1, 4, 7, 10), (1, 4, 4, 17)):
-        assert hs.ntuple_search_check_boards(p, 1, depth, T, L, F, p, p, p, p) == -1
+        assert hs.ntuple_check_search(p, 1, depth, raw_desc(T, L, F), p, p, p) == -1

@@ -1,4 +1,4 @@
-"""CPU: the multi-stage n-tuple code of g2048_device.h compiled for the host (tests/host_ntuple/ntuple_staged_check.cpp)
+"""CPU: the multi-stage n-tuple code of g2048_device.h compiled for the host (tests/host_ntuple/ntuple_check.cpp)
 equals the pure-Python reference (tests/ntuple_staged_ref.py) bit for bit -- mask, stage, evaluate, values, the TD(0), TC and
 trace updates and the depth-1..2 search -- S = 1 equals the unstaged host build, the library refuses a bad staged
 descriptor before it touches a device, and the Python layer checks ``stages=``, ``stage_mask`` and ``promote``.  Every test
@@ -12,11 +12,10 @@ import __graft_entry__ as ge
 import ntuple_ref as ref
 import ntuple_staged_ref as sref
 import ntuple_trace_ref as tref
-from ntuple_helpers import TUPLES_17x4, TUPLES_8x4, host_evaluate as host_evaluate_1, host_update as host_update_1
-from ntuple_helpers import host_values as host_values_1, load_host_ntuple, assert_eval_equal
-from ntuple_staged_helpers import (LOW_THR, THR_8, host_base, host_evaluate, host_mask, host_search, host_stage, host_trace_update,
-                                   host_update, host_values, load_host_ntuple_staged, preload_tc, small_boards, with_deficit_bits,
-                                   depth2_boards, sparse_boards, ONE_TUPLE)
+from ntuple_helpers import (TUPLES_17x4, TUPLES_8x4, assert_eval_equal, host_base, host_evaluate, host_mask, host_search, host_stage,
+                            host_trace_update, host_update, host_values, load_host_ntuple)
+from ntuple_staged_helpers import (LOW_THR, THR_8, preload_tc, small_boards, with_deficit_bits, depth2_boards, sparse_boards,
+                                   ONE_TUPLE)
 from ntuple_tc_helpers import assert_tables_equal
 from ntuple_trace_helpers import trace_deltas
 
@@ -25,7 +24,7 @@ N = 100
 
 @pytest.fixture(scope="module")
 def hl():
-    return load_host_ntuple_staged()
+    return load_host_ntuple()
 
 
 @pytest.fixture(scope="module")
@@ -153,14 +152,13 @@ def test_trace_updates(hl, net, H):
 
 def test_one_stage_is_the_unstaged_network(hl, boards):
     """S = 1: the same bits as the unstaged host build and the unstaged reference."""
-    h1 = load_host_ntuple()
     one = sref.random_net(TUPLES_8x4[:6], (), 41)
     plain = ref.Net(one.tuples, one.frac_bits, one.weights[0])
-    assert_eval_equal(host_evaluate(hl, boards, one), host_evaluate_1(h1, boards, plain), boards, "S = 1")
+    assert_eval_equal(host_evaluate(hl, boards, one), host_evaluate(hl, boards, plain), boards, "S = 1")
     assert_eval_equal(host_evaluate(hl, boards, one), ref.evaluate_batch(boards, plain), boards, "S = 1 vs reference")
-    assert np.array_equal(host_values(hl, boards, one), host_values_1(h1, boards, plain))
+    assert np.array_equal(host_values(hl, boards, one), host_values(hl, boards, plain))
     deltas = trace_deltas(N, 42)
-    assert np.array_equal(host_update(hl, boards, deltas, 2, 0, one)[0][0], host_update_1(h1, boards, deltas, 2, plain))
+    assert np.array_equal(host_update(hl, boards, deltas, 2, 0, one)[0][0], host_update(hl, boards, deltas, 2, 0, plain)[0])
     assert not host_base(hl, boards, one).any()
 
 

@@ -1,5 +1,5 @@
 """CPU: the temporal-coherence code of g2048_device.h -- the header the kernels are compiled from -- built for the host
-(tests/host_ntuple_tc/ntuple_tc_check.cpp, g++) and compared bit for bit with the pure-Python reference
+(tests/host_ntuple/ntuple_check.cpp, g++) and compared bit for bit with the pure-Python reference
 tests/ntuple_tc_ref.py.  Every test shows from the reference's own trace (never from the code under test) that its input
 reaches the edge it names."""
 import random
@@ -10,8 +10,8 @@ import pytest
 import ntuple_ref as ref
 import ntuple_tc_ref as tcref
 from analysis_helpers import random_boards, trajectory_boards
-from ntuple_helpers import TUPLES_17x4, random_net
-from ntuple_tc_helpers import EDGE_PAIRS, assert_tables_equal, host_tc_update, load_host_ntuple_tc, preload
+from ntuple_helpers import TUPLES_17x4, host_update, load_host_ntuple, random_net, raw_desc
+from ntuple_tc_helpers import EDGE_PAIRS, assert_tables_equal, preload
 
 INT32_MAX, INT32_MIN = (1 << 31) - 1, -(1 << 31)
 INT64_MAX, INT64_MIN = (1 << 63) - 1, -(1 << 63)
@@ -20,14 +20,14 @@ U64 = (1 << 64) - 1
 
 @pytest.fixture(scope="module")
 def ht():
-    return load_host_ntuple_tc()
+    return load_host_ntuple()
 
 
 def check_update(lib, boards, deltas, lr_shift, phases, net, tc):
     """host == reference for one update; returns (the reference's net, tc and trace)."""
     rnet, rtc, trace = net.copy(), tc.copy(), {}
     tcref.tc_update(rnet, rtc, boards, deltas, lr_shift, phases, trace)
-    assert_tables_equal(host_tc_update(lib, boards, deltas, lr_shift, phases, net, tc), (rnet.weights, rtc.err, rtc.mag_i64()))
+    assert_tables_equal(host_update(lib, boards, deltas, lr_shift, phases, net, tc), (rnet.weights, rtc.err, rtc.mag_i64()))
     return rnet, rtc, trace
 
 
@@ -48,7 +48,7 @@ def test_rate_edges(ht):
     for name, pairs in table.items():
         trace = {}
         for e, a in pairs:
-            assert ht.ntuple_tc_check_rate(e, a) == tcref.rate(e, a, trace), (name, e, a)
+            assert ht.ntuple_check_tc_rate(e, a) == tcref.rate(e, a, trace), (name, e, a)
         if name == "never updated":
             assert trace["rate1"] == len(pairs) and "k" not in trace
         elif name == "E = 0":
@@ -75,7 +75,7 @@ def test_rate_random_pairs(ht):
         e = min(e, 1 << 63)
         e = -e if (e == 1 << 63 or rng.randrange(2)) else e
         assert a.bit_length() == bits
-        assert ht.ntuple_tc_check_rate(e, a) == tcref.rate(e, a, trace), (e, a)
+        assert ht.ntuple_check_tc_rate(e, a) == tcref.rate(e, a, trace), (e, a)
     assert trace["k"] > n // 3 and trace["clamp_m"] > 100 and trace["rate1"] > 1000 and trace["rate0"] > 0
 
 
@@ -83,10 +83,10 @@ def test_rate_small_divisors_exhaustive(ht):
     """Every (m, A) with A <= 300, and every m for a few A near powers of two: the quotient's correction step."""
     for a in range(1, 301):
         for m in range(0, a + 1):
-            assert ht.ntuple_tc_check_rate(m, a) == (m << 16) // a, (m, a)
+            assert ht.ntuple_check_tc_rate(m, a) == (m << 16) // a, (m, a)
     for a in (65535, 65536, 65537, (1 << 24) - 1, (1 << 24) + 1, (1 << 32) - 1, (1 << 32) - 65535):
         for m in list(range(0, 2000)) + list(range(a - 2000, a + 1)) + list(range(a // 2 - 1000, a // 2 + 1000)):
-            assert ht.ntuple_tc_check_rate(-m, a) == (m << 16) // a, (m, a)
+            assert ht.ntuple_check_tc_rate(-m, a) == (m << 16) // a, (m, a)
 
 
 def test_step_edges(ht):
@@ -94,7 +94,7 @@ def test_step_edges(ht):
              for r in (0, 1, 32768, 65535, 65536) for s in (0, 5, 40)]
     trace = {}
     for d, r, s in cases:
-        assert ht.ntuple_tc_check_step(d, r, s) == tcref.step(d, r, s, trace), (d, r, s)
+        assert ht.ntuple_check_tc_step(d, r, s) == tcref.step(d, r, s, trace), (d, r, s)
     assert trace["sat"] > 0
     # the clamp: 2^40 + 1 and INT64_MAX step as 2^40 does
     assert tcref.step((1 << 40) + 1, 65536, 10) == tcref.step(INT64_MAX, 65536, 10) == tcref.step(1 << 40, 65536, 10) == 1 << 30
@@ -103,13 +103,13 @@ def test_step_edges(ht):
     assert tcref.step(1 << 31, 65536, 0) == INT32_MAX and tcref.step(-(1 << 31), 65536, 0) == INT32_MIN == -(1 << 31)
     assert tcref.step((1 << 31) - 1, 65536, 0) == INT32_MAX and tcref.step(-(1 << 31) - 1, 65536, 0) == INT32_MIN
     for d in (1 << 31, -(1 << 31), (1 << 31) - 1, -(1 << 31) - 1, 1 << 40, -(1 << 40)):
-        assert ht.ntuple_tc_check_step(d, 65536, 0) == tcref.step(d, 65536, 0)
+        assert ht.ntuple_check_tc_step(d, 65536, 0) == tcref.step(d, 65536, 0)
     # negative products floor: -1 * 1 >> 16 is -1, not 0; the positive twin is 0
     assert tcref.step(-1, 1, 0) == -1 and tcref.step(1, 1, 0) == 0 and tcref.step(-1, 65536, 40) == -1
-    assert ht.ntuple_tc_check_step(-1, 1, 0) == -1 and ht.ntuple_tc_check_step(1, 1, 0) == 0 and ht.ntuple_tc_check_step(-1, 65536, 40) == -1
+    assert ht.ntuple_check_tc_step(-1, 1, 0) == -1 and ht.ntuple_check_tc_step(1, 1, 0) == 0 and ht.ntuple_check_tc_step(-1, 65536, 40) == -1
     # lr_shift 40: the largest product, 2^56, becomes 1
-    assert tcref.step(1 << 40, 65536, 40) == 1 == ht.ntuple_tc_check_step(1 << 40, 65536, 40)
-    assert all(tcref.step(0, r, s) == 0 == ht.ntuple_tc_check_step(0, r, s) for r in (0, 65536) for s in (0, 40))
+    assert tcref.step(1 << 40, 65536, 40) == 1 == ht.ntuple_check_tc_step(1 << 40, 65536, 40)
+    assert all(tcref.step(0, r, s) == 0 == ht.ntuple_check_tc_step(0, r, s) for r in (0, 65536) for s in (0, 40))
 
 
 BOARDS = np.concatenate([random_boards(40, 2), trajectory_boards(every=211)[:40]])
@@ -147,9 +147,9 @@ def test_phase_w_then_phase_a_is_phases_3(ht):
     net = random_net(TUPLES_17x4, 6, lo=-1000, hi=1000)
     tc = preload(net, 7, BOARDS[:4])
     deltas = edge_deltas(len(BOARDS), 8)
-    w3, e3, m3 = host_tc_update(ht, BOARDS, deltas, 5, 3, net, tc)
-    w1, e1, m1 = host_tc_update(ht, BOARDS, deltas, 5, 1, net, tc)
-    w2, e2, m2 = host_tc_update(ht, BOARDS, deltas, 5, 2, net, tc)
+    w3, e3, m3 = host_update(ht, BOARDS, deltas, 5, 3, net, tc)
+    w1, e1, m1 = host_update(ht, BOARDS, deltas, 5, 1, net, tc)
+    w2, e2, m2 = host_update(ht, BOARDS, deltas, 5, 2, net, tc)
     assert np.array_equal(w1, w3) and np.array_equal(e2, e3) and np.array_equal(m2, m3)
     assert np.array_equal(w2, net.weights) and np.array_equal(e1, tc.err) and np.array_equal(m1, tc.mag_i64())
 
@@ -196,11 +196,11 @@ def test_out_of_range_arguments_are_refused(ht):
     z = np.zeros(64, np.int64)
     p = z.ctypes.data
     for T, L, shift, phases in ((0, 4, 3, 3), (9, 4, 3, 3), (4, 0, 3, 3), (4, 7, 3, 3), (4, 4, 41, 3), (4, 4, 3, 0), (4, 4, 3, 4)):
-        assert ht.ntuple_tc_check_update(p, 1, p, shift, phases, T, L, p, p, p, p) == -1
+        assert ht.ntuple_check_tc_update(p, 1, p, shift, phases, raw_desc(T, L), p, p, p) == -1
 
 
 def test_edge_pairs_cover_the_rate(ht):
     trace = {}
     for e, a in EDGE_PAIRS:
-        assert ht.ntuple_tc_check_rate(e, a) == tcref.rate(e, a, trace)
+        assert ht.ntuple_check_tc_rate(e, a) == tcref.rate(e, a, trace)
     assert trace["k"] >= 6 and trace["rate0"] >= 3 and trace["rate1"] >= 6 and trace["clamp_m"] >= 3

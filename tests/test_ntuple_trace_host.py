@@ -1,5 +1,5 @@
 """CPU: the n-tuple trace code of g2048_device.h -- the header the kernels are compiled from -- built for the host
-(tests/host_ntuple_trace/ntuple_trace_check.cpp, g++) and compared bit for bit with the pure-Python reference
+(tests/host_ntuple/ntuple_check.cpp, g++) and compared bit for bit with the pure-Python reference
 tests/ntuple_trace_ref.py.  Every test shows from the reference's own trace (never from the code under test) that its input
 reaches the edge it names."""
 import numpy as np
@@ -9,17 +9,16 @@ import ntuple_ref as ref
 import ntuple_tc_ref as tcref
 import ntuple_trace_ref as tref
 from analysis_helpers import mixed_boards
-from ntuple_helpers import TUPLES_17x4, random_net
+from ntuple_helpers import TUPLES_17x4, host_push, host_trace_update, host_update, load_host_ntuple, random_net, raw_desc
 from ntuple_tc_helpers import assert_tables_equal, preload
-from ntuple_trace_helpers import (INT64_MAX, INT64_MIN, host_push, host_trace_update, load_host_ntuple_trace, push_inputs,
-                                  trace_deltas)
+from ntuple_trace_helpers import INT64_MAX, INT64_MIN, push_inputs, trace_deltas
 
 LAMS = (0, 1, 32768, 65535, 65536)
 
 
 @pytest.fixture(scope="module")
 def ht():
-    return load_host_ntuple_trace()
+    return load_host_ntuple()
 
 
 def filled(n, H, lam, pushes, seed, trace=None, lib=None):
@@ -55,9 +54,9 @@ def test_push_len_every_byte(ht):
         for old in range(256):
             for term in (0, 1, 0xff):
                 want = tref.push_len(old, H, term, trace)
-                assert ht.ntuple_trace_check_push_len(old, H, term) == want, (old, H, term)
+                assert ht.ntuple_check_push_len(old, H, term) == want, (old, H, term)
                 assert 1 <= (want & 0x7f) <= H and bool(want & 0x80) == bool(term)
-            assert ht.ntuple_trace_check_len(old, H) == min(old & 0x7f, H)
+            assert ht.ntuple_check_len(old, H) == min(old & 0x7f, H)
     assert trace["garbage"] > 0 and trace["ended"] > 0 and trace["saturate"] > 0
     assert tref.push_len(0x7f, 4, 0) == 4 and tref.push_len(0xff, 4, 0) == 1 and tref.push_len(0xff, 4, 1) == 0x81
     assert tref.push_len(0x83, 8, 0) == 1 and tref.push_len(3, 8, 0) == 4 and tref.push_len(8, 8, 1) == 0x88
@@ -102,7 +101,7 @@ def test_garbage_len_bytes(ht):
 def test_decay_for_every_k(ht):
     for lam in LAMS + (2, 255, 256, 257, 40000, 65534):
         for k in range(8):
-            assert ht.ntuple_trace_check_decay(lam, k) == tref.decay(lam, k), (lam, k)
+            assert ht.ntuple_check_decay(lam, k) == tref.decay(lam, k), (lam, k)
     assert [tref.decay(65536, k) for k in range(8)] == [65536] * 8
     assert [tref.decay(0, k) for k in range(4)] == [65536, 0, 0, 0]
     assert [tref.decay(1, k) for k in range(4)] == [65536, 1, 0, 0]
@@ -116,7 +115,7 @@ def test_dk_edges(ht):
     for d in deltas:
         for lam in LAMS:
             for k in range(8):
-                assert ht.ntuple_trace_check_dk(d, lam, k) == tref.d_k(d, lam, k), (d, lam, k)
+                assert ht.ntuple_check_dk(d, lam, k) == tref.d_k(d, lam, k), (d, lam, k)
     # d_k reaches 0 for k > 0 while d_0 != 0
     assert [tref.d_k(3, 32768, k) for k in range(3)] == [3, 1, 0] and tref.d_k(5, 0, 1) == 0 and tref.d_k(5, 1, 1) == 0
     # the negative floor: d = -1 stays -1 as long as p_k > 0, and -3 decays to -1, not to 0
@@ -131,7 +130,7 @@ def test_split_is_k_major(ht):
     for n, H in ((1, 1), (1, 8), (63, 2), (65, 8), (257, 3), ((1 << 32) - 256, 8), ((1 << 25) + 3, 8)):
         for item in {0, 1, n - 1, n, n + 1, 2 * n - 1, H * n - 1, (H - 1) * n, (H // 2) * n + n // 2}:
             if item < H * n:
-                assert ht.ntuple_trace_check_split(item, n, H) == (item // n) << 32 | item % n, (item, n, H)
+                assert ht.ntuple_check_split(item, n, H) == (item // n) << 32 | item % n, (item, n, H)
 
 
 @pytest.mark.parametrize("mode", [0, 1, 2, 3])
@@ -227,6 +226,55 @@ def test_same_entry_from_two_slots_counts_twice(ht):
     assert rnet.weights[0, 0] == H * 8 * (1000 >> 3)
 
 
+def _one_slot_history(boards):
+    """A trace of depth 1 that holds ``boards``: the items of its update are the boards themselves."""
+    tr = tref.Trace(len(boards), 1, 32768)
+    tref.push(tr, boards, np.zeros(len(boards), np.int64), np.zeros(len(boards), np.int64), np.zeros(len(boards), np.uint8))
+    assert tr.slot == 0 and (tr.len == 1).all() and np.array_equal(tr.hist[0], boards)
+    return tr
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2, 3])
+def test_board_items_and_one_slot_trace_items_give_the_same_tables(ht, mode):
+    """The update entry point over the board source and over the trace source with H = 1: the same per-item operations
+    on the same boards, so all three tables agree as long as no delta passes the clamp."""
+    n = 64
+    boards = mixed_boards(n, 81)
+    rng = np.random.default_rng(82)
+    deltas = rng.integers(-(1 << 20), 1 << 20, n) << rng.integers(0, 21, n)
+    deltas[::11] = 0
+    deltas[1:5] = [1 << 40, -(1 << 40), 1, -1]
+    assert np.abs(deltas).max() == 1 << 40 and (deltas < 0).any() and (deltas > 0).any() and (deltas == 0).sum() >= 6
+    net = random_net(TUPLES_17x4, 83, lo=-(1 << 30), hi=1 << 30)
+    tc = preload(net, 84, boards[:8]) if mode else None
+    tr = _one_slot_history(boards)
+    for lr_shift in (0, 6):
+        got_boards = host_update(ht, boards, deltas, lr_shift, mode, net, tc)
+        got_trace = host_trace_update(ht, tr, deltas, lr_shift, mode, net, tc)
+        assert_tables_equal(got_boards, got_trace)
+        assert (got_boards[0] != net.weights).any() == (mode != 2)
+
+
+def test_only_the_plain_td_form_is_unclamped(ht):
+    """Past 2^40 the two sources differ in mode 0, as the definition says: the board source shifts delta as it is, the
+    trace source d_0 = clamp(delta).  Each equals its Python reference."""
+    n = 64
+    boards = mixed_boards(n, 85)
+    deltas = np.random.default_rng(86).integers(-(1 << 30), 1 << 30, n)
+    deltas[[3, 9, 20, 41]] = [(1 << 40) + 1, -(1 << 45), tcref.INT64_MAX, tcref.INT64_MIN]
+    assert (np.abs(deltas.astype(object)) > 1 << 40).sum() == 4
+    net = random_net(TUPLES_17x4, 87, lo=-1000, hi=1000)
+    tr = _one_slot_history(boards)
+    lr_shift = 12                                                        # 2^45 >> 12 does not saturate: the clamp shows
+    got_boards = host_update(ht, boards, deltas, lr_shift, 0, net)[0]
+    got_trace = host_trace_update(ht, tr, deltas, lr_shift, 0, net)[0]
+    one, two = net.copy(), net.copy()
+    ref.update(one, boards, deltas, lr_shift)
+    tref.trace_update(two, tr, deltas, lr_shift)
+    assert (got_boards != got_trace).any()
+    assert_tables_equal((got_boards, got_trace), (one.weights, two.weights), names=("board source", "trace source"))
+
+
 def test_out_of_range_arguments_are_refused(ht):
     z = np.zeros(64, np.int64)
     p = z.ctypes.data
@@ -234,9 +282,9 @@ def test_out_of_range_arguments_are_refused(ht):
     for bad in (dict(T=0), dict(T=9), dict(L=0), dict(L=7), dict(shift=41), dict(mode=4), dict(H=0), dict(H=9), dict(lam=65537),
                 dict(slot=4)):
         a = dict(ok, **bad)
-        assert ht.ntuple_trace_check_update(1, p, a["shift"], a["mode"], a["T"], a["L"], p, p, p, p, a["H"], a["lam"], p, p, a["slot"]) == -1
-    assert ht.ntuple_trace_check_push(p, p, p, p, 1, 0, p, p, 0, p) == -1 and ht.ntuple_trace_check_push(p, p, p, p, 1, 9, p, p, 0, p) == -1
-    assert ht.ntuple_trace_check_push(p, p, p, p, 1, 4, p, p, 4, p) == -1
+        assert ht.ntuple_check_trace_update(1, p, a["shift"], a["mode"], raw_desc(a["T"], a["L"]), p, p, p, a["H"], a["lam"], p, p, a["slot"]) == -1
+    assert ht.ntuple_check_push(p, p, p, p, 1, 0, p, p, 0, p) == -1 and ht.ntuple_check_push(p, p, p, p, 1, 9, p, p, 0, p) == -1
+    assert ht.ntuple_check_push(p, p, p, p, 1, 4, p, p, 4, p) == -1
 
 
 @pytest.mark.parametrize("H, lam", [(1, 32768), (4, 32768), (8, 65536)])

@@ -72,8 +72,8 @@ def isa_rows():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_stats.py"), "ntuple_"], capture_output=True, text=True).stdout
     lines, keep = out.splitlines(), []
     wanted = ("ntuple_eval_kernel<4u, true>", "ntuple_eval_kernel<5u, true>", "ntuple_eval_kernel<4u, false>",
-              "ntuple_eval_kernel<5u, false>", "ntuple_values_kernel<4u>", "ntuple_values_kernel<5u>", "ntuple_update_kernel<4u>",
-              "ntuple_update_kernel<5u>", "ntuple_eval_kernel<8u, true>")
+              "ntuple_eval_kernel<5u, false>", "ntuple_values_kernel<4u>", "ntuple_values_kernel<5u>", "ntuple_update_kernel<4u, g2048::NtupleShape, g2048::NtupleBoardItems>",
+              "ntuple_update_kernel<5u, g2048::NtupleShape, g2048::NtupleBoardItems>", "ntuple_eval_kernel<8u, true>")
     for i, line in enumerate(lines):
         if any(w in line for w in wanted):
             keep += [line.split("(")[0].replace("void g2048::", "")] + lines[i + 1:i + 3]
