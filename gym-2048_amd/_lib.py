@@ -144,6 +144,21 @@ class NTupleTraceC(C.Structure):
     ]
 
 
+class CarouselC(C.Structure):
+    """g2048_carousel (include/g2048.h): S, the thresholds, the ring size, the seed and the device state of a carousel."""
+    _fields_ = [
+        ("n_stages", C.c_uint32),
+        ("thresholds", C.c_uint16 * 7),
+        ("capacity", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("pool", C.c_void_p),
+        ("count", C.c_void_p),
+        ("seen", C.c_void_p),
+        ("episodes", C.c_void_p),
+        ("scratch", C.c_void_p),
+    ]
+
+
 class Stats(C.Structure):
     """g2048_stats (include/g2048.h)."""
     _fields_ = [
@@ -227,6 +242,9 @@ SIGNATURES = {
     "g2048_ntuple_staged_tc_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleStagedNetC),
                                                      C.POINTER(NTupleTCC), C.POINTER(NTupleTraceC), _u32, _S]),
     "g2048_ntuple_stage_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.c_void_p, _S]),
+    "g2048_carousel_scratch_bytes": (_u64, [_u64]),
+    "g2048_carousel_step": (C.c_int, [_E, C.POINTER(CarouselC), C.c_void_p, _S]),
+    "g2048_carousel_step_plain": (C.c_int, [C.c_void_p, _u64, _u64, C.c_void_p, C.POINTER(CarouselC), _S]),
     "g2048_add_tile": (C.c_int, [_E, _u32, _S]),
     "g2048_fill_random_actions": (C.c_int, [_E, _u64, _u32, C.c_void_p, _S]),
     "g2048_onehot": (C.c_int, [_E, C.c_void_p, _i32, _S]),

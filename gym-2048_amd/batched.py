@@ -23,6 +23,7 @@ from .analysis import (MC_DEFAULT_MAX_STEPS, Afterstates, MCSearch, Search, Sear
 from .ntuple import NTupleEval, NTupleNet, NTupleSearch, TUPLES, stage_mask, td_step, train, _eval_io  # noqa: F401
 from .ntuple import NTupleTC, tc_step, tc_train, tc_update  # noqa: F401
 from .ntuple import NTupleTrace, tcl_step, tcl_train, tdl_evaluate, tdl_step, tdl_train  # noqa: F401
+from .ntuple import Carousel  # noqa: F401
 from .ntuple import _search_io as _ntuple_search_io
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}

@@ -1276,6 +1276,19 @@ static int ntuple_net(const g2048_ntuple_net *net, g2048::NtupleNet *out, bool n
     return G2048_OK;
 }
 
+// the first n_stages - 1 thresholds of a staged network or a carousel: non-zero and strictly ascending
+static int stage_thresholds(uint32_t n_stages, const uint16_t *thresholds)
+{
+    for (uint32_t j = 0; j + 1 < n_stages; ++j) {
+        if (thresholds[j] == 0)
+            return fail(G2048_ERR_INVALID, "thresholds[%u]=0: a stage threshold is 1..65535", j);
+        if (j > 0 && thresholds[j] <= thresholds[j - 1])
+            return fail(G2048_ERR_INVALID, "thresholds[%u]=%u: thresholds must be strictly ascending (thresholds[%u]=%u)", j,
+                        thresholds[j], j - 1, thresholds[j - 1]);
+    }
+    return G2048_OK;
+}
+
 // g2048_ntuple_staged_net -> the same network with its stages: every ntuple entry point below is written once, for either
 // descriptor, and reaches the same launchers and kernels (S = 1 is the unstaged network).
 static int ntuple_net(const g2048_ntuple_staged_net *net, g2048::NtupleNet *out, bool need_weights = true)
@@ -1284,13 +1297,8 @@ static int ntuple_net(const g2048_ntuple_staged_net *net, g2048::NtupleNet *out,
         return fail(G2048_ERR_INVALID, "net is NULL");
     if (net->n_stages < 1 || net->n_stages > G2048_NTUPLE_MAX_STAGES)
         return fail(G2048_ERR_INVALID, "n_stages=%u: need 1 <= n_stages <= %d", net->n_stages, G2048_NTUPLE_MAX_STAGES);
-    for (uint32_t j = 0; j + 1 < net->n_stages; ++j) {
-        if (net->thresholds[j] == 0)
-            return fail(G2048_ERR_INVALID, "thresholds[%u]=0: a stage threshold is 1..65535", j);
-        if (j > 0 && net->thresholds[j] <= net->thresholds[j - 1])
-            return fail(G2048_ERR_INVALID, "thresholds[%u]=%u: thresholds must be strictly ascending (thresholds[%u]=%u)", j,
-                        net->thresholds[j], j - 1, net->thresholds[j - 1]);
-    }
+    if (int rc = stage_thresholds(net->n_stages, net->thresholds))
+        return rc;
     if (int rc = ntuple_net(&net->net, out, need_weights))
         return rc;
     out->n_stages = net->n_stages;
@@ -1686,6 +1694,87 @@ int g2048_ntuple_staged_tc_trace_update(uint64_t n, const int64_t *delta, uint32
                                         uint32_t slot, void *stream)
 {
     return ntuple_tc_trace_update(n, delta, lr_shift, phases, net, tc, tr, slot, stream);
+}
+
+// g2048_carousel and the records of a call -> the launcher's arguments, or G2048_ERR_INVALID (before any HIP call: works
+// without a device)
+static int carousel_args(const g2048_carousel *c, uint8_t *records, uint64_t n, uint64_t index_offset, const uint8_t *terminated,
+                         g2048::CarouselArgs *a)
+{
+    if (!c)
+        return fail(G2048_ERR_INVALID, "carousel is NULL");
+    if (c->n_stages < 2 || c->n_stages > G2048_NTUPLE_MAX_STAGES)
+        return fail(G2048_ERR_INVALID, "n_stages=%u: a carousel needs 2 <= n_stages <= %d", c->n_stages, G2048_NTUPLE_MAX_STAGES);
+    if (int rc = stage_thresholds(c->n_stages, c->thresholds))
+        return rc;
+    if (c->capacity < 1 || c->capacity > G2048_CAROUSEL_MAX_CAPACITY)
+        return fail(G2048_ERR_INVALID, "capacity=%u: need 1 <= capacity <= %d", c->capacity, G2048_CAROUSEL_MAX_CAPACITY);
+    if (!c->pool)
+        return fail(G2048_ERR_INVALID, "carousel pool is NULL");
+    if (!c->count)
+        return fail(G2048_ERR_INVALID, "carousel count is NULL");
+    if (!c->seen)
+        return fail(G2048_ERR_INVALID, "carousel seen is NULL");
+    if (!c->episodes)
+        return fail(G2048_ERR_INVALID, "carousel episodes is NULL");
+    if (!c->scratch)
+        return fail(G2048_ERR_INVALID, "carousel scratch is NULL");
+    if (!records)
+        return fail(G2048_ERR_INVALID, "records is NULL");
+    if (!terminated)
+        return fail(G2048_ERR_INVALID, "terminated is NULL");
+    if ((reinterpret_cast<uintptr_t>(c->pool) | reinterpret_cast<uintptr_t>(records)) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: carousel pool and records need 16 bytes");
+    if (reinterpret_cast<uintptr_t>(c->count) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: carousel count needs 8 bytes");
+    if ((reinterpret_cast<uintptr_t>(c->episodes) | reinterpret_cast<uintptr_t>(c->scratch)) & 3u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: carousel episodes and scratch need 4 bytes");
+    if (n == 0 || n > 0xffffff00ull) // (the cap of g2048_create)
+        return fail(G2048_ERR_INVALID, "n=%llu: need 1 <= n <= 2^32 - 256", (unsigned long long)n);
+    if (index_offset > 0x100000000ull || index_offset + n > 0x100000000ull)
+        return fail(G2048_ERR_INVALID, "index_offset=%llu, n=%llu: need index_offset + n <= 2^32", (unsigned long long)index_offset,
+                    (unsigned long long)n);
+    *a = g2048::CarouselArgs{};
+    a->records = reinterpret_cast<uint4 *>(records);
+    a->terminated = terminated;
+    a->n = static_cast<uint32_t>(n);
+    a->index_offset = static_cast<uint32_t>(index_offset);
+    a->n_stages = c->n_stages;
+    a->capacity = c->capacity;
+    for (uint32_t j = 0; j + 1 < c->n_stages; ++j)
+        a->thresholds[j] = c->thresholds[j];
+    a->seed_lo = static_cast<uint32_t>(c->seed);
+    a->seed_hi = static_cast<uint32_t>(c->seed >> 32);
+    a->pool = reinterpret_cast<uint4 *>(c->pool);
+    a->count = c->count;
+    a->seen = c->seen;
+    a->episodes = c->episodes;
+    a->scratch = static_cast<uint32_t *>(c->scratch);
+    return G2048_OK;
+}
+
+uint64_t g2048_carousel_scratch_bytes(uint64_t n) { return n == 0 || n > 0xffffff00ull ? 0 : g2048::kCarouselScratchBytes; }
+
+int g2048_carousel_step(g2048_engine *e, const g2048_carousel *c, const uint8_t *terminated, void *stream)
+{
+    if (int rc = usable(e))
+        return rc;
+    g2048::CarouselArgs a;
+    if (int rc = carousel_args(c, reinterpret_cast<uint8_t *>(e->st.boards), e->n, e->board_offset, terminated, &a))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(g2048::launch_carousel_step(a, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_carousel_step_plain(uint8_t *records, uint64_t n, uint64_t index_offset, const uint8_t *terminated, const g2048_carousel *c,
+                              void *stream)
+{
+    g2048::CarouselArgs a;
+    if (int rc = carousel_args(c, records, n, index_offset, terminated, &a))
+        return rc;
+    G2048_HIP(g2048::launch_carousel_step(a, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
 }
 
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream)

@@ -1274,6 +1274,124 @@ G2048_DEV uint32_t ntuple_search_root(const Board &cells, const Shape &sh, uint3
     return root_key_action(best);
 }
 
+// ------------------------------------------------------------------- carousel shaping
+// Stage-balanced restarts for training a staged network (g2048_carousel_step, include/g2048.h, INTEGRATION.md §14;
+// Jaskowski 2017): every episode starts from an empty board, so the weight sets of the late stages see a vanishing share of
+// the updates.  The carousel remembers, per stage, the boards on which recent episodes ENTERED that stage, and starts new
+// episodes from them, cycling over the stages.  Notation of the staged block: stage(b) from thr[0..S-2], cell = byte & 0x1f
+// of an engine record.  State for n boards:
+//   pool      uint8 [S][C][16]  ring of C records per stage, copied verbatim (cells and packed score); row 0 is never used
+//   count     uint64 [S]        entries ever made into each stage
+//   seen      uint8 [n]         highest stage this episode has been in; 0xff = not yet known
+//   episodes  uint32 [n]        episodes this board has ended; wraps
+// One operation, carousel_step, after a step with auto-reset on; g = index_offset + i.  With pool / count AS THEY WERE BEFORE
+// THE CALL, for every board i:
+//   terminated[i] != 0 (the record is already the fresh auto-reset board):
+//       e = episodes[i];  episodes[i] = e + 1
+//       M = the largest k with count[k] > 0, else 0;   k = (g + e) mod (M + 1)           (the sum in 64 bits)
+//       k > 0 and count[k] > 0:   fill = min(count[k], C)
+//                                 w = Philox4x32-10(ctr = (e, g, k, 0), key = (seed_lo, seed_hi ^ kCarouselKeyTag))[0]
+//                                 j = (w * fill) >> 32;   record[i] = pool[k][j];   seen[i] = k
+//       otherwise:                the fresh board stays;  seen[i] = stage(record[i])
+//   terminated[i] == 0:  st = stage(record[i])
+//       seen[i] == 0xff:  seen[i] = st, nothing is recorded
+//       st > seen[i]:     board i is an ENTRY into stage st;  seen[i] = st
+//       otherwise nothing happens  (stage(b) is not monotone over a game: seen is a maximum, not the last stage)
+// Then the entries are recorded in ascending board index: of the m_k entries into stage k in this call, the one of rank r
+// (0-based among them) is stored at pool[k][(count[k] + r) mod C] when r >= m_k - C, and dropped otherwise; then
+// count[k] += m_k.  This is exactly the sequential loop over i = 0..n-1: the slots 0..min(count, C)-1 are the filled ones,
+// so j is a physical slot; no two surviving entries share a slot.  Nothing about lanes, waves or workgroups enters the
+// result: the rank is an ordered, batch-wide prefix count, not the arrival order at an atomic counter.
+// seen holds 0..S-1 or 0xff between calls.  (Inside a call the per-board pass marks an entry by setting bit 7 of seen, and
+// the scatter pass clears it: the mark is how the scatter pass finds the entries without reading the records again.)
+constexpr uint32_t kCarouselKeyTag = 0x43524F55u; // "CROU": separates the restart stream from the spawn stream (no tag) and
+                                                  // the Monte-Carlo stream (kMcKeyTag) under an equal seed
+constexpr uint32_t kCarouselMinStages = 2, kCarouselMaxCapacity = 65536; // = G2048_CAROUSEL_MAX_CAPACITY (g2048.h)
+constexpr uint32_t kCarouselUnknown = 0xffu, kCarouselEntryBit = 0x80u;
+
+// The thresholds alone, as NtupleStagedShape::thr holds them: the carousel reads no table, and a staged shape would bring its
+// 64 cell lists along as kernel arguments.
+struct CarouselStages {
+    uint32_t thr[kNtupleMaxStages - 1]; // thr[j], j < S - 1; kNtupleNoStage from there on
+};
+
+G2048_HOST_DEV CarouselStages carousel_stages(uint32_t n_stages, const uint16_t *thresholds)
+{
+    CarouselStages cs{};
+    for (uint32_t j = 0; j < kNtupleMaxStages - 1u; ++j)
+        cs.thr[j] = j + 1u < n_stages ? thresholds[j] : kNtupleNoStage;
+    return cs;
+}
+
+// stage(b) of an engine record (or of plain cells): ntuple_stage on the carousel's own thresholds
+G2048_DEV uint32_t carousel_stage(const Board &rec, const CarouselStages &cs)
+{
+    const uint32_t mask = ntuple_stage_mask(ntuple_pack(rec));
+    uint32_t stage = 0;
+    for (uint32_t j = 0; j < kNtupleMaxStages - 1u; ++j)
+        stage += mask >= cs.thr[j] ? 1u : 0u;
+    return stage;
+}
+
+// M: the largest k < S with count[k] > 0, else 0
+G2048_HOST_DEV uint32_t carousel_top_stage(const uint64_t *count, uint32_t n_stages)
+{
+    uint32_t top = 0;
+    for (uint32_t k = 1; k < n_stages; ++k)
+        top = count[k] > 0 ? k : top;
+    return top;
+}
+
+// k = (g + e) mod (M + 1) with the sum in 64 bits, formed from the two residues: M + 1 <= 8, nothing overflows
+G2048_HOST_DEV uint32_t carousel_stage_choice(uint32_t g, uint32_t e, uint32_t top)
+{
+    const uint32_t m = top + 1u;
+    return (g % m + e % m) % m;
+}
+
+// fill = min(count, C): the filled slots of a ring are 0..fill-1
+G2048_HOST_DEV uint32_t carousel_fill(uint64_t count, uint32_t capacity)
+{
+    return count < capacity ? static_cast<uint32_t>(count) : capacity;
+}
+
+// j, the slot a restart of (episode e, global board g) into stage k reads: uniform over 0..fill-1, fill >= 1
+G2048_DEV uint32_t carousel_sample(uint32_t e, uint32_t g, uint32_t k, uint32_t fill, uint32_t seed_lo, uint32_t seed_hi)
+{
+    return g2048_mulhi(philox4x32_10(e, g, k, 0u, seed_lo, seed_hi ^ kCarouselKeyTag).w[0], fill);
+}
+
+// The seen transition of a board whose episode goes on: the new seen byte, with kCarouselEntryBit set when the board is an
+// entry into stage st (the scatter pass clears the bit).  A byte that is neither 0xff nor below st is left as it is.
+G2048_HOST_DEV uint32_t carousel_seen_next(uint32_t seen, uint32_t st)
+{
+    if (seen == kCarouselUnknown)
+        return st;
+    return st > seen ? st | kCarouselEntryBit : seen;
+}
+
+// an entry mark left by carousel_seen_next
+G2048_HOST_DEV bool carousel_is_entry(uint32_t seen) { return (seen & kCarouselEntryBit) != 0u && seen != kCarouselUnknown; }
+
+// Does the entry of rank r among the m of its stage in this call survive (r >= m - C)?  r < m < 2^32.
+G2048_HOST_DEV bool carousel_survives(uint32_t r, uint32_t m, uint32_t capacity) { return static_cast<uint64_t>(r) + capacity >= m; }
+
+// count mod C, once per stage and call, so that the slot of an entry is 32-bit arithmetic
+G2048_HOST_DEV uint32_t carousel_count_mod(uint64_t count, uint32_t capacity) { return static_cast<uint32_t>(count % capacity); }
+
+// (count + r) mod C from count_mod = count mod C: both terms are below C <= 65536
+G2048_HOST_DEV uint32_t carousel_slot(uint32_t count_mod, uint32_t r, uint32_t capacity) { return (count_mod + r % capacity) % capacity; }
+
+// The workgroup ranges of the carousel kernels: workgroup w takes the boards [w * per, min(n, (w + 1) * per)), `per` a
+// multiple of `block` lanes, and there are at most `cap` workgroups -- contiguous ranges, so that the index order of the
+// entries is the order of (workgroup, chunk, wave, lane).
+G2048_HOST_DEV uint64_t carousel_range(uint64_t n, uint32_t block, uint32_t cap)
+{
+    const uint64_t blocks = (n + block - 1u) / block;
+    const uint64_t groups = blocks < cap ? blocks : cap;
+    return (blocks + groups - 1u) / groups * block; // n >= 1
+}
+
 // ------------------------------------------------------------------- the 16-byte board RECORD
 // What the engine keeps per board in HBM is ONE 16-byte record: bits [4:0] of byte j = exponent of
 // cell j (0..31), and the 24-bit SCORE DEFICIT d in the three spare bits [7:5] of bytes 8..15

@@ -161,6 +161,26 @@ hipError_t launch_ntuple_trace_update(uint32_t n, const int64_t *delta, uint32_t
 // phases as in launch_ntuple_tc_update: W, then A, a launch each
 hipError_t launch_ntuple_tc_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const NtupleNet &net,
                                          int64_t *err, int64_t *mag, const NtupleTrace &tr, uint32_t slot, hipStream_t s);
+// g2048_carousel_step: the carousel (g2048_carousel) and the records it works on, both checked by the caller
+struct CarouselArgs {
+    uint4 *records;            // [n] engine records, restarted in place
+    const uint8_t *terminated; // [n]
+    uint32_t n, index_offset;  // index_offset + n <= 2^32
+    uint32_t n_stages, capacity; // S in 2..8, C in 1..65536
+    uint16_t thresholds[7];    // the first S - 1: strictly ascending, >= 1
+    uint32_t seed_lo, seed_hi;
+    uint4 *pool;               // [S][C] records
+    uint64_t *count;           // [S]
+    uint8_t *seen;             // [n]
+    uint32_t *episodes;        // [n]
+    uint32_t *scratch;         // kCarouselScratchBytes
+};
+// The carousel's kernels give every workgroup a contiguous range of boards; the cap on workgroups bounds the scratch
+// (their entry counts per stage, the scanned counts, the totals and count mod C) whatever n is.
+constexpr uint32_t kCarouselMaxGroups = 1024;
+constexpr size_t kCarouselScratchBytes = (2 * 8 * kCarouselMaxGroups + 16) * sizeof(uint32_t);
+// three launches on s: restart (reads the pool), scan, scatter (writes the pool)
+hipError_t launch_carousel_step(const CarouselArgs &a, hipStream_t s);
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s);
 // numpy-RNG mode: every board's PCG64 generator, seeded as numpy seeds it, into the DeviceState::rng planes
 hipError_t launch_seed_numpy(uint64_t *planes, uint32_t n, uint64_t first_seed, hipStream_t s);

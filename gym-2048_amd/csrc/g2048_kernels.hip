@@ -1721,6 +1721,205 @@ __global__ void __launch_bounds__(kBlock) ntuple_trace_push_kernel(const uint4 *
     }
 }
 
+// ---------------------------------------------------------------------------- carousel shaping
+// g2048_carousel_step (the definition of g2048_device.h, "carousel shaping") is three launches on one stream; the launch
+// boundaries are the only synchronisation between workgroups -- no kernel here waits for another workgroup in any form.
+// Workgroup w takes the boards [w * per, (w + 1) * per) (carousel_range: at most kCarouselMaxGroups workgroups, whatever n),
+// in chunks of kBlock, so that ascending board index is the order of (workgroup, chunk, wave, lane).
+//   restart  per board: one 16-byte load; a terminated board reads episodes, count and the pool and stores the restarted
+//            record; a board that goes on computes its stage and updates seen, marking an entry with kCarouselEntryBit.  The
+//            pool and count are only read here, so every lane sees them as they were before the call.  Every workgroup
+//            leaves its entry count per stage in cnt[k][w].
+//   scan     one workgroup: prefix[k][w] = cnt[k][0] + .. + cnt[k][w-1], total[k], count_mod[k] = count[k] mod C, and then
+//            count[k] += total[k].
+//   scatter  a workgroup with entries reads seen again, clears the marks, recomputes every entry's rank -- prefix[k][w],
+//            the entries of the chunks and waves before it (LDS), the lanes before it (ballot) -- and stores the surviving
+//            records into the pool.  A call without entries, and a workgroup without, leaves at once.
+// Scratch (uint32): cnt[8][kCarouselMaxGroups] | prefix[8][kCarouselMaxGroups] | total[8] | count_mod[8].
+static_assert(kCarouselMaxGroups == 4u * kBlock, "carousel_scan_kernel scans four workgroup counts per lane");
+static_assert(kCarouselScratchBytes == (16u * kCarouselMaxGroups + 16u) * sizeof(uint32_t), "the carousel's scratch layout");
+constexpr uint32_t kCarouselWaves = kBlock / 64;
+
+struct CarouselParams {
+    uint4 *records;
+    const uint8_t *terminated;
+    uint4 *pool;
+    uint64_t *count;
+    uint8_t *seen;
+    uint32_t *episodes;
+    uint32_t *scratch;
+    CarouselStages cs;
+    uint32_t n, index_offset, n_stages, capacity, seed_lo, seed_hi;
+    uint64_t per; // boards per workgroup
+};
+
+__device__ __forceinline__ uint32_t *carousel_cnt(const CarouselParams &p, uint32_t k) { return p.scratch + k * kCarouselMaxGroups; }
+__device__ __forceinline__ uint32_t *carousel_prefix(const CarouselParams &p, uint32_t k)
+{
+    return p.scratch + (kNtupleMaxStages + k) * kCarouselMaxGroups;
+}
+__device__ __forceinline__ uint32_t *carousel_total(const CarouselParams &p) { return p.scratch + 2u * kNtupleMaxStages * kCarouselMaxGroups; }
+__device__ __forceinline__ uint32_t *carousel_count_mods(const CarouselParams &p) { return carousel_total(p) + kNtupleMaxStages; }
+
+// the set bits of a ballot below this lane
+__device__ __forceinline__ uint32_t lanes_below(uint64_t mask)
+{
+    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
+}
+
+__global__ void __launch_bounds__(kBlock) carousel_restart_kernel(const CarouselParams p)
+{
+    __shared__ uint32_t s_cnt[kCarouselWaves][kNtupleMaxStages];
+    const uint32_t wave = threadIdx.x / 64u, lane = threadIdx.x % 64u;
+    const uint64_t begin = blockIdx.x * p.per, end = begin + p.per < p.n ? begin + p.per : p.n;
+    const uint32_t top = carousel_top_stage(p.count, p.n_stages);
+    uint32_t wave_cnt[kNtupleMaxStages] = {}; // wave-uniform, statically indexed
+    for (uint64_t base = begin; base < end; base += kBlock) {
+        bool entry = false;
+        uint32_t st = 0;
+        if (base + threadIdx.x < end) {
+            const uint32_t i = static_cast<uint32_t>(base + threadIdx.x);
+            const Board rec = load_board(p.records, i);
+            if (p.terminated[i] != 0) {
+                const uint32_t e = p.episodes[i];
+                p.episodes[i] = e + 1u;
+                const uint32_t g = p.index_offset + i;
+                const uint32_t k = carousel_stage_choice(g, e, top);
+                const uint64_t made = k > 0u ? p.count[k] : 0ull;
+                uint32_t seen;
+                if (made > 0ull) {
+                    const uint32_t j = carousel_sample(e, g, k, carousel_fill(made, p.capacity), p.seed_lo, p.seed_hi);
+                    store_board(p.records, i, load_board(p.pool, k * p.capacity + j));
+                    seen = k;
+                } else {
+                    seen = carousel_stage(rec, p.cs);
+                }
+                p.seen[i] = static_cast<uint8_t>(seen);
+            } else {
+                st = carousel_stage(rec, p.cs);
+                const uint32_t old = p.seen[i], next = carousel_seen_next(old, st);
+                entry = next != old && (next & kCarouselEntryBit) != 0u;
+                if (next != old)
+                    p.seen[i] = static_cast<uint8_t>(next);
+            }
+        }
+        if (g2048_any(entry)) {
+#pragma unroll
+            for (uint32_t k = 1; k < kNtupleMaxStages; ++k)
+                wave_cnt[k] += static_cast<uint32_t>(__popcll(__builtin_amdgcn_ballot_w64(entry && st == k)));
+        }
+    }
+    if (lane == 0u) {
+#pragma unroll
+        for (uint32_t k = 0; k < kNtupleMaxStages; ++k)
+            s_cnt[wave][k] = wave_cnt[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kNtupleMaxStages) {
+        uint32_t sum = 0;
+        for (uint32_t w = 0; w < kCarouselWaves; ++w)
+            sum += s_cnt[w][threadIdx.x];
+        carousel_cnt(p, threadIdx.x)[blockIdx.x] = sum;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) carousel_scan_kernel(const CarouselParams p, uint32_t groups)
+{
+    __shared__ uint32_t s_wave[kCarouselWaves];
+    const uint32_t wave = threadIdx.x / 64u, lane = threadIdx.x % 64u;
+    for (uint32_t k = 1; k < p.n_stages; ++k) {
+        const uint32_t *cnt = carousel_cnt(p, k);
+        uint32_t *prefix = carousel_prefix(p, k);
+        uint32_t v[4], sum = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) {
+            const uint32_t w = 4u * threadIdx.x + j;
+            v[j] = w < groups ? cnt[w] : 0u; // (the scratch beyond `groups` is not this call's)
+            sum += v[j];
+        }
+        uint32_t incl = sum; // inclusive scan over the wave
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d);
+            incl += lane >= d ? up : 0u;
+        }
+        if (lane == 63u)
+            s_wave[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kCarouselWaves; ++w) {
+            before += w < wave ? s_wave[w] : 0u;
+            total += s_wave[w];
+        }
+        uint32_t run = before + incl - sum;
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) {
+            const uint32_t w = 4u * threadIdx.x + j;
+            if (w < groups)
+                prefix[w] = run;
+            run += v[j];
+        }
+        if (threadIdx.x == 0u) {
+            const uint64_t made = p.count[k];
+            carousel_total(p)[k] = total;
+            carousel_count_mods(p)[k] = carousel_count_mod(made, p.capacity);
+            p.count[k] = made + total;
+        }
+        __syncthreads(); // s_wave is written again for the next stage
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) carousel_scatter_kernel(const CarouselParams p)
+{
+    __shared__ uint32_t s_wave[kCarouselWaves][kNtupleMaxStages]; // the entries of each wave in this chunk
+    __shared__ uint32_t s_base[kNtupleMaxStages];                 // the entries before this chunk
+    const uint32_t *total = carousel_total(p), *count_mod = carousel_count_mods(p);
+    uint32_t any = 0, mine = 0;
+    for (uint32_t k = 1; k < p.n_stages; ++k) {
+        any |= total[k];
+        mine |= carousel_cnt(p, k)[blockIdx.x];
+    }
+    if (any == 0u || mine == 0u)
+        return; // (uniform over the workgroup: nobody is left at a barrier)
+    const uint32_t wave = threadIdx.x / 64u, lane = threadIdx.x % 64u;
+    const uint64_t begin = blockIdx.x * p.per, end = begin + p.per < p.n ? begin + p.per : p.n;
+    // lane k < 8 carries the running base of stage k
+    uint32_t base_k = threadIdx.x >= 1u && threadIdx.x < p.n_stages ? carousel_prefix(p, threadIdx.x)[blockIdx.x] : 0u;
+    for (uint64_t base = begin; base < end; base += kBlock) {
+        const bool live = base + threadIdx.x < end;
+        const uint32_t i = static_cast<uint32_t>(base + threadIdx.x);
+        const uint32_t seen = live ? p.seen[i] : kCarouselUnknown;
+        const bool entry = carousel_is_entry(seen);
+        const uint32_t st = seen & (kNtupleMaxStages - 1u);
+        uint32_t below = 0;
+#pragma unroll
+        for (uint32_t k = 1; k < kNtupleMaxStages; ++k) {
+            const uint64_t mask = __builtin_amdgcn_ballot_w64(entry && st == k);
+            below = st == k ? lanes_below(mask) : below;
+            if (lane == 0u)
+                s_wave[wave][k] = static_cast<uint32_t>(__popcll(mask));
+        }
+        if (threadIdx.x < kNtupleMaxStages)
+            s_base[threadIdx.x] = base_k;
+        __syncthreads();
+        if (entry) {
+            uint32_t r = s_base[st] + below;
+            for (uint32_t w = 0; w < wave; ++w)
+                r += s_wave[w][st];
+            p.seen[i] = static_cast<uint8_t>(st);
+            // (st >= 1 and st < S for every mark the restart pass made; the test keeps any other byte inside the pool)
+            if (st >= 1u && st < p.n_stages && carousel_survives(r, total[st], p.capacity))
+                store_board(p.pool, st * p.capacity + carousel_slot(count_mod[st], r, p.capacity), load_board(p.records, i));
+        }
+        if (threadIdx.x >= 1u && threadIdx.x < kNtupleMaxStages) {
+            for (uint32_t w = 0; w < kCarouselWaves; ++w)
+                base_k += s_wave[w][threadIdx.x];
+        }
+        __syncthreads(); // s_wave and s_base are written again for the next chunk
+    }
+}
+
 // ---------------------------------------------------------------------------- augmentation
 // training_data.augment() (training_data.py:257-299) for board pairs on the device: the eight
 // symmetries [orig, hflip, rot1(orig), rot1(hflip), rot2(..), rot2(..), rot3(..), rot3(..)] with the
@@ -2421,6 +2620,21 @@ hipError_t launch_ntuple_tc_trace_update(uint32_t n, const int64_t *delta, uint3
 {
     return launch_items_tc_update(NtupleTraceItems{tr.hist, tr.len, n, tr.depth, tr.lambda, slot}, delta, lr_shift, phases, net, err,
                                   mag, s);
+}
+
+hipError_t launch_carousel_step(const CarouselArgs &a, hipStream_t s)
+{
+    CarouselParams p{a.records, a.terminated, a.pool, a.count, a.seen, a.episodes, a.scratch, carousel_stages(a.n_stages, a.thresholds),
+                     a.n,       a.index_offset, a.n_stages, a.capacity, a.seed_lo, a.seed_hi, carousel_range(a.n, kBlock, kCarouselMaxGroups)};
+    const uint32_t groups = static_cast<uint32_t>((a.n + p.per - 1u) / p.per); // <= kCarouselMaxGroups
+    hipLaunchKernelGGL(carousel_restart_kernel, dim3(groups), dim3(kBlock), 0, s, p);
+    if (const hipError_t rc = hipGetLastError(); rc != hipSuccess)
+        return rc;
+    hipLaunchKernelGGL(carousel_scan_kernel, dim3(1), dim3(kBlock), 0, s, p, groups);
+    if (const hipError_t rc = hipGetLastError(); rc != hipSuccess)
+        return rc;
+    hipLaunchKernelGGL(carousel_scatter_kernel, dim3(groups), dim3(kBlock), 0, s, p);
+    return hipGetLastError();
 }
 
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s)

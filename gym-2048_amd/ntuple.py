@@ -13,6 +13,9 @@ afterstates of the same board (``g2048_ntuple_trace_*``).
 (``g2048_ntuple_search``), one launch for the whole batch.
 ``NTupleNet(..., stages=...)`` is the multi-stage network: a weight set per game stage, chosen per board by the tiles it
 holds (``g2048_ntuple_staged_*``); every method and trainer above works on it unchanged.
+``Carousel`` is carousel shaping for such a network (``g2048_carousel_*``): it remembers, per stage, the
+boards on which recent episodes entered that stage and restarts finished episodes from them, cycling over the stages, so
+that the late weight sets are trained too; every trainer takes it as ``carousel=``.
 """
 from __future__ import annotations
 
@@ -22,7 +25,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import NTupleIO, NTupleNetC, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTraceC, check
+from ._lib import CarouselC, NTupleIO, NTupleNetC, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTraceC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
@@ -31,6 +34,8 @@ SEARCH_MAX_DEPTH = 2                                              # G2048_NTUPLE
 TC_WEIGHTS, TC_ACCUM = 1, 2                                       # G2048_NTUPLE_TC_WEIGHTS, G2048_NTUPLE_TC_ACCUM
 TRACE_MAX = 8                                                     # G2048_NTUPLE_TRACE_MAX
 MAX_STAGES = 8                                                    # G2048_NTUPLE_MAX_STAGES
+CAROUSEL_MAX_CAPACITY = 65536                                     # G2048_CAROUSEL_MAX_CAPACITY
+SEEN_UNKNOWN = 0xff                                               # Carousel.seen: the stage of the episode is not known yet
 
 # Default shapes, as row-major cell indices (cell 4r + c).  The value sums every tuple over the eight symmetries of the
 # board, so a shape lists each tuple once, not once per placement.
@@ -430,6 +435,104 @@ class NTupleTrace:
         self.slot = slot
 
 
+class Carousel:
+    """Carousel shaping for ``n`` boards (``g2048_carousel``; Jaskowski 2017): stage-balanced restarts.
+
+    Every episode starts from an empty board, so the late weight sets of a staged network see only the rare boards that
+    survive that long.  The carousel keeps, per stage ``k >= 1``, a ring ``pool[k]`` of the last ``capacity`` engine records
+    on which an episode *entered* stage ``k`` (its stage rose above every stage the episode had been in), and :meth:`step`,
+    run right after a step with auto-reset on, restarts a board whose episode has just ended from ``pool[k]``,
+    ``k = (global board index + episodes the board has ended) mod (highest stage entered so far + 1)``; ``k = 0``, and a
+    stage nothing has entered yet, keep the fresh board.  Everything is integers and index-ordered: the same bits whatever
+    the launch geometry.
+
+    ``net_or_stages``: a staged :class:`NTupleNet`, or the sequence of thresholds (as its ``stages``).  Tensors on ``device``:
+    ``pool`` uint8 ``[S, capacity, 16]`` (records, verbatim: cells and packed score), ``count`` int64 ``[S]`` (read as
+    unsigned: entries ever made), ``seen`` uint8 ``[n]`` (the highest stage of the running episode, 0xff: not yet known),
+    ``episodes`` int32 ``[n]`` (read as unsigned, wraps).  One per engine or shard -- a pool depends on which boards feed it,
+    so a sharded run does *not* repeat the unsharded one.  A restarted board carries the score it was recorded with:
+    ``engine.scores()`` and the episode statistics then describe composite episodes.  Call :meth:`reset` after
+    ``engine.reset()``.
+
+    Memory: 16 S capacity + 5 n bytes, and 64 KiB of scratch."""
+
+    def __init__(self, net_or_stages, n, capacity=1024, seed=0, device="cuda:0"):
+        if isinstance(net_or_stages, NTupleNet):
+            if net_or_stages.stages is None:
+                raise ValueError("a carousel needs a staged network (NTupleNet(..., stages=...))")
+            stages = net_or_stages.stages
+        else:
+            stages = _stage_thresholds(net_or_stages)
+        if not stages:
+            raise ValueError("a carousel needs at least one stage threshold (two stages)")
+        self.stages = stages
+        self.n = _int_arg("n", n, 1, 0xffffff00)
+        self.capacity = _int_arg("capacity", capacity, 1, CAROUSEL_MAX_CAPACITY)
+        self.seed = _int_arg("seed", seed, 0, 2**64 - 1)
+        self.device = torch.device(device)
+        S = self.n_stages
+        self.pool = torch.zeros((S, self.capacity, 16), dtype=torch.uint8, device=self.device)
+        self.count = torch.zeros(S, dtype=torch.int64, device=self.device)
+        self.seen = torch.full((self.n,), SEEN_UNKNOWN, dtype=torch.uint8, device=self.device)
+        self.episodes = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self._scratch = torch.empty(int(_lib.load().g2048_carousel_scratch_bytes(self.n)) // 4, dtype=torch.int32, device=self.device)
+        self._c = CarouselC(S, (C.c_uint16 * 7)(*stages), self.capacity, self.seed, self.pool.data_ptr(), self.count.data_ptr(),
+                            self.seen.data_ptr(), self.episodes.data_ptr(), self._scratch.data_ptr())
+
+    @property
+    def n_stages(self):
+        return len(self.stages) + 1
+
+    def reset(self):
+        """Forget which stage every running episode has been in (``seen`` = 0xff); the pool and ``episodes`` stay."""
+        self.seen.fill_(SEEN_UNKNOWN)
+
+    def step(self, engine):
+        """The carousel step on the live records of ``engine`` (``g2048_carousel_step``) with ``engine.terminated`` of the
+        step just made (auto-reset on): three launches at most on the engine's stream, no host synchronisation."""
+        if engine.n_envs != self.n or engine.device != self.device:
+            raise ValueError(f"the carousel is for {self.n} boards on {self.device}, the engine has {engine.n_envs} on {engine.device}")
+        check(_lib.load().g2048_carousel_step(engine._h, C.byref(self._c), engine.terminated.data_ptr(), engine._stream()))
+
+    def step_plain(self, records, terminated, index_offset=0):
+        """The same on any device uint8 ``[n, 16]`` tensor of engine records, updated in place (``g2048_carousel_step_plain``);
+        ``terminated`` uint8 or bool ``[n]``; the global index of row i is ``index_offset + i``."""
+        _check_tensor("records", records, (torch.uint8,), (self.n, 16), self.device)
+        _check_tensor("terminated", terminated, (torch.uint8, torch.bool), (self.n,), self.device)
+        index_offset = _int_arg("index_offset", index_offset, 0, 2**32 - self.n)
+        _on_stream(_lib.load().g2048_carousel_step_plain, self.device, records.data_ptr(), self.n, index_offset, terminated.data_ptr(),
+                   C.byref(self._c))
+
+    def state_dict(self):
+        return {"stages": self.stages, "capacity": self.capacity, "seed": self.seed, "pool": self.pool.clone(),
+                "count": self.count.clone(), "seen": self.seen.clone(), "episodes": self.episodes.clone()}
+
+    def load_state_dict(self, state):
+        """Copy the pool, the counters and the per-board state of a ``state_dict()`` of a carousel of the same shape into this
+        one (in place)."""
+        if tuple(int(t) for t in state["stages"]) != self.stages or int(state["capacity"]) != self.capacity:
+            raise ValueError("state_dict is of a carousel with other stages or another capacity")
+        if int(state["seed"]) != self.seed:
+            raise ValueError(f"state_dict is of a carousel with seed {state['seed']}, this one has {self.seed}")
+        new = {}
+        for name, mine in (("pool", self.pool), ("count", self.count), ("seen", self.seen), ("episodes", self.episodes)):
+            t = torch.as_tensor(state[name])
+            if t.dtype != mine.dtype or t.shape != mine.shape:
+                raise ValueError(f"state_dict {name} must be {str(mine.dtype).replace('torch.', '')} {tuple(mine.shape)}")
+            new[name] = t
+        seen = new["seen"]
+        if bool(((seen >= self.n_stages) & (seen != SEEN_UNKNOWN)).any()):
+            raise ValueError(f"state_dict seen must hold stages below {self.n_stages} or 0xff")
+        for name, mine in (("pool", self.pool), ("count", self.count), ("seen", self.seen), ("episodes", self.episodes)):
+            mine.copy_(new[name])
+
+
+def _carousel_of(engine, carousel):
+    if not isinstance(carousel, Carousel) or carousel.n != engine.n_envs or carousel.device != engine.device:
+        raise ValueError(f"carousel must be a Carousel of {engine.n_envs} boards on {engine.device}")
+    return carousel
+
+
 class TDWork(NamedTuple):
     """Preallocated buffers of :func:`td_step` for one engine."""
     before: NTupleEval   # action, after, after_value of the boards before the step
@@ -445,12 +548,19 @@ def td_work(engine) -> TDWork:
                   NTupleEval(None, None, torch.empty(n, **i64), None, None), torch.empty(n, **i64))
 
 
-def td_evaluate(engine, net, work) -> TDWork:
+def td_evaluate(engine, net, work, carousel=None) -> TDWork:
     """Points 1-3 of the TD(0) step and the delta of point 4, leaving the weights alone: evaluate, play the greedy move
     (auto-reset on), evaluate the new boards, ``work.delta = (0 if terminated else best') - V(after)``.  Shards that share
-    one weight tensor run this on every shard before :func:`td_update` on any, so that all of them see the same weights."""
+    one weight tensor run this on every shard before :func:`td_update` on any, so that all of them see the same weights.
+    ``carousel`` (a :class:`Carousel` of this engine): ``carousel.step(engine)`` right behind the step, so a finished
+    episode restarts from the carousel's pool; the second evaluate sees the restarted board, and its ``best`` is masked by
+    ``terminated`` as before.  None: exactly the launches above."""
+    if carousel is not None:
+        _carousel_of(engine, carousel)
     engine.ntuple_evaluate(net, out=work.before)
     engine.step(work.before.action, auto_reset=True, want_info=False)
+    if carousel is not None:
+        carousel.step(engine)
     engine.ntuple_evaluate(net, out=work.after)
     work.delta.copy_(work.after.best)
     work.delta.masked_fill_(engine.terminated.bool(), 0)
@@ -463,21 +573,21 @@ def td_update(net, work, lr_shift):
     net.update(work.before.after, work.delta, lr_shift)
 
 
-def td_step(engine, net, lr_shift, work=None) -> TDWork:
+def td_step(engine, net, lr_shift, work=None, carousel=None) -> TDWork:
     """One afterstate TD(0) step of every board of ``engine`` (a ``Batched2048``) under ``net``, on the engine's stream:
     evaluate, play the greedy move, evaluate the new boards, and move V of the afterstate just played towards what
     followed it (:func:`td_evaluate`, then :func:`td_update`).  The weights change only in that last launch.  No host
-    synchronisation; ``work`` (:func:`td_work`) is reused."""
-    work = td_evaluate(engine, net, td_work(engine) if work is None else work)
+    synchronisation; ``work`` (:func:`td_work`) is reused.  ``carousel``: as in :func:`td_evaluate`."""
+    work = td_evaluate(engine, net, td_work(engine) if work is None else work, carousel)
     td_update(net, work, lr_shift)
     return work
 
 
-def train(engine, net, n_steps, lr_shift):
+def train(engine, net, n_steps, lr_shift, carousel=None):
     """``n_steps`` :func:`td_step` calls with one set of buffers."""
     work = td_work(engine)
     for _ in range(int(n_steps)):
-        td_step(engine, net, lr_shift, work)
+        td_step(engine, net, lr_shift, work, carousel)
     return net
 
 
@@ -488,28 +598,33 @@ def tc_update(net, tc, work, lr_shift, phases=3):
     net.tc_update(work.before.after, work.delta, lr_shift, tc, phases)
 
 
-def tc_step(engine, net, tc, lr_shift, work=None) -> TDWork:
+def tc_step(engine, net, tc, lr_shift, work=None, carousel=None) -> TDWork:
     """:func:`td_step` with the temporal-coherence update in place of the TD(0) one: :func:`td_evaluate`, then
     :func:`tc_update` (two launches).  No host synchronisation; ``work`` (:func:`td_work`) is reused."""
-    work = td_evaluate(engine, net, td_work(engine) if work is None else work)
+    work = td_evaluate(engine, net, td_work(engine) if work is None else work, carousel)
     tc_update(net, tc, work, lr_shift)
     return work
 
 
-def tc_train(engine, net, tc, n_steps, lr_shift):
+def tc_train(engine, net, tc, n_steps, lr_shift, carousel=None):
     """``n_steps`` :func:`tc_step` calls with one set of buffers."""
     work = td_work(engine)
     for _ in range(int(n_steps)):
-        tc_step(engine, net, tc, lr_shift, work)
+        tc_step(engine, net, tc, lr_shift, work, carousel)
     return net
 
 
-def tdl_evaluate(engine, net, trace, work) -> TDWork:
+def tdl_evaluate(engine, net, trace, work, carousel=None) -> TDWork:
     """:func:`td_evaluate` for the trace learners: evaluate, play the greedy move, evaluate the new boards, then one
     ``trace.push`` that stores the afterstate just played and forms ``work.delta`` in the same launch (in place of
-    td_evaluate's three element-wise ones).  Shards that share one network run this on every shard before an update on any."""
+    td_evaluate's three element-wise ones).  Shards that share one network run this on every shard before an update on any.
+    ``carousel``: as in :func:`td_evaluate`; the trace needs nothing, its push already sees ``terminated``."""
+    if carousel is not None:
+        _carousel_of(engine, carousel)
     engine.ntuple_evaluate(net, out=work.before)
     engine.step(work.before.action, auto_reset=True, want_info=False)
+    if carousel is not None:
+        carousel.step(engine)
     engine.ntuple_evaluate(net, out=work.after)
     trace.push(work.before.after, work.before.after_value, work.after.best, engine.terminated, work.delta)
     return work
@@ -521,33 +636,33 @@ def _trace_of(engine, trace):
     return trace
 
 
-def tdl_step(engine, net, trace, lr_shift, work=None) -> TDWork:
+def tdl_step(engine, net, trace, lr_shift, work=None, carousel=None) -> TDWork:
     """One afterstate TD(lambda) step of every board of ``engine`` under ``net``: :func:`tdl_evaluate`, then
     ``net.trace_update``.  No host synchronisation; ``work`` (:func:`td_work`) is reused."""
-    work = tdl_evaluate(engine, net, _trace_of(engine, trace), td_work(engine) if work is None else work)
+    work = tdl_evaluate(engine, net, _trace_of(engine, trace), td_work(engine) if work is None else work, carousel)
     net.trace_update(trace, work.delta, lr_shift)
     return work
 
 
-def tdl_train(engine, net, trace, n_steps, lr_shift):
+def tdl_train(engine, net, trace, n_steps, lr_shift, carousel=None):
     """``n_steps`` :func:`tdl_step` calls with one set of buffers."""
     work = td_work(engine)
     for _ in range(int(n_steps)):
-        tdl_step(engine, net, trace, lr_shift, work)
+        tdl_step(engine, net, trace, lr_shift, work, carousel)
     return net
 
 
-def tcl_step(engine, net, tc, trace, lr_shift, work=None) -> TDWork:
+def tcl_step(engine, net, tc, trace, lr_shift, work=None, carousel=None) -> TDWork:
     """:func:`tdl_step` with the temporal-coherence trace update: :func:`tdl_evaluate`, then ``net.tc_trace_update`` (two
     launches, W then A)."""
-    work = tdl_evaluate(engine, net, _trace_of(engine, trace), td_work(engine) if work is None else work)
+    work = tdl_evaluate(engine, net, _trace_of(engine, trace), td_work(engine) if work is None else work, carousel)
     net.tc_trace_update(trace, work.delta, lr_shift, tc)
     return work
 
 
-def tcl_train(engine, net, tc, trace, n_steps, lr_shift):
+def tcl_train(engine, net, tc, trace, n_steps, lr_shift, carousel=None):
     """``n_steps`` :func:`tcl_step` calls with one set of buffers."""
     work = td_work(engine)
     for _ in range(int(n_steps)):
-        tcl_step(engine, net, tc, trace, lr_shift, work)
+        tcl_step(engine, net, tc, trace, lr_shift, work, carousel)
     return net

@@ -586,6 +586,71 @@ int g2048_ntuple_staged_tc_trace_update(uint64_t n, const int64_t *delta, uint32
  * and the thresholds only: net->net.weights may be NULL. */
 int g2048_ntuple_stage_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net, uint8_t *stage, void *stream);
 
+/* Carousel shaping: stage-balanced restarts for training a staged network (Jaskowski 2017).  Every
+ * episode starts from an empty board, so the weight sets of the late stages see only the rare boards that live that long.
+ * A carousel remembers, per stage, the boards on which recent episodes ENTERED that stage, and starts new episodes from
+ * them, cycling over the stages.  Notation of the block above: stage(b) from thr[0..S-2]; cell = byte & 0x1f of an engine
+ * record.  The state of a carousel for n boards, all caller-owned device memory:
+ *   n_stages    S in 2..8, thresholds as for a staged network (the first S - 1: non-zero, strictly ascending)
+ *   capacity    C in 1..G2048_CAROUSEL_MAX_CAPACITY (= 65536): the ring size per stage
+ *   pool        uint8 [S][C][16], 16-byte aligned: engine records, copied verbatim (cells and packed score); row 0 is never used
+ *   count       uint64 [S]: entries ever made into each stage
+ *   seen        uint8 [n]: the highest stage this episode has been in, 0..S-1; 0xff = not yet known
+ *   episodes    uint32 [n]: episodes this board has ended; wraps
+ *   seed        key of the restart randomness
+ *   scratch     g2048_carousel_scratch_bytes(n) bytes, 4-byte aligned; opaque, nothing is kept in it between calls
+ * One operation, the carousel step, after a step with auto-reset on.  Inputs: the live records, terminated[n] (uint8,
+ * non-zero = true) and index_offset; the global index of board i is g = index_offset + i.  With pool and count AS THEY WERE
+ * BEFORE THE CALL, for every board i:
+ *   terminated[i] != 0 (the record is already the fresh auto-reset board):
+ *     e = episodes[i];  episodes[i] = e + 1
+ *     M = the largest k with count[k] > 0, else 0;   k = (g + e) mod (M + 1), the sum in 64 bits
+ *     if k > 0 and count[k] > 0:   fill = min(count[k], C)
+ *                                  w = Philox4x32-10(ctr = (e, g, k, 0), key = (seed_lo, seed_hi ^ 0x43524F55))[0]
+ *                                  j = (w * fill) >> 32;   record[i] = pool[k][j];   seen[i] = k
+ *     otherwise the fresh board stays and seen[i] = stage(record[i])
+ *   terminated[i] == 0:   st = stage(record[i])
+ *     if seen[i] == 0xff:     seen[i] = st, and nothing is recorded
+ *     else if st > seen[i]:   board i is an ENTRY into stage st, and seen[i] = st
+ *     else nothing happens  (the stage is not monotone over a game, so seen is a maximum and not the last stage)
+ * Then the entries are recorded in ascending board index: when stage k has m_k entries in this call, the entry of rank r
+ * (0-based among them) is stored at pool[k][(count[k] + r) mod C] if r >= m_k - C and dropped otherwise; then
+ * count[k] += m_k.  That is exactly a sequential loop over i = 0..n-1.  The slots 0..min(count[k], C)-1 are the filled ones,
+ * so j is a physical slot.  The result does not depend on launch geometry -- the rank is an ordered, batch-wide prefix
+ * count, not an atomic counter -- and no two lanes ever write one slot.  The key tag 0x43524F55 ("CROU") separates the
+ * restart stream from the spawn stream (no tag) and from g2048_mc_search's (0x4D435332) under an equal seed.
+ * One carousel belongs to one engine or shard: a pool depends on which boards feed it, so -- unlike everything above -- the
+ * boards of a sharded run are NOT those of the unsharded one.  A restarted board carries the score it was recorded with:
+ * g2048_get_scores, the last records and the statistics computed from them then describe composite episodes;
+ * g2048_stats.return_sum, kept by conservation of the merge scores played, does not see the recorded prefix of a restart
+ * (and has it subtracted while that episode runs): under a carousel read the last records instead.
+ * A call is at most three launches on `stream` (restart, which reads the pool; a scan of per-workgroup entry counts;
+ * scatter, which writes the pool) and no host synchronisation; no kernel waits for another workgroup.  Every call validates
+ * before any HIP call: S, the thresholds, C, NULL pointers, alignment, n. */
+#define G2048_CAROUSEL_MAX_CAPACITY 65536
+typedef struct g2048_carousel {
+    uint32_t n_stages;             /* S, 2..8 */
+    uint16_t thresholds[7];        /* first S-1 used, strictly ascending, >= 1; the rest ignored */
+    uint32_t capacity;             /* C, 1..65536 */
+    uint64_t seed;
+    uint8_t *pool;                 /* [S][C][16], 16-byte aligned */
+    uint64_t *count;               /* [S] */
+    uint8_t *seen;                 /* [n] */
+    uint32_t *episodes;            /* [n] */
+    void *scratch;                 /* g2048_carousel_scratch_bytes(n) bytes */
+} g2048_carousel;
+/* Bytes of `scratch` for a carousel of n boards (bounded whatever n is); 0 when n is outside 1..2^32 - 256. */
+uint64_t g2048_carousel_scratch_bytes(uint64_t n);
+/* The carousel step on the engine's live records, with index_offset = the engine's board_offset; `terminated` is the
+ * uint8[n] output of the step just made (device memory).  Enqueued on `stream` and ordered against the engine's own
+ * launches the way g2048_ntuple_evaluate is: behind a step, a rollout (either chain count) or a reset enqueued on the same
+ * stream before it.  Consumes no engine randomness and leaves the clock and the episode bookkeeping alone. */
+int g2048_carousel_step(g2048_engine *e, const g2048_carousel *c, const uint8_t *terminated, void *stream);
+/* The same on any device array of n engine records (uint8[n][16], 16-byte aligned), updated in place.  Needs no engine; runs
+ * on the current device.  1 <= n <= 2^32 - 256 and index_offset + n <= 2^32. */
+int g2048_carousel_step_plain(uint8_t *records, uint64_t n, uint64_t index_offset, const uint8_t *terminated,
+                              const g2048_carousel *c, void *stream);
+
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream);
