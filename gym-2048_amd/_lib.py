@@ -87,7 +87,8 @@ class MCIO(C.Structure):
 
 
 class NTupleNetC(C.Structure):
-    """g2048_ntuple_net (include/g2048.h): T tuples of L cells, F fraction bits, the cell lists and the device weights."""
+    """g2048_ntuple_net (include/g2048.h): T tuples of L cells, F fraction bits, the cell lists and the device weights.  A
+    list shorter than tuple_len ends with G2048_NTUPLE_END (0xff) entries: a mixed network, weights [W]."""
     _fields_ = [
         ("n_tuples", C.c_uint32),
         ("tuple_len", C.c_uint32),
@@ -127,7 +128,8 @@ class NTupleSearchIO(C.Structure):
 
 
 class NTupleTCC(C.Structure):
-    """g2048_ntuple_tc (include/g2048.h): the device accumulators of temporal-coherence learning, int64 [T][16^L] each."""
+    """g2048_ntuple_tc (include/g2048.h): the device accumulators of temporal-coherence learning, int64 each, laid out as
+    the weights."""
     _fields_ = [
         ("err", C.c_void_p),
         ("mag", C.c_void_p),

@@ -1254,8 +1254,18 @@ static int ntuple_net(const g2048_ntuple_net *net, g2048::NtupleNet *out, bool n
         return fail(G2048_ERR_INVALID, "frac_bits=%u: need 0 <= frac_bits <= %d", net->frac_bits, G2048_NTUPLE_MAX_FRAC_BITS);
     for (uint32_t t = 0; t < net->n_tuples; ++t) {
         uint32_t seen = 0;
+        bool ended = false; // a G2048_NTUPLE_END at some k' < k: tuple t is shorter than tuple_len (a mixed network)
         for (uint32_t k = 0; k < net->tuple_len; ++k) {
             const uint32_t c = net->cells[t][k];
+            if (c == G2048_NTUPLE_END) {
+                if (k == 0)
+                    return fail(G2048_ERR_INVALID, "cells[%u][0]=G2048_NTUPLE_END: tuple %u is empty, a tuple needs at least one cell", t, t);
+                ended = true;
+                continue;
+            }
+            if (ended)
+                return fail(G2048_ERR_INVALID, "cells[%u][%u]=%u: a cell after G2048_NTUPLE_END in tuple %u (only G2048_NTUPLE_END may follow it)",
+                            t, k, c, t);
             if (c > 15)
                 return fail(G2048_ERR_INVALID, "cells[%u][%u]=%u: a cell index is 0..15", t, k, c);
             if (seen >> c & 1u)

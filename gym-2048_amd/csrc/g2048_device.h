@@ -716,6 +716,21 @@ struct NtupleStagedShape : NtupleShape {
     uint32_t thr[kNtupleMaxStages - 1];  // thr[j], j < S - 1; kNtupleNoStage from there on
 };
 
+// Mixed-length networks (redundant encoding, Jaskowski 2017; include/g2048.h): a cell list may end before
+// tuple_len with kNtupleEnd entries, tuple t then has L_t cells and a table of 16^L_t weights, and the tables lie back to back:
+//   base_t = sum over u < t of 16^L_u,   W = sum over t of 16^L_t,   off(b, s, t) = stage(b) * W + base_t + idx_t(s(b))
+// with idx_t summed over k < L_t.  Still an element index below 2^30 (7 * 8 * 16^6), and every table starts on a multiple of
+// 16 elements.  A third shape type beside the two above, so the uniform kernels keep their arguments and their code: the
+// list words are NtupleShape's with 4 * L_t in the top byte (an END entry reads cell 0 and is masked off the index), and the
+// type carries the thresholds too -- an unstaged mixed network has kNtupleNoStage in all seven and is stage 0.
+constexpr uint32_t kNtupleEnd = 0xffu; // = G2048_NTUPLE_END (g2048.h)
+struct NtupleMixedShape {
+    uint32_t n_tuples, n_weights;        // T, W
+    uint32_t list[8 * kNtupleMaxTuples]; // list[8 * s + t]: bits 0..23 as NtupleShape::list, bits 24..31 = 4 * L_t
+    uint32_t base[kNtupleMaxTuples];     // base_t
+    uint32_t thr[kNtupleMaxStages - 1];  // as NtupleStagedShape::thr
+};
+
 // The cell of b that symmetry s (0..7) puts at cell c: bit 0 transposes, bit 1 reverses the rows, bit 2 the columns.
 G2048_HOST_DEV uint32_t ntuple_sym_cell(uint32_t s, uint32_t c)
 {
@@ -740,7 +755,8 @@ G2048_HOST_DEV NtupleShape ntuple_shape(uint32_t n_tuples, uint32_t tuple_len, c
     for (uint32_t s = 0; s < 8u; ++s)
         for (uint32_t t = 0; t < n_tuples; ++t)
             for (uint32_t k = 0; k < tuple_len; ++k)
-                sh.list[8u * s + t] |= ntuple_sym_cell(s, cells[t][k]) << (4u * k);
+                if (cells[t][k] != kNtupleEnd)
+                    sh.list[8u * s + t] |= ntuple_sym_cell(s, cells[t][k]) << (4u * k);
     return sh;
 }
 
@@ -749,6 +765,43 @@ G2048_HOST_DEV NtupleStagedShape ntuple_staged_shape(const NtupleShape &shape, u
 {
     NtupleStagedShape sh{};
     static_cast<NtupleShape &>(sh) = shape;
+    for (uint32_t j = 0; j < kNtupleMaxStages - 1u; ++j)
+        sh.thr[j] = j + 1u < n_stages ? thresholds[j] : kNtupleNoStage;
+    return sh;
+}
+
+// L_t of a checked descriptor: the entries before the first kNtupleEnd among k < tuple_len
+G2048_HOST_DEV uint32_t ntuple_tuple_len(uint32_t tuple_len, const uint8_t cells[6])
+{
+    uint32_t len = 0;
+    while (len < tuple_len && cells[len] != kNtupleEnd)
+        ++len;
+    return len;
+}
+
+// whether a checked descriptor is a mixed network: some list ends before tuple_len
+G2048_HOST_DEV bool ntuple_is_mixed(uint32_t n_tuples, uint32_t tuple_len, const uint8_t cells[8][6])
+{
+    for (uint32_t t = 0; t < n_tuples; ++t)
+        if (ntuple_tuple_len(tuple_len, cells[t]) != tuple_len)
+            return true;
+    return false;
+}
+
+// thresholds: as ntuple_staged_shape takes them; n_stages = 1 for a network of one weight set
+G2048_HOST_DEV NtupleMixedShape ntuple_mixed_shape(uint32_t n_tuples, uint32_t tuple_len, const uint8_t cells[8][6], uint32_t n_stages,
+                                                   const uint16_t *thresholds)
+{
+    const NtupleShape lists = ntuple_shape(n_tuples, tuple_len, cells);
+    NtupleMixedShape sh{};
+    sh.n_tuples = n_tuples;
+    for (uint32_t t = 0; t < n_tuples; ++t) {
+        const uint32_t len = ntuple_tuple_len(tuple_len, cells[t]);
+        sh.base[t] = sh.n_weights;
+        sh.n_weights += 1u << (4u * len);
+        for (uint32_t s = 0; s < 8u; ++s)
+            sh.list[8u * s + t] = lists.list[8u * s + t] | (4u * len) << 24;
+    }
     for (uint32_t j = 0; j < kNtupleMaxStages - 1u; ++j)
         sh.thr[j] = j + 1u < n_stages ? thresholds[j] : kNtupleNoStage;
     return sh;
@@ -763,8 +816,8 @@ G2048_HOST_DEV uint32_t ntuple_stage_mask(uint64_t packed)
     return mask;
 }
 
-// stage(b) for mask = mask(b): 0..S-1
-G2048_HOST_DEV uint32_t ntuple_stage(uint32_t mask, const NtupleStagedShape &sh)
+// stage(b) for mask = mask(b): 0..S-1; Shape = NtupleStagedShape or NtupleMixedShape
+template <class Shape> G2048_HOST_DEV uint32_t ntuple_stage(uint32_t mask, const Shape &sh)
 {
     uint32_t stage = 0;
     for (uint32_t j = 0; j < kNtupleMaxStages - 1u; ++j)
@@ -811,6 +864,11 @@ G2048_DEV uint32_t ntuple_stage_base(uint64_t packed, const NtupleStagedShape &s
 {
     return (ntuple_stage(ntuple_stage_mask(packed), sh) * sh.n_tuples) << (4u * sh.tuple_len);
 }
+// stage(b) * W of a mixed network, at most 7 * 8 * 16^6 < 2^30
+G2048_DEV uint32_t ntuple_stage_base(uint64_t packed, const NtupleMixedShape &sh)
+{
+    return ntuple_stage(ntuple_stage_mask(packed), sh) * sh.n_weights;
+}
 
 // offset of look-up (s, t) of a board whose weight set starts at element `base` (ntuple_stage_base) in the weight array
 // [S][T][16^L]; < S * T * 16^L <= 2^30: an ELEMENT index that fits uint32.  Every user adds it to a 64-bit pointer (the
@@ -818,6 +876,12 @@ G2048_DEV uint32_t ntuple_stage_base(uint64_t packed, const NtupleStagedShape &s
 G2048_DEV uint32_t ntuple_offset(uint64_t packed, const NtupleShape &sh, uint32_t s, uint32_t t, uint32_t base)
 {
     return base + (t << (4u * sh.tuple_len)) + ntuple_index(packed, sh.list[8u * s + t], sh.tuple_len);
+}
+// the same in a mixed network, < S * W <= 2^30: the index over all six nibbles, cut to the 4 * L_t bits of the list's top byte
+G2048_DEV uint32_t ntuple_offset(uint64_t packed, const NtupleMixedShape &sh, uint32_t s, uint32_t t, uint32_t base)
+{
+    const uint32_t list = sh.list[8u * s + t];
+    return base + sh.base[t] + (ntuple_index(packed, list, kNtupleMaxLen) & ((1u << (list >> 24)) - 1u));
 }
 
 // V(b), read from the tables of stage(b).  T = sh.n_tuples as a template argument: the 8T look-ups are straight-line code,

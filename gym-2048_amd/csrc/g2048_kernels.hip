@@ -2510,13 +2510,17 @@ hipError_t launch_mc_search(const uint4 *boards, uint32_t n, bool plain, const M
 }
 
 // f(std::integral_constant<uint32_t, T>(), shape) for the network's tuple count T = 1..8 and its shape: an NtupleShape for
-// one weight set -- the kernels of the unstaged network, whichever descriptor it came in -- an NtupleStagedShape for S > 1
+// one weight set -- the kernels of the unstaged network, whichever descriptor it came in -- an NtupleStagedShape for S > 1,
+// and for a network with a cell list that ends early (G2048_NTUPLE_END), staged or not, an NtupleMixedShape
 template <class F>
 static hipError_t dispatch_tuples(const NtupleNet &net, F &&f)
 {
+    const bool mixed = ntuple_is_mixed(net.n_tuples, net.tuple_len, net.cells);
     const NtupleShape sh = ntuple_shape(net.n_tuples, net.tuple_len, net.cells);
     return dispatch<1, 8>(static_cast<int>(net.n_tuples), [&](auto tc) {
         const std::integral_constant<uint32_t, static_cast<uint32_t>(decltype(tc)::value)> t;
+        if (mixed)
+            return f(t, ntuple_mixed_shape(net.n_tuples, net.tuple_len, net.cells, net.n_stages, net.thresholds));
         return net.n_stages > 1 ? f(t, ntuple_staged_shape(sh, net.n_stages, net.thresholds)) : f(t, sh);
     });
 }

@@ -16,6 +16,8 @@ holds (``g2048_ntuple_staged_*``); every method and trainer
 ``Carousel`` is carousel shaping for such a network (``g2048_carousel_*``): it remembers, per stage, the
 boards on which recent episodes entered that stage and restarts finished episodes from them, cycling over the stages, so
 that the late weight sets are trained too; every trainer takes it as ``carousel=``.
+``NTupleNet(..., mixed=True)`` and the ragged presets of ``TUPLES`` are networks with tuples of mixed length (redundant
+encoding): tables of 16^L_t weights back to back in one ``[W]`` tensor; everything above works on them.
 """
 from __future__ import annotations
 
@@ -35,6 +37,7 @@ TC_WEIGHTS, TC_ACCUM = 1, 2                                       # G2048_NTUPLE
 TRACE_MAX = 8                                                     # G2048_NTUPLE_TRACE_MAX
 MAX_STAGES = 8                                                    # G2048_NTUPLE_MAX_STAGES
 CAROUSEL_MAX_CAPACITY = 65536                                     # G2048_CAROUSEL_MAX_CAPACITY
+NTUPLE_END = 0xff                                                 # G2048_NTUPLE_END: pads a cell list shorter than tuple_len
 SEEN_UNKNOWN = 0xff                                               # Carousel.seen: the stage of the episode is not known yet
 
 # Default shapes, as row-major cell indices (cell 4r + c).  The value sums every tuple over the eight symmetries of the
@@ -45,6 +48,10 @@ TUPLES = {
     # all 17 straight and square 4-tuples -- 4 rows, 4 columns, 9 2x2 squares -- as the symmetric images of five: the
     # outer and the inner row, the corner, the edge and the centre square
     "17x4": ((0, 1, 2, 3), (4, 5, 6, 7), (0, 1, 4, 5), (1, 2, 5, 6), (5, 6, 9, 10)),
+    # redundant encoding (Jaskowski 2017): the 4x6 network plus four 4-tuples, each a sub-shape of one of its 6-tuples, so
+    # that a rarely visited 6-tuple entry generalises through an often visited 4-tuple entry.  A mixed network.
+    "4x6+4x4": ((0, 1, 2, 3, 4, 5), (4, 5, 6, 7, 8, 9), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10),
+                (0, 1, 2, 3), (4, 5, 6, 7), (0, 1, 4, 5), (5, 6, 9, 10)),
 }
 
 
@@ -143,6 +150,12 @@ class NTupleNet:
     tuples of at most 6 cells).  ``weights`` is the int32 ``[T, 16^L]`` tensor on ``device``, zero-initialised; the
     kernels read and update it in place, so it can be shared between engines.
 
+    ``mixed``: True allows sequences of different lengths -- a mixed network (redundant encoding); a
+    ragged name of ``TUPLES`` needs no flag, and with equal lengths the flag changes nothing.  Tuple t then has
+    ``tuple_lens[t]`` cells and a table of ``16^tuple_lens[t]`` weights, the tables lie back to back from
+    ``table_offsets[t]`` on, and ``weights`` is int32 ``[W]``, ``W = n_weights`` = the sum of the table sizes (``[S, W]``
+    when staged); :meth:`table` views one table.  ``tuple_len`` is the longest length.
+
     ``stages``: None, or a sequence of at most 7 strictly ascending thresholds in 1..65535 (:func:`stage_mask`) for a
     multi-stage network of ``S = len(stages) + 1`` weight sets: ``weights`` is then ``[S, T, 16^L]``,
     a board reads and updates the set ``stage(board)`` = the number of thresholds its tile mask is not below, and every
@@ -150,20 +163,22 @@ class NTupleNet:
     board, the leaves of a search and the slots of a trace may all be in different stages.  Memory: S times the unstaged
     network's."""
 
-    def __init__(self, tuples="4x6", frac_bits=10, device="cuda:0", stages=None):
+    def __init__(self, tuples="4x6", frac_bits=10, device="cuda:0", stages=None, mixed=False):
         if isinstance(tuples, str):
             if tuples not in TUPLES:
                 raise ValueError(f"tuples must be one of {sorted(TUPLES)} or a sequence of cell lists, not {tuples!r}")
-            tuples = TUPLES[tuples]
+            tuples, mixed = TUPLES[tuples], True
         try:
             tuples = tuple(tuple(t) for t in tuples)
         except TypeError:
             raise ValueError("tuples must be a sequence of sequences of cell indices") from None
         if not 1 <= len(tuples) <= MAX_TUPLES:
             raise ValueError(f"tuples: need 1..{MAX_TUPLES} tuples, not {len(tuples)}")
-        length = len(tuples[0])
-        if not 1 <= length <= MAX_LEN or any(len(t) != length for t in tuples):
-            raise ValueError(f"tuples: every tuple needs the same length in 1..{MAX_LEN}")
+        length = max(len(t) for t in tuples)
+        if not all(1 <= len(t) <= MAX_LEN for t in tuples):
+            raise ValueError(f"tuples: every tuple needs a length in 1..{MAX_LEN}")
+        if not mixed and any(len(t) != length for t in tuples):
+            raise ValueError(f"tuples: every tuple needs the same length in 1..{MAX_LEN} (mixed=True allows tuples of mixed length)")
         for t in tuples:
             cells = [_int_arg("tuples cell", c, 0, 15) for c in t]
             if len(set(cells)) != len(cells):
@@ -172,7 +187,12 @@ class NTupleNet:
         self.frac_bits = _int_arg("frac_bits", frac_bits, 0, MAX_FRAC_BITS)
         self.device = torch.device(device)
         self.stages = None if stages is None else _stage_thresholds(stages)
-        shape = (len(tuples), 16 ** length)
+        self.tuple_lens = tuple(len(t) for t in tuples)
+        self.mixed = any(n != length for n in self.tuple_lens)
+        sizes = [16 ** n for n in self.tuple_lens]
+        self.table_offsets = tuple(sum(sizes[:t]) for t in range(len(sizes)))
+        self.n_weights = sum(sizes)
+        shape = (self.n_weights,) if self.mixed else (len(tuples), 16 ** length)
         if self.stages is None:
             self.weights = torch.zeros(shape, dtype=torch.int32, device=self.device)
             self._c = c_net = NTupleNetC(len(tuples), length, self.frac_bits)
@@ -182,8 +202,8 @@ class NTupleNet:
             self._c.thresholds[:len(self.stages)] = self.stages
             c_net = self._c.net
         for t, cells in enumerate(self.tuples):
-            for k, c in enumerate(cells):
-                c_net.cells[t][k] = c
+            for k in range(length):
+                c_net.cells[t][k] = cells[k] if k < len(cells) else NTUPLE_END
         c_net.weights = self.weights.data_ptr()
 
     @property
@@ -192,7 +212,21 @@ class NTupleNet:
 
     @property
     def tuple_len(self):
-        return len(self.tuples[0])
+        return max(self.tuple_lens)
+
+    def table(self, t, stage=None) -> torch.Tensor:
+        """The table of tuple ``t`` as an int32 ``[16^tuple_lens[t]]`` view of ``weights``, of either layout; ``stage``: the
+        weight set of a staged network (required there, None otherwise)."""
+        t = _int_arg("t", t, 0, self.n_tuples - 1)
+        if self.stages is None:
+            if stage is not None:
+                raise ValueError("table: stage is for a staged network (NTupleNet(..., stages=...))")
+            flat = self.weights.reshape(-1)
+        else:
+            if stage is None:
+                raise ValueError(f"table: a staged network needs stage in 0..{self.n_stages - 1}")
+            flat = self.weights[_int_arg("stage", stage, 0, self.n_stages - 1)].reshape(-1)
+        return flat[self.table_offsets[t]:self.table_offsets[t] + 16 ** self.tuple_lens[t]]
 
     @property
     def n_stages(self):
@@ -351,11 +385,12 @@ class NTupleNet:
 class NTupleTC:
     """The accumulators of temporal-coherence learning for ``net`` (``g2048_ntuple_tc``): ``err``, the
     signed sum of the deltas every weight has seen, and ``mag``, the sum of their magnitudes (read as unsigned), both
-    int64 tensors of the shape of ``net.weights`` (``[T, 16^L]``, or ``[S, T, 16^L]`` for a staged network) on the network's
-    device, zero-initialised; a weight learns at rate ``|err| / mag``.
+    int64 tensors of the shape of ``net.weights`` (``[T, 16^L]``, ``[S, T, 16^L]`` for a staged network, ``[W]`` or ``[S, W]``
+    for a mixed one) on the network's device, zero-initialised; a weight learns at rate ``|err| / mag``.
 
-    Memory: 16 bytes per weight on top of the weight's own 4 -- 1 GiB per table for the 4x6 network (4 GiB in all), 5 MiB
-    in all for the 17x4 network; a staged network takes S times that."""
+    Memory: 16 bytes per weight on top of the weight's own 4 -- 256 MiB per table for the 4x6 network (1 GiB in all), 5 MiB
+    in all for the 17x4 network, 1 GiB + 4 MiB for the mixed "4x6+4x4" (the uniform eight 6-tuples it replaces: 2 GiB); a
+    staged network takes S times that."""
 
     def __init__(self, net):
         if not isinstance(net, NTupleNet):

@@ -398,18 +398,31 @@ int g2048_mc_search_plain(const uint8_t *boards, uint64_t n, uint32_t index_offs
  *   TD(0) step of an engine under weights W (unchanged until 4):  1. E = evaluate(boards);  2. g2048_step with E.action,
  *               keep terminated;  3. E' = evaluate(boards after the step; with auto-reset a finished board is already its
  *               fresh board);  4. delta_i = (terminated_i ? 0 : E'.best_i) - E.after_value_i, update(E.after, delta,
- *               lr_shift).  All on one stream, no host synchronisation (gym2048_amd.ntuple.td_step). */
+ *               lr_shift).  All on one stream, no host synchronisation (gym2048_amd.ntuple.td_step).
+ *   mixed       Tuples of mixed length (redundant encoding, Jaskowski 2017): tuple_len stays "how many
+ *               entries of cells[t][] are read", and tuple t has L_t cells, the entries before the first G2048_NTUPLE_END
+ *               among k < tuple_len.  L_t >= 1, every entry from L_t up to tuple_len - 1 is G2048_NTUPLE_END, the first L_t
+ *               are in 0..15 and distinct.  A descriptor without any END is the network above: the same kernels, kernel
+ *               arguments and bits.  With at least one END the network is mixed: table t has 16^L_t entries, the tables lie
+ *               back to back, base_t = sum over u < t of 16^L_u, W = sum over t of 16^L_t, the weights are int32 [W] (and
+ *               [S][W] in a g2048_ntuple_staged_net, the TC accumulators likewise), idx_t sums over k < L_t, and a look-up
+ *               reads element stage(b) * W + base_t + idx_t(s(b)), below 2^30.  Every table starts 16-byte aligned.
+ *               Everything else -- V, evaluate, search, the updates, TC, traces, stages -- is as written, with this offset.
+ *               If every tuple is cut to the same L' < tuple_len the layout is [T][16^L'], and every result equals, bit
+ *               for bit, that of the uniform network with tuple_len = L' on the same arrays. */
 #define G2048_NTUPLE_MAX_TUPLES 8
 #define G2048_NTUPLE_MAX_LEN 6
+#define G2048_NTUPLE_END 0xff
 #define G2048_NTUPLE_MAX_FRAC_BITS 16
 #define G2048_NTUPLE_MAX_LR_SHIFT 40
 #define G2048_NTUPLE_ILLEGAL INT64_MIN
 typedef struct g2048_ntuple_net {
     uint32_t n_tuples;      /* T, 1..8 */
-    uint32_t tuple_len;     /* L, 1..6: every tuple has L cells, its table 16^L entries */
+    uint32_t tuple_len;     /* L, 1..6: every tuple has L cells, its table 16^L entries (mixed: the longest L_t or more) */
     uint32_t frac_bits;     /* F, 0..16: a weight is a score in units of 2^-F */
-    uint8_t cells[8][6];    /* cells[t][k] in 0..15 (row-major cell index), distinct within a tuple */
-    int32_t *weights;       /* device, [T][16^L], 16-byte aligned */
+    uint8_t cells[8][6];    /* cells[t][k] in 0..15 (row-major cell index), distinct within a tuple; mixed: then
+                               G2048_NTUPLE_END up to tuple_len - 1 */
+    int32_t *weights;       /* device, [T][16^L] (mixed: [W]), 16-byte aligned */
 } g2048_ntuple_net;
 /* Outputs of evaluate: device pointers, NULL = not wanted, but at least one must be given. */
 typedef struct g2048_ntuple_io {
