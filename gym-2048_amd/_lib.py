@@ -118,6 +118,16 @@ class NTupleIO(C.Structure):
     ]
 
 
+class NTuplePlayIO(C.Structure):
+    """g2048_ntuple_play_io (include/g2048.h): the device side outputs of play (NULL = not wanted; games_left NULL = no
+    limit)."""
+    _fields_ = [
+        ("games_left", C.c_void_p),
+        ("hist", C.c_void_p),
+        ("moves", C.c_void_p),
+    ]
+
+
 class NTupleSearchIO(C.Structure):
     """g2048_ntuple_search_io (include/g2048.h): depth and device output pointers (NULL = not wanted)."""
     _fields_ = [
@@ -220,6 +230,8 @@ SIGNATURES = {
     "g2048_mc_search_plain": (C.c_int, [C.c_void_p, _u64, _u32, C.POINTER(MCIO), _S]),
     "g2048_ntuple_evaluate": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleIO), _S]),
     "g2048_ntuple_evaluate_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleIO), _S]),
+    "g2048_ntuple_play": (C.c_int, [_E, C.POINTER(NTupleNetC), _u32, C.POINTER(NTuplePlayIO), _S]),
+    "g2048_ntuple_staged_play": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), _u32, C.POINTER(NTuplePlayIO), _S]),
     "g2048_ntuple_search": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), _S]),
     "g2048_ntuple_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), _S]),
     "g2048_ntuple_values_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.c_void_p, _S]),

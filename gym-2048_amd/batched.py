@@ -17,6 +17,7 @@ import torch
 from . import _lib
 from ._lib import G2048Error, HostIO, StepIO, Stats, check
 # the analysis calls on plain boards, re-exported; Batched2048 has them as methods on its live boards
+from .analysis import _int_arg
 from .analysis import (MC_DEFAULT_MAX_STEPS, Afterstates, MCSearch, Search, SearchWeights, afterstates,  # noqa: F401
                        expectimax, mc_search, _OBS_DTYPES, _afterstate_io, _mc_io, _search_io)
 # the n-tuple network value function, re-exported; Batched2048.ntuple_evaluate runs it on the live boards
@@ -25,6 +26,7 @@ from .ntuple import NTupleTC, tc_step, tc_train, tc_update  # noqa: F401
 from .ntuple import NTupleTrace, tcl_step, tcl_train, tdl_evaluate, tdl_step, tdl_train  # noqa: F401
 from .ntuple import Carousel  # noqa: F401
 from .ntuple import _search_io as _ntuple_search_io
+from .ntuple import PlayReport, play_games, _play_io  # noqa: F401
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}
 
@@ -723,6 +725,25 @@ class Batched2048:
         io, out = _eval_io(self.n_envs, self.device, out)
         check(net._fn("evaluate")(self._h, ref, C.byref(io), self._stream()))
         return out
+
+    def ntuple_play(self, net, k_steps, games_left=None, hist=None, moves=None):
+        """``k_steps`` moves of the greedy player of an n-tuple network on every board in ONE launch (``g2048_ntuple_play``,
+        INTEGRATION.md §16), on the engine's stream: the records, the clock, the statistics and the terminal records end up
+        as after ``k_steps`` rounds of ``step(ntuple_evaluate(net).action)``, bit for bit; no per-step output is written.
+        Side outputs, device tensors or None: ``games_left`` uint32 ``[n]``, read and written -- a board at 0 rests, a board's
+        entry drops by one when its episode ends (None: no limit); ``hist`` uint64 ``[32]`` += the episodes that ended with
+        highest tile 2^k; ``moves`` uint64 ``[1]`` += the moves played.  A spawn-stream engine only (``rng="philox"``).
+        Measured (profiles/r19_ntuple_play_probe.txt): per move this launch is NOT faster than the
+        per-move loop at 1 024 boards (23 against 17 µs for "4x6") nor at 2^20 (15 % slower); it ties at 65 536.  What it
+        buys is the budgeted form -- exactly G games per board, :func:`play_games` -- and K moves without the host."""
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        ref = net._ref(self.device)
+        k_steps = _int_arg("k_steps", k_steps, 0, (1 << 32) - 1)
+        io = _play_io(self.n_envs, self.device, games_left, hist, moves)
+        check(net._fn("play")(self._h, ref, k_steps, C.byref(io), self._stream()))
+        if k_steps:
+            self._fresh = False
 
     def ntuple_search(self, net, depth=1, out=None) -> NTupleSearch:
         """Expectimax over an n-tuple network's afterstate values on the live boards (``g2048_ntuple_search``,

@@ -1438,6 +1438,47 @@ static int ntuple_evaluate_plain(const uint8_t *boards, uint64_t n, const Net *n
     return G2048_OK;
 }
 
+// g2048_ntuple_play_io -> the kernel's side outputs, or G2048_ERR_INVALID (before any HIP call: works without a device)
+static int ntuple_play_out(const g2048_ntuple_play_io *io, g2048::NtuplePlayOut *o)
+{
+    *o = g2048::NtuplePlayOut{};
+    if (!io)
+        return G2048_OK;
+    if (reinterpret_cast<uintptr_t>(io->games_left) & 3u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple play games_left needs 4 bytes");
+    if ((reinterpret_cast<uintptr_t>(io->hist) | reinterpret_cast<uintptr_t>(io->moves)) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple play hist and moves need 8 bytes");
+    *o = g2048::NtuplePlayOut{io->games_left, reinterpret_cast<unsigned long long *>(io->hist),
+                              reinterpret_cast<unsigned long long *>(io->moves)};
+    return G2048_OK;
+}
+
+// The clock as in g2048_rollout_random: k_steps transactions, whatever the boards' budgets.
+template <class Net> static int ntuple_play(g2048_engine *e, const Net *net, uint32_t k_steps, const g2048_ntuple_play_io *io, void *stream)
+{
+    if (int rc = usable(e))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtuplePlayOut o;
+    if (int rc = ntuple_play_out(io, &o))
+        return rc;
+    if (e->st.rng)
+        return fail(G2048_ERR_INVALID, "g2048_ntuple_play needs the spawn stream: this engine is in numpy-RNG mode, whose fused "
+                                       "form is not offered (play it with g2048_ntuple_evaluate and g2048_step)");
+    if (k_steps == 0)
+        return G2048_OK;
+    G2048_HIP(hipSetDevice(e->device));
+    e->t += 1; // transaction of the first fused step
+    e->fresh = 0;
+    g2048::StepArgs a = make_args(e, nullptr, 1);
+    a.k_steps = k_steps;
+    G2048_HIP(g2048::launch_ntuple_play(a, nn, o, static_cast<hipStream_t>(stream)));
+    e->t += k_steps - 1;
+    return G2048_OK;
+}
+
 template <class Net> static int ntuple_search(const g2048_engine *e, const Net *net, const g2048_ntuple_search_io *io, void *stream)
 {
     if (int rc = usable(e))
@@ -1569,6 +1610,17 @@ int g2048_ntuple_evaluate(const g2048_engine *e, const g2048_ntuple_net *net, co
 int g2048_ntuple_staged_evaluate(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_io *io, void *stream)
 {
     return ntuple_evaluate(e, net, io, stream);
+}
+
+int g2048_ntuple_play(g2048_engine *e, const g2048_ntuple_net *net, uint32_t k_steps, const g2048_ntuple_play_io *io, void *stream)
+{
+    return ntuple_play(e, net, k_steps, io, stream);
+}
+
+int g2048_ntuple_staged_play(g2048_engine *e, const g2048_ntuple_staged_net *net, uint32_t k_steps, const g2048_ntuple_play_io *io,
+                             void *stream)
+{
+    return ntuple_play(e, net, k_steps, io, stream);
 }
 
 int g2048_ntuple_evaluate_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_io *io,

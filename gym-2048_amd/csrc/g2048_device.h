@@ -1686,6 +1686,19 @@ G2048_DEV StepOut step_record(Board &rec, uint32_t action, const Words &w, uint3
     return o;
 }
 
+// ------------------------------------------------------- one step of the greedy n-tuple player on a record
+// g2048_ntuple_play (include/g2048.h): the action of ntuple_root on the record's cells, then exactly the
+// step g2048_step makes of that action -- the Philox block (t, board) of the spawn stream, board = board_offset + i, and
+// play_record.  No arithmetic of its own.  w comes back for the caller's reset_record, which needs the same block.
+template <uint32_t T, class Shape, class Tables>
+G2048_DEV StepOut ntuple_play_step(Board &rec, uint64_t t, uint32_t board, uint32_t seed_lo, uint32_t seed_hi, const Shape &sh,
+                                   uint32_t F, const int32_t *weights, uint32_t max_exp, const Tables &tb, Words &w)
+{
+    w = philox4x32_10(static_cast<uint32_t>(t), static_cast<uint32_t>(t >> 32), board, 0u, seed_lo, seed_hi);
+    const uint32_t action = ntuple_root<T>(record_cells(rec), sh, F, weights, tb).action;
+    return play_record(rec, action, w, max_exp, tb);
+}
+
 // ------------------------------------------------------------------------------ one env step
 struct StepResult {
     float reward;

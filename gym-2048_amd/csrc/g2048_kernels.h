@@ -137,6 +137,14 @@ struct NtupleSearchOut {
 };
 hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
                                 const NtupleSearchOut &o, hipStream_t s);
+// g2048_ntuple_play: a.k_steps greedy steps with auto-reset in one launch (spawn stream only: a.st.rng is refused by the
+// caller); the side outputs (g2048_ntuple_play_io, checked by the caller; NULL = not wanted)
+struct NtuplePlayOut {
+    uint32_t *games_left;      // [n] in/out: games a board may still finish; 0 = the board rests
+    unsigned long long *hist;  // [32] += episodes that ended with highest exponent k
+    unsigned long long *moves; // [1] += (board, step) pairs played
+};
+hipError_t launch_ntuple_play(const StepArgs &a, const NtupleNet &net, const NtuplePlayOut &io, hipStream_t s);
 hipError_t launch_ntuple_values(const uint4 *boards, uint32_t n, const NtupleNet &net, int64_t *v, hipStream_t s);
 // g2048_ntuple_stage_plain: stage[i] of n plain boards; reads the network's shape and thresholds, not its weights
 hipError_t launch_ntuple_stage(const uint4 *boards, uint32_t n, const NtupleNet &net, uint8_t *stage, hipStream_t s);

@@ -1634,6 +1634,73 @@ __global__ void __launch_bounds__(kBlock) ntuple_stage_kernel(const uint4 *__res
     stage[i] = static_cast<uint8_t>(ntuple_stage(ntuple_stage_mask(ntuple_pack(load_board(boards, i))), sh));
 }
 
+// g2048_ntuple_play: k_steps of the greedy player (ntuple_play_step of g2048_device.h) with auto-reset in ONE launch; the
+// record never leaves registers, as in rollout_random_kernel, whose bookkeeping this is: record_episode_ends, then
+// reset_record, per step; the lane's gains folded every kGainFold steps; one record store and one flush_episode_counts at the
+// end.  One board per lane, 64 boards per wavefront -- the episode slot is private to the wavefront of boards 64w .. 64w + 63
+// and written without atomics, so the four-lanes-per-board layout of ntuple_eval_kernel (four wavefronts per slot) is not an
+// option: a lane does its four directions itself (ntuple_root), up to 32T gathers per move, all offsets of a direction
+// computed before its first load (ntuple_value).  The weights are read with plain loads; nothing in the launch writes them.
+// The side outputs (NtuplePlayOut, any of them NULL): a board whose games_left entry is 0 when a step begins sits that step
+// out -- record untouched, no gain, no episode end, nothing counted -- and an entry drops by one when the board's episode
+// ends, after the reset, so a board that runs out rests on its fresh board; hist[highest exponent of the terminal board] += 1
+// per episode end, one atomic per ending lane (rare); moves += the (board, step) pairs played, summed over the wave first:
+// one atomic per wave per launch.  Integer adds: the same bits for any launch geometry.  A wavefront none of whose boards
+// has a game left stops stepping (nothing it could still do is visible: t is the launch's, not the lane's).
+template <uint32_t T, class Shape>
+__global__ void __launch_bounds__(kBlock) ntuple_play_kernel(const StepArgs p, const Shape sh, uint32_t frac_bits,
+                                                             const int32_t *__restrict__ weights, const NtuplePlayOut io)
+{
+    __shared__ WaveTables s_tables[kBlock / 64];
+    const Lane ln = lane_of<kBlock, false>(p.n);
+    Board rec = load_board(p.st.boards, ln.i);
+    const LdsTables tb = stage_tables(s_tables, load_tables_piece());
+    const EpisodeCounters counters = load_episode_counters(p, ln.i_raw);
+    uint32_t left = io.games_left ? io.games_left[ln.i] : 1u; // (no limit: never decremented)
+    uint64_t t = (static_cast<uint64_t>(p.t_hi) << 32) | p.t_lo; // transaction of the first step
+    uint32_t episodes = 0, illegal_ends = 0, played = 0, gained32 = 0;
+    unsigned long long gained = 0; // as in rollout_random_kernel: 32-bit adds, folded into 64 bits every kGainFold steps
+    for (uint32_t j = 0; j < p.k_steps; ++j, ++t) {
+        const bool go = left != 0u;
+        if (__builtin_amdgcn_ballot_w64(go) == 0ull)
+            break;
+        StepOut o{}; // a board that sits the step out: gain 0, not terminated
+        Words w{};
+        if (go)
+            o = ntuple_play_step<T>(rec, t, p.board_offset + ln.i, p.seed_lo, p.seed_hi, sh, frac_bits, weights, p.max_exp, tb, w);
+        played += go ? 1u : 0u;
+        gained32 += o.gain;
+        const bool fin = o.terminated && ln.valid;
+        record_episode_ends(p, ln.i, fin, !o.legal, rec, episodes, illegal_ends);
+        if (o.terminated) {
+            if (fin && io.hist)
+                atomicAdd(io.hist + highest(record_cells(rec)), 1ull);
+            reset_record(rec, o, w, tb);
+            if (io.games_left)
+                left -= 1u;
+        }
+        if ((j + 1u) % kGainFold == 0u) {
+            gained += gained32;
+            gained32 = 0;
+        }
+    }
+    gained += gained32;
+    if (ln.valid) {
+        store_board(p.st.boards, ln.i, rec);
+        if (io.games_left)
+            io.games_left[ln.i] = left;
+    }
+    // a board that was stepped has been reset at every episode end; one that sat the whole launch out keeps its mark
+    const unsigned long long pending = ((static_cast<unsigned long long>(counters.pend_hi) << 32) | counters.pend_lo) &
+                                       ~__builtin_amdgcn_ballot_w64(played != 0u);
+    flush_episode_counts(counters, episodes, illegal_ends, wave_sum64_lane63(ln.valid ? gained : 0ull), pending);
+    if (io.moves) { // (wave-uniform)
+        const unsigned long long total = wave_sum64_lane63(ln.valid ? played : 0u);
+        if ((threadIdx.x & 63u) == 63u && total != 0ull)
+            atomicAdd(io.moves, total);
+    }
+}
+
 // The six updates (g2048_ntuple_update_plain, g2048_ntuple_tc_update_plain, g2048_ntuple_trace_update,
 // g2048_ntuple_tc_trace_update; the definitions of g2048_device.h, "n-tuple network value function", "Temporal-coherence
 // learning" and "n-tuple traces") are three kernels, each over either item source of g2048_device.h ("The work items of an
@@ -2532,6 +2599,15 @@ hipError_t launch_ntuple_eval(const uint4 *boards, uint32_t n, bool plain, const
             return launch_1d(ntuple_eval_kernel<tc, plain_c, decltype(sh)>, group_lanes(n, 4u), 0, s, boards, n, sh, net.frac_bits,
                              static_cast<const int32_t *>(net.weights), o);
         });
+    });
+}
+
+hipError_t launch_ntuple_play(const StepArgs &a, const NtupleNet &net, const NtuplePlayOut &io, hipStream_t s)
+{
+    if (a.k_steps == 0)
+        return hipSuccess;
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        return launch_1d(ntuple_play_kernel<tc, decltype(sh)>, a.n, 0, s, a, sh, net.frac_bits, static_cast<const int32_t *>(net.weights), io);
     });
 }
 

@@ -16,6 +16,9 @@ holds (``g2048_ntuple_staged_*``); every method and trainer
 ``Carousel`` is carousel shaping for such a network (``g2048_carousel_*``): it remembers, per stage, the
 boards on which recent episodes entered that stage and restarts finished episodes from them, cycling over the stages, so
 that the late weight sets are trained too; every trainer takes it as ``carousel=``.
+``Batched2048.ntuple_play`` plays K greedy moves of every board in one launch and :func:`play_games` turns that into the
+game report of the papers -- exactly G games per board, mean score and the share of games that reach each tile
+(``g2048_ntuple_play``).
 ``NTupleNet(..., mixed=True)`` and the ragged presets of ``TUPLES`` are networks with tuples of mixed length (redundant
 encoding): tables of 16^L_t weights back to back in one ``[W]`` tensor; everything above works on them.
 """
@@ -27,7 +30,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import CarouselC, NTupleIO, NTupleNetC, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTraceC, check
+from ._lib import CarouselC, NTupleIO, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTraceC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
@@ -141,6 +144,17 @@ def _search_io(n, device, depth, out):
     io = NTupleSearchIO(depth)
     _bind_out(io, out, {"action": ((n,), (torch.uint8,)), "value": ((n, 4), (torch.int64,))}, device)
     return io, out
+
+
+def _play_io(n, device, games_left, hist, moves):
+    """NTuplePlayIO for n boards: every side output that is not None checked as ``_check_tensor`` checks."""
+    io = NTuplePlayIO()
+    for name, t, dtype, shape in (("games_left", games_left, torch.uint32, (n,)), ("hist", hist, torch.uint64, (32,)),
+                                  ("moves", moves, torch.uint64, (1,))):
+        if t is not None:
+            _check_tensor(name, t, (dtype,), shape, device)
+            setattr(io, name, t.data_ptr())
+    return io
 
 
 class NTupleNet:
@@ -701,3 +715,50 @@ def tcl_train(engine, net, tc, trace, n_steps, lr_shift, carousel=None):
     for _ in range(int(n_steps)):
         tcl_step(engine, net, tc, trace, lr_shift, work, carousel)
     return net
+
+
+class PlayReport(NamedTuple):
+    """Result of :func:`play_games`: the table the n-tuple papers report."""
+    games: int                        # games played to the end
+    unfinished: int                   # games still owed when max_steps ran out (0 otherwise)
+    mean_score: float                 # return_sum of those games / games: exact integers, one division (0.0 for no game)
+    hist: list                        # [32]: games whose highest tile was 2^k
+    reach: dict                       # {2048: share, ..., 32768: share} of the games whose highest tile was at least that tile
+    moves: int                        # moves played, the last (possibly illegal) move of every game included
+    scores: Optional[torch.Tensor]    # int32 [n]: every game's score when games == 1 and the engine keeps terminal records
+
+
+REACH_TILES = (2048, 4096, 8192, 16384, 32768)
+
+
+def play_games(engine, net, games=1, chunk=1024, max_steps=None) -> PlayReport:
+    """Exactly ``games`` games of the greedy player of ``net`` on every board of ``engine`` (a spawn-stream ``Batched2048``),
+    played to the end: resets the engine, then ``engine.ntuple_play(net, chunk, ...)`` until no board has a game left, with
+    one host read per chunk.  A board that has finished its games rests, so short games are not over-weighted the way
+    counting every episode of a fixed step budget over-weights them.  ``max_steps``: stop after at least that many steps
+    per board (a multiple of ``chunk``) and report what is missing as ``unfinished``.  The engine's statistics keep
+    running: the report is the difference of two ``episode_stats()`` readings.  The games are a function of the engine's
+    seed and of its clock at the reset: ``engine.seed(s)`` first makes a report reproducible."""
+    games = _int_arg("games", games, 1, (1 << 32) - 1)
+    chunk = _int_arg("chunk", chunk, 1, (1 << 32) - 1)
+    if max_steps is not None:
+        max_steps = _int_arg("max_steps", max_steps, 1, 1 << 62)
+    n, dev = engine.n_envs, engine.device
+    engine.reset()
+    # (filled as the signed types of the same width and viewed: every torch build fills and sums those on the device)
+    left = torch.full((n,), games - (1 << 32) if games >> 31 else games, dtype=torch.int32, device=dev).view(torch.uint32)
+    hist = torch.zeros(32, dtype=torch.int64, device=dev).view(torch.uint64)
+    moves = torch.zeros(1, dtype=torch.int64, device=dev).view(torch.uint64)
+    before, steps = engine.episode_stats(), 0
+    while max_steps is None or steps < max_steps:
+        engine.ntuple_play(net, chunk, games_left=left, hist=hist, moves=moves)
+        steps += chunk
+        if not bool(left.view(torch.int32).any()):
+            break
+    after = engine.episode_stats()
+    played = after["episodes"] - before["episodes"]
+    counts = [int(c) for c in hist.view(torch.int64).tolist()]
+    reach = {tile: (sum(counts[tile.bit_length() - 1:]) / played if played else 0.0) for tile in REACH_TILES}
+    scores = engine.last_scores() if games == 1 and engine.last_records_enabled else None
+    return PlayReport(played, n * games - played, (after["return_sum"] - before["return_sum"]) / played if played else 0.0, counts,
+                      reach, int(moves.view(torch.int64).item()), scores)

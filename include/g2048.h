@@ -664,6 +664,38 @@ int g2048_carousel_step(g2048_engine *e, const g2048_carousel *c, const uint8_t 
 int g2048_carousel_step_plain(uint8_t *records, uint64_t n, uint64_t index_offset, const uint8_t *terminated,
                               const g2048_carousel *c, void *stream);
 
+/* N-tuple play: k_steps moves of the greedy player on every board in ONE launch, and the counts of a game report
+ * (the evaluation protocol of Szubert & Jaskowski 2014: N games played to the end, mean score and the
+ * share of games that reach each tile).  The contract in one sentence: with io == NULL the records, the clock, the episode
+ * slots and the terminal records end up as the same bits as after k_steps rounds of g2048_ntuple_evaluate ->
+ * g2048_step(its `action`, auto_reset = 1); with games_left every board follows that same trajectory up to and including
+ * the reset after its last allowed episode, and then rests.  The record stays in registers over the launch and the weights
+ * are only read.  The clock and the engine's randomness advance by exactly k_steps transactions whether boards rest or
+ * not: the spawn stream is a function of (transaction, board), so a resting board consumes nothing and every board is
+ * independent of the others' budgets.  max_tile is honoured as g2048_step honours it; the step outputs (reward,
+ * terminated, ...) do not exist here.  The side outputs, all caller-owned device memory, each of them -- or io -- may be NULL:
+ *   games_left  uint32 [n], read and written.  A board whose entry is 0 when a step begins sits that step out: its record
+ *               is untouched, it gains nothing, no episode ends and nothing is counted.  When a board's episode ends its
+ *               entry drops by one AFTER the auto-reset, so a board that runs out rests on its fresh board.  NULL: no limit.
+ *   hist        uint64 [32], accumulated (never cleared here): hist[k] += 1 for every episode that ends in the call on a
+ *               terminal board whose highest exponent is k.
+ *   moves       uint64 [1], accumulated: the (board, step) pairs that were played, i.e. not sat out, including the
+ *               illegal move that ends a board with no legal move.
+ * All three are sums of integer adds: the same bits for any launch geometry or sharding (shards add into their own
+ * arrays; the sums of the parts are the whole's).  k_steps == 0 is G2048_OK and changes nothing.  G2048_ERR_INVALID, before
+ * any HIP call: a NULL engine or net, a descriptor g2048_ntuple_evaluate refuses, games_left not 4-byte or hist / moves not
+ * 8-byte aligned, and an engine in numpy-RNG mode -- the fused form of that mode is another kernel and is not offered:
+ * play such an engine with g2048_ntuple_evaluate and g2048_step. */
+typedef struct g2048_ntuple_play_io {
+    uint32_t *games_left;          /* [n] in/out, 4-byte aligned, or NULL: no limit */
+    uint64_t *hist;                /* [32] accumulated, 8-byte aligned, or NULL */
+    uint64_t *moves;               /* [1] accumulated, 8-byte aligned, or NULL */
+} g2048_ntuple_play_io;
+int g2048_ntuple_play(g2048_engine *e, const g2048_ntuple_net *net, uint32_t k_steps, const g2048_ntuple_play_io *io /* may be NULL */,
+                      void *stream);
+int g2048_ntuple_staged_play(g2048_engine *e, const g2048_ntuple_staged_net *net, uint32_t k_steps, const g2048_ntuple_play_io *io,
+                             void *stream);
+
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream);
