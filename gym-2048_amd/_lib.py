@@ -232,7 +232,9 @@ SIGNATURES = {
     "g2048_ntuple_evaluate_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleIO), _S]),
     "g2048_ntuple_play": (C.c_int, [_E, C.POINTER(NTupleNetC), _u32, C.POINTER(NTuplePlayIO), _S]),
     "g2048_ntuple_staged_play": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), _u32, C.POINTER(NTuplePlayIO), _S]),
+    "g2048_play_step": (C.c_int, [_E, C.c_void_p, _i32, C.POINTER(NTuplePlayIO), _S]),
     "g2048_ntuple_search": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), _S]),
+    "g2048_ntuple_search_active": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), C.c_void_p, _S]),
     "g2048_ntuple_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), _S]),
     "g2048_ntuple_values_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.c_void_p, _S]),
     "g2048_ntuple_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, C.POINTER(NTupleNetC), _S]),
@@ -246,6 +248,7 @@ SIGNATURES = {
     "g2048_ntuple_staged_evaluate": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleIO), _S]),
     "g2048_ntuple_staged_evaluate_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleIO), _S]),
     "g2048_ntuple_staged_search": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleSearchIO), _S]),
+    "g2048_ntuple_staged_search_active": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleSearchIO), C.c_void_p, _S]),
     "g2048_ntuple_staged_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleSearchIO), _S]),
     "g2048_ntuple_staged_values_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.c_void_p, _S]),
     "g2048_ntuple_staged_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, C.POINTER(NTupleStagedNetC), _S]),

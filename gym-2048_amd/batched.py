@@ -26,7 +26,7 @@ from .ntuple import NTupleTC, tc_step, tc_train, tc_update  # noqa: F401
 from .ntuple import NTupleTrace, tcl_step, tcl_train, tdl_evaluate, tdl_step, tdl_train  # noqa: F401
 from .ntuple import Carousel  # noqa: F401
 from .ntuple import _search_io as _ntuple_search_io
-from .ntuple import PlayReport, play_games, _play_io  # noqa: F401
+from .ntuple import PlayReport, play_games, _check_tensor, _play_io  # noqa: F401
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}
 
@@ -296,6 +296,14 @@ class Batched2048:
             io.obs, io.obs_dtype = obs.data_ptr(), _OBS_DTYPES[obs.dtype]
         return io
 
+    def _step_actions(self, actions):
+        """The ``[n]`` actions of one step on the engine's device, or None (the synthetic policy)."""
+        if actions is not None:
+            actions = self._as_device(actions)
+            if actions.shape != (self.n_envs,):
+                raise ValueError(f"actions must have shape ({self.n_envs},), got {tuple(actions.shape)}")
+        return actions
+
     def step(self, actions=None, auto_reset: bool = True, want_info: bool = True, obs=None):
         """game2048_env.py:76-100 for every board; ``actions=None`` plays the synthetic random policy.
 
@@ -305,10 +313,7 @@ class Batched2048:
         uint8 / float16 / float32 tensor that receives ``stack(board)`` of every board after the step (of the
         fresh board where an episode ended and ``auto_reset``), written by the SAME launch (:100).
         """
-        if actions is not None:
-            actions = self._as_device(actions)
-            if actions.shape != (self.n_envs,):
-                raise ValueError(f"actions must have shape ({self.n_envs},), got {tuple(actions.shape)}")
+        actions = self._step_actions(actions)
         io = self._io(actions, self.reward, self.terminated,
                       self.illegal if want_info else None, self.highest if want_info else None,
                       self.terminal_boards if want_info else None, None if obs is None else self._check_obs(obs))
@@ -745,16 +750,35 @@ class Batched2048:
         if k_steps:
             self._fresh = False
 
-    def ntuple_search(self, net, depth=1, out=None) -> NTupleSearch:
+    def play_step(self, actions=None, games_left=None, hist=None, moves=None):
+        """One step of every board with ``actions`` (as :meth:`step` takes them; None plays the synthetic random policy) under
+        the budget of :meth:`ntuple_play` (``g2048_play_step``), on the engine's stream: ``ntuple_play``
+        with ``k_steps=1`` for any player.  Auto-reset is always on and nothing is returned: no step output is written.  The
+        side outputs are ``ntuple_play``'s -- a board whose ``games_left`` is 0 rests and its action is not looked at; without
+        any of them the engine ends up as after ``step(actions)``, bit for bit.  A spawn-stream engine only."""
+        actions = self._step_actions(actions)
+        act = self._io(actions, None, None, None, None, None)
+        io = _play_io(self.n_envs, self.device, games_left, hist, moves)
+        check(self._lib.g2048_play_step(self._h, act.actions, act.action_dtype, C.byref(io), self._stream()))
+        self._fresh = False
+
+    def ntuple_search(self, net, depth=1, out=None, active=None) -> NTupleSearch:
         """Expectimax over an n-tuple network's afterstate values on the live boards (``g2048_ntuple_search``,
         INTEGRATION.md §10): ``NTupleSearch(action [n], value [n, 4])`` on the engine's stream, as
         :meth:`NTupleNet.search`.  ``depth`` 1..2; ``step(result.action)`` plays the chosen move.  ``out``: a preallocated
-        ``NTupleSearch`` (fields that are None are not written).  Touches no record, clock, statistic or randomness."""
+        ``NTupleSearch`` (fields that are None are not written).  ``active``: a uint32 ``[n]`` device tensor -- a board at 0
+        is not searched and gets ``action`` 0 and four ``ILLEGAL`` values, every other board the bits of the unmasked call
+        (``g2048_ntuple_search_active``; ``games_left`` of :meth:`play_step` is such a mask).  Touches no
+        record, clock, statistic or randomness."""
         if not isinstance(net, NTupleNet):
             raise ValueError("net must be an NTupleNet")
         ref = net._ref(self.device)
         io, out = _ntuple_search_io(self.n_envs, self.device, depth, out)
-        check(net._fn("search")(self._h, ref, C.byref(io), self._stream()))
+        if active is None:
+            check(net._fn("search")(self._h, ref, C.byref(io), self._stream()))
+        else:
+            _check_tensor("active", active, (torch.uint32,), (self.n_envs,), self.device)
+            check(net._fn("search_active")(self._h, ref, C.byref(io), active.data_ptr(), self._stream()))
         return out
 
     def isend_numpy(self) -> np.ndarray:

@@ -1479,8 +1479,12 @@ template <class Net> static int ntuple_play(g2048_engine *e, const Net *net, uin
     return G2048_OK;
 }
 
-template <class Net> static int ntuple_search(const g2048_engine *e, const Net *net, const g2048_ntuple_search_io *io, void *stream)
+// active: g2048_ntuple_search_active's mask, NULL for every board
+template <class Net>
+static int ntuple_search(const g2048_engine *e, const Net *net, const g2048_ntuple_search_io *io, const uint32_t *active, void *stream)
 {
+    if (reinterpret_cast<uintptr_t>(active) & 3u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple search active needs 4 bytes");
     if (int rc = usable(e))
         return rc;
     g2048::NtupleNet nn;
@@ -1489,6 +1493,7 @@ template <class Net> static int ntuple_search(const g2048_engine *e, const Net *
     g2048::NtupleSearchOut o;
     if (int rc = ntuple_search_out(io, &o))
         return rc;
+    o.active = active;
     G2048_HIP(hipSetDevice(e->device));
     G2048_HIP(g2048::launch_ntuple_search(e->st.boards, static_cast<uint32_t>(e->n), io->depth, false, nn, o,
                                           static_cast<hipStream_t>(stream)));
@@ -1623,6 +1628,34 @@ int g2048_ntuple_staged_play(g2048_engine *e, const g2048_ntuple_staged_net *net
     return ntuple_play(e, net, k_steps, io, stream);
 }
 
+// One budgeted step with the caller's actions: g2048_ntuple_play's contract and clock at k_steps == 1, g2048_step's checks of
+// the action buffer.  What can be refused without the engine is refused first.
+int g2048_play_step(g2048_engine *e, const void *actions, int32_t action_dtype, const g2048_ntuple_play_io *io, void *stream)
+{
+    if (action_dtype < G2048_ACT_RANDOM || action_dtype > G2048_ACT_I64)
+        return fail(G2048_ERR_INVALID, "unknown action_dtype %d", action_dtype);
+    if (action_dtype != G2048_ACT_RANDOM && !actions)
+        return fail(G2048_ERR_INVALID, "actions is NULL but action_dtype is %d", action_dtype);
+    if (action_dtype != G2048_ACT_RANDOM && (reinterpret_cast<uintptr_t>(actions) & (action_size(action_dtype) - 1)))
+        return fail(G2048_ERR_INVALID, "misaligned buffer: actions need their element size");
+    g2048::NtuplePlayOut o;
+    if (int rc = ntuple_play_out(io, &o))
+        return rc;
+    if (int rc = usable(e))
+        return rc;
+    if (e->st.rng)
+        return fail(G2048_ERR_INVALID, "g2048_play_step needs the spawn stream: this engine is in numpy-RNG mode, whose budgeted "
+                                       "form is not offered (play it with g2048_step)");
+    G2048_HIP(hipSetDevice(e->device));
+    e->t += 1;
+    e->fresh = 0;
+    g2048::StepArgs a = make_args(e, nullptr, 1);
+    a.actions = action_dtype == G2048_ACT_RANDOM ? nullptr : actions;
+    a.k_steps = 1;
+    G2048_HIP(g2048::launch_play_step(a, action_dtype, o, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 int g2048_ntuple_evaluate_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_io *io,
                                 void *stream)
 {
@@ -1637,13 +1670,25 @@ int g2048_ntuple_staged_evaluate_plain(const uint8_t *boards, uint64_t n, const 
 
 int g2048_ntuple_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io, void *stream)
 {
-    return ntuple_search(e, net, io, stream);
+    return ntuple_search(e, net, io, nullptr, stream);
 }
 
 int g2048_ntuple_staged_search(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_search_io *io,
                                void *stream)
 {
-    return ntuple_search(e, net, io, stream);
+    return ntuple_search(e, net, io, nullptr, stream);
+}
+
+int g2048_ntuple_search_active(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io,
+                               const uint32_t *active, void *stream)
+{
+    return ntuple_search(e, net, io, active, stream);
+}
+
+int g2048_ntuple_staged_search_active(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_search_io *io,
+                                      const uint32_t *active, void *stream)
+{
+    return ntuple_search(e, net, io, active, stream);
 }
 
 int g2048_ntuple_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io,

@@ -134,6 +134,8 @@ hipError_t launch_ntuple_eval(const uint4 *boards, uint32_t n, bool plain, const
 struct NtupleSearchOut {
     uint8_t *action; // [n]
     int64_t *value;  // [n][4]
+    const uint32_t *active = nullptr; // [n] or NULL (g2048_ntuple_search_active): a board at 0 is not searched, its outputs
+                                      //     are those of a board with no legal move
 };
 hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
                                 const NtupleSearchOut &o, hipStream_t s);
@@ -145,6 +147,8 @@ struct NtuplePlayOut {
     unsigned long long *moves; // [1] += (board, step) pairs played
 };
 hipError_t launch_ntuple_play(const StepArgs &a, const NtupleNet &net, const NtuplePlayOut &io, hipStream_t s);
+// g2048_play_step: one step of that launch with the actions of a.actions (action_dtype G2048_ACT_*, checked by the caller)
+hipError_t launch_play_step(const StepArgs &a, int action_dtype, const NtuplePlayOut &io, hipStream_t s);
 hipError_t launch_ntuple_values(const uint4 *boards, uint32_t n, const NtupleNet &net, int64_t *v, hipStream_t s);
 // g2048_ntuple_stage_plain: stage[i] of n plain boards; reads the network's shape and thresholds, not its weights
 hipError_t launch_ntuple_stage(const uint4 *boards, uint32_t n, const NtupleNet &net, uint8_t *stage, hipStream_t s);

@@ -1580,7 +1580,7 @@ __global__ void __launch_bounds__(kBlock) ntuple_eval_kernel(const uint4 *__rest
 // grid cap (kSearchMaxLanes); PLAIN as in expectimax_kernel.
 template <int D> constexpr uint32_t kNtupleSearchGroup = D == 1 ? 16u : 64u;
 
-template <int D, uint32_t T, bool PLAIN, class Shape>
+template <int D, uint32_t T, bool PLAIN, class Shape, bool MASKED = false>
 __global__ void __launch_bounds__(kBlock) ntuple_search_kernel(const uint4 *__restrict__ boards, uint32_t n, const Shape sh,
                                                                uint32_t frac_bits, const int32_t *__restrict__ weights,
                                                                const NtupleSearchOut o)
@@ -1595,7 +1595,13 @@ __global__ void __launch_bounds__(kBlock) ntuple_search_kernel(const uint4 *__re
         const Board cells = input_cells<PLAIN>(in);
         Board after = cells;
         uint32_t gain;
-        const bool legal = move_sel(after, tb.move_sel(d), gain);
+        bool legal = move_sel(after, tb.move_sel(d), gain);
+        // MASKED (g2048_ntuple_search_active): a board the caller masked out has no legal direction -- nothing below is
+        // searched and its outputs are those of a dead board.  The G lanes of a group read the same word: wave-uniform at
+        // G = 64.  A template parameter, not a test of o.active: the nullable pointer alone moved the register allocation of
+        // the unmasked kernels (profiles/r20_ntuple_search_resource_usage.txt).
+        if constexpr (MASKED)
+            legal = legal && o.active[i] != 0u;
         long long part = 0;
         if (legal)
             part = ntuple_chance_partial<D, T>(after, sub, K, sh, frac_bits, weights, tb);
@@ -1698,6 +1704,66 @@ __global__ void __launch_bounds__(kBlock) ntuple_play_kernel(const StepArgs p, c
         const unsigned long long total = wave_sum64_lane63(ln.valid ? played : 0u);
         if ((threadIdx.x & 63u) == 63u && total != 0ull)
             atomicAdd(io.moves, total);
+    }
+}
+
+// g2048_play_step: ONE step of every board under that contract with the action read from a buffer (ACT as in step_kernel: 0 =
+// the synthetic policy of the transaction, 1 / 2 / 3 = uint8 / int32 / int64) -- g2048_ntuple_play with k_steps == 1 for any
+// player.  The same lane layout for the same reason: one board per lane, the wavefront owns its episode slot.  The body is
+// ntuple_play_kernel's per-step body, copied, with the action loaded instead of computed and no loop around it: sharing it
+// as one __device__ function moved the register allocation of 19 of ntuple_play_kernel's 24 instantiations
+// (profiles/r20_play_step_resource_usage.txt), so that kernel stays as it was.  A board that rests is not checked for an
+// action outside 0..3 either (strict actions): its entry is loaded -- the buffer holds n -- and dropped.  No step output.
+template <int ACT>
+__global__ void __launch_bounds__(kBlock) play_step_kernel(const StepArgs p, const NtuplePlayOut io)
+{
+    __shared__ WaveTables s_tables[kBlock / 64];
+    const Lane ln = lane_of<kBlock, false>(p.n);
+    Board rec = load_board(p.st.boards, ln.i);
+    const auto raw = load_action_at<ACT>(p.actions, ln.i);
+    const LdsTables tb = stage_tables(s_tables, load_tables_piece());
+    const EpisodeCounters counters = load_episode_counters(p, ln.i_raw);
+    uint32_t left = io.games_left ? io.games_left[ln.i] : 1u; // (no limit: never decremented)
+    uint32_t episodes = 0, illegal_ends = 0;
+    const bool go = left != 0u;
+    StepOut o{}; // a board that sits the step out: gain 0, not terminated
+    Words w{};
+    BadAction bad; // (stays unset on a board that rests)
+    if (go) {
+        w = philox4x32_10(p.t_lo, p.t_hi, p.board_offset + ln.i, 0u, p.seed_lo, p.seed_hi);
+        uint32_t action;
+        if constexpr (ACT == 0)
+            action = w.w[3] >> 30;
+        else
+            action = bad.note_only(raw);
+        o = play_record(rec, action, w, p.max_exp, tb);
+    }
+    const bool fin = o.terminated && ln.valid;
+    record_episode_ends(p, ln.i, fin, !o.legal, rec, episodes, illegal_ends);
+    if (o.terminated) {
+        if (fin && io.hist)
+            atomicAdd(io.hist + highest(record_cells(rec)), 1ull);
+        reset_record(rec, o, w, tb);
+        if (io.games_left)
+            left -= 1u;
+    }
+    if (ln.valid) {
+        store_board(p.st.boards, ln.i, rec);
+        if (io.games_left)
+            io.games_left[ln.i] = left;
+    }
+    // a board that was stepped has been reset if its episode ended; one that sat the step out keeps its mark
+    const unsigned long long played = __builtin_amdgcn_ballot_w64(go);
+    const unsigned long long pending = ((static_cast<unsigned long long>(counters.pend_hi) << 32) | counters.pend_lo) & ~played;
+    flush_episode_counts(counters, episodes, illegal_ends, wave_sum_lane63(ln.valid ? o.gain : 0u), pending);
+    if (io.moves) { // (wave-uniform)
+        const unsigned long long total = static_cast<unsigned long long>(__popcll(played & __builtin_amdgcn_ballot_w64(ln.valid)));
+        if ((threadIdx.x & 63u) == 63u && total != 0ull)
+            atomicAdd(io.moves, total);
+    }
+    if constexpr (ACT != 0) {
+        if (p.action_err) // (wave-uniform)
+            report_bad_action(p.action_err, bad.bad && ln.valid, bad.raw, p.board_offset + ln.i);
     }
 }
 
@@ -2611,11 +2677,19 @@ hipError_t launch_ntuple_play(const StepArgs &a, const NtupleNet &net, const Ntu
     });
 }
 
+hipError_t launch_play_step(const StepArgs &a, int action_dtype, const NtuplePlayOut &io, hipStream_t s)
+{
+    return dispatch<0, 3>(action_dtype, [&](auto act) { return launch_1d(play_step_kernel<act>, a.n, 0, s, a, io); });
+}
+
 hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
                                 const NtupleSearchOut &o, hipStream_t s)
 {
     return dispatch<1, static_cast<int>(kNtupleSearchMaxDepth)>(static_cast<int>(depth), [&](auto dc) {
         return dispatch_tuples(net, [&](auto tc, auto sh) {
+            if (o.active) // (engine records only: the caller gives no mask for plain boards)
+                return launch_1d(ntuple_search_kernel<dc, tc, false, decltype(sh), true>, group_lanes(n, kNtupleSearchGroup<dc>), 0, s, boards,
+                                 n, sh, net.frac_bits, static_cast<const int32_t *>(net.weights), o);
             return dispatch_bool(plain, [&](auto plain_c) {
                 return launch_1d(ntuple_search_kernel<dc, tc, plain_c, decltype(sh)>, group_lanes(n, kNtupleSearchGroup<dc>), 0, s, boards, n, sh,
                                  net.frac_bits, static_cast<const int32_t *>(net.weights), o);

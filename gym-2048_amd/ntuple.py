@@ -18,7 +18,9 @@ boards on which recent episodes entered that stage and restarts finished episode
 that the late weight sets are trained too; every trainer takes it as ``carousel=``.
 ``Batched2048.ntuple_play`` plays K greedy moves of every board in one launch and :func:`play_games` turns that into the
 game report of the papers -- exactly G games per board, mean score and the share of games that reach each tile
-(``g2048_ntuple_play``).
+(``g2048_ntuple_play``).  ``play_games(depth=1 or 2)`` is that report for the expectimax player over the
+network and ``play_games(player=...)`` for any policy, through ``Batched2048.play_step`` and ``ntuple_search(active=)``
+(``g2048_play_step``, ``g2048_ntuple_search_active``).
 ``NTupleNet(..., mixed=True)`` and the ragged presets of ``TUPLES`` are networks with tuples of mixed length (redundant
 encoding): tables of 16^L_t weights back to back in one ``[W]`` tensor; everything above works on them.
 """
@@ -731,18 +733,31 @@ class PlayReport(NamedTuple):
 REACH_TILES = (2048, 4096, 8192, 16384, 32768)
 
 
-def play_games(engine, net, games=1, chunk=1024, max_steps=None) -> PlayReport:
-    """Exactly ``games`` games of the greedy player of ``net`` on every board of ``engine`` (a spawn-stream ``Batched2048``),
-    played to the end: resets the engine, then ``engine.ntuple_play(net, chunk, ...)`` until no board has a game left, with
-    one host read per chunk.  A board that has finished its games rests, so short games are not over-weighted the way
-    counting every episode of a fixed step budget over-weights them.  ``max_steps``: stop after at least that many steps
-    per board (a multiple of ``chunk``) and report what is missing as ``unfinished``.  The engine's statistics keep
-    running: the report is the difference of two ``episode_stats()`` readings.  The games are a function of the engine's
-    seed and of its clock at the reset: ``engine.seed(s)`` first makes a report reproducible."""
+def play_games(engine, net, games=1, chunk=1024, max_steps=None, depth=0, player=None) -> PlayReport:
+    """Exactly ``games`` games on every board of ``engine`` (a spawn-stream ``Batched2048``), played to the end, by one of
+    three players.  ``depth=0`` (the default): the greedy player of ``net`` -- resets the engine, then
+    ``engine.ntuple_play(net, chunk, ...)`` until no board has a game left, with one host read per chunk.  ``depth`` 1..2: the
+    expectimax player over ``net`` -- per move ``engine.ntuple_search(net, depth, active=left)``
+    into one preallocated action tensor, then ``engine.play_step`` of it; boards that have finished their games are not
+    searched.  ``player``: any policy, a callable ``player(engine, actions)`` that fills the uint8 ``[n]`` device tensor
+    ``actions`` on the engine's stream; ``net`` may then be None and ``depth`` must be 0.  Either way the loop runs
+    ``chunk`` moves between two host reads.  A board that has finished its games rests, so short games are not
+    over-weighted the way counting every episode of a fixed step budget over-weights them.  ``max_steps``: stop after at
+    least that many steps per board (a multiple of ``chunk``) and report what is missing as ``unfinished``.  The engine's
+    statistics keep running: the report is the difference of two ``episode_stats()`` readings.  The games are a function of
+    the engine's seed and of its clock at the reset: ``engine.seed(s)`` first makes a report reproducible."""
     games = _int_arg("games", games, 1, (1 << 32) - 1)
     chunk = _int_arg("chunk", chunk, 1, (1 << 32) - 1)
     if max_steps is not None:
         max_steps = _int_arg("max_steps", max_steps, 1, 1 << 62)
+    depth = _int_arg("depth", depth, 0, SEARCH_MAX_DEPTH)
+    if player is not None:
+        if not callable(player):
+            raise ValueError("player must be a callable player(engine, actions)")
+        if depth != 0:
+            raise ValueError(f"depth={depth} with a player: depth searches net, a player chooses its own actions")
+    elif not isinstance(net, NTupleNet):
+        raise ValueError("net must be an NTupleNet (or give a player)")
     n, dev = engine.n_envs, engine.device
     engine.reset()
     # (filled as the signed types of the same width and viewed: every torch build fills and sums those on the device)
@@ -750,8 +765,17 @@ def play_games(engine, net, games=1, chunk=1024, max_steps=None) -> PlayReport:
     hist = torch.zeros(32, dtype=torch.int64, device=dev).view(torch.uint64)
     moves = torch.zeros(1, dtype=torch.int64, device=dev).view(torch.uint64)
     before, steps = engine.episode_stats(), 0
+    act = torch.empty(n, dtype=torch.uint8, device=dev) if player is not None or depth else None
     while max_steps is None or steps < max_steps:
-        engine.ntuple_play(net, chunk, games_left=left, hist=hist, moves=moves)
+        if act is None:
+            engine.ntuple_play(net, chunk, games_left=left, hist=hist, moves=moves)
+        else:
+            for _ in range(chunk):        # (a chunk that outlives every game steps resting boards: launches, no work)
+                if player is not None:
+                    player(engine, act)
+                else:
+                    engine.ntuple_search(net, depth, out=NTupleSearch(act, None), active=left)
+                engine.play_step(act, games_left=left, hist=hist, moves=moves)
         steps += chunk
         if not bool(left.view(torch.int32).any()):
             break

@@ -541,6 +541,13 @@ typedef struct g2048_ntuple_search_io {
  * clock, the episode bookkeeping and cached graphs alone, in either RNG mode (like g2048_ntuple_evaluate).  At least one
  * of action and value must be given. */
 int g2048_ntuple_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io, void *stream);
+/* The same search of the boards a mask selects: `active` is uint32 [n] in device memory, 4-byte aligned
+ * (G2048_ERR_INVALID otherwise), or NULL, which is g2048_ntuple_search exactly.  A board with active[i] == 0 is not searched and
+ * gets the outputs of a board with no legal move: action[i] = 0 and, where asked for, value[i][0..3] = G2048_NTUPLE_ILLEGAL;
+ * every other board gets the bits of the unmasked call.  g2048_ntuple_play_io's games_left is such a mask: a board that has
+ * finished its games rests on a fresh two-tile board, the most expensive input a search can get. */
+int g2048_ntuple_search_active(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io,
+                               const uint32_t *active /* [n], or NULL */, void *stream);
 /* The same for n plain boards (uint8[n][16] exponents, device memory, 16-byte aligned).  Needs no engine; runs on the
  * current device.  1 <= n <= 2^32 - 256. */
 int g2048_ntuple_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io,
@@ -583,6 +590,8 @@ int g2048_ntuple_staged_evaluate_plain(const uint8_t *boards, uint64_t n, const 
                                        const g2048_ntuple_io *io, void *stream);
 int g2048_ntuple_staged_search(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_search_io *io,
                                void *stream);
+int g2048_ntuple_staged_search_active(const g2048_engine *e, const g2048_ntuple_staged_net *net,
+                                      const g2048_ntuple_search_io *io, const uint32_t *active, void *stream);
 int g2048_ntuple_staged_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
                                      const g2048_ntuple_search_io *io, void *stream);
 int g2048_ntuple_staged_values_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net, int64_t *v, void *stream);
@@ -695,6 +704,21 @@ int g2048_ntuple_play(g2048_engine *e, const g2048_ntuple_net *net, uint32_t k_s
                       void *stream);
 int g2048_ntuple_staged_play(g2048_engine *e, const g2048_ntuple_staged_net *net, uint32_t k_steps, const g2048_ntuple_play_io *io,
                              void *stream);
+
+/* Budgeted play step: ONE step of every board under the contract above with the action read from a
+ * buffer instead of computed -- g2048_ntuple_play with k_steps == 1 for any player, so that a look-ahead search or a
+ * caller's own policy gets the same game report.  `actions` is [n] of action_dtype G2048_ACT_U8 / I32 / I64 (device memory,
+ * aligned to its element size); G2048_ACT_RANDOM takes no buffer and plays the synthetic policy of the transaction.
+ * Auto-reset is always on.  With io == NULL the records, the clock, the episode slots and the terminal records are the same
+ * bits as after g2048_step(actions, auto_reset = 1); with io, games_left, hist and moves mean exactly what they mean above:
+ * a board at 0 sits the step out and its action is not looked at (not for strict actions either).  The clock and the spawn
+ * stream advance by one transaction whatever the budgets.  max_tile is honoured; no step output is written.  An action
+ * outside 0..3 plays its low two bits and, with strict actions, is reported by the next call on the engine, as g2048_step's.
+ * G2048_ERR_INVALID, before any HIP call: a NULL engine, a NULL or misaligned buffer with a buffer dtype, an unknown dtype,
+ * misaligned side outputs, and an engine in numpy-RNG mode.  Search only the boards that still play with
+ * g2048_ntuple_search_active(..., games_left, ...): the loop search -> play_step needs no host read between moves. */
+int g2048_play_step(g2048_engine *e, const void *actions, int32_t action_dtype, const g2048_ntuple_play_io *io /* may be NULL */,
+                    void *stream);
 
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
