@@ -26,6 +26,7 @@ from .ntuple import NTupleTC, tc_step, tc_train, tc_update  # noqa: F401
 from .ntuple import NTupleTrace, tcl_step, tcl_train, tdl_evaluate, tdl_step, tdl_train  # noqa: F401
 from .ntuple import Carousel  # noqa: F401
 from .ntuple import _search_io as _ntuple_search_io
+from .ntuple import DeepPlayer, _deep_io as _ntuple_deep_io  # noqa: F401
 from .ntuple import PlayReport, play_games, _check_tensor, _play_io  # noqa: F401
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}
@@ -779,6 +780,18 @@ class Batched2048:
         else:
             _check_tensor("active", active, (torch.uint32,), (self.n_envs,), self.device)
             check(net._fn("search_active")(self._h, ref, C.byref(io), active.data_ptr(), self._stream()))
+        return out
+
+    def ntuple_deep_search(self, net, depth=3, out=None, active=None) -> NTupleSearch:
+        """:meth:`ntuple_search` at ``depth`` 2..3 on the live boards (``g2048_ntuple_deep_search``), from
+        the kernel that gives every board a workgroup: the same ``NTupleSearch`` on the engine's stream, depth 2 the bits
+        of ``ntuple_search(net, 2)``.  ``out`` and ``active`` as in :meth:`ntuple_search`; mask out what needs no search: a
+        fresh two-tile board is the most expensive input.  Touches no record, clock, statistic or randomness."""
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        ref = net._ref(self.device)
+        io, out = _ntuple_deep_io(self.n_envs, self.device, depth, out, active)
+        check(net._fn("deep_search")(self._h, ref, C.byref(io), self._stream()))
         return out
 
     def isend_numpy(self) -> np.ndarray:

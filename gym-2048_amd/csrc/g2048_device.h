@@ -1338,6 +1338,193 @@ G2048_DEV uint32_t ntuple_search_root(const Board &cells, const Shape &sh, uint3
     return root_key_action(best);
 }
 
+// ------------------------------------------------------------------- n-tuple deep search
+// g2048_ntuple_deep_search (include/g2048.h): the definition of above at D = 2..3, split so that a whole
+// workgroup works on ONE board.  Bounds at D = 3, re-derived: a leaf is |V| <= 8 * 8 * 2^31 = 2^37; S_0 adds one gain << F with
+// gain < 2^31 and F <= 16, below 2^47; every level above adds one more, and floor() of a weighted mean does not leave the range
+// of its terms: |value| <= 2^37 + 4 * 2^47 < 2^50 with the root's own gain.  The weights of a chance node add up to
+// 10 E <= 150: any partial sum of it, in any order, stays below 150 * 2^50 < 2^58 -- an int64, and value + 2^60 of ntuple_key
+// is still positive.  (Depth 2 has one gain less.)
+//
+// The tree has a floor() at every chance node, so it is no flat sum: it is reduced in two levels over a table that the
+// kernel keeps in LDS and the host check in a plain struct (NtupleDeepLds).  P lanes, lane = 0 .. P-1, run the steps below with
+// a barrier after each; every step is a function here, so the host runs the kernel's split with any P:
+//   root     lanes 0..3: the root afterstate of direction d1, its gain and its 2 E chance items (0: illegal or masked out)
+//   expand   entry e = 4 * item1 + d2 for the level-1 items item1 = (d1, cell, tile) in direction order, at most 4 * 30:
+//            the afterstate of move d2 on the item's child board, its gain, and its count of work units: its 2 E chance
+//            items, 0 where d2 is illegal
+//   scan     prefix sums of the counts: unit u belongs to the entry e with first[e] <= u < first[e + 1]
+//   leaves   unit u = lane, lane + P, ...: acc[e] += weight * S_{D-2}(child of the unit) -- a unit is a depth-1 tree at
+//            D = 3 and the four look-ups of evaluate at D = 2, the straight-line code of ntuple_search_state; integer adds commute
+//   fold     item1 = lane, lane + P, ...: S_{D-1}(child) = max over legal d2 of (gain << F) + floor(acc / 10 E), 0 when no
+//            d2 is legal; sum[d1] += weight * S_{D-1}
+//   finish   lane 0: value[d1] = (gain << F) + floor(sum[d1] / 10 E), the keys and the action
+constexpr uint32_t kNtupleDeepMinDepth = 2, kNtupleDeepMaxDepth = 3; // = G2048_NTUPLE_DEEP_MIN/MAX_DEPTH (g2048.h)
+constexpr uint32_t kNtupleDeepMaxItems = 4u * 30u;                  // level-1 items: a root afterstate has at most 15 empty cells
+constexpr uint32_t kNtupleDeepMaxEntries = 4u * kNtupleDeepMaxItems;
+
+struct NtupleDeepLds {
+    Board after[kNtupleDeepMaxEntries];     // afterstate of entry e
+    long long acc[kNtupleDeepMaxEntries];   // its chance sum
+    uint32_t gain[kNtupleDeepMaxEntries];
+    uint32_t first[kNtupleDeepMaxEntries + 1u]; // first work unit of entry e; [4 * items] = the number of units
+    uint32_t count[kNtupleDeepMaxItems];    // byte d2 = the units of entry 4 * item1 + d2 (<= 30)
+    Board root_after[4];
+    long long root_sum[4];
+    uint32_t root_gain[4], root_items[4];   // 2 E of the root afterstate; 0 = illegal
+};
+
+// Chance item t of afterstate `a` (the order of chance_items): the child board and its weight
+G2048_DEV Board ntuple_deep_item(const Board &a, uint32_t t, uint32_t &weight)
+{
+    uint32_t m = empty_bits(a);
+#pragma unroll 1
+    for (uint32_t k = 0; k < (t >> 1); ++k)
+        m &= m - 1u;
+    const uint32_t v = 1u + (t & 1u);
+    weight = v == 1u ? 9u : 1u;
+    return place(a, g2048_ctz(m), v);
+}
+
+// Where level-1 item t sits: its root direction and its item index there.  t < the sum of root_items.
+G2048_DEV void ntuple_deep_item1(const NtupleDeepLds &l, uint32_t t, uint32_t &d1, uint32_t &local)
+{
+    d1 = 0;
+    local = t;
+#pragma unroll
+    for (uint32_t d = 0; d < 3u; ++d) {
+        const bool past = d1 == d && local >= l.root_items[d];
+        local -= past ? l.root_items[d] : 0u;
+        d1 += past ? 1u : 0u;
+    }
+}
+G2048_DEV uint32_t ntuple_deep_items(const NtupleDeepLds &l)
+{
+    return l.root_items[0] + l.root_items[1] + l.root_items[2] + l.root_items[3];
+}
+
+// root: lanes 0..3 (the others return).  active = false: a masked-out board has no legal direction.
+template <class Tables>
+G2048_DEV void ntuple_deep_root(NtupleDeepLds &l, const Board &cells, bool active, uint32_t lane, const Tables &tb)
+{
+    if (lane >= 4u)
+        return;
+    Board a = cells;
+    uint32_t gain;
+    const bool legal = move_sel(a, tb.move_sel(lane), gain) && active;
+    l.root_after[lane] = a;
+    l.root_gain[lane] = gain;
+    l.root_items[lane] = legal ? 2u * count_empty(a) : 0u;
+    l.root_sum[lane] = 0;
+}
+
+template <class Tables> G2048_DEV void ntuple_deep_expand(NtupleDeepLds &l, uint32_t lane, uint32_t P, const Tables &tb)
+{
+    const uint32_t entries = 4u * ntuple_deep_items(l);
+#pragma unroll 1
+    for (uint32_t e = lane; e < entries; e += P) {
+        uint32_t d1, local, weight, gain;
+        ntuple_deep_item1(l, e >> 2, d1, local);
+        Board a = ntuple_deep_item(l.root_after[d1], local, weight);
+        const bool legal = move_sel(a, tb.move_sel(e & 3u), gain);
+        l.after[e] = a;
+        l.gain[e] = gain;
+        l.acc[e] = 0;
+        reinterpret_cast<uint8_t *>(l.count)[e] = static_cast<uint8_t>(legal ? 2u * count_empty(a) : 0u);
+    }
+}
+
+G2048_DEV uint32_t ntuple_deep_byte_sum(uint32_t w) { return (w * 0x01010101u) >> 24; } // four bytes, each <= 30
+
+G2048_DEV void ntuple_deep_scan(NtupleDeepLds &l, uint32_t lane, uint32_t P)
+{
+    const uint32_t items = ntuple_deep_items(l);
+    if (lane == 0u)
+        l.first[0] = 0u;
+#pragma unroll 1
+    for (uint32_t t = lane; t < items; t += P) {
+        uint32_t at = 0;
+#pragma unroll 1
+        for (uint32_t u = 0; u < t; ++u)
+            at += ntuple_deep_byte_sum(l.count[u]);
+        uint32_t w = l.count[t];
+#pragma unroll
+        for (uint32_t d2 = 0; d2 < 4u; ++d2, w >>= 8) {
+            at += w & 0xffu;
+            l.first[4u * t + d2 + 1u] = at;
+        }
+    }
+}
+
+// the entry of work unit u < first[entries]: the last e with first[e] <= u (an entry without units is never the answer)
+G2048_DEV uint32_t ntuple_deep_entry(const NtupleDeepLds &l, uint32_t entries, uint32_t u)
+{
+    uint32_t lo = 0, hi = entries; // first[lo] <= u < first[hi]
+#pragma unroll 1
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        const bool left = l.first[mid] > u;
+        hi = left ? mid : hi;
+        lo = left ? lo : mid;
+    }
+    return lo;
+}
+
+// add(e, x): acc[e] += x, atomically among the lanes
+template <int D, uint32_t T, class Shape, class Tables, class Add>
+G2048_DEV void ntuple_deep_leaves(const NtupleDeepLds &l, uint32_t lane, uint32_t P, const Shape &sh, uint32_t F, const int32_t *weights,
+                                  const Tables &tb, Add add)
+{
+    static_assert(D == 2 || D == 3, "kNtupleDeepMinDepth .. kNtupleDeepMaxDepth");
+    const uint32_t entries = 4u * ntuple_deep_items(l), units = l.first[entries];
+#pragma unroll 1
+    for (uint32_t u = lane; u < units; u += P) {
+        const uint32_t e = ntuple_deep_entry(l, entries, u);
+        uint32_t weight;
+        const Board child = ntuple_deep_item(l.after[e], u - l.first[e], weight);
+        add(e, static_cast<int64_t>(weight) * ntuple_search_state<D - 2, T>(child, sh, F, weights, tb));
+    }
+}
+
+// add(d1, x): root_sum[d1] += x, atomically among the lanes
+template <class Add> G2048_DEV void ntuple_deep_fold(const NtupleDeepLds &l, uint32_t lane, uint32_t P, uint32_t F, Add add)
+{
+    const uint32_t items = ntuple_deep_items(l);
+#pragma unroll 1
+    for (uint32_t t = lane; t < items; t += P) {
+        int64_t best = 0;
+        bool any = false;
+        uint32_t w = l.count[t];
+#pragma unroll 1
+        for (uint32_t d2 = 0; d2 < 4u; ++d2, w >>= 8) {
+            const uint32_t e = 4u * t + d2, units = w & 0xffu;
+            if (units == 0u)
+                continue;
+            const int64_t q = static_cast<int64_t>(static_cast<uint64_t>(l.gain[e]) << F) + floor_div(l.acc[e], 5 * static_cast<int64_t>(units));
+            best = !any || q > best ? q : best;
+            any = true;
+        }
+        uint32_t d1, local;
+        ntuple_deep_item1(l, t, d1, local);
+        add(d1, ((local & 1u) ? 1 : 9) * best);
+    }
+}
+
+// finish: one lane.  value[4] and the action, as ntuple_search_root gives them.
+G2048_DEV uint32_t ntuple_deep_finish(const NtupleDeepLds &l, uint32_t F, int64_t value[4])
+{
+    uint64_t best = 0;
+    for (uint32_t d = 0; d < 4u; ++d) {
+        const bool legal = l.root_items[d] != 0u;
+        value[d] = legal ? static_cast<int64_t>(static_cast<uint64_t>(l.root_gain[d]) << F) +
+                               floor_div(l.root_sum[d], 5 * static_cast<int64_t>(l.root_items[d]))
+                         : kNtupleIllegal;
+        const uint64_t key = ntuple_key(value[d], legal, d);
+        best = key > best ? key : best;
+    }
+    return root_key_action(best);
+}
+
 // ------------------------------------------------------------------- carousel shaping
 // Stage-balanced restarts for training a staged network (g2048_carousel_step, include/g2048.h, INTEGRATION.md §14;
 // Jaskowski 2017): every episode starts from an empty board, so the weight sets of the late stages see a vanishing share of

@@ -139,6 +139,9 @@ struct NtupleSearchOut {
 };
 hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
                                 const NtupleSearchOut &o, hipStream_t s);
+// g2048_ntuple_deep_search: the same outputs from the workgroup-per-board kernel; depth in 2..3
+hipError_t launch_ntuple_deep_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
+                                     const NtupleSearchOut &o, hipStream_t s);
 // g2048_ntuple_play: a.k_steps greedy steps with auto-reset in one launch (spawn stream only: a.st.rng is refused by the
 // caller); the side outputs (g2048_ntuple_play_io, checked by the caller; NULL = not wanted)
 struct NtuplePlayOut {

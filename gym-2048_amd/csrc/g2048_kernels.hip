@@ -1619,6 +1619,67 @@ __global__ void __launch_bounds__(kBlock) ntuple_search_kernel(const uint4 *__re
     }
 }
 
+// g2048_ntuple_deep_search: the depth-D search, D = 2..3, with ONE WORKGROUP (kBlock lanes, four wavefronts) per board -- the
+// steps of g2048_device.h ("n-tuple deep search") with a barrier after each.  In ntuple_search_kernel a lane walks its chance
+// items one after the other; at depth 3 an item would be a whole depth-2 tree on one lane.  Here the level-1 items and their
+// afterstates (at most 480) are laid out in LDS once, and all 256 lanes share the list of their chance items, each a
+// depth-1 tree at depth 3 and one evaluate at depth 2: the straight-line code of ntuple_search_state<D - 2>.  A lane adds
+// its weight * S to the entry's int64 in LDS with one 64-bit LDS atomic per unit (hundreds of gathers stand behind each add);
+// integer adds commute, so the bits
+// do not depend on who took which unit.  LDS: sizeof(NtupleDeepLds) + the wave tables, about 18 KB, static.  Workgroups
+// stride over the boards when n * kBlock exceeds the grid cap (kSearchMaxLanes): at most 65 536 workgroups.  Nothing but the
+// outputs is written.  MASKED: a board at 0 in o.active has no legal root direction (ntuple_deep_root), so every step finds
+// nothing to do and finish writes the outputs of a dead board -- the path the host check runs; no barrier is skipped.
+// Measured on the MI355X (profiles/r21_ntuple_deep_probe.txt): depth 3 of 1 024 late-game boards (1..4 empty cells), 4x6 network:
+// 14.6 ms per launch against 53.0 ms for ntuple_search_kernel<3> (the same template at one wavefront per board), 2.9 to 4.3
+// times faster over both networks and 1 024 / 4 096 boards, which is why this kernel and not that instantiation is shipped; at
+// depth 2 it takes 0.32 to 0.61 of the existing kernel's time at 1 024 boards (recorded; g2048_ntuple_search is unchanged).
+// Not measured: other block sizes, a finer split of a unit, T other than 4 and 8, occupancy-limited shapes against each other.
+template <int D, uint32_t T, bool PLAIN, class Shape, bool MASKED = false>
+__global__ void __launch_bounds__(kBlock) ntuple_deep_search_kernel(const uint4 *__restrict__ boards, uint32_t n, const Shape sh,
+                                                                    uint32_t frac_bits, const int32_t *__restrict__ weights,
+                                                                    const NtupleSearchOut o)
+{
+    __shared__ WaveTables s_tables[kBlock / 64];
+    __shared__ NtupleDeepLds s_deep;
+    const LdsTables tb = stage_tables(s_tables, load_tables_piece());
+    const uint32_t lane = threadIdx.x;
+    for (uint64_t i = blockIdx.x; i < n; i += gridDim.x) { // (64 bits: n may be within one grid of 2^32)
+        // MASKED: the board's root directions count as illegal, so it has no items, no entries and no units: every step below
+        // falls through and finish writes the outputs of a dead board.  The word is the same for the whole workgroup.
+        bool active = true;
+        if constexpr (MASKED)
+            active = o.active[i] != 0u;
+        const Board cells = input_cells<PLAIN>(load_board(boards, static_cast<uint32_t>(i)));
+        ntuple_deep_root(s_deep, cells, active, lane, tb);
+        __syncthreads();
+        ntuple_deep_expand(s_deep, lane, kBlock, tb);
+        __syncthreads();
+        ntuple_deep_scan(s_deep, lane, kBlock);
+        __syncthreads();
+        ntuple_deep_leaves<D, T>(s_deep, lane, kBlock, sh, frac_bits, weights, tb, [&](uint32_t e, int64_t x) {
+            atomicAdd(reinterpret_cast<unsigned long long *>(&s_deep.acc[e]), static_cast<unsigned long long>(x));
+        });
+        __syncthreads();
+        ntuple_deep_fold(s_deep, lane, kBlock, frac_bits, [&](uint32_t d1, int64_t x) {
+            atomicAdd(reinterpret_cast<unsigned long long *>(&s_deep.root_sum[d1]), static_cast<unsigned long long>(x));
+        });
+        __syncthreads();
+        if (lane == 0u) {
+            int64_t value[4];
+            const uint32_t action = ntuple_deep_finish(s_deep, frac_bits, value);
+            if (o.value) {
+#pragma unroll
+                for (uint32_t d = 0; d < 4u; ++d)
+                    o.value[i * 4u + d] = value[d];
+            }
+            if (o.action)
+                o.action[i] = static_cast<uint8_t>(action);
+        }
+        __syncthreads(); // the next board's root step overwrites what lane 0 reads above
+    }
+}
+
 // g2048_ntuple_values_plain: V of every board, one board per lane, the same gathers.
 template <uint32_t T, class Shape>
 __global__ void __launch_bounds__(kBlock) ntuple_values_kernel(const uint4 *__restrict__ boards, uint32_t n, const Shape sh,
@@ -2692,6 +2753,35 @@ hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth,
                                  n, sh, net.frac_bits, static_cast<const int32_t *>(net.weights), o);
             return dispatch_bool(plain, [&](auto plain_c) {
                 return launch_1d(ntuple_search_kernel<dc, tc, plain_c, decltype(sh)>, group_lanes(n, kNtupleSearchGroup<dc>), 0, s, boards, n, sh,
+                                 net.frac_bits, static_cast<const int32_t *>(net.weights), o);
+            });
+        });
+    });
+}
+
+// One workgroup per board: group_lanes(n, kBlock) lanes, so at most kSearchMaxLanes / kBlock = 65 536 workgroups.
+// -DG2048_PROBE_WAVE_DEPTH3 (never the product's build; `python tools/ntuple_deep_probe.py --build-wave-lib FILE` compiles such
+// a library with build_hip's flags) sends depth 3 without a mask to the alternative this kernel was timed against:
+// ntuple_search_kernel<3>, one wavefront per board.
+hipError_t launch_ntuple_deep_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
+                                     const NtupleSearchOut &o, hipStream_t s)
+{
+#ifdef G2048_PROBE_WAVE_DEPTH3
+    if (depth == 3 && !o.active)
+        return dispatch_tuples(net, [&](auto tc, auto sh) {
+            return dispatch_bool(plain, [&](auto plain_c) {
+                return launch_1d(ntuple_search_kernel<3, tc, plain_c, decltype(sh)>, group_lanes(n, kNtupleSearchGroup<3>), 0, s, boards, n, sh,
+                                 net.frac_bits, static_cast<const int32_t *>(net.weights), o);
+            });
+        });
+#endif
+    return dispatch<static_cast<int>(kNtupleDeepMinDepth), static_cast<int>(kNtupleDeepMaxDepth)>(static_cast<int>(depth), [&](auto dc) {
+        return dispatch_tuples(net, [&](auto tc, auto sh) {
+            if (o.active) // (engine records only: the caller gives no mask for plain boards)
+                return launch_1d(ntuple_deep_search_kernel<dc, tc, false, decltype(sh), true>, group_lanes(n, kBlock), 0, s, boards, n, sh,
+                                 net.frac_bits, static_cast<const int32_t *>(net.weights), o);
+            return dispatch_bool(plain, [&](auto plain_c) {
+                return launch_1d(ntuple_deep_search_kernel<dc, tc, plain_c, decltype(sh)>, group_lanes(n, kBlock), 0, s, boards, n, sh,
                                  net.frac_bits, static_cast<const int32_t *>(net.weights), o);
             });
         });

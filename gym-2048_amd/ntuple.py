@@ -11,6 +11,9 @@ per update.  Everything is an integer: the same bits however the batch is split 
 afterstates of the same board (``g2048_ntuple_trace_*``).
 ``NTupleNet.search`` / ``Batched2048.ntuple_search`` play the network through a depth-1..2 expectimax
 (``g2048_ntuple_search``), one launch for the whole batch.
+``NTupleNet.deep_search`` / ``Batched2048.ntuple_deep_search`` are the same search at depth 2..3 from a kernel that gives a
+board a whole workgroup (``g2048_ntuple_deep_search``), and ``DeepPlayer`` plays it in :func:`play_games`:
+the 3-ply row of the papers.
 ``NTupleNet(..., stages=...)`` is the multi-stage network: a weight set per game stage, chosen per board by the tiles it
 holds (``g2048_ntuple_staged_*``); every method and trainer above works on it unchanged.
 ``Carousel`` is carousel shaping for such a network (``g2048_carousel_*``): it remembers, per stage, the
@@ -32,12 +35,13 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import CarouselC, NTupleIO, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTraceC, check
+from ._lib import CarouselC, NTupleDeepIO, NTupleIO, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTraceC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
 ILLEGAL = -(1 << 63)                                              # G2048_NTUPLE_ILLEGAL: q of an illegal move
 SEARCH_MAX_DEPTH = 2                                              # G2048_NTUPLE_SEARCH_MAX_DEPTH
+DEEP_MIN_DEPTH, DEEP_MAX_DEPTH = 2, 3                             # G2048_NTUPLE_DEEP_MIN_DEPTH, G2048_NTUPLE_DEEP_MAX_DEPTH
 TC_WEIGHTS, TC_ACCUM = 1, 2                                       # G2048_NTUPLE_TC_WEIGHTS, G2048_NTUPLE_TC_ACCUM
 TRACE_MAX = 8                                                     # G2048_NTUPLE_TRACE_MAX
 MAX_STAGES = 8                                                    # G2048_NTUPLE_MAX_STAGES
@@ -134,17 +138,28 @@ class NTupleSearch(NamedTuple):
     value: Optional[torch.Tensor]        # int64 [n, 4]: (merge score << F) + A_depth(afterstate d); ILLEGAL where d is illegal
 
 
-def _search_io(n, device, depth, out):
-    """(NTupleSearchIO, NTupleSearch) for n boards: ``depth`` checked, ``out`` checked field by field or freshly allocated."""
-    depth = _int_arg("depth", depth, 1, SEARCH_MAX_DEPTH)
+def _search_io(n, device, depth, out, io_type=NTupleSearchIO, depths=(1, SEARCH_MAX_DEPTH)):
+    """(io_type(depth, ...), NTupleSearch) for n boards: ``depth`` checked against ``depths``, ``out`` checked field by field or
+    freshly allocated."""
+    depth = _int_arg("depth", depth, *depths)
     if out is None:
         out = NTupleSearch(torch.empty(n, dtype=torch.uint8, device=device), torch.empty((n, 4), dtype=torch.int64, device=device))
     else:
         out = NTupleSearch(*out)
         if out.action is None and out.value is None:
             raise ValueError("out requests no output (action and value are both None)")
-    io = NTupleSearchIO(depth)
+    io = io_type(depth)
     _bind_out(io, out, {"action": ((n,), (torch.uint8,)), "value": ((n, 4), (torch.int64,))}, device)
+    return io, out
+
+
+def _deep_io(n, device, depth, out, active=None):
+    """``_search_io`` for the deep search: (NTupleDeepIO, NTupleSearch), depth 2..3, and ``active`` (engine forms) checked as
+    ``_check_tensor`` checks."""
+    io, out = _search_io(n, device, depth, out, NTupleDeepIO, (DEEP_MIN_DEPTH, DEEP_MAX_DEPTH))
+    if active is not None:
+        _check_tensor("active", active, (torch.uint32,), (n,), device)
+        io.active = active.data_ptr()
     return io, out
 
 
@@ -329,6 +344,20 @@ class NTupleNet:
         net = self._ref(device)
         io, out = _search_io(n, device, depth, out)
         self._launch(self._fn("search_plain"), boards, net, C.byref(io))
+        return out
+
+    def deep_search(self, boards, depth=3, out=None) -> NTupleSearch:
+        """:meth:`search` at ``depth`` 2..3 on plain boards (``g2048_ntuple_deep_search_plain``): the same
+        definition and the same :class:`NTupleSearch`, from the kernel that gives every board a workgroup; depth 2 gives the
+        bits of ``search(boards, 2)``.  One launch on the current stream of the boards' device.  The cost grows steeply with
+        the empty cells of a board: about 10^4..10^5 network evaluations on a board with 1..6 empty cells at depth 3, up to
+        about 2 * 10^6 on a nearly empty one (counts from the definition).  Measured on the MI355X
+        (``profiles/r21_ntuple_deep_probe.txt``): 14.6 ms per launch for 1 024 late-game boards and 120 ms for 1 024 mid-game
+        boards with the 4x6 network; other shapes, sizes above 4 096 boards and staged networks have not been timed."""
+        n, device = _plain_boards(boards)
+        net = self._ref(device)
+        io, out = _deep_io(n, device, depth, out)
+        self._launch(self._fn("deep_search_plain"), boards, net, C.byref(io))
         return out
 
     def update(self, boards, delta, lr_shift):
@@ -733,6 +762,22 @@ class PlayReport(NamedTuple):
 REACH_TILES = (2048, 4096, 8192, 16384, 32768)
 
 
+class DeepPlayer:
+    """The expectimax player over ``net`` at ``depth`` 2..3 for :func:`play_games` (``g2048_ntuple_deep_search``,
+    INTEGRATION.md §18): ``play_games(engine, net, games, player=DeepPlayer(net))`` is the 3-ply row of the n-tuple papers.
+    A callable ``player(engine, actions, active=None)``; ``takes_active`` tells :func:`play_games` to pass the boards' games
+    left as ``active``, so that boards that have finished their games are not searched."""
+    takes_active = True
+
+    def __init__(self, net, depth=3):
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        self.net, self.depth = net, _int_arg("depth", depth, DEEP_MIN_DEPTH, DEEP_MAX_DEPTH)
+
+    def __call__(self, engine, actions, active=None):
+        engine.ntuple_deep_search(self.net, self.depth, out=NTupleSearch(actions, None), active=active)
+
+
 def play_games(engine, net, games=1, chunk=1024, max_steps=None, depth=0, player=None) -> PlayReport:
     """Exactly ``games`` games on every board of ``engine`` (a spawn-stream ``Batched2048``), played to the end, by one of
     three players.  ``depth=0`` (the default): the greedy player of ``net`` -- resets the engine, then
@@ -740,7 +785,9 @@ def play_games(engine, net, games=1, chunk=1024, max_steps=None, depth=0, player
     expectimax player over ``net`` -- per move ``engine.ntuple_search(net, depth, active=left)``
     into one preallocated action tensor, then ``engine.play_step`` of it; boards that have finished their games are not
     searched.  ``player``: any policy, a callable ``player(engine, actions)`` that fills the uint8 ``[n]`` device tensor
-    ``actions`` on the engine's stream; ``net`` may then be None and ``depth`` must be 0.  Either way the loop runs
+    ``actions`` on the engine's stream; ``net`` may then be None and ``depth`` must be 0.  A player with a true attribute
+    ``takes_active`` (:class:`DeepPlayer`) is called as ``player(engine, actions, active=left)`` with the uint32 ``[n]`` tensor
+    of the games each board still owes, 0 for a board that rests.  Either way the loop runs
     ``chunk`` moves between two host reads.  A board that has finished its games rests, so short games are not
     over-weighted the way counting every episode of a fixed step budget over-weights them.  ``max_steps``: stop after at
     least that many steps per board (a multiple of ``chunk``) and report what is missing as ``unfinished``.  The engine's
@@ -766,12 +813,15 @@ def play_games(engine, net, games=1, chunk=1024, max_steps=None, depth=0, player
     moves = torch.zeros(1, dtype=torch.int64, device=dev).view(torch.uint64)
     before, steps = engine.episode_stats(), 0
     act = torch.empty(n, dtype=torch.uint8, device=dev) if player is not None or depth else None
+    takes_active = bool(getattr(player, "takes_active", False))
     while max_steps is None or steps < max_steps:
         if act is None:
             engine.ntuple_play(net, chunk, games_left=left, hist=hist, moves=moves)
         else:
             for _ in range(chunk):        # (a chunk that outlives every game steps resting boards: launches, no work)
-                if player is not None:
+                if takes_active:
+                    player(engine, act, active=left)
+                elif player is not None:
                     player(engine, act)
                 else:
                     engine.ntuple_search(net, depth, out=NTupleSearch(act, None), active=left)

@@ -608,6 +608,38 @@ int g2048_ntuple_staged_tc_trace_update(uint64_t n, const int64_t *delta, uint32
  * and the thresholds only: net->net.weights may be NULL. */
 int g2048_ntuple_stage_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net, uint8_t *stage, void *stream);
 
+/* N-tuple deep search: the search of the n-tuple expectimax block above at depth 2..3, by a kernel that gives every board a
+ * whole workgroup.  3-ply is the row the n-tuple papers lead with; g2048_ntuple_search stops at depth 2
+ * because its kernel walks a chance item on one lane, and at depth 3 an item is a whole depth-2 tree.  The definition is
+ * unchanged -- A_k, S_k, value, action, the floor division, G2048_NTUPLE_ILLEGAL, and how boards are read (byte & 0x1f of an
+ * engine record, exponents mod 32 of a plain board) -- with D = depth in G2048_NTUPLE_DEEP_MIN_DEPTH..G2048_NTUPLE_DEEP_MAX_DEPTH.
+ * Depth 2 is allowed on purpose: it gives the bits of g2048_ntuple_search at depth 2.  Bounds at depth 3: |V| <= 2^37, and a
+ * value is V plus at most four gains << F (gain < 2^31, F <= 16), so |value| < 4 * 2^47 + 2^37 < 2^50; the weights of a chance
+ * node add up to 10 E <= 150, so every partial sum stays below 150 * 2^50 < 2^58 in an int64, in any split.
+ * Each call is one launch on `stream` and writes nothing but the outputs: records, clock, episode bookkeeping, randomness and
+ * cached graphs are untouched, in either RNG mode.  Uniform, mixed-length and staged networks, T = 1..8.  Cost: the leaves of
+ * a depth-3 tree number up to about 2 * 10^6 on a nearly empty board and 10^4..10^5 on a board with 1..6 empty cells; mask
+ * out the boards that need no search. */
+#define G2048_NTUPLE_DEEP_MIN_DEPTH 2
+#define G2048_NTUPLE_DEEP_MAX_DEPTH 3
+typedef struct g2048_ntuple_deep_io {
+    uint32_t depth;          /* G2048_NTUPLE_DEEP_MIN_DEPTH..G2048_NTUPLE_DEEP_MAX_DEPTH */
+    uint8_t *action;         /* [n], or NULL */
+    int64_t *value;          /* [n][4], 16-byte aligned, or NULL */
+    const uint32_t *active;  /* [n] in device memory, 4-byte aligned, or NULL; engine forms only (G2048_ERR_INVALID with a
+                              * plain form): a board at 0 is not searched and gets the outputs of a board with no legal
+                              * move, action 0 and value G2048_NTUPLE_ILLEGAL four times, as g2048_ntuple_search_active */
+} g2048_ntuple_deep_io;
+/* At least one of action and value must be given.  The plain forms: n plain boards (uint8[n][16] exponents, device memory,
+ * 16-byte aligned), no engine, the current device, 1 <= n <= 2^32 - 256. */
+int g2048_ntuple_deep_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_deep_io *io, void *stream);
+int g2048_ntuple_deep_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_deep_io *io,
+                                   void *stream);
+int g2048_ntuple_staged_deep_search(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_deep_io *io,
+                                    void *stream);
+int g2048_ntuple_staged_deep_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
+                                          const g2048_ntuple_deep_io *io, void *stream);
+
 /* Carousel shaping: stage-balanced restarts for training a staged network (Jaskowski 2017).  Every
  * episode starts from an empty board, so the weight sets of the late stages see only the rare boards that live that long.
  * A carousel remembers, per stage, the boards on which recent episodes ENTERED that stage, and starts new episodes from
