@@ -18,7 +18,8 @@ def __getattr__(name):
     if name in ("Batched2048", "afterstates", "Afterstates", "expectimax", "Search", "SearchWeights", "mc_search",
                 "MCSearch", "NTupleNet", "NTupleEval", "NTupleSearch", "td_step", "train", "NTupleTC", "tc_update", "tc_step",
                 "tc_train", "NTupleTrace", "tdl_evaluate", "tdl_step", "tdl_train", "tcl_step",
-                "tcl_train", "Carousel", "PlayReport", "play_games", "DeepPlayer"):  # need torch + a GPU; imported on first use
+                "tcl_train", "NTupleDelay", "delayed_evaluate", "delayed_tdl_step", "delayed_tdl_train", "delayed_tcl_step",
+                "delayed_tcl_train", "Carousel", "PlayReport", "play_games", "DeepPlayer"):  # need torch + a GPU; imported on first use
         from . import batched
         return getattr(batched, name)
     raise AttributeError(name)

@@ -167,6 +167,17 @@ class NTupleTraceC(C.Structure):
     ]
 
 
+class NTupleDelayC(C.Structure):
+    """g2048_ntuple_delay (include/g2048.h): the trace history plus the accumulators of the delayed learners."""
+    _fields_ = [
+        ("depth", C.c_uint32),
+        ("lambda_", C.c_uint32),
+        ("hist", C.c_void_p),
+        ("len", C.c_void_p),
+        ("acc", C.c_void_p),
+    ]
+
+
 class CarouselC(C.Structure):
     """g2048_carousel (include/g2048.h): S, the thresholds, the ring size, the seed and the device state of a carousel."""
     _fields_ = [
@@ -260,6 +271,11 @@ SIGNATURES = {
     "g2048_ntuple_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, C.POINTER(NTupleNetC), C.POINTER(NTupleTraceC), _u32, _S]),
     "g2048_ntuple_tc_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleNetC), C.POINTER(NTupleTCC),
                                               C.POINTER(NTupleTraceC), _u32, _S]),
+    "g2048_ntuple_delay_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64, C.POINTER(NTupleDelayC), _u32,
+                                         C.c_void_p, _S]),
+    "g2048_ntuple_delay_update": (C.c_int, [_u64, _u32, _u32, C.POINTER(NTupleNetC), C.POINTER(NTupleDelayC), _u32, _S]),
+    "g2048_ntuple_tc_delay_update": (C.c_int, [_u64, _u32, _u32, _u32, C.POINTER(NTupleNetC), C.POINTER(NTupleTCC),
+                                              C.POINTER(NTupleDelayC), _u32, _S]),
     "g2048_ntuple_staged_evaluate": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleIO), _S]),
     "g2048_ntuple_staged_evaluate_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleIO), _S]),
     "g2048_ntuple_staged_search": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleSearchIO), _S]),
@@ -273,6 +289,9 @@ SIGNATURES = {
                                                   _u32, _S]),
     "g2048_ntuple_staged_tc_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleStagedNetC),
                                                      C.POINTER(NTupleTCC), C.POINTER(NTupleTraceC), _u32, _S]),
+    "g2048_ntuple_staged_delay_update": (C.c_int, [_u64, _u32, _u32, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleDelayC), _u32, _S]),
+    "g2048_ntuple_staged_tc_delay_update": (C.c_int, [_u64, _u32, _u32, _u32, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleTCC),
+                                                     C.POINTER(NTupleDelayC), _u32, _S]),
     "g2048_ntuple_stage_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.c_void_p, _S]),
     "g2048_carousel_scratch_bytes": (_u64, [_u64]),
     "g2048_carousel_step": (C.c_int, [_E, C.POINTER(CarouselC), C.c_void_p, _S]),

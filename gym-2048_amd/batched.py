@@ -24,6 +24,7 @@ from .analysis import (MC_DEFAULT_MAX_STEPS, Afterstates, MCSearch, Search, Sear
 from .ntuple import NTupleEval, NTupleNet, NTupleSearch, TUPLES, stage_mask, td_step, train, _eval_io  # noqa: F401
 from .ntuple import NTupleTC, tc_step, tc_train, tc_update  # noqa: F401
 from .ntuple import NTupleTrace, tcl_step, tcl_train, tdl_evaluate, tdl_step, tdl_train  # noqa: F401
+from .ntuple import NTupleDelay, delayed_evaluate, delayed_tcl_step, delayed_tcl_train, delayed_tdl_step, delayed_tdl_train  # noqa: F401
 from .ntuple import Carousel  # noqa: F401
 from .ntuple import _search_io as _ntuple_search_io
 from .ntuple import DeepPlayer, _deep_io as _ntuple_deep_io  # noqa: F401

@@ -1377,6 +1377,41 @@ static int ntuple_trace(const g2048_ntuple_trace *tr, uint32_t slot, g2048::Ntup
     return G2048_OK;
 }
 
+// g2048_ntuple_delay and a slot -> the launchers' ring, or G2048_ERR_INVALID (before any HIP call: works without a device)
+static int ntuple_delay(const g2048_ntuple_delay *dl, uint32_t slot, g2048::NtupleDelay *out)
+{
+    if (!dl)
+        return fail(G2048_ERR_INVALID, "dl is NULL");
+    if (!dl->hist)
+        return fail(G2048_ERR_INVALID, "delay hist is NULL");
+    if (!dl->len)
+        return fail(G2048_ERR_INVALID, "delay len is NULL");
+    if (!dl->acc)
+        return fail(G2048_ERR_INVALID, "delay acc is NULL");
+    if (dl->depth < 1 || dl->depth > G2048_NTUPLE_TRACE_MAX)
+        return fail(G2048_ERR_INVALID, "depth=%u: need 1 <= depth <= %d", dl->depth, G2048_NTUPLE_TRACE_MAX);
+    if (dl->lambda > 65536u)
+        return fail(G2048_ERR_INVALID, "lambda=%u: need 0 <= lambda <= 65536 (Q16)", dl->lambda);
+    if (slot >= dl->depth)
+        return fail(G2048_ERR_INVALID, "slot=%u: need slot < depth=%u", slot, dl->depth);
+    if (reinterpret_cast<uintptr_t>(dl->hist) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: delay hist needs 16 bytes");
+    if (reinterpret_cast<uintptr_t>(dl->acc) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: delay acc needs 8 bytes");
+    *out = g2048::NtupleDelay{dl->depth, dl->lambda, reinterpret_cast<uint4 *>(dl->hist), dl->len, dl->acc};
+    return G2048_OK;
+}
+
+// lr_shift and mode of a delay update
+static int ntuple_delay_mode(uint32_t lr_shift, uint32_t mode)
+{
+    if (lr_shift > G2048_NTUPLE_MAX_LR_SHIFT)
+        return fail(G2048_ERR_INVALID, "lr_shift=%u: need 0 <= lr_shift <= %d", lr_shift, G2048_NTUPLE_MAX_LR_SHIFT);
+    if (mode > G2048_NTUPLE_DELAY_FLUSH)
+        return fail(G2048_ERR_INVALID, "mode=%u: need G2048_NTUPLE_DELAY_STEP (0) or G2048_NTUPLE_DELAY_FLUSH (1)", mode);
+    return G2048_OK;
+}
+
 // delta and lr_shift of an update, as g2048_ntuple_update_plain checks them
 static int ntuple_delta(const int64_t *delta, uint32_t lr_shift)
 {
@@ -1657,6 +1692,45 @@ static int ntuple_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_
     return G2048_OK;
 }
 
+template <class Net>
+static int ntuple_delay_update(uint64_t n, uint32_t lr_shift, uint32_t mode, const Net *net, const g2048_ntuple_delay *dl, uint32_t slot,
+                               void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (int rc = trace_boards(n))
+        return rc;
+    if (int rc = ntuple_delay_mode(lr_shift, mode))
+        return rc;
+    g2048::NtupleDelay d;
+    if (int rc = ntuple_delay(dl, slot, &d))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_delay_update(static_cast<uint32_t>(n), lr_shift, mode, nn, d, slot, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+template <class Net>
+static int ntuple_tc_delay_update(uint64_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode, const Net *net,
+                                  const g2048_ntuple_tc *tc, const g2048_ntuple_delay *dl, uint32_t slot, void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (int rc = trace_boards(n))
+        return rc;
+    if (int rc = ntuple_delay_mode(lr_shift, mode))
+        return rc;
+    if (int rc = ntuple_tc(phases, tc))
+        return rc;
+    g2048::NtupleDelay d;
+    if (int rc = ntuple_delay(dl, slot, &d))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_tc_delay_update(static_cast<uint32_t>(n), lr_shift, phases, mode, nn, tc->err, tc->mag, d, slot,
+                                                   static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 extern "C" {
 
 int g2048_ntuple_evaluate(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_io *io, void *stream)
@@ -1876,6 +1950,58 @@ int g2048_ntuple_staged_tc_trace_update(uint64_t n, const int64_t *delta, uint32
                                         uint32_t slot, void *stream)
 {
     return ntuple_tc_trace_update(n, delta, lr_shift, phases, net, tc, tr, slot, stream);
+}
+
+int g2048_ntuple_delay_push(const uint8_t *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,
+                            uint64_t n, const g2048_ntuple_delay *dl, uint32_t slot, int64_t *delta, void *stream)
+{
+    if (!after)
+        return fail(G2048_ERR_INVALID, "after is NULL");
+    if (!after_value)
+        return fail(G2048_ERR_INVALID, "after_value is NULL");
+    if (!best_next)
+        return fail(G2048_ERR_INVALID, "best_next is NULL");
+    if (!terminated)
+        return fail(G2048_ERR_INVALID, "terminated is NULL");
+    if (!delta)
+        return fail(G2048_ERR_INVALID, "delta is NULL");
+    if (int rc = trace_boards(n))
+        return rc;
+    g2048::NtupleDelay d;
+    if (int rc = ntuple_delay(dl, slot, &d))
+        return rc;
+    if (reinterpret_cast<uintptr_t>(after) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: delay after needs 16 bytes");
+    if ((reinterpret_cast<uintptr_t>(after_value) | reinterpret_cast<uintptr_t>(best_next) | reinterpret_cast<uintptr_t>(delta)) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: delay after_value, best_next and delta need 8 bytes");
+    G2048_HIP(g2048::launch_ntuple_delay_push(reinterpret_cast<const uint4 *>(after), after_value, best_next, terminated,
+                                              static_cast<uint32_t>(n), d, slot, delta, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_ntuple_delay_update(uint64_t n, uint32_t lr_shift, uint32_t mode, const g2048_ntuple_net *net, const g2048_ntuple_delay *dl,
+                              uint32_t slot, void *stream)
+{
+    return ntuple_delay_update(n, lr_shift, mode, net, dl, slot, stream);
+}
+
+int g2048_ntuple_staged_delay_update(uint64_t n, uint32_t lr_shift, uint32_t mode, const g2048_ntuple_staged_net *net,
+                                     const g2048_ntuple_delay *dl, uint32_t slot, void *stream)
+{
+    return ntuple_delay_update(n, lr_shift, mode, net, dl, slot, stream);
+}
+
+int g2048_ntuple_tc_delay_update(uint64_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode, const g2048_ntuple_net *net,
+                                 const g2048_ntuple_tc *tc, const g2048_ntuple_delay *dl, uint32_t slot, void *stream)
+{
+    return ntuple_tc_delay_update(n, lr_shift, phases, mode, net, tc, dl, slot, stream);
+}
+
+int g2048_ntuple_staged_tc_delay_update(uint64_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode,
+                                        const g2048_ntuple_staged_net *net, const g2048_ntuple_tc *tc, const g2048_ntuple_delay *dl,
+                                        uint32_t slot, void *stream)
+{
+    return ntuple_tc_delay_update(n, lr_shift, phases, mode, net, tc, dl, slot, stream);
 }
 
 // g2048_carousel and the records of a call -> the launcher's arguments, or G2048_ERR_INVALID (before any HIP call: works

@@ -1251,6 +1251,106 @@ G2048_DEV void ntuple_item_tc_accum(const Items &items, const int64_t *delta, ty
         ntuple_tc_accum<T>(items.packed(it), sh, d, add);
 }
 
+// n-tuple delay (g2048_ntuple_delay_push / g2048_ntuple_delay_update / g2048_ntuple_tc_delay_update, include/g2048.h,
+// INTEGRATION.md §19; the delayed TD(lambda) and TC(lambda) of Jaskowski 2017): the errors an afterstate earns over the H
+// pushes after its own are collected in a per-board accumulator and applied to the tables ONCE, when the afterstate leaves
+// the ring or its episode ends -- one board's worth of adds per board per step whatever H is, where a trace update issues up
+// to H.  The delay ring is the trace ring plus accumulators, caller-owned, zero-initialised, one per engine or shard:
+//   H, lam, hist, len   as for the traces
+//   acc   int64 [H][n]  slot-major, 8-byte aligned: the error collected so far by the afterstate in that slot
+// delay push(slot), for every board i (the caller advances slot by one mod H first, as for the trace push):
+//   l = ntuple_trace_kept(len[i], H);   L = min(l + 1, H)
+//   hist[slot][i], delta[i], len[i]     exactly as the trace push writes them
+//   d = ntuple_tc_delta(delta[i])
+//   acc[slot][i] = d                                                                    (k = 0: overwritten, never added to)
+//   for k in 1..L-1:  acc[ntuple_trace_slot(slot, k, H)][i] += ntuple_trace_dk(d, ntuple_trace_decay(lam, k))
+// |acc| <= 8 * 2^40 = 2^43.  Push is total for any len byte.  An accumulator is written by its board's lane only: no atomics.
+// delay update(slot, mode), slot that of the last push, one work item per (k, i), k < L = min(len[i] & 0x7f, H),
+// ended = len[i] & 0x80:
+//   mode kNtupleDelayStep  (after every push):           the item is due iff  ended  or  k == H-1
+//   mode kNtupleDelayFlush (once, when training stops):  the item is due iff  !ended and k != H-1
+//   a due item:  D = ntuple_tc_delta(acc[ntuple_trace_slot(slot, k, H)][i]);   a = hist[the same slot][i]
+//     TD:    step = ntuple_step(D, lr_shift);  ntuple_update(a, step);  a zero step touches nothing
+//     TC W:  ntuple_tc_weights(a, D, ...), err and mag as before the call;   TC A:  ntuple_tc_accum(a, D);   D == 0 touches nothing
+// The update writes nothing to the ring.  FLUSH is defined for the state right after a STEP update, and the caller zeroes len
+// behind it; FLUSH twice, or FLUSH without the STEP update before it, applies errors twice or not at all.  Over any pushes
+// with STEP updates and one FLUSH every pushed afterstate a_t is applied exactly once, with the total
+// sum over k = 0..m of (clamp(delta_{t+k}) * p_k) >> 16, m ending at H-1, at the first push that terminated or at the last
+// push.  The table updates are sums of integer adds from launches that read no entry they write (W and A stay separate
+// launches): the same bits for any lane, wave, block, launch geometry or shard split.  H = 1 is the trace update at H = 1.
+constexpr uint32_t kNtupleDelayStep = 0, kNtupleDelayFlush = 1; // = G2048_NTUPLE_DELAY_STEP, G2048_NTUPLE_DELAY_FLUSH (g2048.h)
+
+// The accumulator pass of push for one board: L as push forms it (1..H), d = ntuple_tc_delta(delta), acc(plane) a reference to
+// the board's accumulator in that plane.  The L-1 read-modify-writes are independent: all loads, then all stores.  p_k by at
+// most kNtupleTraceMax - 1 multiplies.
+template <class Acc> G2048_DEV void ntuple_delay_collect(uint32_t L, int64_t d, uint32_t lam, uint32_t slot, uint32_t H, Acc acc)
+{
+    int64_t old[kNtupleTraceMax - 1u];
+#pragma unroll
+    for (uint32_t k = 1; k < kNtupleTraceMax; ++k)
+        if (k < L)
+            old[k - 1u] = acc(ntuple_trace_slot(slot, k, H));
+    uint64_t p = kNtupleTcOne;
+#pragma unroll
+    for (uint32_t k = 1; k < kNtupleTraceMax; ++k) {
+        p = (p * lam) >> 16; // = ntuple_trace_decay(lam, k)
+        if (k < L)
+            acc(ntuple_trace_slot(slot, k, H)) = old[k - 1u] + ntuple_trace_dk(d, static_cast<uint32_t>(p));
+    }
+    acc(slot) = d;
+}
+
+// One board of the delay push, after its afterstate is stored: returns delta[i] and updates the len byte and the accumulators.
+template <class Acc>
+G2048_DEV int64_t ntuple_delay_push(uint8_t &len_i, int64_t best_next, int64_t after_value, bool terminated, uint32_t lam, uint32_t slot,
+                                    uint32_t H, Acc acc)
+{
+    const uint32_t L = ntuple_trace_kept(len_i, H) + 1u; // <= H + 1; collect needs min(L, H)
+    const int64_t delta = ntuple_trace_delta(best_next, after_value, terminated);
+    len_i = static_cast<uint8_t>(ntuple_trace_push_len(len_i, H, terminated));
+    ntuple_delay_collect(L < H ? L : H, ntuple_tc_delta(delta), lam, slot, H, acc);
+    return delta;
+}
+
+// whether item (k, i) of a delay update has something to apply in this mode; len_i is its only load so far
+G2048_DEV bool ntuple_delay_due(uint32_t len_i, uint32_t k, uint32_t H, uint32_t mode)
+{
+    if (k >= ntuple_trace_len(len_i, H))
+        return false;
+    const bool leaving = (len_i & kNtupleTraceEnded) != 0u || k + 1u == H;
+    return leaving != (mode == kNtupleDelayFlush);
+}
+
+// The third item source: item k * n + i = the afterstate of board i that is k pushes old, as NtupleTraceItems, but what it
+// applies is the accumulator of that slot and only when the item is due.  The accumulators arrive through the `delta`
+// argument of the item operations -- acc, the base of plane 0 -- so the kernels keep one signature for the three sources
+// (as a member the compiler's report is the same: profiles/r22_ntuple_delay_resource_usage.txt).  Item index, slot base of
+// hist and plane base of acc are 64-bit.
+struct NtupleDelayItems {
+    const uint4 *hist;  // [H][n] boards
+    const uint8_t *len; // [n]
+    uint32_t n, H, slot, mode; // slot: that of the last push
+    using Item = NtupleTraceItems::Item;
+    G2048_MEMBER uint64_t size() const { return static_cast<uint64_t>(H) * n; }
+    G2048_MEMBER Item at(uint64_t index) const
+    {
+        Item it;
+        ntuple_trace_split(index, n, H, it.k, it.i);
+        return it;
+    }
+    G2048_MEMBER int64_t td_delta(const int64_t *acc, Item it) const
+    {
+        if (!ntuple_delay_due(len[it.i], it.k, H, mode))
+            return 0;
+        return ntuple_tc_delta(acc[static_cast<uint64_t>(ntuple_trace_slot(slot, it.k, H)) * n + it.i]);
+    }
+    G2048_MEMBER int64_t tc_delta(const int64_t *acc, Item it) const { return td_delta(acc, it); }
+    G2048_MEMBER uint64_t packed(Item it) const
+    {
+        return ntuple_pack(load_board(hist + static_cast<uint64_t>(ntuple_trace_slot(slot, it.k, H)) * n, it.i));
+    }
+};
+
 // ------------------------------------------------------------------- n-tuple expectimax
 // g2048_ntuple_search (include/g2048.h): the expectimax of above with the network at the leaves.
 // Integers only, so every split of the tree across lanes gives the same bits.  With V, move(b, d) = (a_d, g_d, legal)

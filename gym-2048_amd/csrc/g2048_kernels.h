@@ -176,6 +176,22 @@ hipError_t launch_ntuple_trace_update(uint32_t n, const int64_t *delta, uint32_t
 // phases as in launch_ntuple_tc_update: W, then A, a launch each
 hipError_t launch_ntuple_tc_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const NtupleNet &net,
                                          int64_t *err, int64_t *mag, const NtupleTrace &tr, uint32_t slot, hipStream_t s);
+// g2048_ntuple_delay_*: the delay ring (g2048_ntuple_delay), checked by the caller as the history above; mode is
+// kNtupleDelayStep or kNtupleDelayFlush (g2048_device.h)
+struct NtupleDelay {
+    uint32_t depth, lambda;
+    uint4 *hist;  // [depth][n] plain boards
+    uint8_t *len; // [n]
+    int64_t *acc; // [depth][n]
+};
+hipError_t launch_ntuple_delay_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next,
+                                    const uint8_t *terminated, uint32_t n, const NtupleDelay &dl, uint32_t slot, int64_t *delta,
+                                    hipStream_t s);
+hipError_t launch_ntuple_delay_update(uint32_t n, uint32_t lr_shift, uint32_t mode, const NtupleNet &net, const NtupleDelay &dl,
+                                      uint32_t slot, hipStream_t s);
+// phases as in launch_ntuple_tc_update: W, then A, a launch each
+hipError_t launch_ntuple_tc_delay_update(uint32_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode, const NtupleNet &net,
+                                         int64_t *err, int64_t *mag, const NtupleDelay &dl, uint32_t slot, hipStream_t s);
 // g2048_carousel_step: the carousel (g2048_carousel) and the records it works on, both checked by the caller
 struct CarouselArgs {
     uint4 *records;            // [n] engine records, restarted in place

@@ -1828,10 +1828,11 @@ __global__ void __launch_bounds__(kBlock) play_step_kernel(const StepArgs p, con
     }
 }
 
-// The six updates (g2048_ntuple_update_plain, g2048_ntuple_tc_update_plain, g2048_ntuple_trace_update,
-// g2048_ntuple_tc_trace_update; the definitions of g2048_device.h, "n-tuple network value function", "Temporal-coherence
-// learning" and "n-tuple traces") are three kernels, each over either item source of g2048_device.h ("The work items of an
-// update"): NtupleBoardItems, one board per item, or NtupleTraceItems, one (k, i) per item.  A kernel is the header's item
+// The nine updates (g2048_ntuple_update_plain, g2048_ntuple_tc_update_plain, g2048_ntuple_trace_update,
+// g2048_ntuple_tc_trace_update, g2048_ntuple_delay_update, g2048_ntuple_tc_delay_update; the definitions of g2048_device.h,
+// "n-tuple network value function", "Temporal-coherence learning", "n-tuple traces" and "n-tuple delay") are three kernels,
+// each over one of the item sources of g2048_device.h ("The work items of an update"): NtupleBoardItems, one board per item,
+// NtupleTraceItems or NtupleDelayItems, one (k, i) per item.  A kernel is the header's item
 // loop and per-item operation with an atomic add: relaxed, agent scope, its result read by nobody (fire and forget).
 // Integer adds commute, so the tables after a launch do not depend on the order the lanes, waves or launches arrive in.
 // A lane takes the items lane, lane + grid, ...: the grid is capped at kSearchMaxLanes.  delta is an argument of its own, and
@@ -1912,6 +1913,28 @@ __global__ void __launch_bounds__(kBlock) ntuple_trace_push_kernel(const uint4 *
         store_board(slot_boards, static_cast<uint32_t>(i), load_board(after, static_cast<uint32_t>(i)));
         delta[i] = ntuple_trace_delta(best_next[i], after_value[i], term);
         len[i] = static_cast<uint8_t>(ntuple_trace_push_len(len[i], H, term));
+    }
+}
+
+// g2048_ntuple_delay_push (the definition of g2048_device.h, "n-tuple delay"): ntuple_trace_push_kernel plus the accumulator
+// pass, one board per lane, striding past the grid cap.  A lane reads and writes only its own board's accumulators -- up to
+// H - 1 8-byte loads issued together, then as many stores, one per plane, each coalesced over the wave -- so there are no
+// atomics here.  `acc` is the base of plane 0; the plane base plane * n is formed in 64 bits.
+__global__ void __launch_bounds__(kBlock) ntuple_delay_push_kernel(const uint4 *__restrict__ after,
+                                                                   const int64_t *__restrict__ after_value,
+                                                                   const int64_t *__restrict__ best_next,
+                                                                   const uint8_t *__restrict__ terminated, uint32_t n, uint32_t H,
+                                                                   uint32_t lam, uint32_t slot, uint4 *__restrict__ slot_boards,
+                                                                   uint8_t *__restrict__ len, int64_t *__restrict__ acc,
+                                                                   int64_t *__restrict__ delta)
+{
+    const uint32_t stride = gridDim.x * kBlock;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
+        store_board(slot_boards, static_cast<uint32_t>(i), load_board(after, static_cast<uint32_t>(i)));
+        uint8_t l = len[i];
+        delta[i] = ntuple_delay_push(l, best_next[i], after_value[i], terminated[i] != 0, lam, slot, H,
+                                     [&](uint32_t plane) -> int64_t & { return acc[static_cast<uint64_t>(plane) * n + i]; });
+        len[i] = l;
     }
 }
 
@@ -2864,6 +2887,27 @@ hipError_t launch_ntuple_tc_trace_update(uint32_t n, const int64_t *delta, uint3
 {
     return launch_items_tc_update(NtupleTraceItems{tr.hist, tr.len, n, tr.depth, tr.lambda, slot}, delta, lr_shift, phases, net, err,
                                   mag, s);
+}
+
+hipError_t launch_ntuple_delay_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next,
+                                    const uint8_t *terminated, uint32_t n, const NtupleDelay &dl, uint32_t slot, int64_t *delta,
+                                    hipStream_t s)
+{
+    return launch_1d(ntuple_delay_push_kernel, group_lanes(n, 1u), 0, s, after, after_value, best_next, terminated, n, dl.depth,
+                     dl.lambda, slot, dl.hist + static_cast<uint64_t>(slot) * n, dl.len, dl.acc, delta);
+}
+
+// the accumulators go where the other sources' delta goes (NtupleDelayItems, g2048_device.h)
+hipError_t launch_ntuple_delay_update(uint32_t n, uint32_t lr_shift, uint32_t mode, const NtupleNet &net, const NtupleDelay &dl,
+                                      uint32_t slot, hipStream_t s)
+{
+    return launch_items_update(NtupleDelayItems{dl.hist, dl.len, n, dl.depth, slot, mode}, dl.acc, lr_shift, net, s);
+}
+
+hipError_t launch_ntuple_tc_delay_update(uint32_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode, const NtupleNet &net,
+                                         int64_t *err, int64_t *mag, const NtupleDelay &dl, uint32_t slot, hipStream_t s)
+{
+    return launch_items_tc_update(NtupleDelayItems{dl.hist, dl.len, n, dl.depth, slot, mode}, dl.acc, lr_shift, phases, net, err, mag, s);
 }
 
 hipError_t launch_carousel_step(const CarouselArgs &a, hipStream_t s)

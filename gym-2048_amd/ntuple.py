@@ -9,6 +9,9 @@ per update.  Everything is an integer: the same bits however the batch is split 
 (``g2048_ntuple_tc_update_plain``).  ``NTupleTrace`` and ``tdl_step`` / ``tdl_train`` / ``tcl_step`` /
 ``tcl_train`` are the multi-step forms, TD(lambda) and TC(lambda): the error of a step also moves, decayed, the last few
 afterstates of the same board (``g2048_ntuple_trace_*``).
+``NTupleDelay`` and ``delayed_tdl_step`` / ``delayed_tdl_train`` / ``delayed_tcl_step`` / ``delayed_tcl_train`` are the delayed
+forms of those two (Jaskowski 2017): the errors an afterstate earns are collected per board and applied to the tables once,
+when it leaves the ring (``g2048_ntuple_delay_*``).
 ``NTupleNet.search`` / ``Batched2048.ntuple_search`` play the network through a depth-1..2 expectimax
 (``g2048_ntuple_search``), one launch for the whole batch.
 ``NTupleNet.deep_search`` / ``Batched2048.ntuple_deep_search`` are the same search at depth 2..3 from a kernel that gives a
@@ -35,7 +38,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import CarouselC, NTupleDeepIO, NTupleIO, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTraceC, check
+from ._lib import CarouselC, NTupleDeepIO, NTupleDelayC, NTupleIO, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTraceC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
@@ -44,6 +47,7 @@ SEARCH_MAX_DEPTH = 2                                              # G2048_NTUPLE
 DEEP_MIN_DEPTH, DEEP_MAX_DEPTH = 2, 3                             # G2048_NTUPLE_DEEP_MIN_DEPTH, G2048_NTUPLE_DEEP_MAX_DEPTH
 TC_WEIGHTS, TC_ACCUM = 1, 2                                       # G2048_NTUPLE_TC_WEIGHTS, G2048_NTUPLE_TC_ACCUM
 TRACE_MAX = 8                                                     # G2048_NTUPLE_TRACE_MAX
+DELAY_STEP, DELAY_FLUSH = 0, 1                                    # G2048_NTUPLE_DELAY_STEP, G2048_NTUPLE_DELAY_FLUSH
 MAX_STAGES = 8                                                    # G2048_NTUPLE_MAX_STAGES
 CAROUSEL_MAX_CAPACITY = 65536                                     # G2048_CAROUSEL_MAX_CAPACITY
 NTUPLE_END = 0xff                                                 # G2048_NTUPLE_END: pads a cell list shorter than tuple_len
@@ -411,6 +415,37 @@ class NTupleNet:
         _on_stream(self._fn("tc_trace_update"), trace.device, trace.n, delta.data_ptr(), shift, phases, net, C.byref(tc._c),
                    C.byref(trace._c), trace.slot)
 
+    def _delay_args(self, delay, lr_shift, flush):
+        """(net, lr_shift, mode) for a delay update: ``delay`` checked as :meth:`trace_update` checks its trace."""
+        if not isinstance(delay, NTupleDelay):
+            raise ValueError("delay must be an NTupleDelay")
+        net = self._ref(delay.device)
+        if not isinstance(flush, (bool, int)) or int(flush) not in (DELAY_STEP, DELAY_FLUSH):
+            raise ValueError(f"flush must be False (the step update) or True (the flush), not {flush!r}")
+        return net, _int_arg("lr_shift", lr_shift, 0, MAX_LR_SHIFT), int(flush)
+
+    def delay_update(self, delay, lr_shift, flush=False):
+        """The delayed TD(lambda) update (``g2048_ntuple_delay_update``): :meth:`update` of every
+        afterstate of ``delay`` (an :class:`NTupleDelay`) that is due, with the error it has collected, clamped to
+        +-2^40.  ``flush=False`` is the update after every push: due are the afterstate that leaves the ring at the next push
+        and every afterstate of a board whose episode ended at the last push.  ``flush=True`` applies what is still pending,
+        once, right after a step update and before ``delay.reset()``; twice, or without that step update, errors are
+        applied twice or not at all.  One launch of integer atomic adds.  Measured (profiles/r22_ntuple_delay_probe.txt): at
+        2^20 boards and H = 4 it takes 1.08 to 1.2 times the one-step update where the trace update takes 4.2 to 4.4 times; at
+        1 024 boards a training step is bound by launch issue and the delayed trainers are not faster end to end."""
+        net, shift, mode = self._delay_args(delay, lr_shift, flush)
+        _on_stream(self._fn("delay_update"), delay.device, delay.n, shift, mode, net, C.byref(delay._c), delay.slot)
+
+    def tc_delay_update(self, delay, lr_shift, tc, phases=3, flush=False):
+        """The delayed TC(lambda) update (``g2048_ntuple_tc_delay_update``): :meth:`tc_update` of every
+        due afterstate of ``delay`` with its collected error; ``flush`` as in :meth:`delay_update`.  ``phases=3`` is two
+        launches, W then A; shards that share the network run W on every shard, then A on every shard."""
+        net, shift, mode = self._delay_args(delay, lr_shift, flush)
+        phases = _int_arg("phases", phases, TC_WEIGHTS, TC_WEIGHTS | TC_ACCUM)
+        self._own_tc(tc)
+        _on_stream(self._fn("tc_delay_update"), delay.device, delay.n, shift, phases, mode, net, C.byref(tc._c), C.byref(delay._c),
+                   delay.slot)
+
     def state_dict(self):
         return {"tuples": self.tuples, "frac_bits": self.frac_bits, "stages": self.stages, "weights": self.weights.clone()}
 
@@ -512,6 +547,67 @@ class NTupleTrace:
         slot = _int_arg("state_dict slot", state["slot"], 0, self.depth - 1)
         self.hist.copy_(hist)
         self.len.copy_(ln)
+        self.slot = slot
+
+
+class NTupleDelay:
+    """The delay ring of the delayed learners for ``n`` boards (``g2048_ntuple_delay``): the ``hist`` and
+    ``len`` of an :class:`NTupleTrace`, plus ``acc``, int64 ``[H, n]``, the error every afterstate of the ring has collected
+    so far, and the slot of the last push.  ``depth`` (H) in 1..8, ``lam`` a float in 0..1 stored as
+    ``lam_q16 = round(lam * 65536)``.  One per engine or shard.  An afterstate is applied to the tables once, by
+    ``NTupleNet.delay_update`` / ``tc_delay_update``, when it leaves the ring or its episode ends; before the ring is dropped
+    or :meth:`reset`, the pending errors are applied by one update with ``flush=True`` (the ``delayed_*_train`` functions
+    do that).
+
+    Memory: 24 H + 1 bytes per board."""
+
+    def __init__(self, n, depth=4, lam=0.5, device="cuda:0"):
+        self.n = _int_arg("n", n, 1, 0xffffff00)
+        self.depth = _int_arg("depth", depth, 1, TRACE_MAX)
+        if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0.0 <= lam <= 1.0:
+            raise ValueError(f"lam must be a number in 0..1, not {lam!r}")
+        self.lam_q16 = int(round(lam * 65536))
+        self.device = torch.device(device)
+        self.hist = torch.zeros((self.depth, self.n, 16), dtype=torch.uint8, device=self.device)
+        self.len = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        self.acc = torch.zeros((self.depth, self.n), dtype=torch.int64, device=self.device)
+        self.slot = self.depth - 1                      # the slot of the last push: the first push goes into slot 0
+        self._c = NTupleDelayC(self.depth, self.lam_q16, self.hist.data_ptr(), self.len.data_ptr(), self.acc.data_ptr())
+
+    def reset(self):
+        """Forget every board's history (``len`` = 0), pending errors included: flush first.  The slot counter keeps running."""
+        self.len.zero_()
+
+    def push(self, after, after_value, best_next, terminated, out):
+        """Advance the slot and push (``g2048_ntuple_delay_push``), one launch on the current stream: what
+        ``NTupleTrace.push`` does with the same arguments, and ``clamp(out)``, decayed, added to the accumulators of the
+        board's valid slots.  Returns ``out``."""
+        n, dev = self.n, self.device
+        for name, t, shape, dtypes in (("after", after, (n, 16), (torch.uint8,)), ("after_value", after_value, (n,), (torch.int64,)),
+                                       ("best_next", best_next, (n,), (torch.int64,)),
+                                       ("terminated", terminated, (n,), (torch.uint8, torch.bool)), ("out", out, (n,), (torch.int64,))):
+            _check_tensor(name, t, dtypes, shape, dev)
+        slot = (self.slot + 1) % self.depth
+        _on_stream(_lib.load().g2048_ntuple_delay_push, dev, after.data_ptr(), after_value.data_ptr(), best_next.data_ptr(),
+                   terminated.data_ptr(), n, C.byref(self._c), slot, out.data_ptr())
+        self.slot = slot
+        return out
+
+    def state_dict(self):
+        return {"depth": self.depth, "lam_q16": self.lam_q16, "slot": self.slot, "hist": self.hist.clone(), "len": self.len.clone(),
+                "acc": self.acc.clone()}
+
+    def load_state_dict(self, state):
+        """Copy the ring and the slot counter of a ``state_dict()`` of a delay of the same shape into this one (in place)."""
+        if int(state["depth"]) != self.depth or int(state["lam_q16"]) != self.lam_q16:
+            raise ValueError("state_dict is of a delay with another depth or lam")
+        new = {name: torch.as_tensor(state[name]) for name in ("hist", "len", "acc")}
+        for name, mine in (("hist", self.hist), ("len", self.len), ("acc", self.acc)):
+            if new[name].dtype != mine.dtype or new[name].shape != mine.shape:
+                raise ValueError(f"state_dict {name} must be {str(mine.dtype).replace('torch.', '')} {tuple(mine.shape)}")
+        slot = _int_arg("state_dict slot", state["slot"], 0, self.depth - 1)
+        for name, mine in (("hist", self.hist), ("len", self.len), ("acc", self.acc)):
+            mine.copy_(new[name])
         self.slot = slot
 
 
@@ -745,6 +841,59 @@ def tcl_train(engine, net, tc, trace, n_steps, lr_shift, carousel=None):
     work = td_work(engine)
     for _ in range(int(n_steps)):
         tcl_step(engine, net, tc, trace, lr_shift, work, carousel)
+    return net
+
+
+def _delay_of(engine, delay):
+    if not isinstance(delay, NTupleDelay) or delay.n != engine.n_envs or delay.device != engine.device:
+        raise ValueError(f"delay must be an NTupleDelay of {engine.n_envs} boards on {engine.device}")
+    return delay
+
+
+def delayed_evaluate(engine, net, delay, work, carousel=None) -> TDWork:
+    """:func:`tdl_evaluate` for the delayed learners: the same launches with ``delay.push`` (an :class:`NTupleDelay`) in place
+    of ``trace.push``.  Shards that share one network run this on every shard before an update on any."""
+    return tdl_evaluate(engine, net, _delay_of(engine, delay), work, carousel)
+
+
+def delayed_tdl_step(engine, net, delay, lr_shift, work=None, carousel=None) -> TDWork:
+    """One delayed TD(lambda) step of every board of ``engine`` under ``net``: :func:`delayed_evaluate`, then
+    ``net.delay_update``.  No host synchronisation; ``work`` (:func:`td_work`) is reused.  Errors stay pending in ``delay``:
+    see :func:`delayed_tdl_train`."""
+    work = delayed_evaluate(engine, net, _delay_of(engine, delay), td_work(engine) if work is None else work, carousel)
+    net.delay_update(delay, lr_shift)
+    return work
+
+
+def delayed_tdl_train(engine, net, delay, n_steps, lr_shift, carousel=None):
+    """``n_steps`` :func:`delayed_tdl_step` calls with one set of buffers, then the flush and ``delay.reset()``: no collected
+    error is lost, and the next call starts every board's history anew."""
+    _delay_of(engine, delay)
+    work = td_work(engine)
+    for _ in range(int(n_steps)):
+        delayed_tdl_step(engine, net, delay, lr_shift, work, carousel)
+    net.delay_update(delay, lr_shift, flush=True)
+    delay.reset()
+    return net
+
+
+def delayed_tcl_step(engine, net, tc, delay, lr_shift, work=None, carousel=None) -> TDWork:
+    """:func:`delayed_tdl_step` with the temporal-coherence update: :func:`delayed_evaluate`, then ``net.tc_delay_update``
+    (two launches, W then A)."""
+    work = delayed_evaluate(engine, net, _delay_of(engine, delay), td_work(engine) if work is None else work, carousel)
+    net.tc_delay_update(delay, lr_shift, tc)
+    return work
+
+
+def delayed_tcl_train(engine, net, tc, delay, n_steps, lr_shift, carousel=None):
+    """``n_steps`` :func:`delayed_tcl_step` calls with one set of buffers, then the flush and ``delay.reset()``, as
+    :func:`delayed_tdl_train`."""
+    _delay_of(engine, delay)
+    work = td_work(engine)
+    for _ in range(int(n_steps)):
+        delayed_tcl_step(engine, net, tc, delay, lr_shift, work, carousel)
+    net.tc_delay_update(delay, lr_shift, tc, flush=True)
+    delay.reset()
     return net
 
 

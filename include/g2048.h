@@ -516,6 +516,53 @@ int g2048_ntuple_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shif
 int g2048_ntuple_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const g2048_ntuple_net *net,
                                  const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr, uint32_t slot, void *stream);
 
+/* N-tuple delay: delayed TD(lambda) and TC(lambda) (Jaskowski 2017, "delayed temporal coherence
+ * learning").  A trace update issues up to H times the adds of the one-step update.  Here the error of a step is added to a
+ * small per-board accumulator for each of the last H afterstates -- private memory, no atomics -- and an afterstate's
+ * accumulated error is applied to the tables ONCE, when the afterstate leaves the ring or its episode ends: one board's
+ * worth of adds per board per step, whatever H is.  A learner of its own: it gives other weights than the trace update,
+ * because each weight moves later and is rounded once instead of H times.  Notation and helpers of the three blocks above.
+ * The delay ring is the trace history plus accumulators, caller-owned device memory, zero-initialised, one per engine or shard:
+ *   H, lam, hist, len   as in g2048_ntuple_trace
+ *   acc   int64 [H][n]  slot-major, 8-byte aligned: the error collected so far by the afterstate in that slot
+ * delay push(slot), for every board i.  The caller advances `slot` by one mod H before each push:
+ *   l = (len[i] & 0x80) ? 0 : min(len[i] & 0x7f, H);   L = min(l + 1, H)
+ *   hist[slot][i], delta[i], len[i]       exactly as g2048_ntuple_trace_push writes them
+ *   d = clamp(delta[i], -2^40, +2^40)
+ *   acc[slot][i] = d                                                       (k = 0: overwritten, never added to)
+ *   for k in 1..L-1:  acc[(slot + H - k) mod H][i] += (d * p_k) >> 16      (p_k and the shift as in the trace update)
+ * |acc| <= 8 * 2^40 = 2^43.  push is total for any byte in len.
+ * delay update(slot, mode), `slot` that of the last push, one work item per (k, i) with k < L = min(len[i] & 0x7f, H),
+ * ended = len[i] & 0x80:
+ *   mode G2048_NTUPLE_DELAY_STEP  (after every push):           the item is due iff  ended  or  k == H-1
+ *   mode G2048_NTUPLE_DELAY_FLUSH (once, when training stops):  the item is due iff  !ended and k != H-1
+ *   a due item:  D = clamp(acc[(slot + H - k) mod H][i], -2^40, +2^40);   a = hist[the same slot][i]
+ *     TD:    step = sat_int32(D >> lr_shift);  weights[off(a,s,t)] += step for all s, t;  a zero step touches nothing
+ *     TC W:  weights[j] += step(D, rate(err[j], mag[j]))  with err, mag as they were before the call
+ *     TC A:  err[j] += D;  mag[j] += |D|                                   D == 0 touches nothing
+ * The update writes nothing to the ring.  FLUSH is defined for the state right after a STEP update; the caller then zeroes
+ * len.  Calling FLUSH twice, or calling it without the STEP update of the last push, applies errors twice or not at all.
+ * Consequences: (1) over any pushes with STEP updates and one FLUSH, every pushed afterstate a_t is applied exactly once,
+ * with the total sum over k = 0..m of (clamp(delta_{t+k}) * p_k) >> 16, m ending at H-1, at the first push that terminated
+ * or at the last push; (2) H = 1 is g2048_ntuple_trace_update / g2048_ntuple_tc_trace_update at H = 1, bit for bit;
+ * (3) lam = 0, TD form, every |delta| <= 2^40: after the FLUSH the tables are those of g2048_ntuple_update_plain over all
+ * (a_t, delta_t), for any H; (4) shards that share a network each own a ring and run push everywhere, then update
+ * everywhere (for TC: W everywhere, then A everywhere), and get the bits of the unsharded run.  The accumulators are written
+ * by their own board's lane only and the table updates are sums of integer adds from launches that read no entry they
+ * write, so the result does not depend on lane, wave, block, launch geometry or shards. */
+#define G2048_NTUPLE_DELAY_STEP  0u
+#define G2048_NTUPLE_DELAY_FLUSH 1u
+typedef struct g2048_ntuple_delay { uint32_t depth; uint32_t lambda; uint8_t *hist; uint8_t *len; int64_t *acc; } g2048_ntuple_delay;
+/* One launch: the arguments of g2048_ntuple_trace_push; delta is written. */
+int g2048_ntuple_delay_push(const uint8_t *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,
+                            uint64_t n, const g2048_ntuple_delay *dl, uint32_t slot, int64_t *delta, void *stream);
+/* The TD delay update in one launch: lr_shift 0..40, mode G2048_NTUPLE_DELAY_STEP or G2048_NTUPLE_DELAY_FLUSH. */
+int g2048_ntuple_delay_update(uint64_t n, uint32_t lr_shift, uint32_t mode, const g2048_ntuple_net *net,
+                              const g2048_ntuple_delay *dl, uint32_t slot, void *stream);
+/* The TC delay update: phases = 1 (W), 2 (A) or 3, one launch per phase, W then A. */
+int g2048_ntuple_tc_delay_update(uint64_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode, const g2048_ntuple_net *net,
+                                 const g2048_ntuple_tc *tc, const g2048_ntuple_delay *dl, uint32_t slot, void *stream);
+
 /* N-tuple expectimax: a depth-1..2 search of every board with the network at the leaves, in one launch (INTEGRATION.md
  * §10) -- the player the n-tuple literature plays with.  Notation of the block above: net (T, L, F, cells, weights),
  * V(a) the sum over the 8 symmetries and T tuples, move(b, d) = (a_d, g_d, legal); cells are exponents, a cell is empty
@@ -584,7 +631,7 @@ typedef struct g2048_ntuple_staged_net {
     uint16_t thresholds[7];        /* first S-1 used, strictly ascending, >= 1; the rest ignored */
 } g2048_ntuple_staged_net;
 /* The staged sibling of every entry point that takes a g2048_ntuple_net: the same arguments, outputs, launches and
- * rules.  g2048_ntuple_trace_push never touches the tables and serves both.  tc->err and tc->mag are [S][T][16^L]. */
+ * rules.  g2048_ntuple_trace_push and g2048_ntuple_delay_push never touch the tables and serve both.  tc->err and tc->mag are [S][T][16^L]. */
 int g2048_ntuple_staged_evaluate(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_io *io, void *stream);
 int g2048_ntuple_staged_evaluate_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
                                        const g2048_ntuple_io *io, void *stream);
@@ -603,6 +650,11 @@ int g2048_ntuple_staged_trace_update(uint64_t n, const int64_t *delta, uint32_t 
                                      const g2048_ntuple_trace *tr, uint32_t slot, void *stream);
 int g2048_ntuple_staged_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
                                         const g2048_ntuple_staged_net *net, const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr,
+                                        uint32_t slot, void *stream);
+int g2048_ntuple_staged_delay_update(uint64_t n, uint32_t lr_shift, uint32_t mode, const g2048_ntuple_staged_net *net,
+                                     const g2048_ntuple_delay *dl, uint32_t slot, void *stream);
+int g2048_ntuple_staged_tc_delay_update(uint64_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode,
+                                        const g2048_ntuple_staged_net *net, const g2048_ntuple_tc *tc, const g2048_ntuple_delay *dl,
                                         uint32_t slot, void *stream);
 /* stage[i] = stage(boards[i]) for n plain boards (as g2048_ntuple_values_plain takes them), one launch; reads the shape
  * and the thresholds only: net->net.weights may be NULL. */
