@@ -54,6 +54,34 @@ def staged_net():
     return cached("staged", lambda: stref.random_net(TUPLES_8x4[:2], LOW_THR[:2], 94))
 
 
+# The families of tests/test_gpu_ntuple_search_matrix.py: network T of a family has the first T cell lists and the first T
+# tables (of every stage) of the family's T = 8 network, full-range random int32, F = 10 -- a launch that took the
+# neighbouring instantiation reads the same numbers and computes something else.
+FAMILIES = {"uniform": range(1, 9), "staged": range(1, 9), "mixed": range(2, 9)}   # (one list alone cannot be mixed)
+
+
+def family_net(family, T):
+    """Network T of "uniform" (TUPLES_8x4[:T]), "staged" (the same lists, three stages on the low thresholds) or "mixed"
+    (ntuple_mixed_ref.MIX_8[:T], three stages): a reference network, one per (family, T)."""
+    def make():
+        if family == "uniform":
+            w = cached("uniform weights", lambda: np.random.default_rng(95).integers(-(1 << 31), 1 << 31, size=(8, 16 ** 4)))
+            return ref.Net(TUPLES_8x4[:T], 10, w[:T])
+        if family == "staged":
+            w = cached("staged weights", lambda: np.random.default_rng(96).integers(-(1 << 31), 1 << 31, size=(3, 8, 16 ** 4)))
+            return stref.StagedNet(TUPLES_8x4[:T], LOW_THR[:2], 10, w[:, :T])
+        flat = cached("mixed weights", lambda: mref.random_flat(mref.MIX_8, 97, 3))
+        tuples = mref.MIX_8[:T]
+        return mref.mixed_net(tuples, LOW_THR[:2], 10, flat[:, :mref.n_weights(tuples)])    # the tables lie back to back
+    assert 1 <= T <= 8      # ("mixed", 1) is a network of one length: the reference of the neighbour of ("mixed", 2) only
+    return cached(("family", family, T), make)
+
+
+# Two near-full boards of 2s and 4s, in stage 1 of the low thresholds: a merge of two 4s makes the 8 that the second threshold
+# asks for, so the leaves of a search lie in two stages (boards of a game in progress hold an 8 everywhere)
+LOW_STAGE = np.array([[1, 2, 1, 2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 0, 0], [0, 2, 1, 2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 2, 0]], np.uint8)
+
+
 def reference_search(boards, depth, net, trace=None):
     """(action, value) by the pure-Python reference of the network's kind."""
     if kind_of(net) == 0:
@@ -71,6 +99,41 @@ def near_full(max_empty, tuples="1x4"):
         want3 = sref.search_batch(boards, 3, net, trace)
         return boards, net, want3, sref.search_batch(boards, 2, net), trace
     return cached(("near full", max_empty, tuples), make)
+
+
+# ------------------------------------------------------------------------------------------------ the device
+_nets = {}
+
+
+def device_net(g, rnet):
+    """An NTupleNet on the GPU with the shape and weights of a reference network of any kind (one per reference network)."""
+    import torch
+    if id(rnet) not in _nets:
+        kind = kind_of(rnet)
+        net = g.NTupleNet(rnet.tuples, frac_bits=rnet.frac_bits, device="cuda:0", stages=rnet.thr if kind else None, mixed=kind == 2)
+        net.weights.copy_(torch.as_tensor(w32_of(rnet)).reshape(net.weights.shape))
+        _nets[id(rnet)] = rnet, net
+    return _nets[id(rnet)][1]
+
+
+def dev(torch, a):
+    return torch.as_tensor(np.ascontiguousarray(a)).to("cuda:0")
+
+
+def to_np(e):
+    return tuple(None if t is None else t.cpu().numpy() for t in e)
+
+
+def dev_u32(torch, a):
+    return torch.from_numpy(np.ascontiguousarray(a, np.uint32).view(np.int32)).to("cuda:0").view(torch.uint32)
+
+
+def engine_with(g, boards, seed=3):
+    """An engine whose records hold ``boards`` with populated score-deficit bits."""
+    eng = g.Batched2048(len(boards), seed=seed)
+    eng.set_boards(np.asarray(boards) % 32)
+    eng.set_scores(np.random.default_rng(1).integers(1, 1 << 24, len(boards)).astype(np.int32))
+    return eng
 
 
 # ------------------------------------------------------------------------------------------------ the host build

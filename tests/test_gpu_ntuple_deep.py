@@ -8,44 +8,13 @@ import pytest
 
 import ntuple_search_ref as sref
 from analysis_helpers import ONE_LEGAL, TERMINAL, assert_rows_periodic, g, mixed_boards, tiled  # noqa: F401 (g: fixture)
-from ntuple_deep_helpers import ILLEGAL, composed_game, compose_depth3, kind_of, mixed_net, near_full, staged_net, w32_of
+from ntuple_deep_helpers import (ILLEGAL, composed_game, compose_depth3, dev, dev_u32, device_net, engine_with, mixed_net, near_full,
+                                 staged_net, to_np)
 from ntuple_helpers import TUPLES_2x6, TUPLES_8x4, random_net
 from ntuple_search_helpers import PAIR_ONLY, WIDE_FANS, assert_search_equal
 
 pytestmark = pytest.mark.gpu
 MAX_WORKGROUPS = (1 << 24) // 256      # kSearchMaxLanes / kBlock (g2048_kernels.hip): the grid cap of the deep search kernel
-_nets = {}
-
-
-def device_net(g, rnet):
-    """An NTupleNet on the GPU with the shape and weights of a reference network of any kind (one per reference network)."""
-    import torch
-    if id(rnet) not in _nets:
-        kind = kind_of(rnet)
-        net = g.NTupleNet(rnet.tuples, frac_bits=rnet.frac_bits, device="cuda:0", stages=rnet.thr if kind else None, mixed=kind == 2)
-        net.weights.copy_(torch.as_tensor(w32_of(rnet)).reshape(net.weights.shape))
-        _nets[id(rnet)] = rnet, net
-    return _nets[id(rnet)][1]
-
-
-def dev(torch, a):
-    return torch.as_tensor(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def to_np(e):
-    return tuple(None if t is None else t.cpu().numpy() for t in e)
-
-
-def dev_u32(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint32).view(np.int32)).to("cuda:0").view(torch.uint32)
-
-
-def engine_with(g, boards, seed=3):
-    """An engine whose records hold ``boards`` with populated score-deficit bits."""
-    eng = g.Batched2048(len(boards), seed=seed)
-    eng.set_boards(np.asarray(boards) % 32)
-    eng.set_scores(np.random.default_rng(1).integers(1, 1 << 24, len(boards)).astype(np.int32))
-    return eng
 
 
 def named_nets():
