@@ -19,7 +19,8 @@ def __getattr__(name):
                 "MCSearch", "NTupleNet", "NTupleEval", "NTupleSearch", "td_step", "train", "NTupleTC", "tc_update", "tc_step",
                 "tc_train", "NTupleTrace", "tdl_evaluate", "tdl_step", "tdl_train", "tcl_step",
                 "tcl_train", "NTupleDelay", "delayed_evaluate", "delayed_tdl_step", "delayed_tdl_train", "delayed_tcl_step",
-                "delayed_tcl_train", "Carousel", "PlayReport", "play_games", "DeepPlayer"):  # need torch + a GPU; imported on first use
+                "delayed_tcl_train", "Carousel", "PlayReport", "play_games", "DeepPlayer", "NTupleAdaptive",
+                "AdaptivePlayer"):  # need torch + a GPU; imported on first use
         from . import batched
         return getattr(batched, name)
     raise AttributeError(name)

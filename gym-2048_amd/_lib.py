@@ -148,6 +148,18 @@ class NTupleDeepIO(C.Structure):
     ]
 
 
+class NTupleAdaptiveIO(C.Structure):
+    """g2048_ntuple_adaptive_io (include/g2048.h): the depth of a board per empty-cell count, device output pointers (NULL = not
+    wanted) and the mask of the engine forms (NULL = every board)."""
+    _fields_ = [
+        ("schedule", C.c_uint8 * 17),
+        ("action", C.c_void_p),
+        ("value", C.c_void_p),
+        ("depth", C.c_void_p),
+        ("active", C.c_void_p),
+    ]
+
+
 class NTupleTCC(C.Structure):
     """g2048_ntuple_tc (include/g2048.h): the device accumulators of temporal-coherence learning, int64 each, laid out as
     the weights."""
@@ -262,6 +274,10 @@ SIGNATURES = {
     "g2048_ntuple_deep_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleDeepIO), _S]),
     "g2048_ntuple_staged_deep_search": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleDeepIO), _S]),
     "g2048_ntuple_staged_deep_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleDeepIO), _S]),
+    "g2048_ntuple_adaptive_search": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleAdaptiveIO), _S]),
+    "g2048_ntuple_adaptive_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleAdaptiveIO), _S]),
+    "g2048_ntuple_staged_adaptive_search": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleAdaptiveIO), _S]),
+    "g2048_ntuple_staged_adaptive_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleAdaptiveIO), _S]),
     "g2048_ntuple_values_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.c_void_p, _S]),
     "g2048_ntuple_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, C.POINTER(NTupleNetC), _S]),
     "g2048_ntuple_tc_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleNetC),

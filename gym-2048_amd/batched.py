@@ -28,6 +28,7 @@ from .ntuple import NTupleDelay, delayed_evaluate, delayed_tcl_step, delayed_tcl
 from .ntuple import Carousel  # noqa: F401
 from .ntuple import _search_io as _ntuple_search_io
 from .ntuple import DeepPlayer, _deep_io as _ntuple_deep_io  # noqa: F401
+from .ntuple import AdaptivePlayer, NTupleAdaptive, _adaptive_io as _ntuple_adaptive_io  # noqa: F401
 from .ntuple import PlayReport, play_games, _check_tensor, _play_io  # noqa: F401
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}
@@ -793,6 +794,19 @@ class Batched2048:
         ref = net._ref(self.device)
         io, out = _ntuple_deep_io(self.n_envs, self.device, depth, out, active)
         check(net._fn("deep_search")(self._h, ref, C.byref(io), self._stream()))
+        return out
+
+    def ntuple_adaptive_search(self, net, schedule, out=None, active=None) -> NTupleAdaptive:
+        """:meth:`ntuple_search` at a depth per board on the live boards (``g2048_ntuple_adaptive_search``):
+        board ``i`` is searched at ``schedule[E]`` in 0..4 for its own number ``E`` of empty cells, one launch on the engine's
+        stream.  ``schedule`` as :meth:`NTupleNet.adaptive_search` takes it; the result is an ``NTupleAdaptive(action, value,
+        depth)``.  ``out`` and ``active`` as in :meth:`ntuple_deep_search`; a masked-out board gets ``depth`` 0xff.  Touches no
+        record, clock, statistic or randomness."""
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        ref = net._ref(self.device)
+        io, out = _ntuple_adaptive_io(self.n_envs, self.device, schedule, out, active)
+        check(net._fn("adaptive_search")(self._h, ref, C.byref(io), self._stream()))
         return out
 
     def isend_numpy(self) -> np.ndarray:

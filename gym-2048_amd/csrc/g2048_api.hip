@@ -1603,6 +1603,59 @@ static int ntuple_deep_search_plain(const uint8_t *boards, uint64_t n, const Net
     return G2048_OK;
 }
 
+// g2048_ntuple_adaptive_io -> the kernel's outputs, or G2048_ERR_INVALID (before any HIP call: works without a device)
+static int ntuple_adaptive_out(const g2048_ntuple_adaptive_io *io, bool plain, g2048::NtupleAdaptiveOut *o)
+{
+    if (!io)
+        return fail(G2048_ERR_INVALID, "io is NULL");
+    for (uint32_t e = 0; e < 17u; ++e)
+        if (io->schedule[e] > G2048_NTUPLE_ADAPTIVE_MAX_DEPTH)
+            return fail(G2048_ERR_INVALID, "schedule[%u]=%u: need a depth of 0..%d", e, io->schedule[e], G2048_NTUPLE_ADAPTIVE_MAX_DEPTH);
+    if (!io->action && !io->value)
+        return fail(G2048_ERR_INVALID, "g2048_ntuple_adaptive_io requests no output (action and value are both NULL)");
+    if (reinterpret_cast<uintptr_t>(io->value) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple adaptive search value needs 16 bytes");
+    if (plain && io->active)
+        return fail(G2048_ERR_INVALID, "g2048_ntuple_adaptive_io active is for the engine forms: a plain form takes no mask");
+    if (reinterpret_cast<uintptr_t>(io->active) & 3u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple adaptive search active needs 4 bytes");
+    *o = g2048::NtupleAdaptiveOut{io->action, io->value, io->depth, io->active};
+    return G2048_OK;
+}
+
+template <class Net>
+static int ntuple_adaptive_search(const g2048_engine *e, const Net *net, const g2048_ntuple_adaptive_io *io, void *stream)
+{
+    if (int rc = usable(e))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleAdaptiveOut o;
+    if (int rc = ntuple_adaptive_out(io, false, &o))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(g2048::launch_ntuple_adaptive_search(e->st.boards, static_cast<uint32_t>(e->n), io->schedule, false, nn, o,
+                                                   static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+template <class Net>
+static int ntuple_adaptive_search_plain(const uint8_t *boards, uint64_t n, const Net *net, const g2048_ntuple_adaptive_io *io, void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleAdaptiveOut o;
+    if (int rc = ntuple_adaptive_out(io, true, &o))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_adaptive_search(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), io->schedule, true,
+                                                   nn, o, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 template <class Net> static int ntuple_values_plain(const uint8_t *boards, uint64_t n, const Net *net, int64_t *v, void *stream)
 {
     if (int rc = plain_boards(boards, n))
@@ -1838,6 +1891,29 @@ int g2048_ntuple_staged_deep_search_plain(const uint8_t *boards, uint64_t n, con
                                           const g2048_ntuple_deep_io *io, void *stream)
 {
     return ntuple_deep_search_plain(boards, n, net, io, stream);
+}
+
+int g2048_ntuple_adaptive_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_adaptive_io *io, void *stream)
+{
+    return ntuple_adaptive_search(e, net, io, stream);
+}
+
+int g2048_ntuple_adaptive_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net,
+                                       const g2048_ntuple_adaptive_io *io, void *stream)
+{
+    return ntuple_adaptive_search_plain(boards, n, net, io, stream);
+}
+
+int g2048_ntuple_staged_adaptive_search(const g2048_engine *e, const g2048_ntuple_staged_net *net,
+                                        const g2048_ntuple_adaptive_io *io, void *stream)
+{
+    return ntuple_adaptive_search(e, net, io, stream);
+}
+
+int g2048_ntuple_staged_adaptive_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
+                                              const g2048_ntuple_adaptive_io *io, void *stream)
+{
+    return ntuple_adaptive_search_plain(boards, n, net, io, stream);
 }
 
 int g2048_ntuple_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io,

@@ -1575,7 +1575,7 @@ template <int D, uint32_t T, class Shape, class Tables, class Add>
 G2048_DEV void ntuple_deep_leaves(const NtupleDeepLds &l, uint32_t lane, uint32_t P, const Shape &sh, uint32_t F, const int32_t *weights,
                                   const Tables &tb, Add add)
 {
-    static_assert(D == 2 || D == 3, "kNtupleDeepMinDepth .. kNtupleDeepMaxDepth");
+    static_assert(D >= 2 && D <= 4, "kNtupleDeepMinDepth .. kNtupleDeepMaxDepth, and kNtupleAdaptiveMaxDepth (n-tuple adaptive search)");
     const uint32_t entries = 4u * ntuple_deep_items(l), units = l.first[entries];
 #pragma unroll 1
     for (uint32_t u = lane; u < units; u += P) {
@@ -1619,6 +1619,91 @@ G2048_DEV uint32_t ntuple_deep_finish(const NtupleDeepLds &l, uint32_t F, int64_
         value[d] = legal ? static_cast<int64_t>(static_cast<uint64_t>(l.root_gain[d]) << F) +
                                floor_div(l.root_sum[d], 5 * static_cast<int64_t>(l.root_items[d]))
                          : kNtupleIllegal;
+        const uint64_t key = ntuple_key(value[d], legal, d);
+        best = key > best ? key : best;
+    }
+    return root_key_action(best);
+}
+
+// ------------------------------------------------------------------- n-tuple adaptive search
+// g2048_ntuple_adaptive_search (include/g2048.h): the definition of "n-tuple expectimax" at a depth per
+// board, D = schedule[E0(b)] in 0..4 with E0 the board's own empty cells.  The table and the steps are those of the deep
+// search above with a run-time D, the same for every lane that works on the board:
+//   D = 0     root, where lane d also looks up V(a_d) into root_sum[d]; finish adds the gain and divides nothing (evaluate's q)
+//   D = 1     root; leaves1: unit = level-1 item = lane, lane + P, ...: root_sum[d1] += weight * S_0(child); finish
+//   D = 2..4  root, expand, scan, leaves, fold, finish with a unit = S_{D-2} of a level-2 item: at D = 4 the depth-2 tree of
+//             ntuple_search_state<2> on one lane
+// Bounds at D = 4: |V| <= 2^37, S_0 adds one gain << F < 2^47 and S_1, S_2, S_3 and the root one more each, floor() of a
+// weighted mean stays within its terms: |value| <= 2^37 + 5 * 2^47 < 2^50.  A chance node's weights add up to 10 E <= 150: a
+// partial sum, in any order, stays below 150 * 2^50 < 2^58, and value + 2^60 of ntuple_key is positive.
+constexpr uint32_t kNtupleAdaptiveMaxDepth = 4;   // = G2048_NTUPLE_ADAPTIVE_MAX_DEPTH (g2048.h)
+constexpr uint32_t kNtupleAdaptiveSkipped = 0xffu; // = G2048_NTUPLE_ADAPTIVE_SKIPPED
+
+// schedule[17] as a kernel argument that no lane indexes in memory: nibble E of lo = schedule[E] for E < 16, hi = schedule[16]
+struct NtupleAdaptiveSchedule {
+    uint64_t lo;
+    uint32_t hi;
+};
+G2048_HOST_DEV NtupleAdaptiveSchedule ntuple_adaptive_schedule(const uint8_t schedule[17])
+{
+    NtupleAdaptiveSchedule s{0u, schedule[16]};
+    for (uint32_t e = 0; e < 16u; ++e)
+        s.lo |= static_cast<uint64_t>(schedule[e] & 0xfu) << (4u * e);
+    return s;
+}
+G2048_DEV uint32_t ntuple_adaptive_depth(const NtupleAdaptiveSchedule &s, const Board &cells)
+{
+    const uint32_t e0 = count_empty(cells);
+    return e0 < 16u ? static_cast<uint32_t>(s.lo >> (4u * e0)) & 0xfu : s.hi;
+}
+
+// root: ntuple_deep_root, and at depth 0 lane d looks up V of its afterstate (a depth above 0 starts its sums at 0)
+template <uint32_t T, class Shape, class Tables>
+G2048_DEV void ntuple_adaptive_root(NtupleDeepLds &l, const Board &cells, bool active, uint32_t depth, uint32_t lane, const Shape &sh,
+                                    const int32_t *weights, const Tables &tb)
+{
+    ntuple_deep_root(l, cells, active, lane, tb);
+    if (depth == 0u && lane < 4u && l.root_items[lane] != 0u)
+        l.root_sum[lane] = ntuple_value<T>(ntuple_pack(l.root_after[lane]), sh, weights);
+}
+
+// leaves of depth 1: add(d1, x): root_sum[d1] += x, atomically among the lanes
+template <uint32_t T, class Shape, class Tables, class Add>
+G2048_DEV void ntuple_adaptive_leaves1(const NtupleDeepLds &l, uint32_t lane, uint32_t P, const Shape &sh, uint32_t F,
+                                       const int32_t *weights, const Tables &tb, Add add)
+{
+    const uint32_t items = ntuple_deep_items(l);
+#pragma unroll 1
+    for (uint32_t t = lane; t < items; t += P) {
+        uint32_t d1, local, weight;
+        ntuple_deep_item1(l, t, d1, local);
+        const Board child = ntuple_deep_item(l.root_after[d1], local, weight);
+        add(d1, static_cast<int64_t>(weight) * ntuple_search_state<0, T>(child, sh, F, weights, tb));
+    }
+}
+
+// leaves of depth 2..4: ntuple_deep_leaves at the board's depth.  The branch is the same for every lane of the board.
+template <uint32_t T, class Shape, class Tables, class Add>
+G2048_DEV void ntuple_adaptive_leaves(const NtupleDeepLds &l, uint32_t depth, uint32_t lane, uint32_t P, const Shape &sh, uint32_t F,
+                                      const int32_t *weights, const Tables &tb, Add add)
+{
+    if (depth == 2u)
+        ntuple_deep_leaves<2, T>(l, lane, P, sh, F, weights, tb, add);
+    else if (depth == 3u)
+        ntuple_deep_leaves<3, T>(l, lane, P, sh, F, weights, tb, add);
+    else
+        ntuple_deep_leaves<4, T>(l, lane, P, sh, F, weights, tb, add);
+}
+
+// finish: one lane.  Depth 0 has V itself in root_sum, every other depth a chance sum to divide (ntuple_deep_finish).
+G2048_DEV uint32_t ntuple_adaptive_finish(const NtupleDeepLds &l, uint32_t depth, uint32_t F, int64_t value[4])
+{
+    if (depth != 0u)
+        return ntuple_deep_finish(l, F, value);
+    uint64_t best = 0;
+    for (uint32_t d = 0; d < 4u; ++d) {
+        const bool legal = l.root_items[d] != 0u;
+        value[d] = legal ? static_cast<int64_t>(static_cast<uint64_t>(l.root_gain[d]) << F) + l.root_sum[d] : kNtupleIllegal;
         const uint64_t key = ntuple_key(value[d], legal, d);
         best = key > best ? key : best;
     }

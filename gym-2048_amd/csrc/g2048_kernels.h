@@ -142,6 +142,15 @@ hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth,
 // g2048_ntuple_deep_search: the same outputs from the workgroup-per-board kernel; depth in 2..3
 hipError_t launch_ntuple_deep_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
                                      const NtupleSearchOut &o, hipStream_t s);
+// g2048_ntuple_adaptive_search: the workgroup-per-board kernel at a depth per board, schedule[E0] in 0..4 (checked by the caller)
+struct NtupleAdaptiveOut {
+    uint8_t *action;        // [n] or NULL
+    int64_t *value;         // [n][4] or NULL
+    uint8_t *depth;         // [n] or NULL: the depth used, kNtupleAdaptiveSkipped where active is 0
+    const uint32_t *active; // [n] or NULL, as NtupleSearchOut::active
+};
+hipError_t launch_ntuple_adaptive_search(const uint4 *boards, uint32_t n, const uint8_t schedule[17], bool plain, const NtupleNet &net,
+                                         const NtupleAdaptiveOut &o, hipStream_t s);
 // g2048_ntuple_play: a.k_steps greedy steps with auto-reset in one launch (spawn stream only: a.st.rng is refused by the
 // caller); the side outputs (g2048_ntuple_play_io, checked by the caller; NULL = not wanted)
 struct NtuplePlayOut {

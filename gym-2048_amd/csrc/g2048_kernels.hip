@@ -1680,6 +1680,73 @@ __global__ void __launch_bounds__(kBlock) ntuple_deep_search_kernel(const uint4 
     }
 }
 
+// g2048_ntuple_adaptive_search: ntuple_deep_search_kernel with a depth per board, D = schedule[E0(board)] in 0..4 -- the steps of
+// g2048_device.h ("n-tuple adaptive search") with a barrier after each.  D is a run-time value, the same for the whole
+// workgroup: every branch on it is wave-uniform and every barrier is reached by all 256 lanes or by none.  One kernel per
+// (T, shape, plain / engine / masked) holds the leaves of all depths, S_0, S_1 and S_2 on a lane, so its registers are those of
+// its deepest leaf, ntuple_search_state<2>, whatever schedule a launch runs: 24 to 26 VGPRs above ntuple_deep_search_kernel<3>
+// and, at T = 1..6, one or two waves per SIMD fewer (profiles/r23_ntuple_adaptive_resource_usage.txt).  A second form of the
+// kernel without the depth-4 unit, for schedules that hold no 4, was built and timed on the MI355X: with the registers and the
+// occupancy of the deep kernel it was no faster at T = 8 and SLOWER at T = 4 than this one (by 3 % on late-game and 12 % on
+// mid-game boards, profiles/r23_ntuple_adaptive_probe.txt), so it is not kept.
+// AdaptiveTables: LdsTables under a type of this kernel's own, so that the device templates it instantiates
+// (ntuple_chance_partial<2, ..> and the lambdas in it) are not the instantiations of ntuple_search_kernel -- shared, the
+// compiler inlined them in another order there and those 72 kernels came out with other register counts than the parent's.
+// LDS, the grid cap, the stride loop and MASKED as in ntuple_deep_search_kernel; a masked-out board skips nothing but work.
+struct AdaptiveTables : LdsTables {};
+
+template <uint32_t T, bool PLAIN, class Shape, bool MASKED = false>
+__global__ void __launch_bounds__(kBlock) ntuple_adaptive_search_kernel(const uint4 *__restrict__ boards, uint32_t n, const Shape sh,
+                                                                        uint32_t frac_bits, const int32_t *__restrict__ weights,
+                                                                        const NtupleAdaptiveSchedule schedule, const NtupleAdaptiveOut o)
+{
+    __shared__ WaveTables s_tables[kBlock / 64];
+    __shared__ NtupleDeepLds s_deep;
+    const AdaptiveTables tb{stage_tables(s_tables, load_tables_piece())};
+    const uint32_t lane = threadIdx.x;
+    const auto add_root = [&](uint32_t d1, int64_t x) {
+        atomicAdd(reinterpret_cast<unsigned long long *>(&s_deep.root_sum[d1]), static_cast<unsigned long long>(x));
+    };
+    for (uint64_t i = blockIdx.x; i < n; i += gridDim.x) { // (64 bits: n may be within one grid of 2^32)
+        bool active = true;
+        if constexpr (MASKED)
+            active = o.active[i] != 0u;
+        const Board cells = input_cells<PLAIN>(load_board(boards, static_cast<uint32_t>(i)));
+        const uint32_t depth = ntuple_adaptive_depth(schedule, cells);
+        ntuple_adaptive_root<T>(s_deep, cells, active, depth, lane, sh, weights, tb);
+        __syncthreads();
+        if (depth == 1u) {
+            ntuple_adaptive_leaves1<T>(s_deep, lane, kBlock, sh, frac_bits, weights, tb, add_root);
+            __syncthreads();
+        } else if (depth >= 2u) {
+            ntuple_deep_expand(s_deep, lane, kBlock, tb);
+            __syncthreads();
+            ntuple_deep_scan(s_deep, lane, kBlock);
+            __syncthreads();
+            ntuple_adaptive_leaves<T>(s_deep, depth, lane, kBlock, sh, frac_bits, weights, tb, [&](uint32_t e, int64_t x) {
+                atomicAdd(reinterpret_cast<unsigned long long *>(&s_deep.acc[e]), static_cast<unsigned long long>(x));
+            });
+            __syncthreads();
+            ntuple_deep_fold(s_deep, lane, kBlock, frac_bits, add_root);
+            __syncthreads();
+        }
+        if (lane == 0u) {
+            int64_t value[4];
+            const uint32_t action = ntuple_adaptive_finish(s_deep, depth, frac_bits, value);
+            if (o.value) {
+#pragma unroll
+                for (uint32_t d = 0; d < 4u; ++d)
+                    o.value[i * 4u + d] = value[d];
+            }
+            if (o.action)
+                o.action[i] = static_cast<uint8_t>(action);
+            if (o.depth)
+                o.depth[i] = static_cast<uint8_t>(active ? depth : kNtupleAdaptiveSkipped);
+        }
+        __syncthreads(); // the next board's root step overwrites what lane 0 reads above
+    }
+}
+
 // g2048_ntuple_values_plain: V of every board, one board per lane, the same gathers.
 template <uint32_t T, class Shape>
 __global__ void __launch_bounds__(kBlock) ntuple_values_kernel(const uint4 *__restrict__ boards, uint32_t n, const Shape sh,
@@ -2807,6 +2874,22 @@ hipError_t launch_ntuple_deep_search(const uint4 *boards, uint32_t n, uint32_t d
                 return launch_1d(ntuple_deep_search_kernel<dc, tc, plain_c, decltype(sh)>, group_lanes(n, kBlock), 0, s, boards, n, sh,
                                  net.frac_bits, static_cast<const int32_t *>(net.weights), o);
             });
+        });
+    });
+}
+
+// One workgroup per board, as launch_ntuple_deep_search; the depth is the kernel's own business
+hipError_t launch_ntuple_adaptive_search(const uint4 *boards, uint32_t n, const uint8_t schedule[17], bool plain, const NtupleNet &net,
+                                         const NtupleAdaptiveOut &o, hipStream_t s)
+{
+    const NtupleAdaptiveSchedule sc = ntuple_adaptive_schedule(schedule);
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        if (o.active) // (engine records only: the caller gives no mask for plain boards)
+            return launch_1d(ntuple_adaptive_search_kernel<tc, false, decltype(sh), true>, group_lanes(n, kBlock), 0, s, boards, n, sh,
+                             net.frac_bits, static_cast<const int32_t *>(net.weights), sc, o);
+        return dispatch_bool(plain, [&](auto plain_c) {
+            return launch_1d(ntuple_adaptive_search_kernel<tc, plain_c, decltype(sh)>, group_lanes(n, kBlock), 0, s, boards, n, sh,
+                             net.frac_bits, static_cast<const int32_t *>(net.weights), sc, o);
         });
     });
 }

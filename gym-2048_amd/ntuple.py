@@ -17,6 +17,9 @@ when it leaves the ring (``g2048_ntuple_delay_*``).
 ``NTupleNet.deep_search`` / ``Batched2048.ntuple_deep_search`` are the same search at depth 2..3 from a kernel that gives a
 board a whole workgroup (``g2048_ntuple_deep_search``), and ``DeepPlayer`` plays it in :func:`play_games`:
 the 3-ply row of the papers.
+``NTupleNet.adaptive_search`` / ``Batched2048.ntuple_adaptive_search`` search every board at a depth 0..4 chosen by a fixed
+rule from its own empty cells, one launch (``g2048_ntuple_adaptive_search``); :func:`schedule_by_empties`
+and ``SCHEDULES`` make the rule, and ``AdaptivePlayer`` plays it in :func:`play_games`.
 ``NTupleNet(..., stages=...)`` is the multi-stage network: a weight set per game stage, chosen per board by the tiles it
 holds (``g2048_ntuple_staged_*``); every method and trainer above works on it unchanged.
 ``Carousel`` is carousel shaping for such a network (``g2048_carousel_*``): it remembers, per stage, the
@@ -38,13 +41,14 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import CarouselC, NTupleDeepIO, NTupleDelayC, NTupleIO, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTraceC, check
+from ._lib import CarouselC, NTupleAdaptiveIO, NTupleDeepIO, NTupleDelayC, NTupleIO, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTraceC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
 ILLEGAL = -(1 << 63)                                              # G2048_NTUPLE_ILLEGAL: q of an illegal move
 SEARCH_MAX_DEPTH = 2                                              # G2048_NTUPLE_SEARCH_MAX_DEPTH
 DEEP_MIN_DEPTH, DEEP_MAX_DEPTH = 2, 3                             # G2048_NTUPLE_DEEP_MIN_DEPTH, G2048_NTUPLE_DEEP_MAX_DEPTH
+ADAPTIVE_MAX_DEPTH, ADAPTIVE_SKIPPED = 4, 0xff                    # G2048_NTUPLE_ADAPTIVE_MAX_DEPTH, G2048_NTUPLE_ADAPTIVE_SKIPPED
 TC_WEIGHTS, TC_ACCUM = 1, 2                                       # G2048_NTUPLE_TC_WEIGHTS, G2048_NTUPLE_TC_ACCUM
 TRACE_MAX = 8                                                     # G2048_NTUPLE_TRACE_MAX
 DELAY_STEP, DELAY_FLUSH = 0, 1                                    # G2048_NTUPLE_DELAY_STEP, G2048_NTUPLE_DELAY_FLUSH
@@ -161,6 +165,67 @@ def _deep_io(n, device, depth, out, active=None):
     """``_search_io`` for the deep search: (NTupleDeepIO, NTupleSearch), depth 2..3, and ``active`` (engine forms) checked as
     ``_check_tensor`` checks."""
     io, out = _search_io(n, device, depth, out, NTupleDeepIO, (DEEP_MIN_DEPTH, DEEP_MAX_DEPTH))
+    if active is not None:
+        _check_tensor("active", active, (torch.uint32,), (n,), device)
+        io.active = active.data_ptr()
+    return io, out
+
+
+class NTupleAdaptive(NamedTuple):
+    """Result of adaptive_search (``g2048_ntuple_adaptive_search``).  Device tensors; a field that is None was not asked for."""
+    action: Optional[torch.Tensor]       # uint8 [n]: as NTupleSearch.action, at the board's own depth
+    value: Optional[torch.Tensor]        # int64 [n, 4]: as NTupleSearch.value (evaluate's q at depth 0)
+    depth: Optional[torch.Tensor]        # uint8 [n]: the depth used, schedule[empty cells]; ADAPTIVE_SKIPPED for a masked-out board
+
+
+def schedule_by_empties(depths, default) -> tuple:
+    """The 17 entries of a search schedule, ``schedule[E]`` = the depth of a board with ``E`` empty cells, from
+    ``{max_empty: depth, ...}``: a board gets the depth of the smallest ``max_empty`` that is not below its ``E``, and
+    ``default`` above the largest.  ``schedule_by_empties({5: 3, 9: 2}, 1)`` is depth 3 for E <= 5, 2 for 6..9 and 1 above."""
+    default = _int_arg("default", default, 0, ADAPTIVE_MAX_DEPTH)
+    if not isinstance(depths, dict):
+        raise ValueError("depths must be a dict {max_empty: depth}")
+    steps = sorted((_int_arg("max_empty", e, 0, 16), _int_arg("depth", d, 0, ADAPTIVE_MAX_DEPTH)) for e, d in depths.items())
+    return tuple(next((d for m, d in steps if e <= m), default) for e in range(17))
+
+
+# Starting values: NOBODY HAS TIMED OR PLAYED THESE schedules against each other or against a fixed depth.  They follow
+# the cost of a ply on a late-game board, about 37 times the ply before it (profiles/r21_ntuple_deep_probe.txt), and give
+# the deepest level to the boards where one wrong move ends the game.
+SCHEDULES = {
+    "3-ply-late": schedule_by_empties({5: 3, 9: 2}, 1),
+    "4-ply-late": schedule_by_empties({1: 4, 5: 3, 9: 2}, 1),
+}
+
+
+def _schedule(schedule) -> tuple:
+    """``schedule`` as 17 depths in 0..ADAPTIVE_MAX_DEPTH: the name of a preset in SCHEDULES, or a sequence."""
+    if isinstance(schedule, str):
+        if schedule not in SCHEDULES:
+            raise ValueError(f"schedule {schedule!r}: the presets are {sorted(SCHEDULES)}")
+        return SCHEDULES[schedule]
+    try:
+        schedule = tuple(schedule)
+    except TypeError:
+        raise ValueError("schedule must be a preset name or a sequence of 17 depths") from None
+    if len(schedule) != 17:
+        raise ValueError(f"schedule needs 17 entries (0..16 empty cells), not {len(schedule)}")
+    return tuple(_int_arg("schedule entry", d, 0, ADAPTIVE_MAX_DEPTH) for d in schedule)
+
+
+def _adaptive_io(n, device, schedule, out, active=None):
+    """(NTupleAdaptiveIO, NTupleAdaptive) for n boards: ``schedule`` checked, ``out`` checked field by field or freshly
+    allocated, ``active`` (engine forms) checked as ``_check_tensor`` checks."""
+    schedule = _schedule(schedule)
+    if out is None:
+        u8 = dict(dtype=torch.uint8, device=device)
+        out = NTupleAdaptive(torch.empty(n, **u8), torch.empty((n, 4), dtype=torch.int64, device=device), torch.empty(n, **u8))
+    else:
+        out = NTupleAdaptive(*out)
+        if out.action is None and out.value is None:
+            raise ValueError("out requests no output (action and value are both None)")
+    io = NTupleAdaptiveIO((C.c_uint8 * 17)(*schedule))
+    _bind_out(io, out, {"action": ((n,), (torch.uint8,)), "value": ((n, 4), (torch.int64,)), "depth": ((n,), (torch.uint8,))}, device)
     if active is not None:
         _check_tensor("active", active, (torch.uint32,), (n,), device)
         io.active = active.data_ptr()
@@ -362,6 +427,19 @@ class NTupleNet:
         net = self._ref(device)
         io, out = _deep_io(n, device, depth, out)
         self._launch(self._fn("deep_search_plain"), boards, net, C.byref(io))
+        return out
+
+    def adaptive_search(self, boards, schedule, out=None) -> NTupleAdaptive:
+        """:meth:`search` at a depth per board on plain boards (``g2048_ntuple_adaptive_search_plain``):
+        board ``i`` is searched at ``schedule[E]`` in 0..4 for its own number ``E`` of empty cells, in one launch on the current
+        stream of the boards' device.  ``schedule``: 17 depths (:func:`schedule_by_empties`) or the name of a preset in
+        ``SCHEDULES``.  Depth 0 gives the bits of :meth:`evaluate`, 1..2 those of :meth:`search`, 2..3 those of
+        :meth:`deep_search`; depth 4 exists here only.  ``out``: a preallocated :class:`NTupleAdaptive` (a field that is None is
+        not written; ``action`` or ``value`` must be given)."""
+        n, device = _plain_boards(boards)
+        net = self._ref(device)
+        io, out = _adaptive_io(n, device, schedule, out)
+        self._launch(self._fn("adaptive_search_plain"), boards, net, C.byref(io))
         return out
 
     def update(self, boards, delta, lr_shift):
@@ -925,6 +1003,22 @@ class DeepPlayer:
 
     def __call__(self, engine, actions, active=None):
         engine.ntuple_deep_search(self.net, self.depth, out=NTupleSearch(actions, None), active=active)
+
+
+class AdaptivePlayer:
+    """The expectimax player over ``net`` at a depth per board for :func:`play_games` (``g2048_ntuple_adaptive_search``,
+    INTEGRATION.md §20): ``play_games(engine, net, games, player=AdaptivePlayer(net, "4-ply-late"))``.  ``schedule`` as
+    :meth:`NTupleNet.adaptive_search` takes it.  A callable ``player(engine, actions, active=None)`` with ``takes_active``, as
+    :class:`DeepPlayer`."""
+    takes_active = True
+
+    def __init__(self, net, schedule):
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        self.net, self.schedule = net, _schedule(schedule)
+
+    def __call__(self, engine, actions, active=None):
+        engine.ntuple_adaptive_search(self.net, self.schedule, out=NTupleAdaptive(actions, None, None), active=active)
 
 
 def play_games(engine, net, games=1, chunk=1024, max_steps=None, depth=0, player=None) -> PlayReport:

@@ -692,6 +692,42 @@ int g2048_ntuple_staged_deep_search(const g2048_engine *e, const g2048_ntuple_st
 int g2048_ntuple_staged_deep_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
                                           const g2048_ntuple_deep_io *io, void *stream);
 
+/* N-tuple adaptive-depth search: ONE launch that searches every board at a depth chosen from its own empty-cell count, 0..4
+ * (INTEGRATION.md §20).  The notation is that of the n-tuple expectimax block above -- A_k, S_k, value, action, the floor
+ * division, G2048_NTUPLE_ILLEGAL.  E0(b) is the number of empty cells of board b as the search reads it (byte & 0x1f of an
+ * engine record, exponent mod 32 of a plain board), and D_i = schedule[E0(b_i)].  Board i gets value and action of that
+ * definition at D = D_i; depth 0 is g2048_ntuple_evaluate's value (q) and action.  The results are the bits of the existing
+ * calls where those exist: g2048_ntuple_evaluate at depth 0, g2048_ntuple_search at 1..2, g2048_ntuple_deep_search at 2..3.
+ * Depth 4 exists here only.  A board with no legal move -- the all-empty board, E0 = 16, among them -- gets action 0 and four
+ * G2048_NTUPLE_ILLEGAL, and its depth output is schedule[E0]; a board at 0 in `active` gets the same outputs and depth
+ * G2048_NTUPLE_ADAPTIVE_SKIPPED.
+ * Bounds at depth 4, re-derived: a leaf is |V| <= 8 * 8 * 2^31 = 2^37.  S_0 adds one gain << F, gain < 2^31 and F <= 16, so
+ * below 2^47; S_1, S_2, S_3 and the root add one more each, and the floor of a weighted mean stays within the range of its
+ * terms: |value| <= 2^37 + 5 * 2^47 < 2^50 (= 8 * 2^47).  The weights of a chance node add up to 10 E <= 150, so every partial
+ * sum of one, in any order and any split, stays below 150 * 2^50 < 2^58 in an int64, and the 2^60 bias of the action key
+ * still makes every legal key positive.
+ * Each call is one launch on `stream`, writes nothing but its outputs and consumes no randomness.  Uniform, mixed-length and
+ * staged networks, T = 1..8.  Cost: each ply multiplies the evaluations of a late-game board by about 37
+ * (profiles/r21_ntuple_deep_probe.txt); give depth 4 to boards with very few empty cells only. */
+#define G2048_NTUPLE_ADAPTIVE_MAX_DEPTH 4
+#define G2048_NTUPLE_ADAPTIVE_SKIPPED 0xff
+typedef struct g2048_ntuple_adaptive_io {
+    uint8_t schedule[17];    /* schedule[E] = search depth of a board with E empty cells, 0..G2048_NTUPLE_ADAPTIVE_MAX_DEPTH each */
+    uint8_t *action;         /* [n], or NULL */
+    int64_t *value;          /* [n][4], 16-byte aligned, or NULL */
+    uint8_t *depth;          /* [n], or NULL: the depth used, G2048_NTUPLE_ADAPTIVE_SKIPPED for a masked-out board */
+    const uint32_t *active;  /* [n] in device memory, 4-byte aligned, or NULL; engine forms only (G2048_ERR_INVALID with a
+                              * plain form), as g2048_ntuple_deep_io.active */
+} g2048_ntuple_adaptive_io;
+/* At least one of action and value must be given.  The plain forms as those of g2048_ntuple_deep_search: 1 <= n <= 2^32 - 256. */
+int g2048_ntuple_adaptive_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_adaptive_io *io, void *stream);
+int g2048_ntuple_adaptive_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net,
+                                       const g2048_ntuple_adaptive_io *io, void *stream);
+int g2048_ntuple_staged_adaptive_search(const g2048_engine *e, const g2048_ntuple_staged_net *net,
+                                        const g2048_ntuple_adaptive_io *io, void *stream);
+int g2048_ntuple_staged_adaptive_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
+                                              const g2048_ntuple_adaptive_io *io, void *stream);
+
 /* Carousel shaping: stage-balanced restarts for training a staged network (Jaskowski 2017).  Every
  * episode starts from an empty board, so the weight sets of the late stages see only the rare boards that live that long.
  * A carousel remembers, per stage, the boards on which recent episodes ENTERED that stage, and starts new episodes from
