@@ -1,7 +1,7 @@
 """Shared by the n-tuple deep search tests (g2048_ntuple_deep_search): the host build of the header's deep
 search code (tests/host_ntuple_deep/deep_check.cpp, g++) behind ctypes, the reference results the CPU and the GPU tests share
-(computed once), the composition of depth 3 from depth-2 calls, and the per-move composition of a DeepPlayer game.  A plain
-module, like ntuple_helpers."""
+(computed once), the composition of depth 3 from depth-2 calls, the boards, networks and anchored composition of the value-extremes
+tests, and the per-move composition of a DeepPlayer game.  A plain module, like ntuple_helpers."""
 import ctypes as C
 import os
 import subprocess
@@ -99,6 +99,193 @@ def near_full(max_empty, tuples="1x4"):
         want3 = sref.search_batch(boards, 3, net, trace)
         return boards, net, want3, sref.search_batch(boards, 2, net), trace
     return cached(("near full", max_empty, tuples), make)
+
+
+# ------------------------------------------------------------------------------------------------ value extremes
+INT32_MAX, INT32_MIN = (1 << 31) - 1, -(1 << 31)
+# 16 + 16 -> 17, then 17 + 17 -> 18: the largest tiles of a game
+MERGING = np.array([[16, 16, 17, 5, 1, 2, 3, 4, 2, 3, 4, 5, 3, 4, 5, 0]], np.uint8)
+# a full board of 2^27 .. 2^29 tiles: every move merges, gains of 2^29 .. 2^30 at the root and on the three levels below it,
+# none reaching 2^31 at the root (asserted where it is used)
+HUGE = np.array([[28, 29, 27, 29, 27, 28, 28, 29, 27, 28, 28, 28, 29, 28, 29, 0]], np.uint8)
+
+
+def quarter_turn(boards):
+    """Every board turned by a quarter (numpy's rot90 of the 4 x 4 cells)."""
+    return np.array([np.rot90(b.reshape(4, 4)).reshape(16) for b in np.asarray(boards).reshape(-1, 16)], np.uint8)
+
+
+TURNED = quarter_turn(HUGE)
+# equal to its transpose, tiles 2^27 .. 2^29 with cell (i, j) = 27 + (i + j + 2) mod 3 and one empty cell on the diagonal: no two
+# neighbours are equal, so the root moves gain nothing and the tree is small (the reference affords depth 4 in a second),
+# while the levels below merge 2^29 tiles; up equals left and right equals down at every depth, so the largest value is shared
+SYMMETRIC = np.array([[29, 27, 28, 29, 27, 28, 29, 27, 28, 29, 0, 28, 29, 27, 28, 29]], np.uint8)
+# one more board of such tiles: under extreme_net("random", 16, 1) the depth-3 chance sum of its direction 2 is odd and above
+# 2^53, 10 052 829 928 238 839 with 10 E = 40, and rounding it to a double moves it across a multiple of 40 (found with the host
+# build; the test that uses it asserts this from the exact sum it composes)
+SENSITIVE = np.array([[28, 27, 29, 28, 28, 29, 27, 27, 0, 28, 29, 28, 28, 27, 29, 28]], np.uint8)
+# HUGE and TURNED with a second empty cell
+TWO_EMPTY = np.concatenate([HUGE, TURNED])
+TWO_EMPTY[0, 0] = TWO_EMPTY[1, 9] = 0
+
+
+def cleared(board, cells):
+    """``board`` [1, 16] with ``cells`` emptied."""
+    out = np.array(board, np.uint8).reshape(1, 16)
+    out[0, list(cells)] = 0
+    return out
+
+
+def bound_fill(kind, shape, seed=93):
+    """int64 weights at the edge of int32: every entry INT32_MIN ("min"), every entry INT32_MAX ("max"), or one of the two at
+    random per entry ("random", a fixed seed)."""
+    if kind == "random":
+        return np.random.default_rng(seed).choice(np.array([INT32_MIN, INT32_MAX]), size=shape)
+    return np.full(shape, {"min": INT32_MIN, "max": INT32_MAX}[kind], np.int64)
+
+
+def extreme_net(kind, frac_bits, T):
+    """The uniform network of the value-extremes tests: TUPLES_8x4[:T] under bound_fill(kind), one per (kind, F, T)."""
+    def make():
+        net = ref.Net(TUPLES_8x4[:T], frac_bits)
+        net.weights[:] = bound_fill(kind, net.weights.shape)
+        return net
+    return cached(("extreme net", kind, frac_bits, T), make)
+
+
+def extreme_staged_net():
+    """Three stages of TUPLES_8x4 on the low thresholds, one of INT32_MIN / INT32_MAX at random per entry, F = 16."""
+    def make():
+        net = stref.StagedNet(TUPLES_8x4, LOW_THR[:2], 16)
+        net.weights[:] = bound_fill("random", net.weights.shape, 98)
+        return net
+    return cached("extreme staged net", make)
+
+
+def extreme_mixed_net():
+    """ntuple_mixed_ref.MIX_8 in three stages on the low thresholds, one of INT32_MIN / INT32_MAX at random per entry, F = 16."""
+    tuples = mref.MIX_8
+    return cached("extreme mixed net", lambda: mref.mixed_net(tuples, LOW_THR[:2], 16, bound_fill("random", (3, mref.n_weights(tuples)), 99)))
+
+
+def chance_sums(board, depth, net):
+    """{d: (gain, empty cells, chance sum before the division)} of the legal root directions, by the reference."""
+    out = {}
+    for d in range(4):
+        a, g, legal = ref.move(ref.plain(board), d)
+        if legal:
+            out[d] = g, sum(x == 0 for x in a), sum(w * sref.state_value(a[:c] + (e,) + a[c + 1:], depth - 1, net)
+                                                    for c in range(16) if a[c] == 0 for e, w in ((1, 9), (2, 1)))
+    return out
+
+
+def values_of(sums, frac_bits):
+    """The reference's value[4] from its own chance sums: (g << F) + sum // (10 E), ILLEGAL where the direction has none."""
+    return np.array([[(sums[d][0] << frac_bits) + sums[d][2] // (10 * sums[d][1]) if d in sums else sref.ILLEGAL for d in range(4)]], np.int64)
+
+
+def search_of(sums, frac_bits):
+    """(action, value) of one board from chance_sums: the smallest direction of the largest value."""
+    value = values_of(sums, frac_bits)
+    return np.array([max(sums, key=lambda d: (int(value[0, d]), -d)) if sums else 0], np.uint8), value
+
+
+_ref_rows, _ref_traces = {}, {}
+
+
+def reference_rows(boards, depth, net):
+    """(action uint8 [n], value int64 [n, 4]) by the pure-Python reference of the network's kind at depth 0..4 (depth 0:
+    evaluate's action and q), every (network, depth, board) computed once per process: the CPU and the GPU tests share it.
+    ``net`` is one of the cached networks of this module (it is remembered by identity)."""
+    boards = np.asarray(boards, np.uint8).reshape(-1, 16)
+    act, val = np.zeros(len(boards), np.uint8), np.zeros((len(boards), 4), np.int64)
+    for i, b in enumerate(boards):
+        key = id(net), depth, b.tobytes()
+        if key not in _ref_rows:
+            if depth == 0:
+                q, a = (ref.evaluate if kind_of(net) == 0 else stref.evaluate)(b, net)[:2]
+                _ref_rows[key] = net, a, np.array(q, np.int64)
+            else:
+                trace = reference_trace(net, depth)
+                a, v = sref.search_batch(b, depth, net, trace) if kind_of(net) == 0 else stref.search_batch(b, depth, net, trace)
+                _ref_rows[key] = net, a[0], v[0]
+        _, act[i], val[i] = _ref_rows[key]
+    return act, val
+
+
+def reference_trace(net, depth):
+    """What reference_rows met so far under ``net`` at ``depth``: an ntuple_search_ref.Trace, or the counter dict of
+    ntuple_staged_ref (its "stage": {stage: afterstates and leaves read from it}) for a staged or mixed network."""
+    return _ref_traces.setdefault((id(net), depth), sref.Trace() if kind_of(net) == 0 else {"memo": {}})
+
+
+def anchored_search(boards, depth, net, lower, direct_depth, stats):
+    """(action, value) of ``boards`` at ``depth`` that owes nothing to the code under test at that depth.  A board with
+    direct_depth(board) >= depth comes from reference_rows.  Any other board is composed (compose_depth3: the top chance sum
+    and its floor division in Python integers) from ``lower(children, depth - 1) -> (action, value)``, the code under test
+    one level down, and of those children a deterministic subset -- the quarter with the fewest empty cells, whose reference
+    is the cheapest (the first of equals), and every child without a legal move (by the reference's move) -- is compared with anchored_search of the same children at depth - 1, down to depth 2, which
+    is always the reference.  ``stats`` counts "direct" and "composed" boards and the "children", "anchored" and "dead" ones,
+    and keeps under "totals" the exact chance sums {(depth, board bytes): [(0, direction, sum, 10 E)]} of the composed boards."""
+    from ntuple_search_helpers import assert_search_equal
+    boards = np.asarray(boards, np.uint8).reshape(-1, 16)
+    act, val = np.zeros(len(boards), np.uint8), np.zeros((len(boards), 4), np.int64)
+
+    def checked(kids):
+        got = lower(kids, depth - 1)
+        dead = np.array([not any(ref.move(ref.plain(k), d)[2] for d in range(4)) for k in kids])
+        few = np.argsort((kids == 0).sum(1), kind="stable")[:(len(kids) + 3) // 4]     # the cheapest references
+        pick = np.nonzero(dead | np.isin(np.arange(len(kids)), few))[0]
+        want = anchored_search(kids[pick], depth - 1, net, lower, direct_depth, stats)
+        assert_search_equal((got[0][pick], got[1][pick]), want, kids[pick], f"anchor at depth {depth - 1}")
+        stats["children"] = stats.get("children", 0) + len(kids)
+        stats["anchored"] = stats.get("anchored", 0) + len(pick)
+        stats["dead"] = stats.get("dead", 0) + int(dead.sum())
+        assert 4 * len(pick) >= len(kids) and dead[pick].sum() == dead.sum()
+        return got[1]
+
+    for i, b in enumerate(boards):
+        if depth <= 2 or direct_depth(b) >= depth:
+            stats["direct"] = stats.get("direct", 0) + 1
+            a, v = reference_rows(b, depth, net)
+        elif not any(ref.move(ref.plain(b), d)[2] for d in range(4)):
+            a, v = np.zeros(1, np.uint8), np.full((1, 4), ILLEGAL, np.int64)    # (no children to compose from)
+        else:
+            stats["composed"] = stats.get("composed", 0) + 1
+            (a, v), _, _ = compose_depth3(b, net.frac_bits, checked, stats.setdefault("totals", {}).setdefault((depth, b.tobytes()), []))
+        act[i], val[i] = a[0], v[0]
+    return act, val
+
+
+def implied_root_sums(boards, value, frac_bits):
+    """A list per board of the root chance sums that ``value`` [n, 4] implies, one per legal direction and exact to within
+    10 E <= 150: (value - (gain << F)) * 10 E, gain and E by the reference's move, in Python integers.  Asserts on the way
+    that every root gain stays below 2^31 and every legal value below 2^50 in magnitude."""
+    out = []
+    for b, row in zip(np.asarray(boards).reshape(-1, 16), value):
+        sums = []
+        for d in range(4):
+            a, g, legal = ref.move(ref.plain(b), d)
+            assert g < 1 << 31 and legal == (int(row[d]) != ILLEGAL)
+            if legal:
+                assert abs(int(row[d])) < 1 << 50
+                sums.append((int(row[d]) - (g << frac_bits)) * 10 * sum(x == 0 for x in a))
+        out.append(sums)
+    return out
+
+
+def fold_sums(board, depth, net):
+    """The chance sums one level below the root of a depth-``depth`` search of ``board``, by the reference: what the fold step
+    divides.  A list of (sum, 10 E) over every (level-1 child, legal move of it)."""
+    out = []
+    for d in range(4):
+        a, _, legal = ref.move(ref.plain(board), d)
+        if legal:
+            for c in range(16):
+                if a[c] == 0:
+                    for e in (1, 2):
+                        out += [(s, 10 * E) for _, E, s in chance_sums(a[:c] + (e,) + a[c + 1:], depth - 1, net).values()]
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ the device
@@ -217,10 +404,11 @@ def children_of(boards):
     return items, gains, empties
 
 
-def compose_depth3(boards, frac_bits, depth2):
+def compose_depth3(boards, frac_bits, depth2, totals=None):
     """(action, value) at depth 3 from the definition and ``depth2(children uint8 [m, 16]) -> value int64 [m, 4]``, a depth-2
     search: S_2(child) = the largest legal depth-2 value, 0 when none is legal; the chance sum and its floor division in Python
-    integers.  Also (the largest item count of a direction, the children without a legal move)."""
+    integers.  Also (the largest item count of a direction, the children without a legal move).  ``totals``: a list that
+    receives (board, direction, the exact chance sum, 10 E) of every legal direction."""
     items, gains, empties = children_of(boards)
     flat = [child for per in items for lst in per if lst is not None for child, _ in lst]
     val2 = depth2(np.array(flat, np.uint8).reshape(-1, 16))
@@ -235,6 +423,8 @@ def compose_depth3(boards, frac_bits, depth2):
             total = sum(w * s2[at + j] for j, (_, w) in enumerate(lst))
             at += len(lst)
             widest = max(widest, len(lst))
+            if totals is not None:
+                totals.append((i, d, total, 10 * empties[i][d]))
             val[i, d] = (gains[i][d] << frac_bits) + total // (10 * empties[i][d])
         legal = [d for d in range(4) if per[d] is not None]
         act[i] = max(legal, key=lambda d: (int(val[i, d]), -d)) if legal else 0

@@ -21,6 +21,7 @@ import ntuple_ref as ref
 import ntuple_search_ref as sref
 import ntuple_tc_ref as tcref
 from analysis_helpers import ONE_LEGAL, TERMINAL, assert_rows_periodic, g, mid_game, mixed_boards, random_boards  # noqa: F401 (g: fixture)
+from ntuple_deep_helpers import bound_fill
 from ntuple_helpers import EVAL_NAMES, TUPLES_3xL, TUPLES_8x4, TUPLES_8x6, assert_eval_equal, random_net
 from ntuple_search_helpers import PAIR_ONLY, SEARCH_NAMES, WIDE_FANS, assert_search_equal
 from ntuple_tc_helpers import EDGE_PAIRS, assert_tables_equal, edge_deltas, preload
@@ -276,12 +277,7 @@ MIRRORED = np.array([[16, 0, 15, 14, 0, 17, 14, 16, 15, 14, 16, 15, 14, 16, 15, 
 
 def bound_case(kind, F):
     rnet = ref.Net(TUPLES_8x4, F)
-    if kind == "min":
-        rnet.weights[:] = INT32_MIN
-    elif kind == "max":
-        rnet.weights[:] = INT32_MAX
-    else:
-        rnet.weights[:] = np.random.default_rng(93).choice(np.array([INT32_MIN, INT32_MAX]), size=rnet.weights.shape)
+    rnet.weights[:] = bound_fill(kind, rnet.weights.shape)
     shallow_b = np.concatenate([bound_boards(20, 94, 10), np.array([[16, 16, 3, 0, 0, 2, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0]], np.uint8),
                                 symmetric_boards(), DEAD_ENDS])
     deep_b = np.concatenate([bound_boards(4, 95, 2), MIRRORED, DEAD_ENDS])

@@ -11,7 +11,8 @@ import ntuple_search_ref as sref
 from analysis_helpers import ONE_LEGAL, TERMINAL, mixed_boards
 from ntuple_adaptive_helpers import (CRAFTED, ILLEGAL, MIXED_SCHEDULE, SKIPPED, compose_next, constant, crafted_net, crafted_reference,
                                      empties_boards, host_root, host_split, load_host_adaptive, named_boards, rows_at)
-from ntuple_deep_helpers import LOW_STAGE, mixed_net, raw_desc, reference_search, staged_net
+from ntuple_deep_helpers import (HUGE, LOW_STAGE, SYMMETRIC, anchored_search, extreme_net, implied_root_sums, mixed_net, raw_desc,
+                                 reference_rows, reference_search, staged_net)
 from ntuple_search_helpers import PAIR_ONLY, WIDE_FANS, assert_search_equal
 
 LANES = (1, 3, 64, 256)
@@ -93,6 +94,36 @@ def test_depth_3_is_composed_the_same_way(ha):
     boards, net, want3, _, _ = near_full(2)
     got, _, _ = compose_next(boards, net.frac_bits, lambda kids: host_root(ha, kids, 2, net)[1])
     assert_search_equal(got, want3, boards, "composition, depth 3")
+
+
+@pytest.mark.parametrize("kind", ["max", "random", "min"])
+def test_value_extremes_depth_4(ha, kind):
+    """Depth 4 at the header's bounds on the CPU: one 4-tuple with every weight INT32_MAX, every weight INT32_MIN or one of the two
+    at random, F = 16, the networks and the expected values of tests/test_gpu_ntuple_deep_extremes.py.  SYMMETRIC (tiles of 2^27 ..
+    2^29, one empty cell, equal to its transpose) goes straight against tests/ntuple_search_ref.py: values of 2^48, a root tie.
+    HUGE, whose depth-4 reference would take minutes, is composed under the random fill: the top chance sum and its floor
+    division in Python integers over the host build's depth-3 values of the children, a quarter of which are composed the same way
+    from depth-2 values, a quarter of which equal the reference (anchored_search).  Its root chance sums pass 2^52."""
+    net = extreme_net(kind, 16, 1)
+    want = reference_rows(SYMMETRIC, 4, net)
+    sums = implied_root_sums(SYMMETRIC, want[1], 16)[0]
+    legal = want[1][0] != ILLEGAL
+    assert legal.all() and min(sums) > 1 << 50 and (want[1] > 1 << 47).all() and (np.abs(want[1]) < 1 << 50).all()
+    assert want[1][0, 0] == want[1][0, 3] and want[1][0, 1] == want[1][0, 2] and want[0][0] == want[1][0].argmax(), "inputs: a root tie"
+    cases = [(SYMMETRIC, want)]
+    if kind == "random":
+        stats = {}
+        composed = anchored_search(HUGE, 4, net, lambda kids, k: host_root(ha, kids, k, net), lambda board: 2, stats)
+        top = implied_root_sums(HUGE, composed[1], 16)[0]
+        assert stats["composed"] >= 9 and 4 * stats["anchored"] >= stats["children"] and stats["direct"] >= 64
+        assert len(top) == 4 and max(top) > 1 << 52 and max(top) < 1 << 58
+        cases.append((HUGE, composed))
+    for board, expect in cases:
+        assert_search_equal(host_root(ha, board, 4, net), expect, board, f"{kind}, root")
+        for P in LANES if board is SYMMETRIC else LANES[-1:]:      # (HUGE at depth 4 takes the host build 2.5 s a run)
+            act, val, dep = host_split(ha, board, constant(4), net, P)
+            assert_search_equal((act, val), expect, board, f"{kind}, split, {P} lanes")
+            assert (dep == 4).all()
 
 
 LEAN_SCHEDULE = tuple(min(d, 3) for d in MIXED_SCHEDULE)        # the same rule cut at depth 3

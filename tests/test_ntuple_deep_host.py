@@ -9,7 +9,8 @@ import pytest
 import ntuple_ref as ref
 import ntuple_search_ref as sref
 from analysis_helpers import ONE_LEGAL, TERMINAL, mixed_boards
-from ntuple_deep_helpers import (host_root, host_split, load_host_deep, mixed_net, near_full, raw_desc, reference_search, staged_net)
+from ntuple_deep_helpers import (HUGE, MERGING, chance_sums, host_root, host_split, load_host_deep, mixed_net, near_full, raw_desc,
+                                 reference_search, staged_net, values_of)
 from ntuple_helpers import TUPLES_8x4, TUPLES_17x4, random_net
 from ntuple_mixed_helpers import near_full_12
 from ntuple_search_helpers import PAIR_ONLY, WIDE_FANS, assert_search_equal
@@ -99,29 +100,6 @@ def test_split_mixed_and_staged_networks(hd, kind):
     want3 = reference_search(few, 3, net)
     assert_search_equal(host_root(hd, few, 3, net), want3, few, f"{kind}, root depth 3")
     assert_split_equals_root(hd, boards, 3, net, kind)
-
-
-def chance_sums(board, depth, net):
-    """{d: (gain, empty cells, chance sum before the division)} of the legal root directions, by the reference."""
-    out = {}
-    for d in range(4):
-        a, g, legal = ref.move(ref.plain(board), d)
-        if legal:
-            out[d] = g, sum(x == 0 for x in a), sum(w * sref.state_value(a[:c] + (e,) + a[c + 1:], depth - 1, net)
-                                                    for c in range(16) if a[c] == 0 for e, w in ((1, 9), (2, 1)))
-    return out
-
-
-def values_of(sums, frac_bits):
-    """The reference's value[4] from its own chance sums: (g << F) + sum // (10 E), ILLEGAL where the direction has none."""
-    return np.array([[(sums[d][0] << frac_bits) + sums[d][2] // (10 * sums[d][1]) if d in sums else sref.ILLEGAL for d in range(4)]], np.int64)
-
-
-# 16 + 16 -> 17, then 17 + 17 -> 18: the tiles the issue names
-MERGING = np.array([[16, 16, 17, 5, 1, 2, 3, 4, 2, 3, 4, 5, 3, 4, 5, 0]], np.uint8)
-# a full board of 2^27 .. 2^29 tiles: every move merges, gains of 2^29 .. 2^30 at the root and on the three levels below it,
-# none reaching 2^31 at the root (asserted)
-HUGE = np.array([[28, 29, 27, 29, 27, 28, 28, 29, 27, 28, 28, 28, 29, 28, 29, 0]], np.uint8)
 
 
 @pytest.mark.parametrize("sign", [1, -1])
