@@ -20,6 +20,7 @@
 #include <mutex>
 #include <new>
 #include <thread>
+#include <type_traits>
 
 namespace {
 
@@ -1081,7 +1082,7 @@ int g2048_legal_actions(const g2048_engine *e, uint8_t *mask_out, void *stream)
 
 } // extern "C"
 
-// The plain board array of the _plain analysis calls (afterstates, expectimax, mc_search): n rows of 16 exponents
+// A plain board array: n rows of 16 exponents
 static int plain_boards(const uint8_t *boards, uint64_t n)
 {
     if (!boards)
@@ -1090,6 +1091,38 @@ static int plain_boards(const uint8_t *boards, uint64_t n)
         return fail(G2048_ERR_INVALID, "misaligned buffer: boards need 16 bytes");
     if (n == 0 || n > 0xffffff00ull) // (32-bit board indices, whole 256-lane blocks: the cap of g2048_create)
         return fail(G2048_ERR_INVALID, "n=%llu: need 1 <= n <= 2^32 - 256", (unsigned long long)n);
+    return G2048_OK;
+}
+
+// Where a read-only call finds its boards.  Every such operation below is written once and entered twice, with an engine's
+// records and with the caller's plain array: `rc` is the opening check of that form, and the body returns it before it
+// looks at anything else.
+struct Source {
+    int rc;
+    g2048::Boards boards;
+    int device;            // the engine's, set before the launch; -1: a plain array is launched on the current device
+    uint64_t index_offset; // global index of board 0 (g2048_mc_search): the engine's board_offset or the caller's
+};
+
+static Source from_engine(const g2048_engine *e)
+{
+    if (int rc = usable(e))
+        return Source{rc, {}, -1, 0};
+    return Source{G2048_OK, {e->st.boards, static_cast<uint32_t>(e->n), false}, e->device, e->board_offset};
+}
+
+static Source from_plain(const uint8_t *boards, uint64_t n, uint64_t index_offset = 0)
+{
+    if (int rc = plain_boards(boards, n))
+        return Source{rc, {}, -1, 0};
+    return Source{G2048_OK, {reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), true}, -1, index_offset};
+}
+
+// after all validation, before the launch
+static int select_device(const Source &src)
+{
+    if (src.device >= 0)
+        G2048_HIP(hipSetDevice(src.device));
     return G2048_OK;
 }
 
@@ -1109,30 +1142,29 @@ static int afterstate_out(const g2048_afterstate_io *io, g2048::AfterstateOut *o
     return G2048_OK;
 }
 
+static int afterstates(const Source &src, const g2048_afterstate_io *io, void *stream)
+{
+    if (src.rc)
+        return src.rc;
+    g2048::AfterstateOut o;
+    if (int rc = afterstate_out(io, &o))
+        return rc;
+    if (int rc = select_device(src))
+        return rc;
+    G2048_HIP(g2048::launch_afterstates(src.boards, o, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 extern "C" {
 
 int g2048_afterstates(const g2048_engine *e, const g2048_afterstate_io *io, void *stream)
 {
-    if (int rc = usable(e))
-        return rc;
-    g2048::AfterstateOut o;
-    if (int rc = afterstate_out(io, &o))
-        return rc;
-    G2048_HIP(hipSetDevice(e->device));
-    G2048_HIP(g2048::launch_afterstates(e->st.boards, static_cast<uint32_t>(e->n), false, o, static_cast<hipStream_t>(stream)));
-    return G2048_OK;
+    return afterstates(from_engine(e), io, stream);
 }
 
 int g2048_afterstates_plain(const uint8_t *boards, uint64_t n, const g2048_afterstate_io *io, void *stream)
 {
-    if (int rc = plain_boards(boards, n))
-        return rc;
-    g2048::AfterstateOut o;
-    if (int rc = afterstate_out(io, &o))
-        return rc;
-    G2048_HIP(g2048::launch_afterstates(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), true, o,
-                                        static_cast<hipStream_t>(stream)));
-    return G2048_OK;
+    return afterstates(from_plain(boards, n), io, stream);
 }
 
 } // extern "C"
@@ -1160,31 +1192,29 @@ static int search_args(const g2048_search_io *io, g2048::SearchArgs *a)
     return G2048_OK;
 }
 
+static int expectimax(const Source &src, const g2048_search_io *io, void *stream)
+{
+    if (src.rc)
+        return src.rc;
+    g2048::SearchArgs a;
+    if (int rc = search_args(io, &a))
+        return rc;
+    if (int rc = select_device(src))
+        return rc;
+    G2048_HIP(g2048::launch_expectimax(src.boards, io->depth, a, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 extern "C" {
 
 int g2048_expectimax(const g2048_engine *e, const g2048_search_io *io, void *stream)
 {
-    if (int rc = usable(e))
-        return rc;
-    g2048::SearchArgs a;
-    if (int rc = search_args(io, &a))
-        return rc;
-    G2048_HIP(hipSetDevice(e->device));
-    G2048_HIP(g2048::launch_expectimax(e->st.boards, static_cast<uint32_t>(e->n), io->depth, false, a,
-                                       static_cast<hipStream_t>(stream)));
-    return G2048_OK;
+    return expectimax(from_engine(e), io, stream);
 }
 
 int g2048_expectimax_plain(const uint8_t *boards, uint64_t n, const g2048_search_io *io, void *stream)
 {
-    if (int rc = plain_boards(boards, n))
-        return rc;
-    g2048::SearchArgs a;
-    if (int rc = search_args(io, &a))
-        return rc;
-    G2048_HIP(g2048::launch_expectimax(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), io->depth, true, a,
-                                       static_cast<hipStream_t>(stream)));
-    return G2048_OK;
+    return expectimax(from_plain(boards, n), io, stream);
 }
 
 } // extern "C"
@@ -1212,30 +1242,29 @@ static int mc_args(const g2048_mc_io *io, uint64_t n, uint64_t index_offset, g20
     return G2048_OK;
 }
 
+static int mc_search(const Source &src, const g2048_mc_io *io, void *stream)
+{
+    if (src.rc)
+        return src.rc;
+    g2048::McArgs a;
+    if (int rc = mc_args(io, src.boards.n, src.index_offset, &a))
+        return rc;
+    if (int rc = select_device(src))
+        return rc;
+    G2048_HIP(g2048::launch_mc_search(src.boards, a, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
 extern "C" {
 
 int g2048_mc_search(const g2048_engine *e, const g2048_mc_io *io, void *stream)
 {
-    if (int rc = usable(e))
-        return rc;
-    g2048::McArgs a;
-    if (int rc = mc_args(io, e->n, e->board_offset, &a))
-        return rc;
-    G2048_HIP(hipSetDevice(e->device));
-    G2048_HIP(g2048::launch_mc_search(e->st.boards, static_cast<uint32_t>(e->n), false, a, static_cast<hipStream_t>(stream)));
-    return G2048_OK;
+    return mc_search(from_engine(e), io, stream);
 }
 
 int g2048_mc_search_plain(const uint8_t *boards, uint64_t n, uint32_t index_offset, const g2048_mc_io *io, void *stream)
 {
-    if (int rc = plain_boards(boards, n))
-        return rc;
-    g2048::McArgs a;
-    if (int rc = mc_args(io, n, index_offset, &a))
-        return rc;
-    G2048_HIP(g2048::launch_mc_search(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), true, a,
-                                      static_cast<hipStream_t>(stream)));
-    return G2048_OK;
+    return mc_search(from_plain(boards, n, index_offset), io, stream);
 }
 
 } // extern "C"
@@ -1356,49 +1385,35 @@ static int trace_boards(uint64_t n)
     return G2048_OK;
 }
 
-// g2048_ntuple_trace and a slot -> the launchers' history, or G2048_ERR_INVALID (before any HIP call: works without a device)
-static int ntuple_trace(const g2048_ntuple_trace *tr, uint32_t slot, g2048::NtupleTrace *out)
+// g2048_ntuple_trace or g2048_ntuple_delay and a slot -> the launchers' history (g2048::NtupleTrace) or ring
+// (g2048::NtupleDelay, which adds acc), or G2048_ERR_INVALID (before any HIP call: works without a device).  The messages
+// call the descriptor `name`, the parameter it came in, and its buffers by `noun`.
+template <class Desc, class Hist> static int ntuple_history(const Desc *h, const char *name, const char *noun, uint32_t slot, Hist *out)
 {
-    if (!tr)
-        return fail(G2048_ERR_INVALID, "tr is NULL");
-    if (!tr->hist)
-        return fail(G2048_ERR_INVALID, "trace hist is NULL");
-    if (!tr->len)
-        return fail(G2048_ERR_INVALID, "trace len is NULL");
-    if (tr->depth < 1 || tr->depth > G2048_NTUPLE_TRACE_MAX)
-        return fail(G2048_ERR_INVALID, "depth=%u: need 1 <= depth <= %d", tr->depth, G2048_NTUPLE_TRACE_MAX);
-    if (tr->lambda > 65536u)
-        return fail(G2048_ERR_INVALID, "lambda=%u: need 0 <= lambda <= 65536 (Q16)", tr->lambda);
-    if (slot >= tr->depth)
-        return fail(G2048_ERR_INVALID, "slot=%u: need slot < depth=%u", slot, tr->depth);
-    if (reinterpret_cast<uintptr_t>(tr->hist) & 15u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: trace hist needs 16 bytes");
-    *out = g2048::NtupleTrace{tr->depth, tr->lambda, reinterpret_cast<uint4 *>(tr->hist), tr->len};
-    return G2048_OK;
-}
-
-// g2048_ntuple_delay and a slot -> the launchers' ring, or G2048_ERR_INVALID (before any HIP call: works without a device)
-static int ntuple_delay(const g2048_ntuple_delay *dl, uint32_t slot, g2048::NtupleDelay *out)
-{
-    if (!dl)
-        return fail(G2048_ERR_INVALID, "dl is NULL");
-    if (!dl->hist)
-        return fail(G2048_ERR_INVALID, "delay hist is NULL");
-    if (!dl->len)
-        return fail(G2048_ERR_INVALID, "delay len is NULL");
-    if (!dl->acc)
-        return fail(G2048_ERR_INVALID, "delay acc is NULL");
-    if (dl->depth < 1 || dl->depth > G2048_NTUPLE_TRACE_MAX)
-        return fail(G2048_ERR_INVALID, "depth=%u: need 1 <= depth <= %d", dl->depth, G2048_NTUPLE_TRACE_MAX);
-    if (dl->lambda > 65536u)
-        return fail(G2048_ERR_INVALID, "lambda=%u: need 0 <= lambda <= 65536 (Q16)", dl->lambda);
-    if (slot >= dl->depth)
-        return fail(G2048_ERR_INVALID, "slot=%u: need slot < depth=%u", slot, dl->depth);
-    if (reinterpret_cast<uintptr_t>(dl->hist) & 15u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: delay hist needs 16 bytes");
-    if (reinterpret_cast<uintptr_t>(dl->acc) & 7u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: delay acc needs 8 bytes");
-    *out = g2048::NtupleDelay{dl->depth, dl->lambda, reinterpret_cast<uint4 *>(dl->hist), dl->len, dl->acc};
+    constexpr bool has_acc = std::is_same<Hist, g2048::NtupleDelay>::value;
+    if (!h)
+        return fail(G2048_ERR_INVALID, "%s is NULL", name);
+    if (!h->hist)
+        return fail(G2048_ERR_INVALID, "%s hist is NULL", noun);
+    if (!h->len)
+        return fail(G2048_ERR_INVALID, "%s len is NULL", noun);
+    if constexpr (has_acc)
+        if (!h->acc)
+            return fail(G2048_ERR_INVALID, "%s acc is NULL", noun);
+    if (h->depth < 1 || h->depth > G2048_NTUPLE_TRACE_MAX)
+        return fail(G2048_ERR_INVALID, "depth=%u: need 1 <= depth <= %d", h->depth, G2048_NTUPLE_TRACE_MAX);
+    if (h->lambda > 65536u)
+        return fail(G2048_ERR_INVALID, "lambda=%u: need 0 <= lambda <= 65536 (Q16)", h->lambda);
+    if (slot >= h->depth)
+        return fail(G2048_ERR_INVALID, "slot=%u: need slot < depth=%u", slot, h->depth);
+    if (reinterpret_cast<uintptr_t>(h->hist) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: %s hist needs 16 bytes", noun);
+    if constexpr (has_acc)
+        if (reinterpret_cast<uintptr_t>(h->acc) & 7u)
+            return fail(G2048_ERR_INVALID, "misaligned buffer: %s acc needs 8 bytes", noun);
+    static_cast<g2048::NtupleTrace &>(*out) = g2048::NtupleTrace{h->depth, h->lambda, reinterpret_cast<uint4 *>(h->hist), h->len};
+    if constexpr (has_acc)
+        out->acc = h->acc;
     return G2048_OK;
 }
 
@@ -1424,52 +1439,47 @@ static int ntuple_delta(const int64_t *delta, uint32_t lr_shift)
     return G2048_OK;
 }
 
-// phases and the accumulators of a TC update
-static int ntuple_tc(uint32_t phases, const g2048_ntuple_tc *tc)
+// phases and the accumulators as a TC entry point got them.  The update bodies below take a pointer to one: NULL from the
+// TD entry points, whose update it is then.
+struct TcArgs {
+    uint32_t phases;
+    const g2048_ntuple_tc *tc;
+};
+
+// -> the launchers' accumulators; nothing to check, and *out is left alone, for the TD update
+static int ntuple_tc(const TcArgs *in, g2048::NtupleTc *out)
 {
-    if (phases < 1 || phases > (G2048_NTUPLE_TC_WEIGHTS | G2048_NTUPLE_TC_ACCUM))
-        return fail(G2048_ERR_INVALID, "phases=%u: need G2048_NTUPLE_TC_WEIGHTS (1), G2048_NTUPLE_TC_ACCUM (2) or both (3)", phases);
-    if (!tc)
+    if (!in)
+        return G2048_OK;
+    if (in->phases < 1 || in->phases > (G2048_NTUPLE_TC_WEIGHTS | G2048_NTUPLE_TC_ACCUM))
+        return fail(G2048_ERR_INVALID, "phases=%u: need G2048_NTUPLE_TC_WEIGHTS (1), G2048_NTUPLE_TC_ACCUM (2) or both (3)", in->phases);
+    if (!in->tc)
         return fail(G2048_ERR_INVALID, "tc is NULL");
-    if (!tc->err)
+    if (!in->tc->err)
         return fail(G2048_ERR_INVALID, "tc err is NULL");
-    if (!tc->mag)
+    if (!in->tc->mag)
         return fail(G2048_ERR_INVALID, "tc mag is NULL");
-    if ((reinterpret_cast<uintptr_t>(tc->err) | reinterpret_cast<uintptr_t>(tc->mag)) & 7u)
+    if ((reinterpret_cast<uintptr_t>(in->tc->err) | reinterpret_cast<uintptr_t>(in->tc->mag)) & 7u)
         return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple tc err and mag need 8 bytes");
+    *out = g2048::NtupleTc{in->phases, in->tc->err, in->tc->mag};
     return G2048_OK;
 }
 
 // The entry points that take a network, once each for Net = g2048_ntuple_net and g2048_ntuple_staged_net (the extern "C"
 // wrappers below): only ntuple_net() differs.
-template <class Net> static int ntuple_evaluate(const g2048_engine *e, const Net *net, const g2048_ntuple_io *io, void *stream)
+template <class Net> static int ntuple_evaluate(const Source &src, const Net *net, const g2048_ntuple_io *io, void *stream)
 {
-    if (int rc = usable(e))
-        return rc;
+    if (src.rc)
+        return src.rc;
     g2048::NtupleNet nn;
     if (int rc = ntuple_net(net, &nn))
         return rc;
     g2048::NtupleOut o;
     if (int rc = ntuple_out(io, &o))
         return rc;
-    G2048_HIP(hipSetDevice(e->device));
-    G2048_HIP(g2048::launch_ntuple_eval(e->st.boards, static_cast<uint32_t>(e->n), false, nn, o, static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-template <class Net>
-static int ntuple_evaluate_plain(const uint8_t *boards, uint64_t n, const Net *net, const g2048_ntuple_io *io, void *stream)
-{
-    if (int rc = plain_boards(boards, n))
+    if (int rc = select_device(src))
         return rc;
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    g2048::NtupleOut o;
-    if (int rc = ntuple_out(io, &o))
-        return rc;
-    G2048_HIP(g2048::launch_ntuple_eval(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), true, nn, o,
-                                        static_cast<hipStream_t>(stream)));
+    G2048_HIP(g2048::launch_ntuple_eval(src.boards, nn, o, static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 
@@ -1514,14 +1524,21 @@ template <class Net> static int ntuple_play(g2048_engine *e, const Net *net, uin
     return G2048_OK;
 }
 
-// active: g2048_ntuple_search_active's mask, NULL for every board
-template <class Net>
-static int ntuple_search(const g2048_engine *e, const Net *net, const g2048_ntuple_search_io *io, const uint32_t *active, void *stream)
+// g2048_ntuple_search_active's mask.  Those entry points check it before they look at the engine (usable() consumes a
+// pending strict-actions report, so it cannot run ahead of this).
+static int ntuple_search_mask(const uint32_t *active)
 {
     if (reinterpret_cast<uintptr_t>(active) & 3u)
         return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple search active needs 4 bytes");
-    if (int rc = usable(e))
-        return rc;
+    return G2048_OK;
+}
+
+// active: the mask, NULL for every board (and always for plain boards)
+template <class Net>
+static int ntuple_search(const Source &src, const Net *net, const g2048_ntuple_search_io *io, const uint32_t *active, void *stream)
+{
+    if (src.rc)
+        return src.rc;
     g2048::NtupleNet nn;
     if (int rc = ntuple_net(net, &nn))
         return rc;
@@ -1529,25 +1546,9 @@ static int ntuple_search(const g2048_engine *e, const Net *net, const g2048_ntup
     if (int rc = ntuple_search_out(io, &o))
         return rc;
     o.active = active;
-    G2048_HIP(hipSetDevice(e->device));
-    G2048_HIP(g2048::launch_ntuple_search(e->st.boards, static_cast<uint32_t>(e->n), io->depth, false, nn, o,
-                                          static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-template <class Net>
-static int ntuple_search_plain(const uint8_t *boards, uint64_t n, const Net *net, const g2048_ntuple_search_io *io, void *stream)
-{
-    if (int rc = plain_boards(boards, n))
+    if (int rc = select_device(src))
         return rc;
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    g2048::NtupleSearchOut o;
-    if (int rc = ntuple_search_out(io, &o))
-        return rc;
-    G2048_HIP(g2048::launch_ntuple_search(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), io->depth, true, nn, o,
-                                          static_cast<hipStream_t>(stream)));
+    G2048_HIP(g2048::launch_ntuple_search(src.boards, io->depth, nn, o, static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 
@@ -1571,35 +1572,19 @@ static int ntuple_deep_out(const g2048_ntuple_deep_io *io, bool plain, g2048::Nt
     return G2048_OK;
 }
 
-template <class Net> static int ntuple_deep_search(const g2048_engine *e, const Net *net, const g2048_ntuple_deep_io *io, void *stream)
+template <class Net> static int ntuple_deep_search(const Source &src, const Net *net, const g2048_ntuple_deep_io *io, void *stream)
 {
-    if (int rc = usable(e))
-        return rc;
+    if (src.rc)
+        return src.rc;
     g2048::NtupleNet nn;
     if (int rc = ntuple_net(net, &nn))
         return rc;
     g2048::NtupleSearchOut o;
-    if (int rc = ntuple_deep_out(io, false, &o))
+    if (int rc = ntuple_deep_out(io, src.boards.plain, &o))
         return rc;
-    G2048_HIP(hipSetDevice(e->device));
-    G2048_HIP(g2048::launch_ntuple_deep_search(e->st.boards, static_cast<uint32_t>(e->n), io->depth, false, nn, o,
-                                               static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-template <class Net>
-static int ntuple_deep_search_plain(const uint8_t *boards, uint64_t n, const Net *net, const g2048_ntuple_deep_io *io, void *stream)
-{
-    if (int rc = plain_boards(boards, n))
+    if (int rc = select_device(src))
         return rc;
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    g2048::NtupleSearchOut o;
-    if (int rc = ntuple_deep_out(io, true, &o))
-        return rc;
-    G2048_HIP(g2048::launch_ntuple_deep_search(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), io->depth, true, nn, o,
-                                               static_cast<hipStream_t>(stream)));
+    G2048_HIP(g2048::launch_ntuple_deep_search(src.boards, io->depth, nn, o, static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 
@@ -1623,36 +1608,19 @@ static int ntuple_adaptive_out(const g2048_ntuple_adaptive_io *io, bool plain, g
     return G2048_OK;
 }
 
-template <class Net>
-static int ntuple_adaptive_search(const g2048_engine *e, const Net *net, const g2048_ntuple_adaptive_io *io, void *stream)
+template <class Net> static int ntuple_adaptive_search(const Source &src, const Net *net, const g2048_ntuple_adaptive_io *io, void *stream)
 {
-    if (int rc = usable(e))
-        return rc;
+    if (src.rc)
+        return src.rc;
     g2048::NtupleNet nn;
     if (int rc = ntuple_net(net, &nn))
         return rc;
     g2048::NtupleAdaptiveOut o;
-    if (int rc = ntuple_adaptive_out(io, false, &o))
+    if (int rc = ntuple_adaptive_out(io, src.boards.plain, &o))
         return rc;
-    G2048_HIP(hipSetDevice(e->device));
-    G2048_HIP(g2048::launch_ntuple_adaptive_search(e->st.boards, static_cast<uint32_t>(e->n), io->schedule, false, nn, o,
-                                                   static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-template <class Net>
-static int ntuple_adaptive_search_plain(const uint8_t *boards, uint64_t n, const Net *net, const g2048_ntuple_adaptive_io *io, void *stream)
-{
-    if (int rc = plain_boards(boards, n))
+    if (int rc = select_device(src))
         return rc;
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    g2048::NtupleAdaptiveOut o;
-    if (int rc = ntuple_adaptive_out(io, true, &o))
-        return rc;
-    G2048_HIP(g2048::launch_ntuple_adaptive_search(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), io->schedule, true,
-                                                   nn, o, static_cast<hipStream_t>(stream)));
+    G2048_HIP(g2048::launch_ntuple_adaptive_search(src.boards, io->schedule, nn, o, static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 
@@ -1672,8 +1640,10 @@ template <class Net> static int ntuple_values_plain(const uint8_t *boards, uint6
     return G2048_OK;
 }
 
+// The three updates, one per item source; tc: the TC entry points' arguments, NULL for the TD update
 template <class Net>
-static int ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, const Net *net, void *stream)
+static int ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, const Net *net, const TcArgs *tc,
+                               void *stream)
 {
     if (int rc = plain_boards(boards, n))
         return rc;
@@ -1681,33 +1651,18 @@ static int ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t 
     if (int rc = ntuple_net(net, &nn))
         return rc;
     if (int rc = ntuple_delta(delta, lr_shift))
+        return rc;
+    g2048::NtupleTc t{};
+    if (int rc = ntuple_tc(tc, &t))
         return rc;
     G2048_HIP(g2048::launch_ntuple_update(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), delta, lr_shift, nn,
-                                          static_cast<hipStream_t>(stream)));
+                                          tc ? &t : nullptr, static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 
 template <class Net>
-static int ntuple_tc_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
-                                  const Net *net, const g2048_ntuple_tc *tc, void *stream)
-{
-    if (int rc = plain_boards(boards, n))
-        return rc;
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    if (int rc = ntuple_delta(delta, lr_shift))
-        return rc;
-    if (int rc = ntuple_tc(phases, tc))
-        return rc;
-    G2048_HIP(g2048::launch_ntuple_tc_update(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), delta, lr_shift,
-                                             phases, nn, tc->err, tc->mag, static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-template <class Net>
-static int ntuple_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, const Net *net, const g2048_ntuple_trace *tr,
-                               uint32_t slot, void *stream)
+static int ntuple_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, const Net *net, const TcArgs *tc,
+                               const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
 {
     g2048::NtupleNet nn;
     if (int rc = ntuple_net(net, &nn))
@@ -1716,38 +1671,20 @@ static int ntuple_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shi
         return rc;
     if (int rc = ntuple_delta(delta, lr_shift))
         return rc;
-    g2048::NtupleTrace t;
-    if (int rc = ntuple_trace(tr, slot, &t))
+    g2048::NtupleTc t{};
+    if (int rc = ntuple_tc(tc, &t))
         return rc;
-    G2048_HIP(g2048::launch_ntuple_trace_update(static_cast<uint32_t>(n), delta, lr_shift, nn, t, slot,
+    g2048::NtupleTrace h;
+    if (int rc = ntuple_history(tr, "tr", "trace", slot, &h))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_trace_update(static_cast<uint32_t>(n), delta, lr_shift, nn, h, slot, tc ? &t : nullptr,
                                                 static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 
 template <class Net>
-static int ntuple_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const Net *net,
-                                  const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
-{
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
-    if (int rc = trace_boards(n))
-        return rc;
-    if (int rc = ntuple_delta(delta, lr_shift))
-        return rc;
-    if (int rc = ntuple_tc(phases, tc))
-        return rc;
-    g2048::NtupleTrace t;
-    if (int rc = ntuple_trace(tr, slot, &t))
-        return rc;
-    G2048_HIP(g2048::launch_ntuple_tc_trace_update(static_cast<uint32_t>(n), delta, lr_shift, phases, nn, tc->err, tc->mag, t, slot,
-                                                   static_cast<hipStream_t>(stream)));
-    return G2048_OK;
-}
-
-template <class Net>
-static int ntuple_delay_update(uint64_t n, uint32_t lr_shift, uint32_t mode, const Net *net, const g2048_ntuple_delay *dl, uint32_t slot,
-                               void *stream)
+static int ntuple_delay_update(uint64_t n, uint32_t lr_shift, uint32_t mode, const Net *net, const TcArgs *tc,
+                               const g2048_ntuple_delay *dl, uint32_t slot, void *stream)
 {
     g2048::NtupleNet nn;
     if (int rc = ntuple_net(net, &nn))
@@ -1756,31 +1693,44 @@ static int ntuple_delay_update(uint64_t n, uint32_t lr_shift, uint32_t mode, con
         return rc;
     if (int rc = ntuple_delay_mode(lr_shift, mode))
         return rc;
-    g2048::NtupleDelay d;
-    if (int rc = ntuple_delay(dl, slot, &d))
+    g2048::NtupleTc t{};
+    if (int rc = ntuple_tc(tc, &t))
         return rc;
-    G2048_HIP(g2048::launch_ntuple_delay_update(static_cast<uint32_t>(n), lr_shift, mode, nn, d, slot, static_cast<hipStream_t>(stream)));
+    g2048::NtupleDelay h;
+    if (int rc = ntuple_history(dl, "dl", "delay", slot, &h))
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_delay_update(static_cast<uint32_t>(n), lr_shift, mode, nn, h, slot, tc ? &t : nullptr,
+                                                static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 
-template <class Net>
-static int ntuple_tc_delay_update(uint64_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode, const Net *net,
-                                  const g2048_ntuple_tc *tc, const g2048_ntuple_delay *dl, uint32_t slot, void *stream)
+// g2048_ntuple_trace_push (Hist = g2048::NtupleTrace) and g2048_ntuple_delay_push (g2048::NtupleDelay); name and noun as in
+// ntuple_history
+template <class Hist, class Desc>
+static int ntuple_push(const uint8_t *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated, uint64_t n,
+                       const Desc *desc, const char *name, const char *noun, uint32_t slot, int64_t *delta, void *stream)
 {
-    g2048::NtupleNet nn;
-    if (int rc = ntuple_net(net, &nn))
-        return rc;
+    if (!after)
+        return fail(G2048_ERR_INVALID, "after is NULL");
+    if (!after_value)
+        return fail(G2048_ERR_INVALID, "after_value is NULL");
+    if (!best_next)
+        return fail(G2048_ERR_INVALID, "best_next is NULL");
+    if (!terminated)
+        return fail(G2048_ERR_INVALID, "terminated is NULL");
+    if (!delta)
+        return fail(G2048_ERR_INVALID, "delta is NULL");
     if (int rc = trace_boards(n))
         return rc;
-    if (int rc = ntuple_delay_mode(lr_shift, mode))
+    Hist h;
+    if (int rc = ntuple_history(desc, name, noun, slot, &h))
         return rc;
-    if (int rc = ntuple_tc(phases, tc))
-        return rc;
-    g2048::NtupleDelay d;
-    if (int rc = ntuple_delay(dl, slot, &d))
-        return rc;
-    G2048_HIP(g2048::launch_ntuple_tc_delay_update(static_cast<uint32_t>(n), lr_shift, phases, mode, nn, tc->err, tc->mag, d, slot,
-                                                   static_cast<hipStream_t>(stream)));
+    if (reinterpret_cast<uintptr_t>(after) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: %s after needs 16 bytes", noun);
+    if ((reinterpret_cast<uintptr_t>(after_value) | reinterpret_cast<uintptr_t>(best_next) | reinterpret_cast<uintptr_t>(delta)) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: %s after_value, best_next and delta need 8 bytes", noun);
+    G2048_HIP(g2048::launch_ntuple_push(reinterpret_cast<const uint4 *>(after), after_value, best_next, terminated, static_cast<uint32_t>(n),
+                                        h, slot, delta, static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 
@@ -1788,12 +1738,12 @@ extern "C" {
 
 int g2048_ntuple_evaluate(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_io *io, void *stream)
 {
-    return ntuple_evaluate(e, net, io, stream);
+    return ntuple_evaluate(from_engine(e), net, io, stream);
 }
 
 int g2048_ntuple_staged_evaluate(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_io *io, void *stream)
 {
-    return ntuple_evaluate(e, net, io, stream);
+    return ntuple_evaluate(from_engine(e), net, io, stream);
 }
 
 int g2048_ntuple_play(g2048_engine *e, const g2048_ntuple_net *net, uint32_t k_steps, const g2048_ntuple_play_io *io, void *stream)
@@ -1838,94 +1788,98 @@ int g2048_play_step(g2048_engine *e, const void *actions, int32_t action_dtype, 
 int g2048_ntuple_evaluate_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_io *io,
                                 void *stream)
 {
-    return ntuple_evaluate_plain(boards, n, net, io, stream);
+    return ntuple_evaluate(from_plain(boards, n), net, io, stream);
 }
 
 int g2048_ntuple_staged_evaluate_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
                                        const g2048_ntuple_io *io, void *stream)
 {
-    return ntuple_evaluate_plain(boards, n, net, io, stream);
+    return ntuple_evaluate(from_plain(boards, n), net, io, stream);
 }
 
 int g2048_ntuple_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io, void *stream)
 {
-    return ntuple_search(e, net, io, nullptr, stream);
+    return ntuple_search(from_engine(e), net, io, nullptr, stream);
 }
 
 int g2048_ntuple_staged_search(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_search_io *io,
                                void *stream)
 {
-    return ntuple_search(e, net, io, nullptr, stream);
+    return ntuple_search(from_engine(e), net, io, nullptr, stream);
 }
 
 int g2048_ntuple_search_active(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io,
                                const uint32_t *active, void *stream)
 {
-    return ntuple_search(e, net, io, active, stream);
+    if (int rc = ntuple_search_mask(active))
+        return rc;
+    return ntuple_search(from_engine(e), net, io, active, stream);
 }
 
 int g2048_ntuple_staged_search_active(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_search_io *io,
                                       const uint32_t *active, void *stream)
 {
-    return ntuple_search(e, net, io, active, stream);
+    if (int rc = ntuple_search_mask(active))
+        return rc;
+    return ntuple_search(from_engine(e), net, io, active, stream);
 }
 
 int g2048_ntuple_deep_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_deep_io *io, void *stream)
 {
-    return ntuple_deep_search(e, net, io, stream);
+    return ntuple_deep_search(from_engine(e), net, io, stream);
 }
 
 int g2048_ntuple_deep_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_deep_io *io,
                                    void *stream)
 {
-    return ntuple_deep_search_plain(boards, n, net, io, stream);
+    return ntuple_deep_search(from_plain(boards, n), net, io, stream);
 }
 
 int g2048_ntuple_staged_deep_search(const g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_deep_io *io,
                                     void *stream)
 {
-    return ntuple_deep_search(e, net, io, stream);
+    return ntuple_deep_search(from_engine(e), net, io, stream);
 }
 
 int g2048_ntuple_staged_deep_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
                                           const g2048_ntuple_deep_io *io, void *stream)
 {
-    return ntuple_deep_search_plain(boards, n, net, io, stream);
+    return ntuple_deep_search(from_plain(boards, n), net, io, stream);
 }
 
 int g2048_ntuple_adaptive_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_adaptive_io *io, void *stream)
 {
-    return ntuple_adaptive_search(e, net, io, stream);
+    return ntuple_adaptive_search(from_engine(e), net, io, stream);
 }
 
 int g2048_ntuple_adaptive_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net,
                                        const g2048_ntuple_adaptive_io *io, void *stream)
 {
-    return ntuple_adaptive_search_plain(boards, n, net, io, stream);
+    return ntuple_adaptive_search(from_plain(boards, n), net, io, stream);
 }
 
 int g2048_ntuple_staged_adaptive_search(const g2048_engine *e, const g2048_ntuple_staged_net *net,
                                         const g2048_ntuple_adaptive_io *io, void *stream)
 {
-    return ntuple_adaptive_search(e, net, io, stream);
+    return ntuple_adaptive_search(from_engine(e), net, io, stream);
 }
 
 int g2048_ntuple_staged_adaptive_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
                                               const g2048_ntuple_adaptive_io *io, void *stream)
 {
-    return ntuple_adaptive_search_plain(boards, n, net, io, stream);
+    return ntuple_adaptive_search(from_plain(boards, n), net, io, stream);
 }
 
 int g2048_ntuple_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_search_io *io,
                               void *stream)
 {
-    return ntuple_search_plain(boards, n, net, io, stream);
+    return ntuple_search(from_plain(boards, n), net, io, nullptr, stream);
 }
 
 int g2048_ntuple_staged_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
                                      const g2048_ntuple_search_io *io, void *stream)
 {
-    return ntuple_search_plain(boards, n, net, io, stream);
+    return ntuple_search(from_plain(boards, n), net, io, nullptr, stream);
 }
 
 int g2048_ntuple_values_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net, int64_t *v, void *stream)
@@ -1955,129 +1909,93 @@ int g2048_ntuple_stage_plain(const uint8_t *boards, uint64_t n, const g2048_ntup
 int g2048_ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift,
                               const g2048_ntuple_net *net, void *stream)
 {
-    return ntuple_update_plain(boards, n, delta, lr_shift, net, stream);
+    return ntuple_update_plain(boards, n, delta, lr_shift, net, nullptr, stream);
 }
 
 int g2048_ntuple_staged_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift,
                                      const g2048_ntuple_staged_net *net, void *stream)
 {
-    return ntuple_update_plain(boards, n, delta, lr_shift, net, stream);
+    return ntuple_update_plain(boards, n, delta, lr_shift, net, nullptr, stream);
 }
 
 int g2048_ntuple_tc_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
                                  const g2048_ntuple_net *net, const g2048_ntuple_tc *tc, void *stream)
 {
-    return ntuple_tc_update_plain(boards, n, delta, lr_shift, phases, net, tc, stream);
+    const TcArgs t{phases, tc};
+    return ntuple_update_plain(boards, n, delta, lr_shift, net, &t, stream);
 }
 
 int g2048_ntuple_staged_tc_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
                                         const g2048_ntuple_staged_net *net, const g2048_ntuple_tc *tc, void *stream)
 {
-    return ntuple_tc_update_plain(boards, n, delta, lr_shift, phases, net, tc, stream);
+    const TcArgs t{phases, tc};
+    return ntuple_update_plain(boards, n, delta, lr_shift, net, &t, stream);
 }
 
 int g2048_ntuple_trace_push(const uint8_t *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,
                             uint64_t n, const g2048_ntuple_trace *tr, uint32_t slot, int64_t *delta, void *stream)
 {
-    if (!after)
-        return fail(G2048_ERR_INVALID, "after is NULL");
-    if (!after_value)
-        return fail(G2048_ERR_INVALID, "after_value is NULL");
-    if (!best_next)
-        return fail(G2048_ERR_INVALID, "best_next is NULL");
-    if (!terminated)
-        return fail(G2048_ERR_INVALID, "terminated is NULL");
-    if (!delta)
-        return fail(G2048_ERR_INVALID, "delta is NULL");
-    if (int rc = trace_boards(n))
-        return rc;
-    g2048::NtupleTrace t;
-    if (int rc = ntuple_trace(tr, slot, &t))
-        return rc;
-    if (reinterpret_cast<uintptr_t>(after) & 15u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: trace after needs 16 bytes");
-    if ((reinterpret_cast<uintptr_t>(after_value) | reinterpret_cast<uintptr_t>(best_next) | reinterpret_cast<uintptr_t>(delta)) & 7u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: trace after_value, best_next and delta need 8 bytes");
-    G2048_HIP(g2048::launch_ntuple_trace_push(reinterpret_cast<const uint4 *>(after), after_value, best_next, terminated,
-                                              static_cast<uint32_t>(n), t, slot, delta, static_cast<hipStream_t>(stream)));
-    return G2048_OK;
+    return ntuple_push<g2048::NtupleTrace>(after, after_value, best_next, terminated, n, tr, "tr", "trace", slot, delta, stream);
 }
 
 int g2048_ntuple_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, const g2048_ntuple_net *net,
                               const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
 {
-    return ntuple_trace_update(n, delta, lr_shift, net, tr, slot, stream);
+    return ntuple_trace_update(n, delta, lr_shift, net, nullptr, tr, slot, stream);
 }
 
 int g2048_ntuple_staged_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, const g2048_ntuple_staged_net *net,
                                      const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
 {
-    return ntuple_trace_update(n, delta, lr_shift, net, tr, slot, stream);
+    return ntuple_trace_update(n, delta, lr_shift, net, nullptr, tr, slot, stream);
 }
 
 int g2048_ntuple_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const g2048_ntuple_net *net,
                                  const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
 {
-    return ntuple_tc_trace_update(n, delta, lr_shift, phases, net, tc, tr, slot, stream);
+    const TcArgs t{phases, tc};
+    return ntuple_trace_update(n, delta, lr_shift, net, &t, tr, slot, stream);
 }
 
 int g2048_ntuple_staged_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
                                         const g2048_ntuple_staged_net *net, const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr,
                                         uint32_t slot, void *stream)
 {
-    return ntuple_tc_trace_update(n, delta, lr_shift, phases, net, tc, tr, slot, stream);
+    const TcArgs t{phases, tc};
+    return ntuple_trace_update(n, delta, lr_shift, net, &t, tr, slot, stream);
 }
 
 int g2048_ntuple_delay_push(const uint8_t *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,
                             uint64_t n, const g2048_ntuple_delay *dl, uint32_t slot, int64_t *delta, void *stream)
 {
-    if (!after)
-        return fail(G2048_ERR_INVALID, "after is NULL");
-    if (!after_value)
-        return fail(G2048_ERR_INVALID, "after_value is NULL");
-    if (!best_next)
-        return fail(G2048_ERR_INVALID, "best_next is NULL");
-    if (!terminated)
-        return fail(G2048_ERR_INVALID, "terminated is NULL");
-    if (!delta)
-        return fail(G2048_ERR_INVALID, "delta is NULL");
-    if (int rc = trace_boards(n))
-        return rc;
-    g2048::NtupleDelay d;
-    if (int rc = ntuple_delay(dl, slot, &d))
-        return rc;
-    if (reinterpret_cast<uintptr_t>(after) & 15u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: delay after needs 16 bytes");
-    if ((reinterpret_cast<uintptr_t>(after_value) | reinterpret_cast<uintptr_t>(best_next) | reinterpret_cast<uintptr_t>(delta)) & 7u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: delay after_value, best_next and delta need 8 bytes");
-    G2048_HIP(g2048::launch_ntuple_delay_push(reinterpret_cast<const uint4 *>(after), after_value, best_next, terminated,
-                                              static_cast<uint32_t>(n), d, slot, delta, static_cast<hipStream_t>(stream)));
-    return G2048_OK;
+    return ntuple_push<g2048::NtupleDelay>(after, after_value, best_next, terminated, n, dl, "dl", "delay", slot, delta, stream);
 }
 
 int g2048_ntuple_delay_update(uint64_t n, uint32_t lr_shift, uint32_t mode, const g2048_ntuple_net *net, const g2048_ntuple_delay *dl,
                               uint32_t slot, void *stream)
 {
-    return ntuple_delay_update(n, lr_shift, mode, net, dl, slot, stream);
+    return ntuple_delay_update(n, lr_shift, mode, net, nullptr, dl, slot, stream);
 }
 
 int g2048_ntuple_staged_delay_update(uint64_t n, uint32_t lr_shift, uint32_t mode, const g2048_ntuple_staged_net *net,
                                      const g2048_ntuple_delay *dl, uint32_t slot, void *stream)
 {
-    return ntuple_delay_update(n, lr_shift, mode, net, dl, slot, stream);
+    return ntuple_delay_update(n, lr_shift, mode, net, nullptr, dl, slot, stream);
 }
 
 int g2048_ntuple_tc_delay_update(uint64_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode, const g2048_ntuple_net *net,
                                  const g2048_ntuple_tc *tc, const g2048_ntuple_delay *dl, uint32_t slot, void *stream)
 {
-    return ntuple_tc_delay_update(n, lr_shift, phases, mode, net, tc, dl, slot, stream);
+    const TcArgs t{phases, tc};
+    return ntuple_delay_update(n, lr_shift, mode, net, &t, dl, slot, stream);
 }
 
 int g2048_ntuple_staged_tc_delay_update(uint64_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode,
                                         const g2048_ntuple_staged_net *net, const g2048_ntuple_tc *tc, const g2048_ntuple_delay *dl,
                                         uint32_t slot, void *stream)
 {
-    return ntuple_tc_delay_update(n, lr_shift, phases, mode, net, tc, dl, slot, stream);
+    const TcArgs t{phases, tc};
+    return ntuple_delay_update(n, lr_shift, mode, net, &t, dl, slot, stream);
 }
 
 // g2048_carousel and the records of a call -> the launcher's arguments, or G2048_ERR_INVALID (before any HIP call: works

@@ -94,16 +94,21 @@ struct AfterstateOut {
     void *obs;          // [n][4][16][4][4] of obs_dtype
     uint32_t obs_dtype; // G2048_OBS_*
 };
-// `plain`: `boards` holds plain exponents (taken mod 32) rather than engine records
-hipError_t launch_afterstates(const uint4 *boards, uint32_t n, bool plain, const AfterstateOut &o, hipStream_t s);
+// The boards a read-only launch works on: n engine records, or (`plain`) n rows of plain exponents (taken mod 32)
+struct Boards {
+    const uint4 *ptr;
+    uint32_t n;
+    bool plain;
+};
+hipError_t launch_afterstates(const Boards &b, const AfterstateOut &o, hipStream_t s);
 // g2048_expectimax: weights and outputs (g2048_search_io, checked by the caller; NULL = not wanted)
 struct SearchArgs {
     uint32_t base, w_empty, w_merge, w_mono; // = g2048::SearchWeights (g2048_device.h)
     uint8_t *action; // [n]
     int32_t *value;  // [n][4]
 };
-// depth 1..3; `plain` as in launch_afterstates
-hipError_t launch_expectimax(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const SearchArgs &a, hipStream_t s);
+// depth 1..3
+hipError_t launch_expectimax(const Boards &b, uint32_t depth, const SearchArgs &a, hipStream_t s);
 // g2048_mc_search: parameters and outputs (g2048_mc_io, checked by the caller; NULL = not wanted)
 struct McArgs {
     uint32_t rollouts, max_steps; // R in 1..65536, L in 1..65535
@@ -113,7 +118,7 @@ struct McArgs {
     int64_t *value;               // [n][4]
     int64_t *steps;               // [n][4]
 };
-hipError_t launch_mc_search(const uint4 *boards, uint32_t n, bool plain, const McArgs &a, hipStream_t s);
+hipError_t launch_mc_search(const Boards &b, const McArgs &a, hipStream_t s);
 // g2048_ntuple_*: the network (g2048_ntuple_net) and evaluate's outputs (g2048_ntuple_io), both checked by the caller
 struct NtupleNet {
     uint32_t n_tuples, tuple_len, frac_bits; // T in 1..8, L in 1..6, F in 0..16
@@ -129,7 +134,7 @@ struct NtupleOut {
     uint4 *after;         // [n] plain cells of the chosen afterstate
     int64_t *after_value; // [n]
 };
-hipError_t launch_ntuple_eval(const uint4 *boards, uint32_t n, bool plain, const NtupleNet &net, const NtupleOut &o, hipStream_t s);
+hipError_t launch_ntuple_eval(const Boards &b, const NtupleNet &net, const NtupleOut &o, hipStream_t s);
 // g2048_ntuple_search's outputs (g2048_ntuple_search_io), checked by the caller; depth in 1..2
 struct NtupleSearchOut {
     uint8_t *action; // [n]
@@ -137,11 +142,9 @@ struct NtupleSearchOut {
     const uint32_t *active = nullptr; // [n] or NULL (g2048_ntuple_search_active): a board at 0 is not searched, its outputs
                                       //     are those of a board with no legal move
 };
-hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
-                                const NtupleSearchOut &o, hipStream_t s);
+hipError_t launch_ntuple_search(const Boards &b, uint32_t depth, const NtupleNet &net, const NtupleSearchOut &o, hipStream_t s);
 // g2048_ntuple_deep_search: the same outputs from the workgroup-per-board kernel; depth in 2..3
-hipError_t launch_ntuple_deep_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
-                                     const NtupleSearchOut &o, hipStream_t s);
+hipError_t launch_ntuple_deep_search(const Boards &b, uint32_t depth, const NtupleNet &net, const NtupleSearchOut &o, hipStream_t s);
 // g2048_ntuple_adaptive_search: the workgroup-per-board kernel at a depth per board, schedule[E0] in 0..4 (checked by the caller)
 struct NtupleAdaptiveOut {
     uint8_t *action;        // [n] or NULL
@@ -149,8 +152,8 @@ struct NtupleAdaptiveOut {
     uint8_t *depth;         // [n] or NULL: the depth used, kNtupleAdaptiveSkipped where active is 0
     const uint32_t *active; // [n] or NULL, as NtupleSearchOut::active
 };
-hipError_t launch_ntuple_adaptive_search(const uint4 *boards, uint32_t n, const uint8_t schedule[17], bool plain, const NtupleNet &net,
-                                         const NtupleAdaptiveOut &o, hipStream_t s);
+hipError_t launch_ntuple_adaptive_search(const Boards &b, const uint8_t schedule[17], const NtupleNet &net, const NtupleAdaptiveOut &o,
+                                         hipStream_t s);
 // g2048_ntuple_play: a.k_steps greedy steps with auto-reset in one launch (spawn stream only: a.st.rng is refused by the
 // caller); the side outputs (g2048_ntuple_play_io, checked by the caller; NULL = not wanted)
 struct NtuplePlayOut {
@@ -164,43 +167,36 @@ hipError_t launch_play_step(const StepArgs &a, int action_dtype, const NtuplePla
 hipError_t launch_ntuple_values(const uint4 *boards, uint32_t n, const NtupleNet &net, int64_t *v, hipStream_t s);
 // g2048_ntuple_stage_plain: stage[i] of n plain boards; reads the network's shape and thresholds, not its weights
 hipError_t launch_ntuple_stage(const uint4 *boards, uint32_t n, const NtupleNet &net, uint8_t *stage, hipStream_t s);
-hipError_t launch_ntuple_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
-                                hipStream_t s);
-// g2048_ntuple_tc_update_plain: phase W (kNtupleTcWeights = G2048_NTUPLE_TC_WEIGHTS), then phase A (kNtupleTcAccum =
-// G2048_NTUPLE_TC_ACCUM), a launch each; phases in 1..3, err and mag [T][16^L], checked by the caller
+// The accumulators of a TC update (g2048_ntuple_tc, checked by the caller): err and mag [T][16^L]; phases in 1..3: phase W
+// (kNtupleTcWeights = G2048_NTUPLE_TC_WEIGHTS), then phase A (kNtupleTcAccum = G2048_NTUPLE_TC_ACCUM), a launch each
 constexpr uint32_t kNtupleTcWeights = 1u, kNtupleTcAccum = 2u;
-hipError_t launch_ntuple_tc_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
-                                   const NtupleNet &net, int64_t *err, int64_t *mag, hipStream_t s);
+struct NtupleTc {
+    uint32_t phases;
+    int64_t *err, *mag;
+};
+// The three updates, one per item source (plain boards, trace, delay ring); tc: NULL for the TD update, else the TC update
+hipError_t launch_ntuple_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
+                                const NtupleTc *tc, hipStream_t s);
 // g2048_ntuple_trace_*: the history (g2048_ntuple_trace), checked by the caller: depth in 1..8, lambda <= 65536, slot < depth
 struct NtupleTrace {
     uint32_t depth, lambda;
     uint4 *hist;  // [depth][n] plain boards
     uint8_t *len; // [n]
 };
-hipError_t launch_ntuple_trace_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next,
-                                    const uint8_t *terminated, uint32_t n, const NtupleTrace &tr, uint32_t slot, int64_t *delta,
-                                    hipStream_t s);
-hipError_t launch_ntuple_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
-                                      const NtupleTrace &tr, uint32_t slot, hipStream_t s);
-// phases as in launch_ntuple_tc_update: W, then A, a launch each
-hipError_t launch_ntuple_tc_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const NtupleNet &net,
-                                         int64_t *err, int64_t *mag, const NtupleTrace &tr, uint32_t slot, hipStream_t s);
-// g2048_ntuple_delay_*: the delay ring (g2048_ntuple_delay), checked by the caller as the history above; mode is
-// kNtupleDelayStep or kNtupleDelayFlush (g2048_device.h)
-struct NtupleDelay {
-    uint32_t depth, lambda;
-    uint4 *hist;  // [depth][n] plain boards
-    uint8_t *len; // [n]
+// g2048_ntuple_delay_*: the delay ring (g2048_ntuple_delay), checked by the caller as the history; mode is kNtupleDelayStep or
+// kNtupleDelayFlush (g2048_device.h)
+struct NtupleDelay : NtupleTrace {
     int64_t *acc; // [depth][n]
 };
-hipError_t launch_ntuple_delay_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next,
-                                    const uint8_t *terminated, uint32_t n, const NtupleDelay &dl, uint32_t slot, int64_t *delta,
-                                    hipStream_t s);
+// g2048_ntuple_trace_push and g2048_ntuple_delay_push: the kernel of the history's kind
+hipError_t launch_ntuple_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,
+                              uint32_t n, const NtupleTrace &tr, uint32_t slot, int64_t *delta, hipStream_t s);
+hipError_t launch_ntuple_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,
+                              uint32_t n, const NtupleDelay &dl, uint32_t slot, int64_t *delta, hipStream_t s);
+hipError_t launch_ntuple_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
+                                      const NtupleTrace &tr, uint32_t slot, const NtupleTc *tc, hipStream_t s);
 hipError_t launch_ntuple_delay_update(uint32_t n, uint32_t lr_shift, uint32_t mode, const NtupleNet &net, const NtupleDelay &dl,
-                                      uint32_t slot, hipStream_t s);
-// phases as in launch_ntuple_tc_update: W, then A, a launch each
-hipError_t launch_ntuple_tc_delay_update(uint32_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode, const NtupleNet &net,
-                                         int64_t *err, int64_t *mag, const NtupleDelay &dl, uint32_t slot, hipStream_t s);
+                                      uint32_t slot, const NtupleTc *tc, hipStream_t s);
 // g2048_carousel_step: the carousel (g2048_carousel) and the records it works on, both checked by the caller
 struct CarouselArgs {
     uint4 *records;            // [n] engine records, restarted in place

@@ -2758,12 +2758,12 @@ hipError_t launch_legal_mask(const uint4 *boards, uint32_t n, uint8_t *mask_out,
     return launch_1d(legal_mask_kernel, n, 0, s, boards, n, mask_out);
 }
 
-hipError_t launch_afterstates(const uint4 *boards, uint32_t n, bool plain, const AfterstateOut &o, hipStream_t s)
+hipError_t launch_afterstates(const Boards &b, const AfterstateOut &o, hipStream_t s)
 {
-    return dispatch_bool(plain, [&](auto plain_c) {
+    return dispatch_bool(b.plain, [&](auto plain_c) {
         if (o.obs)
-            return launch_1d(afterstates_kernel<plain_c, true>, n, kAfterstateObsPad, s, boards, n, o);
-        return launch_1d(afterstates_kernel<plain_c, false>, n, 0, s, boards, n, o);
+            return launch_1d(afterstates_kernel<plain_c, true>, b.n, kAfterstateObsPad, s, b.ptr, b.n, o);
+        return launch_1d(afterstates_kernel<plain_c, false>, b.n, 0, s, b.ptr, b.n, o);
     });
 }
 
@@ -2774,20 +2774,20 @@ static uint64_t group_lanes(uint32_t n, uint32_t G)
     return want < kSearchMaxLanes ? want : kSearchMaxLanes;
 }
 
-hipError_t launch_expectimax(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const SearchArgs &a, hipStream_t s)
+hipError_t launch_expectimax(const Boards &b, uint32_t depth, const SearchArgs &a, hipStream_t s)
 {
     return dispatch<1, 3>(static_cast<int>(depth), [&](auto dc) {
-        return dispatch_bool(plain, [&](auto plain_c) {
-            return launch_1d(expectimax_kernel<dc, plain_c>, group_lanes(n, dc == 1 ? 4u : 64u), 0, s, boards, n, a);
+        return dispatch_bool(b.plain, [&](auto plain_c) {
+            return launch_1d(expectimax_kernel<dc, plain_c>, group_lanes(b.n, dc == 1 ? 4u : 64u), 0, s, b.ptr, b.n, a);
         });
     });
 }
 
-hipError_t launch_mc_search(const uint4 *boards, uint32_t n, bool plain, const McArgs &a, hipStream_t s)
+hipError_t launch_mc_search(const Boards &b, const McArgs &a, hipStream_t s)
 {
     auto go = [&](auto gc) {
-        return dispatch_bool(plain, [&](auto plain_c) {
-            return launch_1d(mc_search_kernel<gc, plain_c>, group_lanes(n, gc), 0, s, boards, n, a);
+        return dispatch_bool(b.plain, [&](auto plain_c) {
+            return launch_1d(mc_search_kernel<gc, plain_c>, group_lanes(b.n, gc), 0, s, b.ptr, b.n, a);
         });
     };
     return a.rollouts >= kMcWaveRollouts ? go(std::integral_constant<uint32_t, 64u>()) : go(std::integral_constant<uint32_t, 16u>());
@@ -2809,11 +2809,11 @@ static hipError_t dispatch_tuples(const NtupleNet &net, F &&f)
     });
 }
 
-hipError_t launch_ntuple_eval(const uint4 *boards, uint32_t n, bool plain, const NtupleNet &net, const NtupleOut &o, hipStream_t s)
+hipError_t launch_ntuple_eval(const Boards &b, const NtupleNet &net, const NtupleOut &o, hipStream_t s)
 {
     return dispatch_tuples(net, [&](auto tc, auto sh) {
-        return dispatch_bool(plain, [&](auto plain_c) {
-            return launch_1d(ntuple_eval_kernel<tc, plain_c, decltype(sh)>, group_lanes(n, 4u), 0, s, boards, n, sh, net.frac_bits,
+        return dispatch_bool(b.plain, [&](auto plain_c) {
+            return launch_1d(ntuple_eval_kernel<tc, plain_c, decltype(sh)>, group_lanes(b.n, 4u), 0, s, b.ptr, b.n, sh, net.frac_bits,
                              static_cast<const int32_t *>(net.weights), o);
         });
     });
@@ -2833,17 +2833,24 @@ hipError_t launch_play_step(const StepArgs &a, int action_dtype, const NtuplePla
     return dispatch<0, 3>(action_dtype, [&](auto act) { return launch_1d(play_step_kernel<act>, a.n, 0, s, a, io); });
 }
 
-hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
-                                const NtupleSearchOut &o, hipStream_t s)
+// f(std::bool_constant<PLAIN>(), std::bool_constant<MASKED>()) for the three forms the search kernels are built in: engine
+// records under a mask, engine records, plain boards.  No <PLAIN, MASKED> form: the caller gives no mask for plain boards,
+// and a fourth form would be 8 x 3 more kernels per search kernel and depth.
+template <class F>
+static hipError_t dispatch_search_form(const Boards &b, const uint32_t *active, F &&f)
+{
+    if (active)
+        return f(std::false_type(), std::true_type());
+    return dispatch_bool(b.plain, [&](auto plain_c) { return f(plain_c, std::false_type()); });
+}
+
+hipError_t launch_ntuple_search(const Boards &b, uint32_t depth, const NtupleNet &net, const NtupleSearchOut &o, hipStream_t s)
 {
     return dispatch<1, static_cast<int>(kNtupleSearchMaxDepth)>(static_cast<int>(depth), [&](auto dc) {
         return dispatch_tuples(net, [&](auto tc, auto sh) {
-            if (o.active) // (engine records only: the caller gives no mask for plain boards)
-                return launch_1d(ntuple_search_kernel<dc, tc, false, decltype(sh), true>, group_lanes(n, kNtupleSearchGroup<dc>), 0, s, boards,
-                                 n, sh, net.frac_bits, static_cast<const int32_t *>(net.weights), o);
-            return dispatch_bool(plain, [&](auto plain_c) {
-                return launch_1d(ntuple_search_kernel<dc, tc, plain_c, decltype(sh)>, group_lanes(n, kNtupleSearchGroup<dc>), 0, s, boards, n, sh,
-                                 net.frac_bits, static_cast<const int32_t *>(net.weights), o);
+            return dispatch_search_form(b, o.active, [&](auto plain_c, auto masked_c) {
+                return launch_1d(ntuple_search_kernel<dc, tc, plain_c, decltype(sh), masked_c>, group_lanes(b.n, kNtupleSearchGroup<dc>), 0,
+                                 s, b.ptr, b.n, sh, net.frac_bits, static_cast<const int32_t *>(net.weights), o);
             });
         });
     });
@@ -2853,43 +2860,36 @@ hipError_t launch_ntuple_search(const uint4 *boards, uint32_t n, uint32_t depth,
 // -DG2048_PROBE_WAVE_DEPTH3 (never the product's build; `python tools/ntuple_deep_probe.py --build-wave-lib FILE` compiles such
 // a library with build_hip's flags) sends depth 3 without a mask to the alternative this kernel was timed against:
 // ntuple_search_kernel<3>, one wavefront per board.
-hipError_t launch_ntuple_deep_search(const uint4 *boards, uint32_t n, uint32_t depth, bool plain, const NtupleNet &net,
-                                     const NtupleSearchOut &o, hipStream_t s)
+hipError_t launch_ntuple_deep_search(const Boards &b, uint32_t depth, const NtupleNet &net, const NtupleSearchOut &o, hipStream_t s)
 {
 #ifdef G2048_PROBE_WAVE_DEPTH3
     if (depth == 3 && !o.active)
         return dispatch_tuples(net, [&](auto tc, auto sh) {
-            return dispatch_bool(plain, [&](auto plain_c) {
-                return launch_1d(ntuple_search_kernel<3, tc, plain_c, decltype(sh)>, group_lanes(n, kNtupleSearchGroup<3>), 0, s, boards, n, sh,
-                                 net.frac_bits, static_cast<const int32_t *>(net.weights), o);
+            return dispatch_bool(b.plain, [&](auto plain_c) {
+                return launch_1d(ntuple_search_kernel<3, tc, plain_c, decltype(sh)>, group_lanes(b.n, kNtupleSearchGroup<3>), 0, s, b.ptr, b.n,
+                                 sh, net.frac_bits, static_cast<const int32_t *>(net.weights), o);
             });
         });
 #endif
     return dispatch<static_cast<int>(kNtupleDeepMinDepth), static_cast<int>(kNtupleDeepMaxDepth)>(static_cast<int>(depth), [&](auto dc) {
         return dispatch_tuples(net, [&](auto tc, auto sh) {
-            if (o.active) // (engine records only: the caller gives no mask for plain boards)
-                return launch_1d(ntuple_deep_search_kernel<dc, tc, false, decltype(sh), true>, group_lanes(n, kBlock), 0, s, boards, n, sh,
-                                 net.frac_bits, static_cast<const int32_t *>(net.weights), o);
-            return dispatch_bool(plain, [&](auto plain_c) {
-                return launch_1d(ntuple_deep_search_kernel<dc, tc, plain_c, decltype(sh)>, group_lanes(n, kBlock), 0, s, boards, n, sh,
-                                 net.frac_bits, static_cast<const int32_t *>(net.weights), o);
+            return dispatch_search_form(b, o.active, [&](auto plain_c, auto masked_c) {
+                return launch_1d(ntuple_deep_search_kernel<dc, tc, plain_c, decltype(sh), masked_c>, group_lanes(b.n, kBlock), 0, s, b.ptr,
+                                 b.n, sh, net.frac_bits, static_cast<const int32_t *>(net.weights), o);
             });
         });
     });
 }
 
 // One workgroup per board, as launch_ntuple_deep_search; the depth is the kernel's own business
-hipError_t launch_ntuple_adaptive_search(const uint4 *boards, uint32_t n, const uint8_t schedule[17], bool plain, const NtupleNet &net,
-                                         const NtupleAdaptiveOut &o, hipStream_t s)
+hipError_t launch_ntuple_adaptive_search(const Boards &b, const uint8_t schedule[17], const NtupleNet &net, const NtupleAdaptiveOut &o,
+                                         hipStream_t s)
 {
     const NtupleAdaptiveSchedule sc = ntuple_adaptive_schedule(schedule);
     return dispatch_tuples(net, [&](auto tc, auto sh) {
-        if (o.active) // (engine records only: the caller gives no mask for plain boards)
-            return launch_1d(ntuple_adaptive_search_kernel<tc, false, decltype(sh), true>, group_lanes(n, kBlock), 0, s, boards, n, sh,
-                             net.frac_bits, static_cast<const int32_t *>(net.weights), sc, o);
-        return dispatch_bool(plain, [&](auto plain_c) {
-            return launch_1d(ntuple_adaptive_search_kernel<tc, plain_c, decltype(sh)>, group_lanes(n, kBlock), 0, s, boards, n, sh,
-                             net.frac_bits, static_cast<const int32_t *>(net.weights), sc, o);
+        return dispatch_search_form(b, o.active, [&](auto plain_c, auto masked_c) {
+            return launch_1d(ntuple_adaptive_search_kernel<tc, plain_c, decltype(sh), masked_c>, group_lanes(b.n, kBlock), 0, s, b.ptr, b.n,
+                             sh, net.frac_bits, static_cast<const int32_t *>(net.weights), sc, o);
         });
     });
 }
@@ -2939,42 +2939,34 @@ static hipError_t launch_items_tc_update(const Items &items, const int64_t *delt
     });
 }
 
+// The three updates: the TD update of the item source, or with accumulators its TC update
 hipError_t launch_ntuple_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
-                                hipStream_t s)
+                                const NtupleTc *tc, hipStream_t s)
 {
-    return launch_items_update(NtupleBoardItems{boards, n}, delta, lr_shift, net, s);
+    const NtupleBoardItems items{boards, n};
+    if (!tc)
+        return launch_items_update(items, delta, lr_shift, net, s);
+    return launch_items_tc_update(items, delta, lr_shift, tc->phases, net, tc->err, tc->mag, s);
 }
 
-hipError_t launch_ntuple_tc_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
-                                   const NtupleNet &net, int64_t *err, int64_t *mag, hipStream_t s)
-{
-    return launch_items_tc_update(NtupleBoardItems{boards, n}, delta, lr_shift, phases, net, err, mag, s);
-}
-
-hipError_t launch_ntuple_trace_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next,
-                                    const uint8_t *terminated, uint32_t n, const NtupleTrace &tr, uint32_t slot, int64_t *delta,
-                                    hipStream_t s)
+hipError_t launch_ntuple_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,
+                              uint32_t n, const NtupleTrace &tr, uint32_t slot, int64_t *delta, hipStream_t s)
 {
     return launch_1d(ntuple_trace_push_kernel, group_lanes(n, 1u), 0, s, after, after_value, best_next, terminated, n, tr.depth,
                      tr.hist + static_cast<uint64_t>(slot) * n, tr.len, delta);
 }
 
 hipError_t launch_ntuple_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
-                                      const NtupleTrace &tr, uint32_t slot, hipStream_t s)
+                                      const NtupleTrace &tr, uint32_t slot, const NtupleTc *tc, hipStream_t s)
 {
-    return launch_items_update(NtupleTraceItems{tr.hist, tr.len, n, tr.depth, tr.lambda, slot}, delta, lr_shift, net, s);
+    const NtupleTraceItems items{tr.hist, tr.len, n, tr.depth, tr.lambda, slot};
+    if (!tc)
+        return launch_items_update(items, delta, lr_shift, net, s);
+    return launch_items_tc_update(items, delta, lr_shift, tc->phases, net, tc->err, tc->mag, s);
 }
 
-hipError_t launch_ntuple_tc_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const NtupleNet &net,
-                                         int64_t *err, int64_t *mag, const NtupleTrace &tr, uint32_t slot, hipStream_t s)
-{
-    return launch_items_tc_update(NtupleTraceItems{tr.hist, tr.len, n, tr.depth, tr.lambda, slot}, delta, lr_shift, phases, net, err,
-                                  mag, s);
-}
-
-hipError_t launch_ntuple_delay_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next,
-                                    const uint8_t *terminated, uint32_t n, const NtupleDelay &dl, uint32_t slot, int64_t *delta,
-                                    hipStream_t s)
+hipError_t launch_ntuple_push(const uint4 *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,
+                              uint32_t n, const NtupleDelay &dl, uint32_t slot, int64_t *delta, hipStream_t s)
 {
     return launch_1d(ntuple_delay_push_kernel, group_lanes(n, 1u), 0, s, after, after_value, best_next, terminated, n, dl.depth,
                      dl.lambda, slot, dl.hist + static_cast<uint64_t>(slot) * n, dl.len, dl.acc, delta);
@@ -2982,15 +2974,12 @@ hipError_t launch_ntuple_delay_push(const uint4 *after, const int64_t *after_val
 
 // the accumulators go where the other sources' delta goes (NtupleDelayItems, g2048_device.h)
 hipError_t launch_ntuple_delay_update(uint32_t n, uint32_t lr_shift, uint32_t mode, const NtupleNet &net, const NtupleDelay &dl,
-                                      uint32_t slot, hipStream_t s)
+                                      uint32_t slot, const NtupleTc *tc, hipStream_t s)
 {
-    return launch_items_update(NtupleDelayItems{dl.hist, dl.len, n, dl.depth, slot, mode}, dl.acc, lr_shift, net, s);
-}
-
-hipError_t launch_ntuple_tc_delay_update(uint32_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode, const NtupleNet &net,
-                                         int64_t *err, int64_t *mag, const NtupleDelay &dl, uint32_t slot, hipStream_t s)
-{
-    return launch_items_tc_update(NtupleDelayItems{dl.hist, dl.len, n, dl.depth, slot, mode}, dl.acc, lr_shift, phases, net, err, mag, s);
+    const NtupleDelayItems items{dl.hist, dl.len, n, dl.depth, slot, mode};
+    if (!tc)
+        return launch_items_update(items, dl.acc, lr_shift, net, s);
+    return launch_items_tc_update(items, dl.acc, lr_shift, tc->phases, net, tc->err, tc->mag, s);
 }
 
 hipError_t launch_carousel_step(const CarouselArgs &a, hipStream_t s)

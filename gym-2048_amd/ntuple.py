@@ -571,13 +571,13 @@ class NTupleTC:
         self.mag.copy_(mag)
 
 
-class NTupleTrace:
-    """The history of the n-tuple traces for ``n`` boards (``g2048_ntuple_trace``, INTEGRATION.md §12): ``hist``, the last
-    ``depth`` (H, 1..8) afterstates of every board as a uint8 ``[H, n, 16]`` ring, ``len``, uint8 ``[n]`` (bits 0..6 the
-    number of valid slots, bit 7 "the episode ended at the last push"), and the slot of the last push.  ``lam`` is a float in
-    0..1, stored as ``lam_q16 = round(lam * 65536)``.  One per engine or shard; call :meth:`reset` after ``engine.reset()``.
+class _NTupleHistory:
+    """What :class:`NTupleTrace` and :class:`NTupleDelay` share: the ring of the last ``depth`` afterstates of ``n`` boards
+    and the slot of the last push.  A subclass names itself in messages (``_noun``), its push in the library (``_push``)
+    and its tensors (``_tensors``, the ``hist`` and ``len`` made here first), and builds ``_c`` over them."""
 
-    Memory: 16 H + 1 bytes per board."""
+    _noun = _push = None
+    _tensors = ("hist", "len")
 
     def __init__(self, n, depth=4, lam=0.5, device="cuda:0"):
         self.n = _int_arg("n", n, 1, 0xffffff00)
@@ -589,46 +589,64 @@ class NTupleTrace:
         self.hist = torch.zeros((self.depth, self.n, 16), dtype=torch.uint8, device=self.device)
         self.len = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
         self.slot = self.depth - 1                      # the slot of the last push: the first push goes into slot 0
-        self._c = NTupleTraceC(self.depth, self.lam_q16, self.hist.data_ptr(), self.len.data_ptr())
 
     def reset(self):
-        """Forget every board's history (``len`` = 0); the slot counter keeps running."""
+        """Forget every board's history (``len`` = 0) -- of a delay, pending errors included: flush first.  The slot counter
+        keeps running."""
         self.len.zero_()
 
     def push(self, after, after_value, best_next, terminated, out):
-        """Advance the slot and push (``g2048_ntuple_trace_push``), one launch on the current stream: store ``after`` (uint8
-        ``[n, 16]``) into the slot, update ``len`` with ``terminated`` (uint8 or bool ``[n]``), and write
-        ``out = (0 if terminated else best_next) - after_value`` (int64 ``[n]`` each).  Returns ``out``."""
+        """Advance the slot and push (``g2048_ntuple_trace_push`` or ``g2048_ntuple_delay_push``), one launch on the current
+        stream: store ``after`` (uint8 ``[n, 16]``) into the slot, update ``len`` with ``terminated`` (uint8 or bool ``[n]``),
+        and write ``out = (0 if terminated else best_next) - after_value`` (int64 ``[n]`` each); a delay also adds
+        ``clamp(out)``, decayed, to the accumulators of the board's valid slots.  Returns ``out``."""
         n, dev = self.n, self.device
         for name, t, shape, dtypes in (("after", after, (n, 16), (torch.uint8,)), ("after_value", after_value, (n,), (torch.int64,)),
                                        ("best_next", best_next, (n,), (torch.int64,)),
                                        ("terminated", terminated, (n,), (torch.uint8, torch.bool)), ("out", out, (n,), (torch.int64,))):
             _check_tensor(name, t, dtypes, shape, dev)
         slot = (self.slot + 1) % self.depth
-        _on_stream(_lib.load().g2048_ntuple_trace_push, dev, after.data_ptr(), after_value.data_ptr(), best_next.data_ptr(),
+        _on_stream(getattr(_lib.load(), self._push), dev, after.data_ptr(), after_value.data_ptr(), best_next.data_ptr(),
                    terminated.data_ptr(), n, C.byref(self._c), slot, out.data_ptr())
         self.slot = slot
         return out
 
     def state_dict(self):
-        return {"depth": self.depth, "lam_q16": self.lam_q16, "slot": self.slot, "hist": self.hist.clone(), "len": self.len.clone()}
+        return {"depth": self.depth, "lam_q16": self.lam_q16, "slot": self.slot,
+                **{name: getattr(self, name).clone() for name in self._tensors}}
 
     def load_state_dict(self, state):
-        """Copy the history and the slot counter of a ``state_dict()`` of a trace of the same shape into this one (in place)."""
+        """Copy the tensors and the slot counter of a ``state_dict()`` of one of the same kind and shape into this one (in
+        place)."""
         if int(state["depth"]) != self.depth or int(state["lam_q16"]) != self.lam_q16:
-            raise ValueError("state_dict is of a trace with another depth or lam")
-        hist, ln = torch.as_tensor(state["hist"]), torch.as_tensor(state["len"])
-        if hist.dtype != torch.uint8 or hist.shape != self.hist.shape:
-            raise ValueError(f"state_dict hist must be uint8 {tuple(self.hist.shape)}")
-        if ln.dtype != torch.uint8 or ln.shape != self.len.shape:
-            raise ValueError(f"state_dict len must be uint8 {tuple(self.len.shape)}")
+            raise ValueError(f"state_dict is of a {self._noun} with another depth or lam")
+        new = {name: torch.as_tensor(state[name]) for name in self._tensors}
+        for name in self._tensors:
+            mine = getattr(self, name)
+            if new[name].dtype != mine.dtype or new[name].shape != mine.shape:
+                raise ValueError(f"state_dict {name} must be {str(mine.dtype).replace('torch.', '')} {tuple(mine.shape)}")
         slot = _int_arg("state_dict slot", state["slot"], 0, self.depth - 1)
-        self.hist.copy_(hist)
-        self.len.copy_(ln)
+        for name in self._tensors:
+            getattr(self, name).copy_(new[name])
         self.slot = slot
 
 
-class NTupleDelay:
+class NTupleTrace(_NTupleHistory):
+    """The history of the n-tuple traces for ``n`` boards (``g2048_ntuple_trace``, INTEGRATION.md §12): ``hist``, the last
+    ``depth`` (H, 1..8) afterstates of every board as a uint8 ``[H, n, 16]`` ring, ``len``, uint8 ``[n]`` (bits 0..6 the
+    number of valid slots, bit 7 "the episode ended at the last push"), and the slot of the last push.  ``lam`` is a float in
+    0..1, stored as ``lam_q16 = round(lam * 65536)``.  One per engine or shard; call :meth:`reset` after ``engine.reset()``.
+
+    Memory: 16 H + 1 bytes per board."""
+
+    _noun, _push = "trace", "g2048_ntuple_trace_push"
+
+    def __init__(self, n, depth=4, lam=0.5, device="cuda:0"):
+        super().__init__(n, depth, lam, device)
+        self._c = NTupleTraceC(self.depth, self.lam_q16, self.hist.data_ptr(), self.len.data_ptr())
+
+
+class NTupleDelay(_NTupleHistory):
     """The delay ring of the delayed learners for ``n`` boards (``g2048_ntuple_delay``): the ``hist`` and
     ``len`` of an :class:`NTupleTrace`, plus ``acc``, int64 ``[H, n]``, the error every afterstate of the ring has collected
     so far, and the slot of the last push.  ``depth`` (H) in 1..8, ``lam`` a float in 0..1 stored as
@@ -639,54 +657,13 @@ class NTupleDelay:
 
     Memory: 24 H + 1 bytes per board."""
 
+    _noun, _push = "delay", "g2048_ntuple_delay_push"
+    _tensors = ("hist", "len", "acc")
+
     def __init__(self, n, depth=4, lam=0.5, device="cuda:0"):
-        self.n = _int_arg("n", n, 1, 0xffffff00)
-        self.depth = _int_arg("depth", depth, 1, TRACE_MAX)
-        if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0.0 <= lam <= 1.0:
-            raise ValueError(f"lam must be a number in 0..1, not {lam!r}")
-        self.lam_q16 = int(round(lam * 65536))
-        self.device = torch.device(device)
-        self.hist = torch.zeros((self.depth, self.n, 16), dtype=torch.uint8, device=self.device)
-        self.len = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        super().__init__(n, depth, lam, device)
         self.acc = torch.zeros((self.depth, self.n), dtype=torch.int64, device=self.device)
-        self.slot = self.depth - 1                      # the slot of the last push: the first push goes into slot 0
         self._c = NTupleDelayC(self.depth, self.lam_q16, self.hist.data_ptr(), self.len.data_ptr(), self.acc.data_ptr())
-
-    def reset(self):
-        """Forget every board's history (``len`` = 0), pending errors included: flush first.  The slot counter keeps running."""
-        self.len.zero_()
-
-    def push(self, after, after_value, best_next, terminated, out):
-        """Advance the slot and push (``g2048_ntuple_delay_push``), one launch on the current stream: what
-        ``NTupleTrace.push`` does with the same arguments, and ``clamp(out)``, decayed, added to the accumulators of the
-        board's valid slots.  Returns ``out``."""
-        n, dev = self.n, self.device
-        for name, t, shape, dtypes in (("after", after, (n, 16), (torch.uint8,)), ("after_value", after_value, (n,), (torch.int64,)),
-                                       ("best_next", best_next, (n,), (torch.int64,)),
-                                       ("terminated", terminated, (n,), (torch.uint8, torch.bool)), ("out", out, (n,), (torch.int64,))):
-            _check_tensor(name, t, dtypes, shape, dev)
-        slot = (self.slot + 1) % self.depth
-        _on_stream(_lib.load().g2048_ntuple_delay_push, dev, after.data_ptr(), after_value.data_ptr(), best_next.data_ptr(),
-                   terminated.data_ptr(), n, C.byref(self._c), slot, out.data_ptr())
-        self.slot = slot
-        return out
-
-    def state_dict(self):
-        return {"depth": self.depth, "lam_q16": self.lam_q16, "slot": self.slot, "hist": self.hist.clone(), "len": self.len.clone(),
-                "acc": self.acc.clone()}
-
-    def load_state_dict(self, state):
-        """Copy the ring and the slot counter of a ``state_dict()`` of a delay of the same shape into this one (in place)."""
-        if int(state["depth"]) != self.depth or int(state["lam_q16"]) != self.lam_q16:
-            raise ValueError("state_dict is of a delay with another depth or lam")
-        new = {name: torch.as_tensor(state[name]) for name in ("hist", "len", "acc")}
-        for name, mine in (("hist", self.hist), ("len", self.len), ("acc", self.acc)):
-            if new[name].dtype != mine.dtype or new[name].shape != mine.shape:
-                raise ValueError(f"state_dict {name} must be {str(mine.dtype).replace('torch.', '')} {tuple(mine.shape)}")
-        slot = _int_arg("state_dict slot", state["slot"], 0, self.depth - 1)
-        for name, mine in (("hist", self.hist), ("len", self.len), ("acc", self.acc)):
-            mine.copy_(new[name])
-        self.slot = slot
 
 
 class Carousel:
