@@ -22,43 +22,10 @@ from ntuple_mixed_helpers import THR_3, random_tc, want_tables
 from ntuple_staged_helpers import small_boards
 from ntuple_tc_helpers import assert_tables_equal
 from ntuple_trace_helpers import push_inputs
+from ntuple_update_matrix import assert_ring_equal, dev, device_state, ref_net, run_against_reference, tables
 
 pytestmark = pytest.mark.gpu
 MAXD = 1 << 40
-
-
-def dev(torch, a):
-    return torch.as_tensor(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def ref_net(tuples, seed, thr=()):
-    """The reference network (a StagedNet on the padded array, S = len(thr) + 1): full-range random int32 everywhere."""
-    return mref.mixed_net(tuples, thr, 10, mref.random_flat(tuples, seed, len(thr) + 1))
-
-
-def device_state(g, torch, rnet, rtc=None):
-    """(NTupleNet, NTupleTC or None) on the GPU with the lists, stages, weights and accumulators of a reference network."""
-    net = g.NTupleNet(rnet.tuples, frac_bits=rnet.frac_bits, stages=rnet.thr or None, mixed=True)
-    net.weights.copy_(torch.as_tensor(mref.flat_of(rnet).astype(np.int32)).reshape(net.weights.shape))
-    if rtc is None:
-        return net, None
-    tc = g.NTupleTC(net)
-    err, mag = mref.tc_flat(rtc, rnet)
-    tc.err.copy_(torch.as_tensor(err).reshape(tc.err.shape))
-    tc.mag.copy_(torch.as_tensor(mag).reshape(tc.mag.shape))
-    return net, tc
-
-
-def tables(net, tc=None):
-    """The device's arrays as flat int64, as ntuple_mixed_helpers.want_tables gives the reference's."""
-    w = net.weights.cpu().numpy().astype(np.int64).reshape(-1)
-    return (w,) if tc is None else (w, tc.err.cpu().numpy().reshape(-1), tc.mag.cpu().numpy().reshape(-1))
-
-
-def assert_ring_equal(dl, rdl, where=""):
-    assert dl.slot == rdl.slot, where
-    for name, got, want in (("hist", dl.hist, rdl.hist), ("len", dl.len, rdl.len), ("acc", dl.acc, rdl.acc_i64())):
-        assert np.array_equal(got.cpu().numpy(), want), f"{where}: {name}"
 
 
 def push_both(torch, dl, rdl, out, after, av, bn, term, where=""):
@@ -67,43 +34,6 @@ def push_both(torch, dl, rdl, out, after, av, bn, term, where=""):
     assert np.array_equal(out.cpu().numpy(), want), f"{where}: delta"
     assert_ring_equal(dl, rdl, where)
     return want
-
-
-def run_against_reference(g, torch, n, H, lam, rnet, pushes, seed, lr_shift=10, boards=None, span=1 << 40, tc_form=True):
-    """``pushes`` synthetic pushes; each is followed by the TD update on one network and by TC W + A on another (one call with
-    phases=3 on even pushes, two calls on odd ones), then the FLUSH: everything against the reference after every call.
-    Returns the number of afterstates applied by STEP updates and by the FLUSH, counted in the reference."""
-    dl, rdl = g.NTupleDelay(n, depth=H, lam=lam / 65536), dref.Delay(n, H, lam)
-    assert dl.lam_q16 == lam and dl.slot == H - 1 and not dl.len.any() and not dl.acc.any()
-    rtc = random_tc(rnet, seed + 1) if tc_form else None
-    td, _ = device_state(g, torch, rnet)
-    want_td = rnet.copy()
-    if tc_form:
-        tcn, tc = device_state(g, torch, rnet, rtc)
-        want_tcn, want_tc = rnet.copy(), rtc.copy()
-    out = torch.empty(n, dtype=torch.int64, device="cuda")
-    applied = {dref.STEP: 0, dref.FLUSH: 0}
-
-    def updates(mode, split, where):
-        applied[mode] += len(dref.due_items(rdl, mode)[1])
-        td.delay_update(dl, lr_shift, flush=bool(mode))
-        dref.delay_update(want_td, rdl, lr_shift, mode)
-        assert_tables_equal(tables(td), want_tables(want_td), names=(f"{where}: td weights",))
-        if tc_form:
-            for p in ((1, 2) if split else (3,)):
-                tcn.tc_delay_update(dl, lr_shift, tc, phases=p, flush=bool(mode))
-            dref.tc_delay_update(want_tcn, want_tc, rdl, lr_shift, 3, mode)
-            assert_tables_equal(tables(tcn, tc), want_tables(want_tcn, want_tc), names=tuple(f"{where}: tc {x}" for x in ("weights", "err", "mag")))
-        assert_ring_equal(dl, rdl, where + ": the update wrote to the ring")
-
-    for t, (after, av, bn, term) in enumerate(push_inputs(n, pushes, seed, span=span)):
-        if boards is not None:
-            after = boards[t]
-        push_both(torch, dl, rdl, out, after, av, bn, term, f"push {t}")
-        updates(dref.STEP, t % 2 == 1, f"push {t}")
-    updates(dref.FLUSH, False, "flush")
-    assert applied[dref.STEP] + applied[dref.FLUSH] == n * pushes                  # every pushed afterstate exactly once
-    return applied, rdl
 
 
 @pytest.mark.parametrize("lam", [0, 32768, 65536])

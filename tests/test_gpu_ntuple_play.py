@@ -3,7 +3,14 @@ ntuple_evaluate -> step on a second engine with the same seed, and against the r
 the smaller cases.  Compared bit for bit: the records as raw bytes, the clock, episode_stats() in full, the terminal
 records, and the records after 20 ordinary steps on both engines, which shows that the clock and the episode slots were
 left right.  Budgets (games_left) have no composition: their expectation is derived, by the reference model's ``limited``,
-from the trace of the composition on the trusted per-move path, or from the reference's own trace."""
+from the trace of the composition on the trusted per-move path, or from the reference's own trace.
+
+Instantiations of ntuple_play_kernel<T, Shape> the module runs: NtupleShape at T = 1..8 (test_every_tuple_count),
+NtupleStagedShape at T = 1..8 and NtupleMixedShape at T = 2..8, both with S = 3 (test_every_staged_and_mixed_instantiation; before
+it the staged shape ran at T = 5 alone and the mixed one at T = 8 alone, with S = 1) -- 23 of the 24 compiled.  NOT reached: the
+mixed shape at T = 1; NTupleNet takes tuple_len from the longest list, so a network of one list is never mixed and the Python
+layer cannot select it.  Measured on the MI355X's host: the module takes 7.1 s on its own; the 15 tests of
+test_every_staged_and_mixed_instantiation take 1 s together, the slowest 0.2 s."""
 import ctypes as C
 import types
 
@@ -12,6 +19,8 @@ import pytest
 
 import late_game as lg
 import ntuple_play_ref as pref
+import ntuple_staged_ref as sref
+from ntuple_deep_helpers import family_net, w32_of
 from ntuple_play_helpers import (ENGINEERED_CLOCK, budgets, engineered, engineered_trace, mixed_case, staged_case, trace_of,
                                  uniform_case)
 
@@ -145,6 +154,46 @@ def test_every_shape(g, torch_cuda, name):
     a, b = pair(g, 65)
     assert_fused_is_composition(a, b, net, 300, name)
     assert a.episode_stats()["episodes"] >= (1 if name == "zero" else 65)
+    close(a, b)
+
+
+FAMILY_CASES = [("staged", T) for T in range(1, 9)] + [("mixed", T) for T in range(2, 9)]
+_family_cases = {}
+
+
+def family_case(family, T):
+    """Network T of a family of ntuple_deep_helpers (TUPLES_8x4[:T] or ntuple_mixed_ref.MIX_8[:T], three stages on the low
+    thresholds, full-range random int32) as a case for net_of."""
+    if (family, T) not in _family_cases:
+        rnet = family_net(family, T)
+        _family_cases[family, T] = types.SimpleNamespace(name=f"{family}-{T}", rnet=rnet, w32=w32_of(rnet).reshape(-1), tuples=tuple(rnet.tuples),
+                                                         stages=rnet.thr)
+    return _family_cases[family, T]
+
+
+@pytest.mark.parametrize("family, T", FAMILY_CASES, ids=[f"{f}-{T}" for f, T in FAMILY_CASES])
+def test_every_staged_and_mixed_instantiation(g, torch_cuda, family, T):
+    """The staged and the mixed player at every tuple count, S = 3, 65 boards: the fused launch against the composition.  The
+    evaluate kernel the composition leans on is tied to the pure-Python reference for exactly these networks by
+    test_gpu_ntuple_search_matrix.py::test_evaluate_and_values_of_staged_and_mixed_networks.  k is the smallest number of steps
+    after which 65 episodes have ended, found on the composed (trusted) path, whose records -- every eighth step's -- are shown
+    by ntuple_staged_ref.stage_batch to lie in at least two stages."""
+    case = family_case(family, T)
+    net = net_of(g, torch_cuda, case)
+    assert net.n_tuples == T and (net.mixed, net.n_stages) == {"staged": (False, 3), "mixed": (True, 3)}[family]
+    scout, k, seen = engine(g, 65), 0, []
+    while scout.episode_stats()["episodes"] < 65:
+        assert k < 1000, "no 65 episodes in 1000 steps"
+        if k % 8 == 0:
+            seen.append(scout.records().cpu().numpy().copy())
+        compose(scout, net, 1)
+        k += 1
+    seen.append(scout.records().cpu().numpy().copy())
+    close(scout)
+    assert len(set(sref.stage_batch(np.concatenate(seen), case.stages).tolist())) >= 2, "inputs: the boards lie in at least two stages"
+    a, b = pair(g, 65)
+    assert_fused_is_composition(a, b, net, k, f"{family} T={T} k={k}")
+    assert a.episode_stats()["episodes"] >= 65
     close(a, b)
 
 
