@@ -128,6 +128,18 @@ class NTuplePlayIO(C.Structure):
     ]
 
 
+class NTupleTDIO(C.Structure):
+    """g2048_ntuple_td_io (include/g2048.h): device output pointers of the fused TD step (NULL = not wanted)."""
+    _fields_ = [
+        ("action", C.c_void_p),
+        ("after", C.c_void_p),
+        ("after_value", C.c_void_p),
+        ("best_next", C.c_void_p),
+        ("terminated", C.c_void_p),
+        ("delta", C.c_void_p),
+    ]
+
+
 class NTupleSearchIO(C.Structure):
     """g2048_ntuple_search_io (include/g2048.h): depth and device output pointers (NULL = not wanted)."""
     _fields_ = [
@@ -267,6 +279,11 @@ SIGNATURES = {
     "g2048_ntuple_play": (C.c_int, [_E, C.POINTER(NTupleNetC), _u32, C.POINTER(NTuplePlayIO), _S]),
     "g2048_ntuple_staged_play": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), _u32, C.POINTER(NTuplePlayIO), _S]),
     "g2048_play_step": (C.c_int, [_E, C.c_void_p, _i32, C.POINTER(NTuplePlayIO), _S]),
+    "g2048_ntuple_td_step": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleTDIO), _S]),
+    "g2048_ntuple_staged_td_step": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleTDIO), _S]),
+    "g2048_ntuple_td_train": (C.c_int, [_E, C.POINTER(NTupleNetC), _u32, _u32, C.POINTER(NTupleTDIO), C.POINTER(NTupleTCC), _S]),
+    "g2048_ntuple_staged_td_train": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), _u32, _u32, C.POINTER(NTupleTDIO),
+                                              C.POINTER(NTupleTCC), _S]),
     "g2048_ntuple_search": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), _S]),
     "g2048_ntuple_search_active": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), C.c_void_p, _S]),
     "g2048_ntuple_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), _S]),

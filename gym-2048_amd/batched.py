@@ -30,6 +30,7 @@ from .ntuple import _search_io as _ntuple_search_io
 from .ntuple import DeepPlayer, _deep_io as _ntuple_deep_io  # noqa: F401
 from .ntuple import AdaptivePlayer, NTupleAdaptive, _adaptive_io as _ntuple_adaptive_io  # noqa: F401
 from .ntuple import PlayReport, play_games, _check_tensor, _play_io  # noqa: F401
+from .ntuple import TDWork, td_evaluate, td_update, td_work, _td_io  # noqa: F401
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}
 
@@ -764,6 +765,45 @@ class Batched2048:
         io = _play_io(self.n_envs, self.device, games_left, hist, moves)
         check(self._lib.g2048_play_step(self._h, act.actions, act.action_dtype, C.byref(io), self._stream()))
         self._fresh = False
+
+    def ntuple_td_step(self, net, work, delta=True) -> TDWork:
+        """The front half of every n-tuple learner in ONE launch (``g2048_ntuple_td_step``), on the engine's
+        stream: evaluate, play the greedy move with auto-reset, evaluate the new boards and form the error.  ``work`` (a
+        :class:`TDWork`, ``td_work(engine)``) gets ``before.action``, ``before.after``, ``before.after_value``, ``after.best``
+        (not masked) and ``delta = (0 if terminated else best) - after_value``; ``self.terminated`` gets the step's; the
+        engine ends up as after ``ntuple_evaluate`` -> ``step(action)`` -> ``ntuple_evaluate``, bit for bit, and every output
+        equals that composition's.  ``self.reward`` is not written.  ``delta=False`` leaves ``work.delta`` alone (the trace
+        and delay learners' push writes it).  The weights are only read.  A spawn-stream engine only (``rng="philox"``).
+        Measured (profiles/r25_ntuple_td_probe.txt): per TD(0) step this launch is NOT faster than the
+        composition at any size timed.  At 1 024 boards a step takes 88 against 66 µs for "4x6" and 132 against 98 µs for
+        "4x6+4x4"; at 16 384 boards it is 15 % and 21 % slower; it ties at 65 536 (1 % faster, inside the spread); at 2^20 it
+        is 7 % and 1 % slower.  There is no crossover: ``fused=False`` is the faster choice below 65 536 boards and no slower
+        above.  What this buys is a TD step in the C ABI and a step of two launches that needs no host between them."""
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        ref = net._ref(self.device)
+        io = _td_io(self, work, bool(delta))
+        check(net._fn("td_step")(self._h, ref, C.byref(io), self._stream()))
+        self._fresh = False
+        return work
+
+    def ntuple_td_train(self, net, work, n_steps, lr_shift, tc=None):
+        """``n_steps`` rounds of :meth:`ntuple_td_step` and the update of ``work.before.after`` by ``work.delta`` in ONE library
+        call (``g2048_ntuple_td_train``): plain launches on the engine's stream, no Python between them.
+        ``tc`` None: ``net.update`` (TD(0)), two launches per step; an :class:`NTupleTC` of ``net``: ``net.tc_update`` with
+        ``phases=3``, three launches per step.  The bits of the same number of ``td_step`` / ``tc_step`` calls; ``work`` holds
+        the last step's values."""
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        ref = net._ref(self.device)
+        n_steps = _int_arg("n_steps", n_steps, 0, (1 << 32) - 1)
+        lr_shift = _int_arg("lr_shift", lr_shift, 0, 40)
+        if tc is not None:
+            net._own_tc(tc)
+        io = _td_io(self, work)
+        check(net._fn("td_train")(self._h, ref, n_steps, lr_shift, C.byref(io), None if tc is None else C.byref(tc._c), self._stream()))
+        if n_steps:
+            self._fresh = False
 
     def ntuple_search(self, net, depth=1, out=None, active=None) -> NTupleSearch:
         """Expectimax over an n-tuple network's afterstate values on the live boards (``g2048_ntuple_search``,

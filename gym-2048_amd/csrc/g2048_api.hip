@@ -1524,6 +1524,89 @@ template <class Net> static int ntuple_play(g2048_engine *e, const Net *net, uin
     return G2048_OK;
 }
 
+// g2048_ntuple_td_io -> the kernel's outputs, or G2048_ERR_INVALID (before any HIP call: works without a device).  what: the
+// entry point, for the one message that names it; train: after and delta are what its update reads
+static int ntuple_td_out(const g2048_ntuple_td_io *io, const char *what, bool train, g2048::NtupleTdIo *o)
+{
+    if (!io)
+        return fail(G2048_ERR_INVALID, "io is NULL");
+    if (reinterpret_cast<uintptr_t>(io->after) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple td after needs 16 bytes");
+    if ((reinterpret_cast<uintptr_t>(io->after_value) | reinterpret_cast<uintptr_t>(io->best_next) | reinterpret_cast<uintptr_t>(io->delta)) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple td after_value, best_next and delta need 8 bytes");
+    if (train && (!io->after || !io->delta))
+        return fail(G2048_ERR_INVALID, "%s needs after and delta: its update reads them (%s is NULL)", what, io->after ? "delta" : "after");
+    *o = g2048::NtupleTdIo{io->action, reinterpret_cast<uint4 *>(io->after), io->after_value, io->best_next, io->terminated, io->delta};
+    return G2048_OK;
+}
+
+// The engine of a fused TD call, looked at after everything that can be refused without it
+static int ntuple_td_engine(const g2048_engine *e, const char *what)
+{
+    if (int rc = usable(e))
+        return rc;
+    if (e->st.rng)
+        return fail(G2048_ERR_INVALID, "%s needs the spawn stream: this engine is in numpy-RNG mode, whose fused "
+                                       "form is not offered (play it with g2048_ntuple_evaluate and g2048_step)", what);
+    return G2048_OK;
+}
+
+// One transaction of the clock and one launch, as g2048_ntuple_play with k_steps == 1
+static hipError_t ntuple_td_launch(g2048_engine *e, const g2048::NtupleNet &nn, const g2048::NtupleTdIo &o, void *stream)
+{
+    e->t += 1;
+    e->fresh = 0;
+    g2048::StepArgs a = make_args(e, nullptr, 1);
+    a.k_steps = 1;
+    return g2048::launch_ntuple_td_step(a, nn, o, static_cast<hipStream_t>(stream));
+}
+
+template <class Net> static int ntuple_td_step(g2048_engine *e, const Net *net, const g2048_ntuple_td_io *io, void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleTdIo o;
+    if (int rc = ntuple_td_out(io, "g2048_ntuple_td_step", false, &o))
+        return rc;
+    if (int rc = ntuple_td_engine(e, "g2048_ntuple_td_step"))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(ntuple_td_launch(e, nn, o, stream));
+    return G2048_OK;
+}
+
+// k_steps times the fused step and the update of what it left in work, plain launches on one stream; tc: NULL for TD(0),
+// else the TC update, W then A
+template <class Net>
+static int ntuple_td_train(g2048_engine *e, const Net *net, uint32_t k_steps, uint32_t lr_shift, const g2048_ntuple_td_io *work,
+                           const g2048_ntuple_tc *tc, void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleTdIo o;
+    if (int rc = ntuple_td_out(work, "g2048_ntuple_td_train", true, &o))
+        return rc;
+    if (int rc = ntuple_delta(o.delta, lr_shift))
+        return rc;
+    const TcArgs tc_args{G2048_NTUPLE_TC_WEIGHTS | G2048_NTUPLE_TC_ACCUM, tc};
+    g2048::NtupleTc t{};
+    if (int rc = ntuple_tc(tc ? &tc_args : nullptr, &t))
+        return rc;
+    if (int rc = ntuple_td_engine(e, "g2048_ntuple_td_train"))
+        return rc;
+    if (k_steps == 0)
+        return G2048_OK;
+    G2048_HIP(hipSetDevice(e->device));
+    for (uint32_t j = 0; j < k_steps; ++j) {
+        G2048_HIP(ntuple_td_launch(e, nn, o, stream));
+        G2048_HIP(g2048::launch_ntuple_update(o.after, static_cast<uint32_t>(e->n), o.delta, lr_shift, nn, tc ? &t : nullptr,
+                                              static_cast<hipStream_t>(stream)));
+    }
+    return G2048_OK;
+}
+
 // g2048_ntuple_search_active's mask.  Those entry points check it before they look at the engine (usable() consumes a
 // pending strict-actions report, so it cannot run ahead of this).
 static int ntuple_search_mask(const uint32_t *active)
@@ -1755,6 +1838,28 @@ int g2048_ntuple_staged_play(g2048_engine *e, const g2048_ntuple_staged_net *net
                              void *stream)
 {
     return ntuple_play(e, net, k_steps, io, stream);
+}
+
+int g2048_ntuple_td_step(g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_td_io *io, void *stream)
+{
+    return ntuple_td_step(e, net, io, stream);
+}
+
+int g2048_ntuple_staged_td_step(g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_td_io *io, void *stream)
+{
+    return ntuple_td_step(e, net, io, stream);
+}
+
+int g2048_ntuple_td_train(g2048_engine *e, const g2048_ntuple_net *net, uint32_t k_steps, uint32_t lr_shift,
+                          const g2048_ntuple_td_io *work, const g2048_ntuple_tc *tc, void *stream)
+{
+    return ntuple_td_train(e, net, k_steps, lr_shift, work, tc, stream);
+}
+
+int g2048_ntuple_staged_td_train(g2048_engine *e, const g2048_ntuple_staged_net *net, uint32_t k_steps, uint32_t lr_shift,
+                                 const g2048_ntuple_td_io *work, const g2048_ntuple_tc *tc, void *stream)
+{
+    return ntuple_td_train(e, net, k_steps, lr_shift, work, tc, stream);
 }
 
 // One budgeted step with the caller's actions: g2048_ntuple_play's contract and clock at k_steps == 1, g2048_step's checks of

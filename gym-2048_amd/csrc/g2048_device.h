@@ -2071,6 +2071,78 @@ G2048_DEV StepOut ntuple_play_step(Board &rec, uint64_t t, uint32_t board, uint3
     return play_record(rec, action, w, max_exp, tb);
 }
 
+// ------------------------------------------------------- one fused TD step of the greedy n-tuple player on a record
+// g2048_ntuple_td_step (include/g2048.h): the front half of every n-tuple learner on one record --
+// ntuple_root, the step g2048_step makes of its action (the Philox block (t, board), play_record), the auto-reset, and
+// ntuple_root again on the record as it then stands (the fresh board after a reset) -- with no arithmetic of its own but the
+// delta, which is ntuple_trace_delta's.  ended(o, rec) is called once, behind play_record and before the reset overwrites the
+// terminal record, whether the episode ended or not: the device's is wave-wide (record_episode_ends), the host's a plain copy.
+//
+// ntuple_root_kept is ntuple_root for a caller that uses the chosen afterstate, its value or `best`: the same keys and so the
+// same choice, with what belongs to the best direction so far kept by a select per direction.  ntuple_root looks them up in
+// m[action] and q[action] afterwards, and an array indexed by a run-time action lives in scratch memory on the device (176
+// bytes per lane and 18 KiB of promoted LDS in the first build of ntuple_td_step_kernel); its callers so far use only
+// `action`, where that look-up is dead code.  q[] is not filled in.
+struct NtupleKept {
+    uint32_t action;
+    int64_t best;        // q[action]; 0 when no move is legal
+    Board after;         // the afterstate of `action`; the board itself when no move is legal
+    int64_t after_value; // V(after); 0 when no move is legal
+};
+
+template <uint32_t T, class Shape, class Tables>
+G2048_DEV NtupleKept ntuple_root_kept(const Board &cells, const Shape &sh, uint32_t F, const int32_t *weights, const Tables &tb)
+{
+    NtupleKept r;
+    r.best = 0;
+    r.after = cells;
+    r.after_value = 0;
+    uint64_t best = 0;
+#pragma nounroll // (one direction's body, four times: unrolled, the kernel holds 161 instead of 93 VGPRs at T = 4 and four times the code)
+    for (uint32_t d = 0; d < 4u; ++d) {
+        const NtupleMove m = ntuple_move<T>(cells, d, sh, F, weights, tb);
+        const uint64_t key = ntuple_key(m.q, m.legal, d);
+        if (m.legal && key > best) { // (a legal key is above every illegal one; two keys never tie: 3 - d is in them)
+            r.best = m.q;
+            r.after = m.after;
+            r.after_value = m.v;
+        }
+        best = key > best ? key : best;
+    }
+    r.action = root_key_action(best);
+    return r;
+}
+
+struct NtupleTdOut {
+    uint32_t action;     // the first root's: the move played
+    Board after;         // ... its afterstate, plain cells
+    int64_t after_value; // ... and V of it
+    int64_t best_next;   // `best` of the board after the step, not masked
+    int64_t delta;       // (terminated ? 0 : best_next) - after_value
+    StepOut step;
+};
+
+template <uint32_t T, class Shape, class Tables, class Ended>
+G2048_DEV NtupleTdOut ntuple_td_step(Board &rec, uint64_t t, uint32_t board, uint32_t seed_lo, uint32_t seed_hi, const Shape &sh,
+                                     uint32_t F, const int32_t *weights, uint32_t max_exp, const Tables &tb, Ended &&ended)
+{
+    NtupleTdOut out;
+    {
+        const NtupleKept r0 = ntuple_root_kept<T>(record_cells(rec), sh, F, weights, tb);
+        out.action = r0.action;
+        out.after = r0.after;
+        out.after_value = r0.after_value;
+    }
+    const Words w = philox4x32_10(static_cast<uint32_t>(t), static_cast<uint32_t>(t >> 32), board, 0u, seed_lo, seed_hi);
+    out.step = play_record(rec, out.action, w, max_exp, tb);
+    ended(out.step, rec);
+    if (out.step.terminated)
+        reset_record(rec, out.step, w, tb);
+    out.best_next = ntuple_root_kept<T>(record_cells(rec), sh, F, weights, tb).best;
+    out.delta = ntuple_trace_delta(out.best_next, out.after_value, out.step.terminated);
+    return out;
+}
+
 // ------------------------------------------------------------------------------ one env step
 struct StepResult {
     float reward;

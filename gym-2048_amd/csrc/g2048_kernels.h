@@ -164,6 +164,17 @@ struct NtuplePlayOut {
 hipError_t launch_ntuple_play(const StepArgs &a, const NtupleNet &net, const NtuplePlayOut &io, hipStream_t s);
 // g2048_play_step: one step of that launch with the actions of a.actions (action_dtype G2048_ACT_*, checked by the caller)
 hipError_t launch_play_step(const StepArgs &a, int action_dtype, const NtuplePlayOut &io, hipStream_t s);
+// g2048_ntuple_td_step: one greedy step with auto-reset and the evaluate on either side of it in one launch (spawn stream
+// only, as launch_ntuple_play); the outputs (g2048_ntuple_td_io, checked by the caller; NULL = not wanted)
+struct NtupleTdIo {
+    uint8_t *action;      // [n]
+    uint4 *after;         // [n] plain cells of the afterstate played
+    int64_t *after_value; // [n]
+    int64_t *best_next;   // [n] `best` of the board after the step, not masked
+    uint8_t *terminated;  // [n]
+    int64_t *delta;       // [n] (terminated ? 0 : best_next) - after_value
+};
+hipError_t launch_ntuple_td_step(const StepArgs &a, const NtupleNet &net, const NtupleTdIo &io, hipStream_t s);
 hipError_t launch_ntuple_values(const uint4 *boards, uint32_t n, const NtupleNet &net, int64_t *v, hipStream_t s);
 // g2048_ntuple_stage_plain: stage[i] of n plain boards; reads the network's shape and thresholds, not its weights
 hipError_t launch_ntuple_stage(const uint4 *boards, uint32_t n, const NtupleNet &net, uint8_t *stage, hipStream_t s);

@@ -1895,6 +1895,48 @@ __global__ void __launch_bounds__(kBlock) play_step_kernel(const StepArgs p, con
     }
 }
 
+// g2048_ntuple_td_step: the front half of every n-tuple learner in ONE launch (ntuple_td_step of g2048_device.h) -- evaluate,
+// play the greedy move with auto-reset, evaluate the board that is then live, form the error.  ntuple_play_kernel's lane
+// layout for its reason (one board per lane, the wavefront owns its episode slot) and its per-step bookkeeping at
+// k_steps == 1 without a budget: record_episode_ends, then reset_record, one record store, one flush_episode_counts; every
+// board is stepped and reset if its episode ended, so no pending mark survives the launch.  A kernel of its own, sharing only
+// what ntuple_play_kernel already calls: that kernel and play_step_kernel keep their register allocation
+// (profiles/r25_ntuple_td_resource_usage.txt).  A lane does both roots itself, up to 64T gathers; the weights are read with
+// plain loads, nothing in the launch writes them.  The outputs (NtupleTdIo, any of them NULL) are the lane's own entries.
+template <uint32_t T, class Shape>
+__global__ void __launch_bounds__(kBlock) ntuple_td_step_kernel(const StepArgs p, const Shape sh, uint32_t frac_bits,
+                                                                const int32_t *__restrict__ weights, const NtupleTdIo io)
+{
+    __shared__ WaveTables s_tables[kBlock / 64];
+    const Lane ln = lane_of<kBlock, false>(p.n);
+    Board rec = load_board(p.st.boards, ln.i);
+    const LdsTables tb = stage_tables(s_tables, load_tables_piece());
+    const EpisodeCounters counters = load_episode_counters(p, ln.i_raw);
+    const uint64_t t = (static_cast<uint64_t>(p.t_hi) << 32) | p.t_lo;
+    uint32_t episodes = 0, illegal_ends = 0;
+    const NtupleTdOut o = ntuple_td_step<T>(rec, t, p.board_offset + ln.i, p.seed_lo, p.seed_hi, sh, frac_bits, weights, p.max_exp, tb,
+                                            [&](const StepOut &st, const Board &terminal) { // (whole wavefronts: a ballot inside)
+                                                record_episode_ends(p, ln.i, st.terminated && ln.valid, !st.legal, terminal, episodes,
+                                                                    illegal_ends);
+                                            });
+    if (ln.valid) {
+        store_board(p.st.boards, ln.i, rec);
+        if (io.action)
+            io.action[ln.i] = static_cast<uint8_t>(o.action);
+        if (io.after)
+            store_board(io.after, ln.i, o.after);
+        if (io.after_value)
+            io.after_value[ln.i] = o.after_value;
+        if (io.best_next)
+            io.best_next[ln.i] = o.best_next;
+        if (io.terminated)
+            io.terminated[ln.i] = static_cast<uint8_t>(o.step.terminated ? 1 : 0);
+        if (io.delta)
+            io.delta[ln.i] = o.delta;
+    }
+    flush_episode_counts(counters, episodes, illegal_ends, wave_sum_lane63(ln.valid ? o.step.gain : 0u), 0ull);
+}
+
 // The nine updates (g2048_ntuple_update_plain, g2048_ntuple_tc_update_plain, g2048_ntuple_trace_update,
 // g2048_ntuple_tc_trace_update, g2048_ntuple_delay_update, g2048_ntuple_tc_delay_update; the definitions of g2048_device.h,
 // "n-tuple network value function", "Temporal-coherence learning", "n-tuple traces" and "n-tuple delay") are three kernels,
@@ -2825,6 +2867,13 @@ hipError_t launch_ntuple_play(const StepArgs &a, const NtupleNet &net, const Ntu
         return hipSuccess;
     return dispatch_tuples(net, [&](auto tc, auto sh) {
         return launch_1d(ntuple_play_kernel<tc, decltype(sh)>, a.n, 0, s, a, sh, net.frac_bits, static_cast<const int32_t *>(net.weights), io);
+    });
+}
+
+hipError_t launch_ntuple_td_step(const StepArgs &a, const NtupleNet &net, const NtupleTdIo &io, hipStream_t s)
+{
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        return launch_1d(ntuple_td_step_kernel<tc, decltype(sh)>, a.n, 0, s, a, sh, net.frac_bits, static_cast<const int32_t *>(net.weights), io);
     });
 }
 

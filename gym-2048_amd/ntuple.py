@@ -32,6 +32,10 @@ network and ``play_games(player=...)`` for any policy, through ``Batched2048.pla
 (``g2048_play_step``, ``g2048_ntuple_search_active``).
 ``NTupleNet(..., mixed=True)`` and the ragged presets of ``TUPLES`` are networks with tuples of mixed length (redundant
 encoding): tables of 16^L_t weights back to back in one ``[W]`` tensor; everything above works on them.
+``Batched2048.ntuple_td_step`` is the front half of every learner above -- evaluate, play, evaluate, form the error -- in one
+launch, and ``Batched2048.ntuple_td_train`` runs K whole TD(0) or TC steps in one library call (``g2048_ntuple_td_step``,
+``g2048_ntuple_td_train``); every trainer takes ``fused=True`` for them, the same bits.  Measured, the
+composition is the faster form, so ``fused=False`` is the default.
 """
 from __future__ import annotations
 
@@ -41,7 +45,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import CarouselC, NTupleAdaptiveIO, NTupleDeepIO, NTupleDelayC, NTupleIO, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTraceC, check
+from ._lib import CarouselC, NTupleAdaptiveIO, NTupleDeepIO, NTupleDelayC, NTupleIO, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTDIO, NTupleTraceC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
@@ -779,13 +783,47 @@ def td_work(engine) -> TDWork:
                   NTupleEval(None, None, torch.empty(n, **i64), None, None), torch.empty(n, **i64))
 
 
-def td_evaluate(engine, net, work, carousel=None) -> TDWork:
+def _td_io(engine, work, delta=True):
+    """NTupleTDIO over the buffers of ``work`` (a :class:`TDWork` of ``engine``) and ``engine.terminated``, each checked as
+    ``_check_tensor`` checks; ``delta=False`` leaves ``work.delta`` out (NULL: not written)."""
+    if not isinstance(work, TDWork) or not isinstance(work.before, NTupleEval) or not isinstance(work.after, NTupleEval):
+        raise ValueError("work must be a TDWork (td_work(engine))")
+    n, dev = engine.n_envs, engine.device
+    io = NTupleTDIO()
+    for name, t, dtype, shape in (("action", work.before.action, torch.uint8, (n,)), ("after", work.before.after, torch.uint8, (n, 16)),
+                                  ("after_value", work.before.after_value, torch.int64, (n,)),
+                                  ("best_next", work.after.best, torch.int64, (n,)),
+                                  ("terminated", engine.terminated, torch.uint8, (n,)), ("delta", work.delta, torch.int64, (n,))):
+        _check_tensor("work " + name, t, (dtype,), shape, dev)
+        if delta or name != "delta":
+            setattr(io, name, t.data_ptr())
+    return io
+
+
+def _fused_args(fused, carousel):
+    """``fused`` as a bool; ValueError for ``fused=True`` with a carousel."""
+    if fused and carousel is not None:
+        raise ValueError("fused=True cannot run a carousel: its launches sit between the step and the second evaluate and need "
+                         "the whole batch's terminated (use fused=False)")
+    return bool(fused)
+
+
+def td_evaluate(engine, net, work, carousel=None, fused=False) -> TDWork:
     """Points 1-3 of the TD(0) step and the delta of point 4, leaving the weights alone: evaluate, play the greedy move
     (auto-reset on), evaluate the new boards, ``work.delta = (0 if terminated else best') - V(after)``.  Shards that share
     one weight tensor run this on every shard before :func:`td_update` on any, so that all of them see the same weights.
     ``carousel`` (a :class:`Carousel` of this engine): ``carousel.step(engine)`` right behind the step, so a finished
     episode restarts from the carousel's pool; the second evaluate sees the restarted board, and its ``best`` is masked by
-    ``terminated`` as before.  None: exactly the launches above."""
+    ``terminated`` as before.  None: exactly the launches above.
+    ``fused=True``: all seven launches as ONE (``Batched2048.ntuple_td_step``, ``g2048_ntuple_td_step``) --
+    the same bits in ``work``, ``engine.terminated`` and the engine; ``engine.reward`` is not written.  A spawn-stream engine
+    only, and not with a ``carousel`` (ValueError): the carousel's three launches sit between the step and the second
+    evaluate and need the whole batch's ``terminated``.  Measured on the MI355X (INTEGRATION.md §21,
+    profiles/r25_ntuple_td_probe.txt): the fused step is NOT faster at any size timed -- 88 against 66 µs per TD(0) step at
+    1 024 boards ("4x6"), 15 % slower at 16 384, a tie at 65 536, 7 % slower at 2^20 -- so ``fused=False`` is the faster
+    choice below 65 536 boards and no slower above."""
+    if _fused_args(fused, carousel):
+        return engine.ntuple_td_step(net, work)
     if carousel is not None:
         _carousel_of(engine, carousel)
     engine.ntuple_evaluate(net, out=work.before)
@@ -804,18 +842,24 @@ def td_update(net, work, lr_shift):
     net.update(work.before.after, work.delta, lr_shift)
 
 
-def td_step(engine, net, lr_shift, work=None, carousel=None) -> TDWork:
+def td_step(engine, net, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """One afterstate TD(0) step of every board of ``engine`` (a ``Batched2048``) under ``net``, on the engine's stream:
     evaluate, play the greedy move, evaluate the new boards, and move V of the afterstate just played towards what
     followed it (:func:`td_evaluate`, then :func:`td_update`).  The weights change only in that last launch.  No host
-    synchronisation; ``work`` (:func:`td_work`) is reused.  ``carousel``: as in :func:`td_evaluate`."""
-    work = td_evaluate(engine, net, td_work(engine) if work is None else work, carousel)
+    synchronisation; ``work`` (:func:`td_work`) is reused.  ``carousel`` and ``fused``: as in :func:`td_evaluate`."""
+    work = td_evaluate(engine, net, td_work(engine) if work is None else work, carousel, fused)
     td_update(net, work, lr_shift)
     return work
 
 
-def train(engine, net, n_steps, lr_shift, carousel=None):
-    """``n_steps`` :func:`td_step` calls with one set of buffers."""
+def train(engine, net, n_steps, lr_shift, carousel=None, fused=False):
+    """``n_steps`` :func:`td_step` calls with one set of buffers.  ``fused=True``: ONE library call for all of them
+    (``Batched2048.ntuple_td_train``, ``g2048_ntuple_td_train``) -- two launches per step and no Python
+    between the steps, the same bits; not with a ``carousel`` (:func:`td_evaluate`).  Measured: no faster than ``fused=False``
+    at any size timed, and 34 % slower at 1 024 boards (:func:`td_evaluate`)."""
+    if _fused_args(fused, carousel):
+        engine.ntuple_td_train(net, td_work(engine), n_steps, lr_shift)
+        return net
     work = td_work(engine)
     for _ in range(int(n_steps)):
         td_step(engine, net, lr_shift, work, carousel)
@@ -829,27 +873,39 @@ def tc_update(net, tc, work, lr_shift, phases=3):
     net.tc_update(work.before.after, work.delta, lr_shift, tc, phases)
 
 
-def tc_step(engine, net, tc, lr_shift, work=None, carousel=None) -> TDWork:
+def tc_step(engine, net, tc, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """:func:`td_step` with the temporal-coherence update in place of the TD(0) one: :func:`td_evaluate`, then
-    :func:`tc_update` (two launches).  No host synchronisation; ``work`` (:func:`td_work`) is reused."""
-    work = td_evaluate(engine, net, td_work(engine) if work is None else work, carousel)
+    :func:`tc_update` (two launches).  No host synchronisation; ``work`` (:func:`td_work`) is reused.  ``fused``: as in
+    :func:`td_evaluate`."""
+    work = td_evaluate(engine, net, td_work(engine) if work is None else work, carousel, fused)
     tc_update(net, tc, work, lr_shift)
     return work
 
 
-def tc_train(engine, net, tc, n_steps, lr_shift, carousel=None):
-    """``n_steps`` :func:`tc_step` calls with one set of buffers."""
+def tc_train(engine, net, tc, n_steps, lr_shift, carousel=None, fused=False):
+    """``n_steps`` :func:`tc_step` calls with one set of buffers.  ``fused=True``: ONE library call for all of them, as in
+    :func:`train` (three launches per step); not with a ``carousel``."""
+    if _fused_args(fused, carousel):
+        net._own_tc(tc)
+        engine.ntuple_td_train(net, td_work(engine), n_steps, lr_shift, tc)
+        return net
     work = td_work(engine)
     for _ in range(int(n_steps)):
         tc_step(engine, net, tc, lr_shift, work, carousel)
     return net
 
 
-def tdl_evaluate(engine, net, trace, work, carousel=None) -> TDWork:
+def tdl_evaluate(engine, net, trace, work, carousel=None, fused=False) -> TDWork:
     """:func:`td_evaluate` for the trace learners: evaluate, play the greedy move, evaluate the new boards, then one
     ``trace.push`` that stores the afterstate just played and forms ``work.delta`` in the same launch (in place of
     td_evaluate's three element-wise ones).  Shards that share one network run this on every shard before an update on any.
-    ``carousel``: as in :func:`td_evaluate`; the trace needs nothing, its push already sees ``terminated``."""
+    ``carousel``: as in :func:`td_evaluate`; the trace needs nothing, its push already sees ``terminated``.
+    ``fused=True``: the first three launches as one (``Batched2048.ntuple_td_step`` without its ``delta``: the push writes the
+    same values); the same bits, and the exclusions of :func:`td_evaluate`."""
+    if _fused_args(fused, carousel):
+        engine.ntuple_td_step(net, work, delta=False)
+        trace.push(work.before.after, work.before.after_value, work.after.best, engine.terminated, work.delta)
+        return work
     if carousel is not None:
         _carousel_of(engine, carousel)
     engine.ntuple_evaluate(net, out=work.before)
@@ -867,35 +923,36 @@ def _trace_of(engine, trace):
     return trace
 
 
-def tdl_step(engine, net, trace, lr_shift, work=None, carousel=None) -> TDWork:
+def tdl_step(engine, net, trace, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """One afterstate TD(lambda) step of every board of ``engine`` under ``net``: :func:`tdl_evaluate`, then
-    ``net.trace_update``.  No host synchronisation; ``work`` (:func:`td_work`) is reused."""
-    work = tdl_evaluate(engine, net, _trace_of(engine, trace), td_work(engine) if work is None else work, carousel)
+    ``net.trace_update``.  No host synchronisation; ``work`` (:func:`td_work`) is reused.  ``fused``: as in
+    :func:`tdl_evaluate`."""
+    work = tdl_evaluate(engine, net, _trace_of(engine, trace), td_work(engine) if work is None else work, carousel, fused)
     net.trace_update(trace, work.delta, lr_shift)
     return work
 
 
-def tdl_train(engine, net, trace, n_steps, lr_shift, carousel=None):
+def tdl_train(engine, net, trace, n_steps, lr_shift, carousel=None, fused=False):
     """``n_steps`` :func:`tdl_step` calls with one set of buffers."""
     work = td_work(engine)
     for _ in range(int(n_steps)):
-        tdl_step(engine, net, trace, lr_shift, work, carousel)
+        tdl_step(engine, net, trace, lr_shift, work, carousel, fused)
     return net
 
 
-def tcl_step(engine, net, tc, trace, lr_shift, work=None, carousel=None) -> TDWork:
+def tcl_step(engine, net, tc, trace, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """:func:`tdl_step` with the temporal-coherence trace update: :func:`tdl_evaluate`, then ``net.tc_trace_update`` (two
     launches, W then A)."""
-    work = tdl_evaluate(engine, net, _trace_of(engine, trace), td_work(engine) if work is None else work, carousel)
+    work = tdl_evaluate(engine, net, _trace_of(engine, trace), td_work(engine) if work is None else work, carousel, fused)
     net.tc_trace_update(trace, work.delta, lr_shift, tc)
     return work
 
 
-def tcl_train(engine, net, tc, trace, n_steps, lr_shift, carousel=None):
+def tcl_train(engine, net, tc, trace, n_steps, lr_shift, carousel=None, fused=False):
     """``n_steps`` :func:`tcl_step` calls with one set of buffers."""
     work = td_work(engine)
     for _ in range(int(n_steps)):
-        tcl_step(engine, net, tc, trace, lr_shift, work, carousel)
+        tcl_step(engine, net, tc, trace, lr_shift, work, carousel, fused)
     return net
 
 
@@ -905,48 +962,49 @@ def _delay_of(engine, delay):
     return delay
 
 
-def delayed_evaluate(engine, net, delay, work, carousel=None) -> TDWork:
+def delayed_evaluate(engine, net, delay, work, carousel=None, fused=False) -> TDWork:
     """:func:`tdl_evaluate` for the delayed learners: the same launches with ``delay.push`` (an :class:`NTupleDelay`) in place
-    of ``trace.push``.  Shards that share one network run this on every shard before an update on any."""
-    return tdl_evaluate(engine, net, _delay_of(engine, delay), work, carousel)
+    of ``trace.push``.  Shards that share one network run this on every shard before an update on any.  ``fused``: as in
+    :func:`tdl_evaluate`."""
+    return tdl_evaluate(engine, net, _delay_of(engine, delay), work, carousel, fused)
 
 
-def delayed_tdl_step(engine, net, delay, lr_shift, work=None, carousel=None) -> TDWork:
+def delayed_tdl_step(engine, net, delay, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """One delayed TD(lambda) step of every board of ``engine`` under ``net``: :func:`delayed_evaluate`, then
     ``net.delay_update``.  No host synchronisation; ``work`` (:func:`td_work`) is reused.  Errors stay pending in ``delay``:
     see :func:`delayed_tdl_train`."""
-    work = delayed_evaluate(engine, net, _delay_of(engine, delay), td_work(engine) if work is None else work, carousel)
+    work = delayed_evaluate(engine, net, _delay_of(engine, delay), td_work(engine) if work is None else work, carousel, fused)
     net.delay_update(delay, lr_shift)
     return work
 
 
-def delayed_tdl_train(engine, net, delay, n_steps, lr_shift, carousel=None):
+def delayed_tdl_train(engine, net, delay, n_steps, lr_shift, carousel=None, fused=False):
     """``n_steps`` :func:`delayed_tdl_step` calls with one set of buffers, then the flush and ``delay.reset()``: no collected
     error is lost, and the next call starts every board's history anew."""
     _delay_of(engine, delay)
     work = td_work(engine)
     for _ in range(int(n_steps)):
-        delayed_tdl_step(engine, net, delay, lr_shift, work, carousel)
+        delayed_tdl_step(engine, net, delay, lr_shift, work, carousel, fused)
     net.delay_update(delay, lr_shift, flush=True)
     delay.reset()
     return net
 
 
-def delayed_tcl_step(engine, net, tc, delay, lr_shift, work=None, carousel=None) -> TDWork:
+def delayed_tcl_step(engine, net, tc, delay, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """:func:`delayed_tdl_step` with the temporal-coherence update: :func:`delayed_evaluate`, then ``net.tc_delay_update``
     (two launches, W then A)."""
-    work = delayed_evaluate(engine, net, _delay_of(engine, delay), td_work(engine) if work is None else work, carousel)
+    work = delayed_evaluate(engine, net, _delay_of(engine, delay), td_work(engine) if work is None else work, carousel, fused)
     net.tc_delay_update(delay, lr_shift, tc)
     return work
 
 
-def delayed_tcl_train(engine, net, tc, delay, n_steps, lr_shift, carousel=None):
+def delayed_tcl_train(engine, net, tc, delay, n_steps, lr_shift, carousel=None, fused=False):
     """``n_steps`` :func:`delayed_tcl_step` calls with one set of buffers, then the flush and ``delay.reset()``, as
     :func:`delayed_tdl_train`."""
     _delay_of(engine, delay)
     work = td_work(engine)
     for _ in range(int(n_steps)):
-        delayed_tcl_step(engine, net, tc, delay, lr_shift, work, carousel)
+        delayed_tcl_step(engine, net, tc, delay, lr_shift, work, carousel, fused)
     net.tc_delay_update(delay, lr_shift, tc, flush=True)
     delay.reset()
     return net

@@ -840,6 +840,43 @@ int g2048_ntuple_staged_play(g2048_engine *e, const g2048_ntuple_staged_net *net
 int g2048_play_step(g2048_engine *e, const void *actions, int32_t action_dtype, const g2048_ntuple_play_io *io /* may be NULL */,
                     void *stream);
 
+/* Fused n-tuple TD step: the front half every n-tuple learner runs each step -- evaluate, play the greedy
+ * move, evaluate the new boards, form the error -- in ONE launch.  The contract in one sentence: the engine ends in the same
+ * bits as after g2048_ntuple_evaluate -> g2048_step(its `action`, auto_reset = 1) -> g2048_ntuple_evaluate -- the records, the
+ * clock, the episode slots and the terminal records -- and every requested output equals the corresponding output of that
+ * composition: `action`, `after` and `after_value` are the first evaluate's, `terminated` is the step's, `best_next` is the
+ * second evaluate's `best` (of the fresh board where the episode ended; NOT masked by terminated) and
+ * delta = (terminated ? 0 : best_next) - after_value, the error of afterstate TD(0) and what g2048_ntuple_trace_push writes.
+ * max_tile is honoured as g2048_step honours it; the step's other outputs (reward, illegal, highest, terminal boards) are not
+ * written.  The clock and the spawn stream advance by one transaction, exactly as g2048_ntuple_play with k_steps == 1
+ * advances them.  The weights are only read, so shards that share one weight array run this on every shard and then the
+ * update on any, as with the composition.  All outputs are caller-owned device memory, each of them may be NULL (with all of
+ * them NULL the call is g2048_ntuple_play with k_steps == 1).
+ * G2048_ERR_INVALID, before any HIP call: a NULL engine, net or io, a descriptor g2048_ntuple_evaluate refuses, `after` not
+ * 16-byte or after_value / best_next / delta not 8-byte aligned, and an engine in numpy-RNG mode -- the fused form of that
+ * mode is not offered: the composition remains for it. */
+typedef struct g2048_ntuple_td_io {
+    uint8_t *action;               /* [n], or NULL */
+    uint8_t *after;                /* [n][16] plain cells of the afterstate played, 16-byte aligned, or NULL */
+    int64_t *after_value;          /* [n], or NULL */
+    int64_t *best_next;            /* [n], or NULL: `best` of the board after the step (after the auto-reset), not masked */
+    uint8_t *terminated;           /* [n], or NULL */
+    int64_t *delta;                /* [n], or NULL: (terminated ? 0 : best_next) - after_value */
+} g2048_ntuple_td_io;
+int g2048_ntuple_td_step(g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_td_io *io, void *stream);
+int g2048_ntuple_staged_td_step(g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_td_io *io, void *stream);
+/* The whole learner without the host between steps: k_steps times { g2048_ntuple_td_step into `work`, then the update of
+ * work->after by work->delta } enqueued on `stream` as plain launches (no graph capture).  tc == NULL: the update is
+ * g2048_ntuple_update_plain(work->after, n, work->delta, lr_shift, net) -- afterstate TD(0); otherwise it is
+ * g2048_ntuple_tc_update_plain(..., phases = 3, net, tc), two launches, W then A.  The result is the bits of k_steps rounds of
+ * those two calls.  work->after and work->delta are required, the other outputs are written when given; all of them hold the
+ * last step's values afterwards.  k_steps == 0 is G2048_OK and changes nothing.  G2048_ERR_INVALID, before any HIP call: what
+ * g2048_ntuple_td_step refuses, a missing after or delta, lr_shift > 40, and a tc g2048_ntuple_tc_update_plain refuses. */
+int g2048_ntuple_td_train(g2048_engine *e, const g2048_ntuple_net *net, uint32_t k_steps, uint32_t lr_shift,
+                          const g2048_ntuple_td_io *work, const g2048_ntuple_tc *tc /* NULL: TD(0) */, void *stream);
+int g2048_ntuple_staged_td_train(g2048_engine *e, const g2048_ntuple_staged_net *net, uint32_t k_steps, uint32_t lr_shift,
+                                 const g2048_ntuple_td_io *work, const g2048_ntuple_tc *tc, void *stream);
+
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream);
