@@ -17,7 +17,7 @@ ENV_ID = "2048-v0"  # the reference's registration id (env/__init__.py:3-6)
 def __getattr__(name):
     if name in ("Batched2048", "afterstates", "Afterstates", "expectimax", "Search", "SearchWeights", "mc_search",
                 "MCSearch", "NTupleNet", "NTupleEval", "NTupleSearch", "td_step", "train", "NTupleTC", "tc_update", "tc_step",
-                "tc_train", "NTupleTrace", "tdl_evaluate", "tdl_step", "tdl_train", "tcl_step",
+                "tc_train", "NTupleMean", "mean_update", "mean_step", "mean_train", "mean_tdl_step", "mean_tdl_train", "NTupleTrace", "tdl_evaluate", "tdl_step", "tdl_train", "tcl_step",
                 "tcl_train", "NTupleDelay", "delayed_evaluate", "delayed_tdl_step", "delayed_tdl_train", "delayed_tcl_step",
                 "delayed_tcl_train", "Carousel", "PlayReport", "play_games", "DeepPlayer", "NTupleAdaptive",
                 "AdaptivePlayer", "TDWork", "td_work", "td_evaluate", "td_update"):  # need torch + a GPU; imported on first use

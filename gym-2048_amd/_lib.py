@@ -181,6 +181,15 @@ class NTupleTCC(C.Structure):
     ]
 
 
+class NTupleMeanC(C.Structure):
+    """g2048_ntuple_mean (include/g2048.h): the device state of the batch-mean update, int64 sums and uint32 counts, laid out
+    as the weights."""
+    _fields_ = [
+        ("sum", C.c_void_p),
+        ("count", C.c_void_p),
+    ]
+
+
 class NTupleTraceC(C.Structure):
     """g2048_ntuple_trace (include/g2048.h): depth H, lambda in Q16 and the device history of the n-tuple traces."""
     _fields_ = [
@@ -304,6 +313,14 @@ SIGNATURES = {
     "g2048_ntuple_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, C.POINTER(NTupleNetC), C.POINTER(NTupleTraceC), _u32, _S]),
     "g2048_ntuple_tc_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleNetC), C.POINTER(NTupleTCC),
                                               C.POINTER(NTupleTraceC), _u32, _S]),
+    "g2048_ntuple_mean_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleNetC),
+                                                C.POINTER(NTupleMeanC), _S]),
+    "g2048_ntuple_mean_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleNetC), C.POINTER(NTupleMeanC),
+                                                C.POINTER(NTupleTraceC), _u32, _S]),
+    "g2048_ntuple_staged_mean_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleStagedNetC),
+                                                       C.POINTER(NTupleMeanC), _S]),
+    "g2048_ntuple_staged_mean_trace_update": (C.c_int, [_u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleStagedNetC),
+                                                       C.POINTER(NTupleMeanC), C.POINTER(NTupleTraceC), _u32, _S]),
     "g2048_ntuple_delay_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u64, C.POINTER(NTupleDelayC), _u32,
                                          C.c_void_p, _S]),
     "g2048_ntuple_delay_update": (C.c_int, [_u64, _u32, _u32, C.POINTER(NTupleNetC), C.POINTER(NTupleDelayC), _u32, _S]),

@@ -23,6 +23,7 @@ from .analysis import (MC_DEFAULT_MAX_STEPS, Afterstates, MCSearch, Search, Sear
 # the n-tuple network value function, re-exported; Batched2048.ntuple_evaluate runs it on the live boards
 from .ntuple import NTupleEval, NTupleNet, NTupleSearch, TUPLES, stage_mask, td_step, train, _eval_io  # noqa: F401
 from .ntuple import NTupleTC, tc_step, tc_train, tc_update  # noqa: F401
+from .ntuple import NTupleMean, mean_step, mean_tdl_step, mean_tdl_train, mean_train, mean_update  # noqa: F401
 from .ntuple import NTupleTrace, tcl_step, tcl_train, tdl_evaluate, tdl_step, tdl_train  # noqa: F401
 from .ntuple import NTupleDelay, delayed_evaluate, delayed_tcl_step, delayed_tcl_train, delayed_tdl_step, delayed_tdl_train  # noqa: F401
 from .ntuple import Carousel  # noqa: F401

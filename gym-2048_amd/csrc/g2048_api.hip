@@ -1465,6 +1465,36 @@ static int ntuple_tc(const TcArgs *in, g2048::NtupleTc *out)
     return G2048_OK;
 }
 
+// phases and the state as a batch-mean entry point got them; NULL from every other entry point
+struct MeanArgs {
+    uint32_t phases;
+    const g2048_ntuple_mean *mean;
+};
+
+// -> the launchers' state, for a call of `items` = H * n work items; nothing to check, and *out is left alone, for the other
+// updates
+static int ntuple_mean(const MeanArgs *in, uint64_t items, g2048::NtupleMean *out)
+{
+    if (!in)
+        return G2048_OK;
+    if (in->phases < 1 || in->phases > (G2048_NTUPLE_MEAN_SUM | G2048_NTUPLE_MEAN_APPLY))
+        return fail(G2048_ERR_INVALID, "phases=%u: need G2048_NTUPLE_MEAN_SUM (1), G2048_NTUPLE_MEAN_APPLY (2) or both (3)", in->phases);
+    if (!in->mean)
+        return fail(G2048_ERR_INVALID, "mean is NULL");
+    if (!in->mean->sum)
+        return fail(G2048_ERR_INVALID, "mean sum is NULL");
+    if (!in->mean->count)
+        return fail(G2048_ERR_INVALID, "mean count is NULL");
+    if (reinterpret_cast<uintptr_t>(in->mean->sum) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple mean sum needs 8 bytes");
+    if (reinterpret_cast<uintptr_t>(in->mean->count) & 3u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple mean count needs 4 bytes");
+    if (items >= (1ull << 29)) // 8 reaches of one entry per item: count stays below 2^32
+        return fail(G2048_ERR_INVALID, "items=%llu: a batch-mean update needs H * n < 2^29", (unsigned long long)items);
+    *out = g2048::NtupleMean{in->phases, in->mean->sum, in->mean->count};
+    return G2048_OK;
+}
+
 // The entry points that take a network, once each for Net = g2048_ntuple_net and g2048_ntuple_staged_net (the extern "C"
 // wrappers below): only ntuple_net() differs.
 template <class Net> static int ntuple_evaluate(const Source &src, const Net *net, const g2048_ntuple_io *io, void *stream)
@@ -1723,10 +1753,11 @@ template <class Net> static int ntuple_values_plain(const uint8_t *boards, uint6
     return G2048_OK;
 }
 
-// The three updates, one per item source; tc: the TC entry points' arguments, NULL for the TD update
+// The three updates, one per item source; tc: the TC entry points' arguments, NULL for the TD update; mean: the batch-mean
+// entry points', NULL for the others (never both)
 template <class Net>
 static int ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, const Net *net, const TcArgs *tc,
-                               void *stream)
+                               void *stream, const MeanArgs *mean = nullptr)
 {
     if (int rc = plain_boards(boards, n))
         return rc;
@@ -1738,6 +1769,14 @@ static int ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t 
     g2048::NtupleTc t{};
     if (int rc = ntuple_tc(tc, &t))
         return rc;
+    g2048::NtupleMean m{};
+    if (int rc = ntuple_mean(mean, n, &m))
+        return rc;
+    if (mean) {
+        G2048_HIP(g2048::launch_ntuple_mean_update(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), delta, lr_shift, nn, m,
+                                                   static_cast<hipStream_t>(stream)));
+        return G2048_OK;
+    }
     G2048_HIP(g2048::launch_ntuple_update(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), delta, lr_shift, nn,
                                           tc ? &t : nullptr, static_cast<hipStream_t>(stream)));
     return G2048_OK;
@@ -1745,7 +1784,7 @@ static int ntuple_update_plain(const uint8_t *boards, uint64_t n, const int64_t 
 
 template <class Net>
 static int ntuple_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, const Net *net, const TcArgs *tc,
-                               const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
+                               const g2048_ntuple_trace *tr, uint32_t slot, void *stream, const MeanArgs *mean = nullptr)
 {
     g2048::NtupleNet nn;
     if (int rc = ntuple_net(net, &nn))
@@ -1760,6 +1799,14 @@ static int ntuple_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shi
     g2048::NtupleTrace h;
     if (int rc = ntuple_history(tr, "tr", "trace", slot, &h))
         return rc;
+    g2048::NtupleMean m{};
+    if (int rc = ntuple_mean(mean, static_cast<uint64_t>(h.depth) * n, &m))
+        return rc;
+    if (mean) {
+        G2048_HIP(g2048::launch_ntuple_mean_trace_update(static_cast<uint32_t>(n), delta, lr_shift, nn, h, slot, m,
+                                                         static_cast<hipStream_t>(stream)));
+        return G2048_OK;
+    }
     G2048_HIP(g2048::launch_ntuple_trace_update(static_cast<uint32_t>(n), delta, lr_shift, nn, h, slot, tc ? &t : nullptr,
                                                 static_cast<hipStream_t>(stream)));
     return G2048_OK;
@@ -2037,6 +2084,20 @@ int g2048_ntuple_staged_tc_update_plain(const uint8_t *boards, uint64_t n, const
     return ntuple_update_plain(boards, n, delta, lr_shift, net, &t, stream);
 }
 
+int g2048_ntuple_mean_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                   const g2048_ntuple_net *net, const g2048_ntuple_mean *mean, void *stream)
+{
+    const MeanArgs m{phases, mean};
+    return ntuple_update_plain(boards, n, delta, lr_shift, net, nullptr, stream, &m);
+}
+
+int g2048_ntuple_staged_mean_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                          const g2048_ntuple_staged_net *net, const g2048_ntuple_mean *mean, void *stream)
+{
+    const MeanArgs m{phases, mean};
+    return ntuple_update_plain(boards, n, delta, lr_shift, net, nullptr, stream, &m);
+}
+
 int g2048_ntuple_trace_push(const uint8_t *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,
                             uint64_t n, const g2048_ntuple_trace *tr, uint32_t slot, int64_t *delta, void *stream)
 {
@@ -2068,6 +2129,21 @@ int g2048_ntuple_staged_tc_trace_update(uint64_t n, const int64_t *delta, uint32
 {
     const TcArgs t{phases, tc};
     return ntuple_trace_update(n, delta, lr_shift, net, &t, tr, slot, stream);
+}
+
+int g2048_ntuple_mean_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const g2048_ntuple_net *net,
+                                   const g2048_ntuple_mean *mean, const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
+{
+    const MeanArgs m{phases, mean};
+    return ntuple_trace_update(n, delta, lr_shift, net, nullptr, tr, slot, stream, &m);
+}
+
+int g2048_ntuple_staged_mean_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                          const g2048_ntuple_staged_net *net, const g2048_ntuple_mean *mean,
+                                          const g2048_ntuple_trace *tr, uint32_t slot, void *stream)
+{
+    const MeanArgs m{phases, mean};
+    return ntuple_trace_update(n, delta, lr_shift, net, nullptr, tr, slot, stream, &m);
 }
 
 int g2048_ntuple_delay_push(const uint8_t *after, const int64_t *after_value, const int64_t *best_next, const uint8_t *terminated,

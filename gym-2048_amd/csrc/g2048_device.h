@@ -1251,6 +1251,80 @@ G2048_DEV void ntuple_item_tc_accum(const Items &items, const int64_t *delta, ty
         ntuple_tc_accum<T>(items.packed(it), sh, d, add);
 }
 
+// Batch-mean update (g2048_ntuple_mean_update_plain / g2048_ntuple_mean_trace_update, include/g2048.h):
+// every entry reached in a call moves ONCE, by the mean of the errors that reached it, where the updates above move it once
+// per reach.  Two caller-owned arrays shaped like the weights, zero before and after every complete call: sum (int64, wraps
+// mod 2^64) and count (uint32, wraps mod 2^32).  d = tc_delta of the item; d == 0 touches nothing in either phase.
+//   phase SUM:    sum[j] += d;  count[j] += 1                                    for each of the item's 8T look-ups j
+//   phase APPLY:  c = exchange(count[j], 0);  if c != 0:  a = exchange(sum[j], 0),
+//                 weights[j] += ntuple_step(floor(a / c), lr_shift)              for the same items and look-ups
+// Whichever reach of an entry comes first in APPLY owns it; all the others read c == 0 and do nothing.  sum and count are
+// sums of integer adds and are complete before APPLY starts (a launch of its own), so the step does not depend on who the
+// owner is: the same bits in any lane order.  An entry two symmetries of one board reach has both reaches in sum and count.
+
+// floor(a / c) for c >= 1: C++ division truncates, so a negative a with a remainder is one too high
+G2048_DEV int64_t ntuple_mean_floor_div(int64_t a, uint32_t c)
+{
+    const int64_t q = a / static_cast<int64_t>(c);
+    return q - ((a % static_cast<int64_t>(c)) < 0 ? 1 : 0);
+}
+
+// Phase SUM of one board, d != 0: add(offset, d) for each of the 8T look-ups (sum += d, count += 1).
+template <uint32_t T, class Shape, class Add> G2048_DEV void ntuple_mean_sum(uint64_t packed, const Shape &sh, int64_t d, Add add)
+{
+    const uint32_t base = ntuple_stage_base(packed, sh);
+#pragma unroll
+    for (uint32_t s = 0; s < 8u; ++s)
+#pragma unroll
+        for (uint32_t t = 0; t < T; ++t)
+            add(ntuple_offset(packed, sh, s, t, base), d);
+}
+
+// Phase APPLY of one board: all 8T offsets, then all 8T claims c = claim(offset) (exchange(count, 0): independent, in flight
+// together, as the loads of ntuple_tc_weights), then for every claim that is not 0 a = take(offset) (exchange(sum, 0)), the
+// one 64-bit division of that entry, and add(offset, step) where the step is not 0.
+template <uint32_t T, class Shape, class Claim, class Take, class Add>
+G2048_DEV void ntuple_mean_apply(uint64_t packed, const Shape &sh, uint32_t lr_shift, Claim claim, Take take, Add add)
+{
+    uint32_t off[8u * T];
+    uint32_t c[8u * T];
+    const uint32_t base = ntuple_stage_base(packed, sh);
+#pragma unroll
+    for (uint32_t s = 0; s < 8u; ++s)
+#pragma unroll
+        for (uint32_t t = 0; t < T; ++t)
+            off[s * T + t] = ntuple_offset(packed, sh, s, t, base);
+#pragma unroll
+    for (uint32_t j = 0; j < 8u * T; ++j)
+        c[j] = claim(off[j]);
+#pragma unroll
+    for (uint32_t j = 0; j < 8u * T; ++j) {
+        if (c[j] == 0)
+            continue;
+        const int32_t step = ntuple_step(ntuple_mean_floor_div(take(off[j]), c[j]), lr_shift);
+        if (step != 0)
+            add(off[j], step);
+    }
+}
+
+// One item of phase SUM: d == 0 touches nothing.  add as ntuple_mean_sum takes it.
+template <uint32_t T, class Items, class Shape, class Add>
+G2048_DEV void ntuple_item_mean_sum(const Items &items, const int64_t *delta, typename Items::Item it, const Shape &sh, Add add)
+{
+    const int64_t d = items.tc_delta(delta, it);
+    if (d != 0)
+        ntuple_mean_sum<T>(items.packed(it), sh, d, add);
+}
+
+// One item of phase APPLY, the same items as phase SUM.  claim, take and add as ntuple_mean_apply takes them.
+template <uint32_t T, class Items, class Shape, class Claim, class Take, class Add>
+G2048_DEV void ntuple_item_mean_apply(const Items &items, const int64_t *delta, typename Items::Item it, uint32_t lr_shift,
+                                      const Shape &sh, Claim claim, Take take, Add add)
+{
+    if (items.tc_delta(delta, it) != 0)
+        ntuple_mean_apply<T>(items.packed(it), sh, lr_shift, claim, take, add);
+}
+
 // n-tuple delay (g2048_ntuple_delay_push / g2048_ntuple_delay_update / g2048_ntuple_tc_delay_update, include/g2048.h,
 // INTEGRATION.md §19; the delayed TD(lambda) and TC(lambda) of Jaskowski 2017): the errors an afterstate earns over the H
 // pushes after its own are collected in a per-board accumulator and applied to the tables ONCE, when the afterstate leaves

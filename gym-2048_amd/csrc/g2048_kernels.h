@@ -208,6 +208,20 @@ hipError_t launch_ntuple_trace_update(uint32_t n, const int64_t *delta, uint32_t
                                       const NtupleTrace &tr, uint32_t slot, const NtupleTc *tc, hipStream_t s);
 hipError_t launch_ntuple_delay_update(uint32_t n, uint32_t lr_shift, uint32_t mode, const NtupleNet &net, const NtupleDelay &dl,
                                       uint32_t slot, const NtupleTc *tc, hipStream_t s);
+// The state of a batch-mean update (g2048_ntuple_mean, checked by the caller): sum and count shaped like the weights; phases
+// in 1..3: phase SUM (kNtupleMeanSum = G2048_NTUPLE_MEAN_SUM), then phase APPLY (kNtupleMeanApply = G2048_NTUPLE_MEAN_APPLY), a
+// launch each
+constexpr uint32_t kNtupleMeanSum = 1u, kNtupleMeanApply = 2u;
+struct NtupleMean {
+    uint32_t phases;
+    int64_t *sum;
+    uint32_t *count;
+};
+// g2048_ntuple_mean_update_plain and g2048_ntuple_mean_trace_update: the batch-mean update over plain boards and over a trace
+hipError_t launch_ntuple_mean_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
+                                     const NtupleMean &mean, hipStream_t s);
+hipError_t launch_ntuple_mean_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
+                                           const NtupleTrace &tr, uint32_t slot, const NtupleMean &mean, hipStream_t s);
 // g2048_carousel_step: the carousel (g2048_carousel) and the records it works on, both checked by the caller
 struct CarouselArgs {
     uint4 *records;            // [n] engine records, restarted in place

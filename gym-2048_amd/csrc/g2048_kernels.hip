@@ -2005,6 +2005,56 @@ __global__ void __launch_bounds__(kBlock) ntuple_tc_accum_kernel(const Items ite
     lane_items(items, [&](typename Items::Item it) { ntuple_item_tc_accum<T>(items, delta, it, sh, add); });
 }
 
+// The batch-mean update (g2048_ntuple_mean_update_plain, g2048_ntuple_mean_trace_update; g2048_device.h "Batch-mean update"):
+// two kernels, a launch each, over board or trace items.  All atomics are relaxed and agent scope.  SUM's adds return nothing.
+// APPLY's exchanges return the old value: the first reach of an entry to arrive reads count != 0 and owns the entry, every
+// other reads the 0 it left.  sum is taken with an exchange too, not a load and a store: an atomic is performed at L2, so
+// nothing rests on what a cache of this XCD holds of another XCD's adds, and the array is zero again without a second pass.
+struct AtomicAddMean { // sum[off] += d, wrapping mod 2^64; count[off] += 1, wrapping mod 2^32
+    unsigned long long *sum;
+    uint32_t *count;
+    __device__ void operator()(uint32_t off, int64_t d) const
+    {
+        __hip_atomic_fetch_add(sum + off, static_cast<unsigned long long>(d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(count + off, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+struct AtomicClaimCount { // exchange(count[off], 0)
+    uint32_t *count;
+    __device__ uint32_t operator()(uint32_t off) const
+    {
+        return __hip_atomic_exchange(count + off, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+struct AtomicTakeSum { // exchange(sum[off], 0)
+    unsigned long long *sum;
+    __device__ int64_t operator()(uint32_t off) const
+    {
+        return static_cast<int64_t>(__hip_atomic_exchange(sum + off, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+};
+
+// Phase SUM: 8T 64-bit and 8T 32-bit adds for every item with d != 0.
+template <uint32_t T, class Shape, class Items>
+__global__ void __launch_bounds__(kBlock) ntuple_mean_sum_kernel(const Items items, const int64_t *__restrict__ delta, const Shape sh,
+                                                                 int64_t *sum, uint32_t *count)
+{
+    const AtomicAddMean add{reinterpret_cast<unsigned long long *>(sum), count};
+    lane_items(items, [&](typename Items::Item it) { ntuple_item_mean_sum<T>(items, delta, it, sh, add); });
+}
+
+// Phase APPLY: the 8T offsets, the 8T exchanges on count in flight together, then per entry this lane owns one exchange on
+// sum, one 64-bit division and one add -- once per distinct reached entry of the call, not once per reach.
+template <uint32_t T, class Shape, class Items>
+__global__ void __launch_bounds__(kBlock) ntuple_mean_apply_kernel(const Items items, const int64_t *__restrict__ delta, uint32_t lr_shift,
+                                                                   const Shape sh, int32_t *weights, int64_t *sum, uint32_t *count)
+{
+    const AtomicAddWeights add{reinterpret_cast<uint32_t *>(weights)};
+    const AtomicClaimCount claim{count};
+    const AtomicTakeSum take{reinterpret_cast<unsigned long long *>(sum)};
+    lane_items(items, [&](typename Items::Item it) { ntuple_item_mean_apply<T>(items, delta, it, lr_shift, sh, claim, take, add); });
+}
+
 // g2048_ntuple_trace_push (the definition of g2048_device.h, "n-tuple traces"): one board per lane -- one 16-byte load of
 // the afterstate and one 16-byte store into the slot, the len byte, and delta formed in the same pass (what td_evaluate
 // forms with three element-wise launches).  `slot_boards` is the slot's base, hist + slot * n, formed in 64 bits by the
@@ -2986,6 +3036,37 @@ static hipError_t launch_items_tc_update(const Items &items, const int64_t *delt
             return launch_1d(ntuple_tc_accum_kernel<tc, decltype(sh), Items>, item_lanes(items), 0, s, items, delta, sh, err, mag);
         return hipSuccess;
     });
+}
+
+// phase SUM, then phase APPLY, a launch each
+template <class Items>
+static hipError_t launch_items_mean_update(const Items &items, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
+                                           const NtupleMean &mean, hipStream_t s)
+{
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        if (mean.phases & kNtupleMeanSum) {
+            const hipError_t rc =
+                launch_1d(ntuple_mean_sum_kernel<tc, decltype(sh), Items>, item_lanes(items), 0, s, items, delta, sh, mean.sum, mean.count);
+            if (rc != hipSuccess)
+                return rc;
+        }
+        if (mean.phases & kNtupleMeanApply)
+            return launch_1d(ntuple_mean_apply_kernel<tc, decltype(sh), Items>, item_lanes(items), 0, s, items, delta, lr_shift, sh,
+                             net.weights, mean.sum, mean.count);
+        return hipSuccess;
+    });
+}
+
+hipError_t launch_ntuple_mean_update(const uint4 *boards, uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
+                                     const NtupleMean &mean, hipStream_t s)
+{
+    return launch_items_mean_update(NtupleBoardItems{boards, n}, delta, lr_shift, net, mean, s);
+}
+
+hipError_t launch_ntuple_mean_trace_update(uint32_t n, const int64_t *delta, uint32_t lr_shift, const NtupleNet &net,
+                                           const NtupleTrace &tr, uint32_t slot, const NtupleMean &mean, hipStream_t s)
+{
+    return launch_items_mean_update(NtupleTraceItems{tr.hist, tr.len, n, tr.depth, tr.lambda, slot}, delta, lr_shift, net, mean, s);
 }
 
 // The three updates: the TD update of the item source, or with accumulators its TC update

@@ -36,6 +36,9 @@ encoding): tables of 16^L_t weights back to back in one ``[
 launch, and ``Batched2048.ntuple_td_train`` runs K whole TD(0) or TC steps in one library call (``g2048_ntuple_td_step``,
 ``g2048_ntuple_td_train``); every trainer takes ``fused=True`` for them, the same bits.  Measured, the
 composition is the faster form, so ``fused=False`` is the default.
+``NTupleMean`` and ``mean_step`` / ``mean_train`` / ``mean_tdl_step`` / ``mean_tdl_train`` are the batch-mean learners: every
+table entry a batch reaches moves once, by the mean of the errors that reached it, so its learning rate does not grow with the
+batch (``g2048_ntuple_mean_update_plain``, ``g2048_ntuple_mean_trace_update``).  Opt-in.
 """
 from __future__ import annotations
 
@@ -45,7 +48,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import CarouselC, NTupleAdaptiveIO, NTupleDeepIO, NTupleDelayC, NTupleIO, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTDIO, NTupleTraceC, check
+from ._lib import CarouselC, NTupleAdaptiveIO, NTupleDeepIO, NTupleDelayC, NTupleIO, NTupleMeanC, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTDIO, NTupleTraceC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
@@ -54,6 +57,7 @@ SEARCH_MAX_DEPTH = 2                                              # G2048_NTUPLE
 DEEP_MIN_DEPTH, DEEP_MAX_DEPTH = 2, 3                             # G2048_NTUPLE_DEEP_MIN_DEPTH, G2048_NTUPLE_DEEP_MAX_DEPTH
 ADAPTIVE_MAX_DEPTH, ADAPTIVE_SKIPPED = 4, 0xff                    # G2048_NTUPLE_ADAPTIVE_MAX_DEPTH, G2048_NTUPLE_ADAPTIVE_SKIPPED
 TC_WEIGHTS, TC_ACCUM = 1, 2                                       # G2048_NTUPLE_TC_WEIGHTS, G2048_NTUPLE_TC_ACCUM
+MEAN_SUM, MEAN_APPLY = 1, 2                                       # G2048_NTUPLE_MEAN_SUM, G2048_NTUPLE_MEAN_APPLY
 TRACE_MAX = 8                                                     # G2048_NTUPLE_TRACE_MAX
 DELAY_STEP, DELAY_FLUSH = 0, 1                                    # G2048_NTUPLE_DELAY_STEP, G2048_NTUPLE_DELAY_FLUSH
 MAX_STAGES = 8                                                    # G2048_NTUPLE_MAX_STAGES
@@ -353,6 +357,10 @@ class NTupleNet:
         if not isinstance(tc, NTupleTC) or tc.net is not self:
             raise ValueError("tc must be the NTupleTC of this network")
 
+    def _own_mean(self, mean):
+        if not isinstance(mean, NTupleMean) or mean.net is not self:
+            raise ValueError("mean must be the NTupleMean of this network")
+
     def values(self, boards, out=None) -> torch.Tensor:
         """V of plain boards (``g2048_ntuple_values_plain``): ``boards`` a device ``uint8`` ``[n, 16]`` or ``[n, 4, 4]``
         tensor of exponents; returns int64 ``[n]``."""
@@ -497,6 +505,32 @@ class NTupleNet:
         _on_stream(self._fn("tc_trace_update"), trace.device, trace.n, delta.data_ptr(), shift, phases, net, C.byref(tc._c),
                    C.byref(trace._c), trace.slot)
 
+    def mean_update(self, boards, delta, lr_shift, mean, phases=3):
+        """The batch-mean update (``g2048_ntuple_mean_update_plain``) with the state of ``mean`` (an
+        :class:`NTupleMean` of this network): every entry the boards reach moves ONCE, by
+        ``sat_int32(floor(sum / count) >> lr_shift)``, the mean of the clamped deltas that reached it -- not once per reach as in
+        :meth:`update` -- so the learning rate of an entry does not grow with the batch.  Phase SUM (``phases`` bit 1) adds every
+        ``d_i`` to ``mean.sum`` and 1 to ``mean.count``; phase APPLY (bit 2) moves the weights and zeroes both.  ``boards``,
+        ``delta`` and ``lr_shift`` as in :meth:`update`; fewer than 2^29 boards.  ``phases=3`` is two launches, SUM then APPLY;
+        shards that share the network and ``mean`` run SUM on every shard, then APPLY on every shard."""
+        n, device = _plain_boards(boards)
+        net = self._ref(device)
+        _check_tensor("delta", delta, (torch.int64,), (n,), device)
+        shift = _int_arg("lr_shift", lr_shift, 0, MAX_LR_SHIFT)
+        phases = _int_arg("phases", phases, MEAN_SUM, MEAN_SUM | MEAN_APPLY)
+        self._own_mean(mean)
+        self._launch(self._fn("mean_update_plain"), boards, delta.data_ptr(), shift, phases, net, C.byref(mean._c))
+
+    def mean_trace_update(self, trace, delta, lr_shift, mean, phases=3):
+        """The batch-mean TD(lambda) update (``g2048_ntuple_mean_trace_update``): :meth:`mean_update` with
+        ``d_k`` for the k-th last afterstate of ``trace``, the items of :meth:`trace_update`; ``trace.depth * trace.n`` below
+        2^29.  ``phases=3`` is two launches, SUM then APPLY; shards run SUM on every shard, then APPLY on every shard."""
+        net, shift = self._trace_args(trace, delta, lr_shift)
+        phases = _int_arg("phases", phases, MEAN_SUM, MEAN_SUM | MEAN_APPLY)
+        self._own_mean(mean)
+        _on_stream(self._fn("mean_trace_update"), trace.device, trace.n, delta.data_ptr(), shift, phases, net, C.byref(mean._c),
+                   C.byref(trace._c), trace.slot)
+
     def _delay_args(self, delay, lr_shift, flush):
         """(net, lr_shift, mode) for a delay update: ``delay`` checked as :meth:`trace_update` checks its trace."""
         if not isinstance(delay, NTupleDelay):
@@ -573,6 +607,28 @@ class NTupleTC:
                 raise ValueError(f"state_dict {name} must be int64 {tuple(self.err.shape)}")
         self.err.copy_(err)
         self.mag.copy_(mag)
+
+
+class NTupleMean:
+    """The state of the batch-mean update for ``net`` (``g2048_ntuple_mean``): ``sum``, int64, the sum of
+    the errors that have reached every weight in the call under way, and ``count``, int32 storage read as unsigned 32-bit, the
+    number of reaches -- both of the shape of ``net.weights`` on the network's device.  Both are zero between calls: phase APPLY
+    zeroes what phase SUM wrote.  :meth:`reset` zeroes them by hand, after a call that ran SUM without APPLY.
+
+    Memory: 12 bytes per weight on top of the weight's own 4 -- 768 MiB in all for the 4x6 network."""
+
+    def __init__(self, net):
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        self.net = net
+        self.sum = torch.zeros(tuple(net.weights.shape), dtype=torch.int64, device=net.device)
+        self.count = torch.zeros(tuple(net.weights.shape), dtype=torch.int32, device=net.device)
+        self._c = NTupleMeanC(self.sum.data_ptr(), self.count.data_ptr())
+
+    def reset(self):
+        """Zero ``sum`` and ``count`` on the current stream: drops whatever a phase SUM without its APPLY left pending."""
+        self.sum.zero_()
+        self.count.zero_()
 
 
 class _NTupleHistory:
@@ -895,6 +951,35 @@ def tc_train(engine, net, tc, n_steps, lr_shift, carousel=None, fused=False):
     return net
 
 
+def mean_update(net, mean, work, lr_shift, phases=3):
+    """``net.mean_update(after, delta, lr_shift, mean, phases)`` with what :func:`td_evaluate` left in ``work``.  Shards that
+    share one network and one :class:`NTupleMean` run :func:`td_evaluate` on every shard, then this with ``phases=1`` on every
+    shard, then with ``phases=2`` on every shard: the bits of the unsharded step."""
+    net.mean_update(work.before.after, work.delta, lr_shift, mean, phases)
+
+
+def mean_step(engine, net, mean, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
+    """:func:`td_step` with the batch-mean update in place of the summed one: :func:`td_evaluate`, then :func:`mean_update` (two
+    launches).  Measured (profiles/r26_ntuple_mean_probe.txt): "4x6" with ``lr_shift`` 6 scores the same at
+    1 024 and at 65 536 boards for the same number of board-steps, where the summed update loses more than half its score; not
+    at 2^20 boards, where 2^28 board-steps are 256 updates; a step costs 1.8 to 2.15 times a :func:`td_step`.  No host synchronisation;
+    ``work`` (:func:`td_work`) is reused.  ``carousel`` and ``fused``: as in :func:`td_evaluate`."""
+    work = td_evaluate(engine, net, td_work(engine) if work is None else work, carousel, fused)
+    mean_update(net, mean, work, lr_shift)
+    return work
+
+
+def mean_train(engine, net, mean, n_steps, lr_shift, carousel=None, fused=False):
+    """``n_steps`` :func:`mean_step` calls with one set of buffers.  ``fused=True`` is the fused front half per step; there is no
+    one-call trainer for this update."""
+    net._own_mean(mean)
+    _fused_args(fused, carousel)
+    work = td_work(engine)
+    for _ in range(int(n_steps)):
+        mean_step(engine, net, mean, lr_shift, work, carousel, fused)
+    return net
+
+
 def tdl_evaluate(engine, net, trace, work, carousel=None, fused=False) -> TDWork:
     """:func:`td_evaluate` for the trace learners: evaluate, play the greedy move, evaluate the new boards, then one
     ``trace.push`` that stores the afterstate just played and forms ``work.delta`` in the same launch (in place of
@@ -937,6 +1022,22 @@ def tdl_train(engine, net, trace, n_steps, lr_shift, carousel=None, fused=False)
     work = td_work(engine)
     for _ in range(int(n_steps)):
         tdl_step(engine, net, trace, lr_shift, work, carousel, fused)
+    return net
+
+
+def mean_tdl_step(engine, net, mean, trace, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
+    """:func:`tdl_step` with the batch-mean trace update: :func:`tdl_evaluate`, then ``net.mean_trace_update`` (two launches, SUM
+    then APPLY)."""
+    work = tdl_evaluate(engine, net, _trace_of(engine, trace), td_work(engine) if work is None else work, carousel, fused)
+    net.mean_trace_update(trace, work.delta, lr_shift, mean)
+    return work
+
+
+def mean_tdl_train(engine, net, mean, trace, n_steps, lr_shift, carousel=None, fused=False):
+    """``n_steps`` :func:`mean_tdl_step` calls with one set of buffers."""
+    work = td_work(engine)
+    for _ in range(int(n_steps)):
+        mean_tdl_step(engine, net, mean, trace, lr_shift, work, carousel, fused)
     return net
 
 

@@ -516,6 +516,51 @@ int g2048_ntuple_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shif
 int g2048_ntuple_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const g2048_ntuple_net *net,
                                  const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr, uint32_t slot, void *stream);
 
+/* Batch-mean update for the network above: every learner above is lock-step -- all boards of a call see
+ * the same weights, and every board adds its own step to every entry it reaches, so an entry reached by c boards moves by c
+ * steps: its effective learning rate is c * 2^-lr_shift, and c grows with the batch.  Here every entry reached in a call moves
+ * ONCE, by the mean of the errors that reached it (the per-weight mini-batch mean), so an lr_shift chosen at 1 K boards holds
+ * at 2^20.  Notation of the TC and trace blocks; an item is a board of the call, or a (k, i) of a trace ring.
+ *   state       sum: int64 [T][16^L], 8-byte aligned;  count: uint32 [T][16^L], 4-byte aligned; both shaped like the weights
+ *               (mixed [W], staged [S][W]), device memory, caller-owned, zero-initialised by the caller and ZERO AGAIN AFTER
+ *               EVERY COMPLETE CALL (phase SUM and phase APPLY over the same items, on every shard).
+ *   d           of an item: for plain boards clamp(delta_i, -2^40, +2^40); for a trace d_k.  d == 0 touches nothing, in
+ *               either phase.
+ *   phase SUM   for every item with d != 0, every symmetry s and tuple t, j = off(a, s, t):
+ *               sum[j] += d (wraps mod 2^64), count[j] += 1 (wraps mod 2^32); fire-and-forget adds.
+ *   phase APPLY for the same items and the same (s, t):  c = exchange(count[j], 0).  c != 0: this reach owns the entry,
+ *               a = exchange(sum[j], 0), weights[j] += sat_int32(floor(a / c) >> lr_shift) -- the step of
+ *               g2048_ntuple_update_plain (a wrapping 32-bit add, a flooring shift) on the floored mean.  Every other reach of
+ *               j reads c == 0 and does nothing.
+ * Consequences:
+ *   - every entry reached in the call moves exactly once, by sat_int32(floor(floor(sum_j / count_j) / 2^lr_shift))
+ *     = sat_int32(floor(sum_j / (count_j * 2^lr_shift)));
+ *   - sum_j and count_j are sums of integer adds, complete before APPLY starts, and the claim picks an owner without
+ *     affecting the value: the weights after the call are the same bits for any lane, wave, block or launch geometry;
+ *   - an entry reached twice by one board (a symmetric board) has both reaches in sum and in count, and still moves once;
+ *   - if no entry is reached twice in a call and every |delta| <= 2^40, the result is the bits of g2048_ntuple_update_plain
+ *     (or of g2048_ntuple_trace_update);
+ *   - a batch of c copies of one (board, delta) gives the bits of one copy;
+ *   - shards that share a network and this state run SUM on every shard, then APPLY on every shard, and get the bits of the
+ *     unsharded call; APPLY on only some of the shards leaves the other shards' entries pending in sum and count;
+ *   - SUM and APPLY are separate launches on one stream, never one kernel, for the reason the TC block gives: no lane reads
+ *     an accumulator another lane of its launch adds to;
+ *   - the item count H * n (n for plain boards) must be below 2^29, else G2048_ERR_INVALID: an item reaches one entry at
+ *     most 8 times, so count cannot wrap;
+ *   - sum cannot wrap while |d| < 2^31 for every item, or while H * n <= 2^19 (8 * 2^19 * 2^40 = 2^62); otherwise it wraps
+ *     mod 2^64, a defined result.
+ * Cost: a second pass of returning atomics, and one 64-bit division per distinct reached entry. */
+#define G2048_NTUPLE_MEAN_SUM   1u
+#define G2048_NTUPLE_MEAN_APPLY 2u
+typedef struct g2048_ntuple_mean { int64_t *sum; uint32_t *count; } g2048_ntuple_mean;   /* shaped like the weights */
+/* n plain boards, delta int64[n] (device), lr_shift 0..40, as in g2048_ntuple_tc_update_plain; phases = 1 (SUM), 2 (APPLY)
+ * or 3: two launches on `stream`, SUM then APPLY.  n < 2^29. */
+int g2048_ntuple_mean_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                   const g2048_ntuple_net *net, const g2048_ntuple_mean *mean, void *stream);
+/* The batch-mean trace update: the items and d_k of g2048_ntuple_trace_update; phases as above.  tr->depth * n < 2^29. */
+int g2048_ntuple_mean_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const g2048_ntuple_net *net,
+                                   const g2048_ntuple_mean *mean, const g2048_ntuple_trace *tr, uint32_t slot, void *stream);
+
 /* N-tuple delay: delayed TD(lambda) and TC(lambda) (Jaskowski 2017, "delayed temporal coherence
  * learning").  A trace update issues up to H times the adds of the one-step update.  Here the error of a step is added to a
  * small per-board accumulator for each of the last H afterstates -- private memory, no atomics -- and an afterstate's
@@ -651,6 +696,12 @@ int g2048_ntuple_staged_trace_update(uint64_t n, const int64_t *delta, uint32_t 
 int g2048_ntuple_staged_tc_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
                                         const g2048_ntuple_staged_net *net, const g2048_ntuple_tc *tc, const g2048_ntuple_trace *tr,
                                         uint32_t slot, void *stream);
+/* mean->sum and mean->count are [S][T][16^L] ([S][W] for a mixed network). */
+int g2048_ntuple_staged_mean_update_plain(const uint8_t *boards, uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                          const g2048_ntuple_staged_net *net, const g2048_ntuple_mean *mean, void *stream);
+int g2048_ntuple_staged_mean_trace_update(uint64_t n, const int64_t *delta, uint32_t lr_shift, uint32_t phases,
+                                          const g2048_ntuple_staged_net *net, const g2048_ntuple_mean *mean,
+                                          const g2048_ntuple_trace *tr, uint32_t slot, void *stream);
 int g2048_ntuple_staged_delay_update(uint64_t n, uint32_t lr_shift, uint32_t mode, const g2048_ntuple_staged_net *net,
                                      const g2048_ntuple_delay *dl, uint32_t slot, void *stream);
 int g2048_ntuple_staged_tc_delay_update(uint64_t n, uint32_t lr_shift, uint32_t phases, uint32_t mode,
