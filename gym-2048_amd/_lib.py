@@ -172,6 +172,19 @@ class NTupleAdaptiveIO(C.Structure):
     ]
 
 
+class NTupleReducedIO(C.Structure):
+    """g2048_ntuple_reduced_io (include/g2048.h): g2048_ntuple_adaptive_io with ``reduce4``, the plies by which the children of
+    a 4 spawn are searched shallower."""
+    _fields_ = [
+        ("schedule", C.c_uint8 * 17),
+        ("reduce4", C.c_uint32),
+        ("action", C.c_void_p),
+        ("value", C.c_void_p),
+        ("depth", C.c_void_p),
+        ("active", C.c_void_p),
+    ]
+
+
 class NTupleTCC(C.Structure):
     """g2048_ntuple_tc (include/g2048.h): the device accumulators of temporal-coherence learning, int64 each, laid out as
     the weights."""
@@ -304,6 +317,10 @@ SIGNATURES = {
     "g2048_ntuple_adaptive_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleAdaptiveIO), _S]),
     "g2048_ntuple_staged_adaptive_search": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleAdaptiveIO), _S]),
     "g2048_ntuple_staged_adaptive_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleAdaptiveIO), _S]),
+    "g2048_ntuple_reduced_search": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleReducedIO), _S]),
+    "g2048_ntuple_reduced_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleReducedIO), _S]),
+    "g2048_ntuple_staged_reduced_search": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleReducedIO), _S]),
+    "g2048_ntuple_staged_reduced_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleReducedIO), _S]),
     "g2048_ntuple_values_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.c_void_p, _S]),
     "g2048_ntuple_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, C.POINTER(NTupleNetC), _S]),
     "g2048_ntuple_tc_update_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, _u32, _u32, C.POINTER(NTupleNetC),

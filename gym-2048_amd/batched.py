@@ -29,7 +29,7 @@ from .ntuple import NTupleDelay, delayed_evaluate, delayed_tcl_step, delayed_tcl
 from .ntuple import Carousel  # noqa: F401
 from .ntuple import _search_io as _ntuple_search_io
 from .ntuple import DeepPlayer, _deep_io as _ntuple_deep_io  # noqa: F401
-from .ntuple import AdaptivePlayer, NTupleAdaptive, _adaptive_io as _ntuple_adaptive_io  # noqa: F401
+from .ntuple import AdaptivePlayer, NTupleAdaptive, ReducedPlayer, _adaptive_io as _ntuple_adaptive_io  # noqa: F401
 from .ntuple import PlayReport, play_games, _check_tensor, _play_io  # noqa: F401
 from .ntuple import TDWork, td_evaluate, td_update, td_work, _td_io  # noqa: F401
 
@@ -848,6 +848,18 @@ class Batched2048:
         ref = net._ref(self.device)
         io, out = _ntuple_adaptive_io(self.n_envs, self.device, schedule, out, active)
         check(net._fn("adaptive_search")(self._h, ref, C.byref(io), self._stream()))
+        return out
+
+    def ntuple_reduced_search(self, net, schedule, reduce4=1, out=None, active=None) -> NTupleAdaptive:
+        """:meth:`ntuple_adaptive_search` with the children of a 4 spawn searched ``reduce4`` (1..2) plies shallower than their 2
+        siblings (``g2048_ntuple_reduced_search``), one launch on the engine's stream.  ``schedule``, ``out``
+        and ``active`` as in :meth:`ntuple_adaptive_search`; ``depth`` of the result is the schedule's depth.  Touches no record,
+        clock, statistic or randomness."""
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        ref = net._ref(self.device)
+        io, out = _ntuple_adaptive_io(self.n_envs, self.device, schedule, out, active, reduce4=reduce4)
+        check(net._fn("reduced_search")(self._h, ref, C.byref(io), self._stream()))
         return out
 
     def isend_numpy(self) -> np.ndarray:

@@ -1701,27 +1701,50 @@ template <class Net> static int ntuple_deep_search(const Source &src, const Net 
     return G2048_OK;
 }
 
-// g2048_ntuple_adaptive_io -> the kernel's outputs, or G2048_ERR_INVALID (before any HIP call: works without a device)
-static int ntuple_adaptive_out(const g2048_ntuple_adaptive_io *io, bool plain, g2048::NtupleAdaptiveOut *o)
+// The outputs of the two searches that take a schedule, g2048_ntuple_adaptive_io (`type`, "adaptive") and
+// g2048_ntuple_reduced_io: the kernel's outputs, or G2048_ERR_INVALID (before any HIP call: works without a device)
+static int ntuple_schedule_out(const char *type, const char *what, const uint8_t schedule[17], uint8_t *action, int64_t *value,
+                               uint8_t *depth, const uint32_t *active, bool plain, g2048::NtupleAdaptiveOut *o)
 {
-    if (!io)
-        return fail(G2048_ERR_INVALID, "io is NULL");
     for (uint32_t e = 0; e < 17u; ++e)
-        if (io->schedule[e] > G2048_NTUPLE_ADAPTIVE_MAX_DEPTH)
-            return fail(G2048_ERR_INVALID, "schedule[%u]=%u: need a depth of 0..%d", e, io->schedule[e], G2048_NTUPLE_ADAPTIVE_MAX_DEPTH);
-    if (!io->action && !io->value)
-        return fail(G2048_ERR_INVALID, "g2048_ntuple_adaptive_io requests no output (action and value are both NULL)");
-    if (reinterpret_cast<uintptr_t>(io->value) & 15u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple adaptive search value needs 16 bytes");
-    if (plain && io->active)
-        return fail(G2048_ERR_INVALID, "g2048_ntuple_adaptive_io active is for the engine forms: a plain form takes no mask");
-    if (reinterpret_cast<uintptr_t>(io->active) & 3u)
-        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple adaptive search active needs 4 bytes");
-    *o = g2048::NtupleAdaptiveOut{io->action, io->value, io->depth, io->active};
+        if (schedule[e] > G2048_NTUPLE_ADAPTIVE_MAX_DEPTH)
+            return fail(G2048_ERR_INVALID, "schedule[%u]=%u: need a depth of 0..%d", e, schedule[e], G2048_NTUPLE_ADAPTIVE_MAX_DEPTH);
+    if (!action && !value)
+        return fail(G2048_ERR_INVALID, "%s requests no output (action and value are both NULL)", type);
+    if (reinterpret_cast<uintptr_t>(value) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple %s search value needs 16 bytes", what);
+    if (plain && active)
+        return fail(G2048_ERR_INVALID, "%s active is for the engine forms: a plain form takes no mask", type);
+    if (reinterpret_cast<uintptr_t>(active) & 3u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: ntuple %s search active needs 4 bytes", what);
+    *o = g2048::NtupleAdaptiveOut{action, value, depth, active};
     return G2048_OK;
 }
 
-template <class Net> static int ntuple_adaptive_search(const Source &src, const Net *net, const g2048_ntuple_adaptive_io *io, void *stream)
+// *reduce4 = 0: the adaptive search, which reduces nothing
+static int ntuple_adaptive_out(const g2048_ntuple_adaptive_io *io, bool plain, g2048::NtupleAdaptiveOut *o, uint32_t *reduce4)
+{
+    if (!io)
+        return fail(G2048_ERR_INVALID, "io is NULL");
+    *reduce4 = 0u;
+    return ntuple_schedule_out("g2048_ntuple_adaptive_io", "adaptive", io->schedule, io->action, io->value, io->depth, io->active, plain, o);
+}
+
+static int ntuple_adaptive_out(const g2048_ntuple_reduced_io *io, bool plain, g2048::NtupleAdaptiveOut *o, uint32_t *reduce4)
+{
+    if (!io)
+        return fail(G2048_ERR_INVALID, "io is NULL");
+    if (io->reduce4 == 0u)
+        return fail(G2048_ERR_INVALID, "reduce4=0: need %d <= reduce4 <= %d; the search that reduces nothing is g2048_ntuple_adaptive_search",
+                    G2048_NTUPLE_REDUCE4_MIN, G2048_NTUPLE_REDUCE4_MAX);
+    if (io->reduce4 > G2048_NTUPLE_REDUCE4_MAX)
+        return fail(G2048_ERR_INVALID, "reduce4=%u: need %d <= reduce4 <= %d", io->reduce4, G2048_NTUPLE_REDUCE4_MIN, G2048_NTUPLE_REDUCE4_MAX);
+    *reduce4 = io->reduce4;
+    return ntuple_schedule_out("g2048_ntuple_reduced_io", "reduced", io->schedule, io->action, io->value, io->depth, io->active, plain, o);
+}
+
+// Io: g2048_ntuple_adaptive_io or g2048_ntuple_reduced_io -- one body for both searches
+template <class Net, class Io> static int ntuple_adaptive_search(const Source &src, const Net *net, const Io *io, void *stream)
 {
     if (src.rc)
         return src.rc;
@@ -1729,11 +1752,15 @@ template <class Net> static int ntuple_adaptive_search(const Source &src, const 
     if (int rc = ntuple_net(net, &nn))
         return rc;
     g2048::NtupleAdaptiveOut o;
-    if (int rc = ntuple_adaptive_out(io, src.boards.plain, &o))
+    uint32_t reduce4;
+    if (int rc = ntuple_adaptive_out(io, src.boards.plain, &o, &reduce4))
         return rc;
     if (int rc = select_device(src))
         return rc;
-    G2048_HIP(g2048::launch_ntuple_adaptive_search(src.boards, io->schedule, nn, o, static_cast<hipStream_t>(stream)));
+    if (reduce4 != 0u)
+        G2048_HIP(g2048::launch_ntuple_reduced_search(src.boards, io->schedule, reduce4, nn, o, static_cast<hipStream_t>(stream)));
+    else
+        G2048_HIP(g2048::launch_ntuple_adaptive_search(src.boards, io->schedule, nn, o, static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 
@@ -2018,6 +2045,29 @@ int g2048_ntuple_staged_adaptive_search(const g2048_engine *e, const g2048_ntupl
 
 int g2048_ntuple_staged_adaptive_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
                                               const g2048_ntuple_adaptive_io *io, void *stream)
+{
+    return ntuple_adaptive_search(from_plain(boards, n), net, io, stream);
+}
+
+int g2048_ntuple_reduced_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_reduced_io *io, void *stream)
+{
+    return ntuple_adaptive_search(from_engine(e), net, io, stream);
+}
+
+int g2048_ntuple_reduced_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net,
+                                      const g2048_ntuple_reduced_io *io, void *stream)
+{
+    return ntuple_adaptive_search(from_plain(boards, n), net, io, stream);
+}
+
+int g2048_ntuple_staged_reduced_search(const g2048_engine *e, const g2048_ntuple_staged_net *net,
+                                       const g2048_ntuple_reduced_io *io, void *stream)
+{
+    return ntuple_adaptive_search(from_engine(e), net, io, stream);
+}
+
+int g2048_ntuple_staged_reduced_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
+                                             const g2048_ntuple_reduced_io *io, void *stream)
 {
     return ntuple_adaptive_search(from_plain(boards, n), net, io, stream);
 }

@@ -1784,6 +1784,167 @@ G2048_DEV uint32_t ntuple_adaptive_finish(const NtupleDeepLds &l, uint32_t depth
     return root_key_action(best);
 }
 
+// ------------------------------------------------------------------- n-tuple reduced search
+// g2048_ntuple_reduced_search (include/g2048.h): the adaptive search of above with the rare branches
+// searched shallower.  A child board made by a 4 spawn is searched R = reduce4 (1..2) plies shallower than its 2 sibling:
+//   A^R_0(a) = V(a)
+//   S^R_k(b) = max over legal d of ((g_d << F) + A^R_k(a_d));   0 when no move is legal
+//   A^R_k(a) = floor(sum over empty c of (9 S^R_{k-1}(a, 2 in c) + S^R_{max(k-1-R, 0)}(a, 4 in c)) / (10 E(a)))   for k >= 1
+//   value[d] = (g_d << F) + A^R_D(a_d), D = schedule[E0(b)] in 0..4; kNtupleIllegal, the action and the mask as above.
+// The rule is integer and path-local: no probability and no threshold, so the bits do not depend on the split.  S^R_0 = S_0 and
+// S^R_1 = S_1 for both R (the children of S_1 are leaves already); D = 0 and D = 1 are the adaptive search.  Bounds: every term
+// is one the adaptive block bounds -- a tree here is a tree there with some levels left out -- so |value| < 2^50, a partial
+// sum of a chance node stays below 150 * 2^50 < 2^58, and value + 2^60 of ntuple_key is positive.
+//
+// The table and the steps are those of the deep search; what differs at D = 2..4:
+//   r1    the remaining depth of a level-1 item with tile v1: max(D - 1 - R [v1 is 4], 0), in 0..3
+//   r2    the remaining depth of a unit, a level-2 item with tile v2 under an item of r1 >= 1: max(r1 - 1 - R [v2 is 4], 0), 0..2
+//   expand   as ntuple_deep_expand, but an entry of an item with r1 = 0 is a LEAF ENTRY: its count is 1 where d2 is legal.  An
+//            entry with a chance node has 2 E >= 2 units, always even, so the count byte holds the three states by itself:
+//            0 illegal, 1 leaf entry, 2 E chance node.  No flag is stored anywhere else.
+//   scan     ntuple_deep_scan, unchanged (a count is still <= 30)
+//   leaves   a unit of a leaf entry: acc[e] += V(after[e]); any other unit: acc[e] += weight * S^R_{r2}(child), the tree of
+//            ntuple_reduced_state on the lane.  Units of one wave differ by up to two plies; they run ONE loop nest with run-time
+//            depths (below), so lanes of unequal depth share its instructions where their trip counts overlap.
+//   fold     S^R_{r1}(child) = max over legal d2 of (gain << F) + (count 1: acc, no division; else floor(acc / 10 E))
+//   D = 0, D = 1, root, finish: the adaptive steps, unchanged.
+constexpr uint32_t kNtupleReduce4Min = 1, kNtupleReduce4Max = 2; // = G2048_NTUPLE_REDUCE4_MIN/MAX (g2048.h)
+
+G2048_DEV uint32_t ntuple_reduced_below(uint32_t r, uint32_t R, bool four) // max(r - 1 - R [four], 0) for r >= 1
+{
+    const uint32_t less = 1u + (four ? R : 0u);
+    return r > less ? r - less : 0u;
+}
+// r1 of level-1 item `local` of a root afterstate (odd = the 4 tile), D >= 1
+G2048_DEV uint32_t ntuple_reduced_r1(uint32_t depth, uint32_t R, uint32_t local) { return ntuple_reduced_below(depth, R, (local & 1u) != 0u); }
+
+// S^R_k(b) for a run-time k in 0..1, where it is S_k: every child of the chance node is a leaf.  One loop body for both k.
+template <uint32_t T, class Shape, class Tables>
+G2048_DEV int64_t ntuple_reduced_state1(const Board &b, uint32_t k, const Shape &sh, uint32_t F, const int32_t *weights, const Tables &tb)
+{
+    int64_t best = 0;
+    bool any = false;
+#pragma unroll 1
+    for (uint32_t m = 0; m < 4u; ++m) {
+        Board a = b;
+        uint32_t gain;
+        if (move_sel(a, tb.move_sel(m), gain)) {
+            int64_t v;
+            if (k == 0u) {
+                v = ntuple_value<T>(ntuple_pack(a), sh, weights);
+            } else {
+                int64_t sum = 0;
+                chance_items(a, 0u, 1u, [&](const Board &child, uint32_t weight) {
+                    sum += static_cast<int64_t>(weight) * ntuple_search_state<0, T>(child, sh, F, weights, tb);
+                });
+                v = floor_div(sum, 10 * static_cast<int64_t>(count_empty(a)));
+            }
+            const int64_t q = static_cast<int64_t>(static_cast<uint64_t>(gain) << F) + v;
+            best = !any || q > best ? q : best;
+            any = true;
+        }
+    }
+    return best;
+}
+
+// S^R_k(b) for a run-time k in 0..2: the tree of a work unit on one lane.  At k = 2 the 2 children of the chance node are S_1
+// and the 4 children S_0, for both R (max(1 - R, 0) = 0); at k = 1 both are S_0.  No recursion and no per-lane array.
+template <uint32_t T, class Shape, class Tables>
+G2048_DEV int64_t ntuple_reduced_state(const Board &b, uint32_t k, const Shape &sh, uint32_t F, const int32_t *weights, const Tables &tb)
+{
+    int64_t best = 0;
+    bool any = false;
+#pragma unroll 1
+    for (uint32_t m = 0; m < 4u; ++m) {
+        Board a = b;
+        uint32_t gain;
+        if (move_sel(a, tb.move_sel(m), gain)) {
+            int64_t v;
+            if (k == 0u) {
+                v = ntuple_value<T>(ntuple_pack(a), sh, weights);
+            } else {
+                int64_t sum = 0;
+                chance_items(a, 0u, 1u, [&](const Board &child, uint32_t weight) {
+                    const uint32_t below = k == 2u && weight == 9u ? 1u : 0u;
+                    sum += static_cast<int64_t>(weight) * ntuple_reduced_state1<T>(child, below, sh, F, weights, tb);
+                });
+                v = floor_div(sum, 10 * static_cast<int64_t>(count_empty(a)));
+            }
+            const int64_t q = static_cast<int64_t>(static_cast<uint64_t>(gain) << F) + v;
+            best = !any || q > best ? q : best;
+            any = true;
+        }
+    }
+    return best;
+}
+
+// expand at depth 2..4: ntuple_deep_expand with the leaf entries of the items whose r1 is 0
+template <class Tables>
+G2048_DEV void ntuple_reduced_expand(NtupleDeepLds &l, uint32_t depth, uint32_t R, uint32_t lane, uint32_t P, const Tables &tb)
+{
+    const uint32_t entries = 4u * ntuple_deep_items(l);
+#pragma unroll 1
+    for (uint32_t e = lane; e < entries; e += P) {
+        uint32_t d1, local, weight, gain;
+        ntuple_deep_item1(l, e >> 2, d1, local);
+        Board a = ntuple_deep_item(l.root_after[d1], local, weight);
+        const bool legal = move_sel(a, tb.move_sel(e & 3u), gain);
+        const uint32_t units = ntuple_reduced_r1(depth, R, local) == 0u ? 1u : 2u * count_empty(a);
+        l.after[e] = a;
+        l.gain[e] = gain;
+        l.acc[e] = 0;
+        reinterpret_cast<uint8_t *>(l.count)[e] = static_cast<uint8_t>(legal ? units : 0u);
+    }
+}
+
+// leaves at depth 2..4.  add(e, x): acc[e] += x, atomically among the lanes
+template <uint32_t T, class Shape, class Tables, class Add>
+G2048_DEV void ntuple_reduced_leaves(const NtupleDeepLds &l, uint32_t depth, uint32_t R, uint32_t lane, uint32_t P, const Shape &sh,
+                                     uint32_t F, const int32_t *weights, const Tables &tb, Add add)
+{
+    const uint32_t entries = 4u * ntuple_deep_items(l), units = l.first[entries];
+#pragma unroll 1
+    for (uint32_t u = lane; u < units; u += P) {
+        const uint32_t e = ntuple_deep_entry(l, entries, u);
+        uint32_t d1, local;
+        ntuple_deep_item1(l, e >> 2, d1, local);
+        const uint32_t r1 = ntuple_reduced_r1(depth, R, local);
+        if (r1 == 0u) { // a leaf entry: its one unit is V of the entry's afterstate
+            add(e, ntuple_value<T>(ntuple_pack(l.after[e]), sh, weights));
+            continue;
+        }
+        uint32_t weight;
+        const Board child = ntuple_deep_item(l.after[e], u - l.first[e], weight);
+        const uint32_t r2 = ntuple_reduced_below(r1, R, weight == 1u);
+        add(e, static_cast<int64_t>(weight) * ntuple_reduced_state<T>(child, r2, sh, F, weights, tb));
+    }
+}
+
+// fold at depth 2..4: ntuple_deep_fold, where an entry of count 1 is a leaf entry and divides nothing
+template <class Add> G2048_DEV void ntuple_reduced_fold(const NtupleDeepLds &l, uint32_t lane, uint32_t P, uint32_t F, Add add)
+{
+    const uint32_t items = ntuple_deep_items(l);
+#pragma unroll 1
+    for (uint32_t t = lane; t < items; t += P) {
+        int64_t best = 0;
+        bool any = false;
+        uint32_t w = l.count[t];
+#pragma unroll 1
+        for (uint32_t d2 = 0; d2 < 4u; ++d2, w >>= 8) {
+            const uint32_t e = 4u * t + d2, units = w & 0xffu;
+            if (units == 0u)
+                continue;
+            const int64_t chance = units == 1u ? l.acc[e] : floor_div(l.acc[e], 5 * static_cast<int64_t>(units));
+            const int64_t q = static_cast<int64_t>(static_cast<uint64_t>(l.gain[e]) << F) + chance;
+            best = !any || q > best ? q : best;
+            any = true;
+        }
+        uint32_t d1, local;
+        ntuple_deep_item1(l, t, d1, local);
+        add(d1, ((local & 1u) ? 1 : 9) * best);
+    }
+}
+
 // ------------------------------------------------------------------- carousel shaping
 // Stage-balanced restarts for training a staged network (g2048_carousel_step, include/g2048.h, INTEGRATION.md §14;
 // Jaskowski 2017): every episode starts from an empty board, so the weight sets of the late stages see a vanishing share of

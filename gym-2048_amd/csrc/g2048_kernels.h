@@ -154,6 +154,10 @@ struct NtupleAdaptiveOut {
 };
 hipError_t launch_ntuple_adaptive_search(const Boards &b, const uint8_t schedule[17], const NtupleNet &net, const NtupleAdaptiveOut &o,
                                          hipStream_t s);
+// g2048_ntuple_reduced_search: the same outputs with the children of a 4 spawn searched reduce4 (1..2, checked by the caller)
+// plies shallower
+hipError_t launch_ntuple_reduced_search(const Boards &b, const uint8_t schedule[17], uint32_t reduce4, const NtupleNet &net,
+                                        const NtupleAdaptiveOut &o, hipStream_t s);
 // g2048_ntuple_play: a.k_steps greedy steps with auto-reset in one launch (spawn stream only: a.st.rng is refused by the
 // caller); the side outputs (g2048_ntuple_play_io, checked by the caller; NULL = not wanted)
 struct NtuplePlayOut {

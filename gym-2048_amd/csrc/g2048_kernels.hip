@@ -1747,6 +1747,74 @@ __global__ void __launch_bounds__(kBlock) ntuple_adaptive_search_kernel(const ui
     }
 }
 
+// g2048_ntuple_reduced_search: ntuple_adaptive_search_kernel with the children of a 4 spawn searched `reduce4` plies shallower
+// -- the steps of g2048_device.h ("n-tuple reduced search") with a barrier after each.  The depth is a run-time value of the
+// workgroup and reduce4 one of the launch: every branch on them around a barrier is wave-uniform.  Depths 0 and 1 run the
+// adaptive steps.  At depth 2..4 the units of a board differ by up to two plies; a lane runs ntuple_reduced_state, ONE loop
+// nest with run-time depths that holds three bodies of the look-up where the adaptive kernel's S_0, S_1 and S_2 hold six, so
+// lanes of unequal depth share instructions.  The deepest path is still three nested move loops on a lane, and the registers
+// and waves per SIMD are the adaptive kernel's to within 1 VGPR (profiles/r27_ntuple_reduced_resource_usage.txt).
+// Measured on the MI355X (profiles/r27_ntuple_reduced_probe.txt): depth 4 of 1 024 late-game boards, 4x6 network, 371 ms per
+// launch against the adaptive kernel's 918 ms with 0.15 of its evaluations; depth 3 takes 0.80 (reduce4 = 1) or 0.47 (2) of its
+// time with 0.28.  The units are NOT ordered by depth: every chance entry starts at an even unit, so an even lane always draws
+// a 2 child and an odd lane a 4 child, and half of every wavefront waits for the deeper half -- which is what the rows point to;
+// ordering them in the scan was not built and not timed.  ReducedTables: as AdaptiveTables, so that this kernel shares no
+// template instantiation with the existing ones.  LDS, the grid cap, the stride loop and MASKED as in ntuple_deep_search_kernel.
+struct ReducedTables : LdsTables {};
+
+template <uint32_t T, bool PLAIN, class Shape, bool MASKED = false>
+__global__ void __launch_bounds__(kBlock) ntuple_reduced_search_kernel(const uint4 *__restrict__ boards, uint32_t n, const Shape sh,
+                                                                       uint32_t frac_bits, const int32_t *__restrict__ weights,
+                                                                       const NtupleAdaptiveSchedule schedule, uint32_t reduce4,
+                                                                       const NtupleAdaptiveOut o)
+{
+    __shared__ WaveTables s_tables[kBlock / 64];
+    __shared__ NtupleDeepLds s_deep;
+    const ReducedTables tb{stage_tables(s_tables, load_tables_piece())};
+    const uint32_t lane = threadIdx.x;
+    const auto add_root = [&](uint32_t d1, int64_t x) {
+        atomicAdd(reinterpret_cast<unsigned long long *>(&s_deep.root_sum[d1]), static_cast<unsigned long long>(x));
+    };
+    for (uint64_t i = blockIdx.x; i < n; i += gridDim.x) { // (64 bits: n may be within one grid of 2^32)
+        bool active = true;
+        if constexpr (MASKED)
+            active = o.active[i] != 0u;
+        const Board cells = input_cells<PLAIN>(load_board(boards, static_cast<uint32_t>(i)));
+        const uint32_t depth = ntuple_adaptive_depth(schedule, cells);
+        ntuple_adaptive_root<T>(s_deep, cells, active, depth, lane, sh, weights, tb);
+        __syncthreads();
+        if (depth == 1u) {
+            ntuple_adaptive_leaves1<T>(s_deep, lane, kBlock, sh, frac_bits, weights, tb, add_root);
+            __syncthreads();
+        } else if (depth >= 2u) {
+            ntuple_reduced_expand(s_deep, depth, reduce4, lane, kBlock, tb);
+            __syncthreads();
+            ntuple_deep_scan(s_deep, lane, kBlock);
+            __syncthreads();
+            ntuple_reduced_leaves<T>(s_deep, depth, reduce4, lane, kBlock, sh, frac_bits, weights, tb, [&](uint32_t e, int64_t x) {
+                atomicAdd(reinterpret_cast<unsigned long long *>(&s_deep.acc[e]), static_cast<unsigned long long>(x));
+            });
+            __syncthreads();
+            ntuple_reduced_fold(s_deep, lane, kBlock, frac_bits, add_root);
+            __syncthreads();
+        }
+        if (lane == 0u) {
+            int64_t value[4];
+            const uint32_t action = ntuple_adaptive_finish(s_deep, depth, frac_bits, value);
+            if (o.value) {
+#pragma unroll
+                for (uint32_t d = 0; d < 4u; ++d)
+                    o.value[i * 4u + d] = value[d];
+            }
+            if (o.action)
+                o.action[i] = static_cast<uint8_t>(action);
+            if (o.depth)
+                o.depth[i] = static_cast<uint8_t>(active ? depth : kNtupleAdaptiveSkipped);
+        }
+        __syncthreads(); // the next board's root step overwrites what lane 0 reads above
+    }
+}
+
 // g2048_ntuple_values_plain: V of every board, one board per lane, the same gathers.
 template <uint32_t T, class Shape>
 __global__ void __launch_bounds__(kBlock) ntuple_values_kernel(const uint4 *__restrict__ boards, uint32_t n, const Shape sh,
@@ -2989,6 +3057,19 @@ hipError_t launch_ntuple_adaptive_search(const Boards &b, const uint8_t schedule
         return dispatch_search_form(b, o.active, [&](auto plain_c, auto masked_c) {
             return launch_1d(ntuple_adaptive_search_kernel<tc, plain_c, decltype(sh), masked_c>, group_lanes(b.n, kBlock), 0, s, b.ptr, b.n,
                              sh, net.frac_bits, static_cast<const int32_t *>(net.weights), sc, o);
+        });
+    });
+}
+
+// As launch_ntuple_adaptive_search; reduce4 in kNtupleReduce4Min..Max (checked by the caller) is the same for the whole launch
+hipError_t launch_ntuple_reduced_search(const Boards &b, const uint8_t schedule[17], uint32_t reduce4, const NtupleNet &net,
+                                        const NtupleAdaptiveOut &o, hipStream_t s)
+{
+    const NtupleAdaptiveSchedule sc = ntuple_adaptive_schedule(schedule);
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        return dispatch_search_form(b, o.active, [&](auto plain_c, auto masked_c) {
+            return launch_1d(ntuple_reduced_search_kernel<tc, plain_c, decltype(sh), masked_c>, group_lanes(b.n, kBlock), 0, s, b.ptr, b.n,
+                             sh, net.frac_bits, static_cast<const int32_t *>(net.weights), sc, reduce4, o);
         });
     });
 }

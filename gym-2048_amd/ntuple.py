@@ -20,6 +20,8 @@ the 3-ply row of the papers.
 ``NTupleNet.adaptive_search`` / ``Batched2048.ntuple_adaptive_search`` search every board at a depth 0..4 chosen by a fixed
 rule from its own empty cells, one launch (``g2048_ntuple_adaptive_search``); :func:`schedule_by_empties`
 and ``SCHEDULES`` make the rule, and ``AdaptivePlayer`` plays it in :func:`play_games`.
+``NTupleNet.reduced_search`` / ``Batched2048.ntuple_reduced_search`` are that search with the children of a 4 spawn searched
+``reduce4`` plies shallower (``g2048_ntuple_reduced_search``); ``ReducedPlayer`` plays it.
 ``NTupleNet(..., stages=...)`` is the multi-stage network: a weight set per game stage, chosen per board by the tiles it
 holds (``g2048_ntuple_staged_*``); every method and trainer above works on it unchanged.
 ``Carousel`` is carousel shaping for such a network (``g2048_carousel_*``): it remembers, per stage, the
@@ -48,7 +50,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import CarouselC, NTupleAdaptiveIO, NTupleDeepIO, NTupleDelayC, NTupleIO, NTupleMeanC, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTDIO, NTupleTraceC, check
+from ._lib import CarouselC, NTupleAdaptiveIO, NTupleDeepIO, NTupleReducedIO, NTupleDelayC, NTupleIO, NTupleMeanC, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTDIO, NTupleTraceC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
@@ -56,6 +58,7 @@ ILLEGAL = -(1 << 63)                                              # G2048_NTUPLE
 SEARCH_MAX_DEPTH = 2                                              # G2048_NTUPLE_SEARCH_MAX_DEPTH
 DEEP_MIN_DEPTH, DEEP_MAX_DEPTH = 2, 3                             # G2048_NTUPLE_DEEP_MIN_DEPTH, G2048_NTUPLE_DEEP_MAX_DEPTH
 ADAPTIVE_MAX_DEPTH, ADAPTIVE_SKIPPED = 4, 0xff                    # G2048_NTUPLE_ADAPTIVE_MAX_DEPTH, G2048_NTUPLE_ADAPTIVE_SKIPPED
+REDUCE4_MIN, REDUCE4_MAX = 1, 2                                     # G2048_NTUPLE_REDUCE4_MIN, G2048_NTUPLE_REDUCE4_MAX
 TC_WEIGHTS, TC_ACCUM = 1, 2                                       # G2048_NTUPLE_TC_WEIGHTS, G2048_NTUPLE_TC_ACCUM
 MEAN_SUM, MEAN_APPLY = 1, 2                                       # G2048_NTUPLE_MEAN_SUM, G2048_NTUPLE_MEAN_APPLY
 TRACE_MAX = 8                                                     # G2048_NTUPLE_TRACE_MAX
@@ -221,10 +224,13 @@ def _schedule(schedule) -> tuple:
     return tuple(_int_arg("schedule entry", d, 0, ADAPTIVE_MAX_DEPTH) for d in schedule)
 
 
-def _adaptive_io(n, device, schedule, out, active=None):
+def _adaptive_io(n, device, schedule, out, active=None, reduce4=None):
     """(NTupleAdaptiveIO, NTupleAdaptive) for n boards: ``schedule`` checked, ``out`` checked field by field or freshly
-    allocated, ``active`` (engine forms) checked as ``_check_tensor`` checks."""
+    allocated, ``active`` (engine forms) checked as ``_check_tensor`` checks.  With ``reduce4`` (checked) the structure is the
+    NTupleReducedIO of the reduced search."""
     schedule = _schedule(schedule)
+    if reduce4 is not None:
+        reduce4 = _int_arg("reduce4", reduce4, REDUCE4_MIN, REDUCE4_MAX)
     if out is None:
         u8 = dict(dtype=torch.uint8, device=device)
         out = NTupleAdaptive(torch.empty(n, **u8), torch.empty((n, 4), dtype=torch.int64, device=device), torch.empty(n, **u8))
@@ -232,7 +238,8 @@ def _adaptive_io(n, device, schedule, out, active=None):
         out = NTupleAdaptive(*out)
         if out.action is None and out.value is None:
             raise ValueError("out requests no output (action and value are both None)")
-    io = NTupleAdaptiveIO((C.c_uint8 * 17)(*schedule))
+    sched = (C.c_uint8 * 17)(*schedule)
+    io = NTupleAdaptiveIO(sched) if reduce4 is None else NTupleReducedIO(sched, reduce4)
     _bind_out(io, out, {"action": ((n,), (torch.uint8,)), "value": ((n, 4), (torch.int64,)), "depth": ((n,), (torch.uint8,))}, device)
     if active is not None:
         _check_tensor("active", active, (torch.uint32,), (n,), device)
@@ -452,6 +459,18 @@ class NTupleNet:
         net = self._ref(device)
         io, out = _adaptive_io(n, device, schedule, out)
         self._launch(self._fn("adaptive_search_plain"), boards, net, C.byref(io))
+        return out
+
+    def reduced_search(self, boards, schedule, reduce4=1, out=None) -> NTupleAdaptive:
+        """:meth:`adaptive_search` with the rare branches searched shallower (``g2048_ntuple_reduced_search_plain``,
+        INTEGRATION.md §23): a child board made by a 4 spawn, a tenth of its chance node's weight, is searched ``reduce4``
+        (1..2) plies shallower than its 2 sibling, at every level of the tree.  ``schedule`` and ``out`` as
+        :meth:`adaptive_search` takes them; ``depth`` of the result is the schedule's depth, not a reduced one.  Depth 0 gives
+        the bits of :meth:`evaluate` and depth 1 those of :meth:`search` at depth 1."""
+        n, device = _plain_boards(boards)
+        net = self._ref(device)
+        io, out = _adaptive_io(n, device, schedule, out, reduce4=reduce4)
+        self._launch(self._fn("reduced_search_plain"), boards, net, C.byref(io))
         return out
 
     def update(self, boards, delta, lr_shift):
@@ -1155,6 +1174,24 @@ class AdaptivePlayer:
 
     def __call__(self, engine, actions, active=None):
         engine.ntuple_adaptive_search(self.net, self.schedule, out=NTupleAdaptive(actions, None, None), active=active)
+
+
+class ReducedPlayer:
+    """The expectimax player over ``net`` at a depth per board with the children of a 4 spawn searched ``reduce4`` plies
+    shallower, for :func:`play_games` (``g2048_ntuple_reduced_search``):
+    ``play_games(engine, net, games, player=ReducedPlayer(net, "4-ply-late"))``.  ``schedule`` as
+    :meth:`NTupleNet.adaptive_search` takes it.  A callable ``player(engine, actions, active=None)`` with ``takes_active``, as
+    :class:`AdaptivePlayer`."""
+    takes_active = True
+
+    def __init__(self, net, schedule, reduce4=1):
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        self.net, self.schedule = net, _schedule(schedule)
+        self.reduce4 = _int_arg("reduce4", reduce4, REDUCE4_MIN, REDUCE4_MAX)
+
+    def __call__(self, engine, actions, active=None):
+        engine.ntuple_reduced_search(self.net, self.schedule, self.reduce4, out=NTupleAdaptive(actions, None, None), active=active)
 
 
 def play_games(engine, net, games=1, chunk=1024, max_steps=None, depth=0, player=None) -> PlayReport:

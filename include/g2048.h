@@ -779,6 +779,46 @@ int g2048_ntuple_staged_adaptive_search(const g2048_engine *e, const g2048_ntupl
 int g2048_ntuple_staged_adaptive_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
                                               const g2048_ntuple_adaptive_io *io, void *stream);
 
+/* N-tuple reduced search: the adaptive search above with the rare branches searched shallower.  A child
+ * board made by a 4 spawn, which carries a tenth of its chance node's weight, is searched R = reduce4 plies shallower than its
+ * 2 sibling.  The rule is integer and path-local -- no probability and no threshold -- so the result does not depend on the
+ * split, the lane order or the shard.  Notation of the blocks above:
+ *   A^R_0(a) = V(a)
+ *   S^R_k(b) = max over legal d of ((g_d << F) + A^R_k(a_d));   0 when no move is legal
+ *   A^R_k(a) = floor(sum over empty c of (9 S^R_{k-1}(a, 2 in c) + S^R_{max(k-1-R, 0)}(a, 4 in c)) / (10 E(a)))   for k >= 1
+ *   value[d] = (g_d << F) + A^R_D(a_d), G2048_NTUPLE_ILLEGAL where d is illegal; action = the smallest d of largest value
+ *   among the legal d, 0 when none is legal.
+ * D = D_i = schedule[E0(b_i)], 0..4, the board reading, `active`, a board with no legal move and the depth output are those
+ * of g2048_ntuple_adaptive_search; the depth output is the schedule's depth, not a reduced one.  Depth 0 is
+ * g2048_ntuple_evaluate's value (q) and action and depth 1 is g2048_ntuple_search at depth 1, bit for bit, for any R.
+ * Bounds: every term is one the adaptive block bounds -- a tree here is a tree there with levels left out -- so
+ * |value| < 2^50, every partial sum of a chance node stays below 150 * 2^50 < 2^58 in an int64, and the 2^60 bias of the
+ * action key still makes every legal key positive.
+ * Each call is one launch on `stream`, writes nothing but its outputs, consumes no randomness and leaves the engine alone.
+ * Uniform, mixed-length and staged networks, T = 1..8.  reduce4 = 0 is refused: that search is g2048_ntuple_adaptive_search.
+ * Cost, measured on the MI355X (profiles/r27_ntuple_reduced_probe.txt), 1 024 late-game boards, 4x6 network: depth 4 takes 371 ms
+ * per launch where g2048_ntuple_adaptive_search takes 918 ms (0.40 of the time for 0.15 of the evaluations), depth 3 takes 0.80
+ * (reduce4 = 1) or 0.47 (reduce4 = 2) of its time for 0.28 of the evaluations: faster in every row measured, and far below what
+ * the evaluations promise, because the work units are not ordered by depth. */
+#define G2048_NTUPLE_REDUCE4_MIN 1
+#define G2048_NTUPLE_REDUCE4_MAX 2
+typedef struct g2048_ntuple_reduced_io {
+    uint8_t schedule[17];    /* as g2048_ntuple_adaptive_io */
+    uint32_t reduce4;        /* R: G2048_NTUPLE_REDUCE4_MIN..G2048_NTUPLE_REDUCE4_MAX */
+    uint8_t *action;         /* [n], or NULL */
+    int64_t *value;          /* [n][4], 16-byte aligned, or NULL */
+    uint8_t *depth;          /* [n], or NULL: schedule[E0], G2048_NTUPLE_ADAPTIVE_SKIPPED for a masked-out board */
+    const uint32_t *active;  /* [n] in device memory, 4-byte aligned, or NULL; engine forms only, as g2048_ntuple_adaptive_io.active */
+} g2048_ntuple_reduced_io;
+/* At least one of action and value must be given.  The plain forms as those of g2048_ntuple_adaptive_search. */
+int g2048_ntuple_reduced_search(const g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_reduced_io *io, void *stream);
+int g2048_ntuple_reduced_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_net *net,
+                                      const g2048_ntuple_reduced_io *io, void *stream);
+int g2048_ntuple_staged_reduced_search(const g2048_engine *e, const g2048_ntuple_staged_net *net,
+                                       const g2048_ntuple_reduced_io *io, void *stream);
+int g2048_ntuple_staged_reduced_search_plain(const uint8_t *boards, uint64_t n, const g2048_ntuple_staged_net *net,
+                                             const g2048_ntuple_reduced_io *io, void *stream);
+
 /* Carousel shaping: stage-balanced restarts for training a staged network (Jaskowski 2017).  Every
  * episode starts from an empty board, so the weight sets of the late stages see only the rare boards that live that long.
  * A carousel remembers, per stage, the boards on which recent episodes ENTERED that stage, and starts new episodes from
