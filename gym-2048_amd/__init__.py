@@ -20,7 +20,8 @@ def __getattr__(name):
                 "tc_train", "NTupleMean", "mean_update", "mean_step", "mean_train", "mean_tdl_step", "mean_tdl_train", "NTupleTrace", "tdl_evaluate", "tdl_step", "tdl_train", "tcl_step",
                 "tcl_train", "NTupleDelay", "delayed_evaluate", "delayed_tdl_step", "delayed_tdl_train", "delayed_tcl_step",
                 "delayed_tcl_train", "Carousel", "PlayReport", "play_games", "DeepPlayer", "NTupleAdaptive",
-                "AdaptivePlayer", "ReducedPlayer", "TDWork", "td_work", "td_evaluate", "td_update"):  # need torch + a GPU; imported on first use
+                "AdaptivePlayer", "ReducedPlayer", "TDWork", "td_work", "td_evaluate", "td_update", "NTupleLog", "log_sweep",
+                "backward_train"):  # need torch + a GPU; imported on first use
         from . import batched
         return getattr(batched, name)
     raise AttributeError(name)

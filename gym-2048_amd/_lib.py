@@ -140,6 +140,16 @@ class NTupleTDIO(C.Structure):
     ]
 
 
+class NTupleLogC(C.Structure):
+    """g2048_ntuple_log (include/g2048.h): depth M and the device tensors of the move log, M + 1 slots each, slot-major."""
+    _fields_ = [
+        ("depth", C.c_uint32),
+        ("after", C.c_void_p),
+        ("gain", C.c_void_p),
+        ("flag", C.c_void_p),
+    ]
+
+
 class NTupleSearchIO(C.Structure):
     """g2048_ntuple_search_io (include/g2048.h): depth and device output pointers (NULL = not wanted)."""
     _fields_ = [
@@ -306,6 +316,16 @@ SIGNATURES = {
     "g2048_ntuple_td_train": (C.c_int, [_E, C.POINTER(NTupleNetC), _u32, _u32, C.POINTER(NTupleTDIO), C.POINTER(NTupleTCC), _S]),
     "g2048_ntuple_staged_td_train": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), _u32, _u32, C.POINTER(NTupleTDIO),
                                               C.POINTER(NTupleTCC), _S]),
+    "g2048_ntuple_play_log": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleLogC), _S]),
+    "g2048_ntuple_staged_play_log": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleLogC), _S]),
+    "g2048_ntuple_log_delta": (C.c_int, [_u64, C.POINTER(NTupleNetC), C.POINTER(NTupleLogC), _u32, C.c_void_p, _S]),
+    "g2048_ntuple_staged_log_delta": (C.c_int, [_u64, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleLogC), _u32, C.c_void_p, _S]),
+    "g2048_ntuple_log_sweep": (C.c_int, [_u64, C.POINTER(NTupleNetC), C.POINTER(NTupleLogC), _u32, C.c_void_p, C.POINTER(NTupleTCC), _S]),
+    "g2048_ntuple_staged_log_sweep": (C.c_int, [_u64, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleLogC), _u32, C.c_void_p,
+                                               C.POINTER(NTupleTCC), _S]),
+    "g2048_ntuple_log_train": (C.c_int, [_E, C.POINTER(NTupleNetC), _u32, _u32, C.POINTER(NTupleLogC), C.c_void_p, C.POINTER(NTupleTCC), _S]),
+    "g2048_ntuple_staged_log_train": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), _u32, _u32, C.POINTER(NTupleLogC), C.c_void_p,
+                                               C.POINTER(NTupleTCC), _S]),
     "g2048_ntuple_search": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), _S]),
     "g2048_ntuple_search_active": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), C.c_void_p, _S]),
     "g2048_ntuple_search_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(NTupleNetC), C.POINTER(NTupleSearchIO), _S]),

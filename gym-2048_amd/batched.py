@@ -32,6 +32,7 @@ from .ntuple import DeepPlayer, _deep_io as _ntuple_deep_io  # noqa: F401
 from .ntuple import AdaptivePlayer, NTupleAdaptive, ReducedPlayer, _adaptive_io as _ntuple_adaptive_io  # noqa: F401
 from .ntuple import PlayReport, play_games, _check_tensor, _play_io  # noqa: F401
 from .ntuple import TDWork, td_evaluate, td_update, td_work, _td_io  # noqa: F401
+from .ntuple import NTupleLog, backward_train, log_sweep, _log_of  # noqa: F401
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}
 
@@ -804,6 +805,38 @@ class Batched2048:
         io = _td_io(self, work)
         check(net._fn("td_train")(self._h, ref, n_steps, lr_shift, C.byref(io), None if tc is None else C.byref(tc._c), self._stream()))
         if n_steps:
+            self._fresh = False
+
+    def ntuple_play_log(self, net, log):
+        """``log.depth`` moves of the greedy player on every board in ONE launch that also keeps them
+        (``g2048_ntuple_play_log``), on the engine's stream: the engine ends up as after
+        ``ntuple_play(net, log.depth)``, bit for bit, slot ``m`` = 1..M of ``log`` (an :class:`NTupleLog` of this engine)
+        holds the afterstate, the shifted merge gain and the flag of move ``m``, and slot 0 what slot M held before the call.
+        The weights are only read.  A spawn-stream engine only (``rng="philox"``)."""
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        ref = net._ref(self.device)
+        check(net._fn("play_log")(self._h, ref, C.byref(_log_of(self, log)._c), self._stream()))
+        self._fresh = False
+
+    def ntuple_log_train(self, net, log, rounds, lr_shift, delta, tc=None):
+        """``rounds`` times { :meth:`ntuple_play_log`; the backward sweep of ``log`` } in ONE library call
+        (``g2048_ntuple_log_train``): plain launches on the engine's stream, no Python between them.
+        ``delta``: int64 ``[n]`` work buffer (the errors of slot 0 of the last round afterwards).  ``tc`` None: ``net.update``
+        per slot; an :class:`NTupleTC` of ``net``: ``net.tc_update`` with ``phases=3``.  The bits of
+        :func:`backward_train`'s Python loop."""
+        if not isinstance(net, NTupleNet):
+            raise ValueError("net must be an NTupleNet")
+        ref = net._ref(self.device)
+        rounds = _int_arg("rounds", rounds, 0, (1 << 32) - 1)
+        lr_shift = _int_arg("lr_shift", lr_shift, 0, 40)
+        if tc is not None:
+            net._own_tc(tc)
+        log = _log_of(self, log)
+        _check_tensor("delta", delta, (torch.int64,), (self.n_envs,), self.device)
+        check(net._fn("log_train")(self._h, ref, rounds, lr_shift, C.byref(log._c), delta.data_ptr(),
+                                   None if tc is None else C.byref(tc._c), self._stream()))
+        if rounds:
             self._fresh = False
 
     def ntuple_search(self, net, depth=1, out=None, active=None) -> NTupleSearch:

@@ -1570,7 +1570,7 @@ static int ntuple_td_out(const g2048_ntuple_td_io *io, const char *what, bool tr
     return G2048_OK;
 }
 
-// The engine of a fused TD call, looked at after everything that can be refused without it
+// The engine of a fused TD or play_log call, looked at after everything that can be refused without it
 static int ntuple_td_engine(const g2048_engine *e, const char *what)
 {
     if (int rc = usable(e))
@@ -1633,6 +1633,142 @@ static int ntuple_td_train(g2048_engine *e, const Net *net, uint32_t k_steps, ui
         G2048_HIP(ntuple_td_launch(e, nn, o, stream));
         G2048_HIP(g2048::launch_ntuple_update(o.after, static_cast<uint32_t>(e->n), o.delta, lr_shift, nn, tc ? &t : nullptr,
                                               static_cast<hipStream_t>(stream)));
+    }
+    return G2048_OK;
+}
+
+// g2048_ntuple_log -> the launchers' log, or G2048_ERR_INVALID (before any HIP call: works without a device)
+static int ntuple_log(const g2048_ntuple_log *log, g2048::NtupleLog *out)
+{
+    if (!log)
+        return fail(G2048_ERR_INVALID, "log is NULL");
+    if (!log->after)
+        return fail(G2048_ERR_INVALID, "log after is NULL");
+    if (!log->gain)
+        return fail(G2048_ERR_INVALID, "log gain is NULL");
+    if (!log->flag)
+        return fail(G2048_ERR_INVALID, "log flag is NULL");
+    if (log->depth < 1 || log->depth > G2048_NTUPLE_LOG_MAX_DEPTH)
+        return fail(G2048_ERR_INVALID, "depth=%u: need 1 <= depth <= %d", log->depth, G2048_NTUPLE_LOG_MAX_DEPTH);
+    if (reinterpret_cast<uintptr_t>(log->after) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: log after needs 16 bytes");
+    if (reinterpret_cast<uintptr_t>(log->gain) & 7u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: log gain needs 8 bytes");
+    *out = g2048::NtupleLog{log->depth, reinterpret_cast<uint4 *>(log->after), log->gain, log->flag};
+    return G2048_OK;
+}
+
+// log.depth transactions of the clock and one launch, as g2048_ntuple_play with k_steps == log.depth
+static hipError_t ntuple_play_log_launch(g2048_engine *e, const g2048::NtupleNet &nn, const g2048::NtupleLog &lg, void *stream)
+{
+    e->t += 1; // transaction of the first move
+    e->fresh = 0;
+    g2048::StepArgs a = make_args(e, nullptr, 1);
+    a.k_steps = lg.depth;
+    const hipError_t err = g2048::launch_ntuple_play_log(a, nn, lg, static_cast<hipStream_t>(stream));
+    if (err == hipSuccess)
+        e->t += lg.depth - 1;
+    return err;
+}
+
+// for m = M - 1 down to 0: the error of slot m into delta, then the update of slot m by it; tc: NULL for the TD update, else
+// the TC update, W then A.  Plain launches on one stream.
+static hipError_t ntuple_log_sweep_launch(uint32_t n, const g2048::NtupleNet &nn, const g2048::NtupleLog &lg, uint32_t lr_shift, int64_t *delta,
+                                          const g2048::NtupleTc *tc, void *stream)
+{
+    for (uint32_t m = lg.depth; m-- > 0u;) {
+        if (hipError_t err = g2048::launch_ntuple_log_delta(n, nn, lg, m, delta, static_cast<hipStream_t>(stream)))
+            return err;
+        if (hipError_t err = g2048::launch_ntuple_update(lg.after + static_cast<uint64_t>(m) * n, n, delta, lr_shift, nn, tc,
+                                                         static_cast<hipStream_t>(stream)))
+            return err;
+    }
+    return hipSuccess;
+}
+
+template <class Net> static int ntuple_play_log(g2048_engine *e, const Net *net, const g2048_ntuple_log *log, void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleLog lg;
+    if (int rc = ntuple_log(log, &lg))
+        return rc;
+    if (int rc = ntuple_td_engine(e, "g2048_ntuple_play_log"))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(ntuple_play_log_launch(e, nn, lg, stream));
+    return G2048_OK;
+}
+
+template <class Net>
+static int ntuple_log_delta(uint64_t n, const Net *net, const g2048_ntuple_log *log, uint32_t m, int64_t *delta, void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (int rc = trace_boards(n))
+        return rc;
+    g2048::NtupleLog lg;
+    if (int rc = ntuple_log(log, &lg))
+        return rc;
+    if (m >= lg.depth)
+        return fail(G2048_ERR_INVALID, "m=%u: need m < depth=%u (slot m + 1 is read)", m, lg.depth);
+    if (int rc = ntuple_delta(delta, 0)) // (an output here: the same NULL and alignment checks, no lr_shift to refuse)
+        return rc;
+    G2048_HIP(g2048::launch_ntuple_log_delta(static_cast<uint32_t>(n), nn, lg, m, delta, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+// What a sweep takes besides the network: the log, delta and lr_shift, and tc (NULL: the TD update) -> the launchers' forms
+static int ntuple_log_sweep_args(const g2048_ntuple_log *log, uint32_t lr_shift, const int64_t *delta, const g2048_ntuple_tc *tc,
+                                 g2048::NtupleLog *lg, g2048::NtupleTc *t)
+{
+    if (int rc = ntuple_log(log, lg))
+        return rc;
+    if (int rc = ntuple_delta(delta, lr_shift))
+        return rc;
+    const TcArgs tc_args{G2048_NTUPLE_TC_WEIGHTS | G2048_NTUPLE_TC_ACCUM, tc};
+    return ntuple_tc(tc ? &tc_args : nullptr, t);
+}
+
+template <class Net>
+static int ntuple_log_sweep(uint64_t n, const Net *net, const g2048_ntuple_log *log, uint32_t lr_shift, int64_t *delta,
+                            const g2048_ntuple_tc *tc, void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    if (int rc = trace_boards(n))
+        return rc;
+    g2048::NtupleLog lg;
+    g2048::NtupleTc t{};
+    if (int rc = ntuple_log_sweep_args(log, lr_shift, delta, tc, &lg, &t))
+        return rc;
+    G2048_HIP(ntuple_log_sweep_launch(static_cast<uint32_t>(n), nn, lg, lr_shift, delta, tc ? &t : nullptr, stream));
+    return G2048_OK;
+}
+
+// rounds times { play_log; sweep }, plain launches on one stream
+template <class Net>
+static int ntuple_log_train(g2048_engine *e, const Net *net, uint32_t rounds, uint32_t lr_shift, const g2048_ntuple_log *log, int64_t *delta,
+                            const g2048_ntuple_tc *tc, void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::NtupleLog lg;
+    g2048::NtupleTc t{};
+    if (int rc = ntuple_log_sweep_args(log, lr_shift, delta, tc, &lg, &t))
+        return rc;
+    if (int rc = ntuple_td_engine(e, "g2048_ntuple_log_train"))
+        return rc;
+    if (rounds == 0)
+        return G2048_OK;
+    G2048_HIP(hipSetDevice(e->device));
+    for (uint32_t r = 0; r < rounds; ++r) {
+        G2048_HIP(ntuple_play_log_launch(e, nn, lg, stream));
+        G2048_HIP(ntuple_log_sweep_launch(static_cast<uint32_t>(e->n), nn, lg, lr_shift, delta, tc ? &t : nullptr, stream));
     }
     return G2048_OK;
 }
@@ -1934,6 +2070,51 @@ int g2048_ntuple_staged_td_train(g2048_engine *e, const g2048_ntuple_staged_net 
                                  const g2048_ntuple_td_io *work, const g2048_ntuple_tc *tc, void *stream)
 {
     return ntuple_td_train(e, net, k_steps, lr_shift, work, tc, stream);
+}
+
+int g2048_ntuple_play_log(g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_log *log, void *stream)
+{
+    return ntuple_play_log(e, net, log, stream);
+}
+
+int g2048_ntuple_staged_play_log(g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_log *log, void *stream)
+{
+    return ntuple_play_log(e, net, log, stream);
+}
+
+int g2048_ntuple_log_delta(uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_log *log, uint32_t m, int64_t *delta, void *stream)
+{
+    return ntuple_log_delta(n, net, log, m, delta, stream);
+}
+
+int g2048_ntuple_staged_log_delta(uint64_t n, const g2048_ntuple_staged_net *net, const g2048_ntuple_log *log, uint32_t m, int64_t *delta,
+                                  void *stream)
+{
+    return ntuple_log_delta(n, net, log, m, delta, stream);
+}
+
+int g2048_ntuple_log_sweep(uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_log *log, uint32_t lr_shift, int64_t *delta,
+                           const g2048_ntuple_tc *tc, void *stream)
+{
+    return ntuple_log_sweep(n, net, log, lr_shift, delta, tc, stream);
+}
+
+int g2048_ntuple_staged_log_sweep(uint64_t n, const g2048_ntuple_staged_net *net, const g2048_ntuple_log *log, uint32_t lr_shift,
+                                  int64_t *delta, const g2048_ntuple_tc *tc, void *stream)
+{
+    return ntuple_log_sweep(n, net, log, lr_shift, delta, tc, stream);
+}
+
+int g2048_ntuple_log_train(g2048_engine *e, const g2048_ntuple_net *net, uint32_t rounds, uint32_t lr_shift, const g2048_ntuple_log *log,
+                           int64_t *delta, const g2048_ntuple_tc *tc, void *stream)
+{
+    return ntuple_log_train(e, net, rounds, lr_shift, log, delta, tc, stream);
+}
+
+int g2048_ntuple_staged_log_train(g2048_engine *e, const g2048_ntuple_staged_net *net, uint32_t rounds, uint32_t lr_shift,
+                                  const g2048_ntuple_log *log, int64_t *delta, const g2048_ntuple_tc *tc, void *stream)
+{
+    return ntuple_log_train(e, net, rounds, lr_shift, log, delta, tc, stream);
 }
 
 // One budgeted step with the caller's actions: g2048_ntuple_play's contract and clock at k_steps == 1, g2048_step's checks of

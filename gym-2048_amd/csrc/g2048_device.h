@@ -2378,6 +2378,60 @@ G2048_DEV NtupleTdOut ntuple_td_step(Board &rec, uint64_t t, uint32_t board, uin
     return out;
 }
 
+// ------------------------------------------------------- the n-tuple move log and its backward error
+// g2048_ntuple_play_log and g2048_ntuple_log_delta (include/g2048.h).  A log of depth M holds M + 1 slots
+// of n entries, slot-major: the afterstate played, (its merge gain) << F, and a flag byte.  Slot m = 1..M of a play_log call
+// is what the m-th round of g2048_ntuple_evaluate -> g2048_step wrote; slot 0 is slot M of the call before.
+constexpr uint32_t kNtupleLogMaxDepth = 1024u;
+constexpr uint32_t kNtupleLogValid = 1u, kNtupleLogEnded = 2u; // = G2048_NTUPLE_LOG_VALID, G2048_NTUPLE_LOG_ENDED
+
+struct NtupleLogEntry {
+    Board after;   // E.after: the afterstate of the move played; the board itself when no move is legal
+    int64_t gain;  // E.best - E.after_value = (merge gain) << F; 0 when no move is legal
+    uint32_t flag; // 0 when the board had no legal move, else kNtupleLogValid | (terminated ? kNtupleLogEnded : 0)
+};
+
+// One move of g2048_ntuple_play_log on a record: ntuple_play_step with ntuple_root_kept in place of ntuple_root -- the same
+// keys, so the same action and the same step -- and the entry the move leaves in the log.  A root with a legal move plays a
+// legal one, so `!legal` of the step is "the board had no legal move".  w comes back for the caller's reset_record.
+template <uint32_t T, class Shape, class Tables>
+G2048_DEV StepOut ntuple_play_log_step(Board &rec, uint64_t t, uint32_t board, uint32_t seed_lo, uint32_t seed_hi, const Shape &sh,
+                                       uint32_t F, const int32_t *weights, uint32_t max_exp, const Tables &tb, Words &w, NtupleLogEntry &e)
+{
+    w = philox4x32_10(static_cast<uint32_t>(t), static_cast<uint32_t>(t >> 32), board, 0u, seed_lo, seed_hi);
+    uint32_t action;
+    {
+        const NtupleKept r = ntuple_root_kept<T>(record_cells(rec), sh, F, weights, tb);
+        action = r.action;
+        e.after = r.after;
+        e.gain = static_cast<int64_t>(static_cast<uint64_t>(r.best) - static_cast<uint64_t>(r.after_value));
+    }
+    const StepOut o = play_record(rec, action, w, max_exp, tb);
+    e.flag = o.legal ? (kNtupleLogValid | (o.terminated ? kNtupleLogEnded : 0u)) : 0u;
+    return o;
+}
+
+// The backward error of slot m from the flag bytes f = flag[m], f1 = flag[m + 1] (any byte: only bits 0 and 1 are read):
+//   !(f & VALID) -> 0;  f & ENDED -> 0 - V(after[m]);  !(f1 & VALID) -> 0;  else gain[m + 1] + V(after[m + 1]) - V(after[m])
+// ntuple_log_reads_self: V(after[m]) is read; ntuple_log_reads_next: gain[m + 1] and V(after[m + 1]) are.  int64, wraps.
+G2048_DEV bool ntuple_log_reads_self(uint32_t f, uint32_t f1)
+{
+    return (f & kNtupleLogValid) != 0u && ((f & kNtupleLogEnded) != 0u || (f1 & kNtupleLogValid) != 0u);
+}
+G2048_DEV bool ntuple_log_reads_next(uint32_t f, uint32_t f1)
+{
+    return (f & kNtupleLogValid) != 0u && (f & kNtupleLogEnded) == 0u && (f1 & kNtupleLogValid) != 0u;
+}
+// v0 = V(after[m]) where ntuple_log_reads_self, gain1 and v1 = gain[m + 1] and V(after[m + 1]) where ntuple_log_reads_next;
+// what is not read is not looked at
+G2048_DEV int64_t ntuple_log_delta(uint32_t f, uint32_t f1, int64_t gain1, int64_t v1, int64_t v0)
+{
+    if (!ntuple_log_reads_self(f, f1))
+        return 0;
+    const uint64_t target = ntuple_log_reads_next(f, f1) ? static_cast<uint64_t>(gain1) + static_cast<uint64_t>(v1) : 0ull;
+    return static_cast<int64_t>(target - static_cast<uint64_t>(v0));
+}
+
 // ------------------------------------------------------------------------------ one env step
 struct StepResult {
     float reward;

@@ -179,6 +179,19 @@ struct NtupleTdIo {
     int64_t *delta;       // [n] (terminated ? 0 : best_next) - after_value
 };
 hipError_t launch_ntuple_td_step(const StepArgs &a, const NtupleNet &net, const NtupleTdIo &io, hipStream_t s);
+// g2048_ntuple_play_log and g2048_ntuple_log_delta: the move log (g2048_ntuple_log, checked by the caller): depth M in
+// 1..1024, M + 1 slots of n entries each, slot-major
+struct NtupleLog {
+    uint32_t depth;
+    uint4 *after;  // [M + 1][n] plain boards
+    int64_t *gain; // [M + 1][n]
+    uint8_t *flag; // [M + 1][n]
+};
+// log.depth greedy steps with auto-reset in one launch, as launch_ntuple_play without side outputs (a.k_steps == log.depth,
+// spawn stream only); slot 0 takes what slot M held, slot m the entry of move m
+hipError_t launch_ntuple_play_log(const StepArgs &a, const NtupleNet &net, const NtupleLog &log, hipStream_t s);
+// delta[i] of slot m < log.depth for the n boards of the log; reads the log and the weights only
+hipError_t launch_ntuple_log_delta(uint32_t n, const NtupleNet &net, const NtupleLog &log, uint32_t m, int64_t *delta, hipStream_t s);
 hipError_t launch_ntuple_values(const uint4 *boards, uint32_t n, const NtupleNet &net, int64_t *v, hipStream_t s);
 // g2048_ntuple_stage_plain: stage[i] of n plain boards; reads the network's shape and thresholds, not its weights
 hipError_t launch_ntuple_stage(const uint4 *boards, uint32_t n, const NtupleNet &net, uint8_t *stage, hipStream_t s);

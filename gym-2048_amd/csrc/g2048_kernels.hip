@@ -2005,6 +2005,90 @@ __global__ void __launch_bounds__(kBlock) ntuple_td_step_kernel(const StepArgs p
     flush_episode_counts(counters, episodes, illegal_ends, wave_sum_lane63(ln.valid ? o.step.gain : 0u), 0ull);
 }
 
+// g2048_ntuple_play_log: ntuple_play_kernel without a budget -- log.depth moves of the greedy player in ONE launch, the record
+// in registers, the same bookkeeping (record_episode_ends, then reset_record, per move; the gains folded every kGainFold moves;
+// one record store and one flush_episode_counts at the end; every board is stepped, so no pending mark survives) -- that also
+// leaves every move in the log (ntuple_play_log_step of g2048_device.h: ntuple_root_kept keeps the afterstate and both values
+// by selects, no array indexed by the action).  The per-move body is ntuple_play_kernel's, copied: shared as a __device__
+// function it would move that kernel's register allocation (the comment above play_step_kernel).  One board per lane for
+// ntuple_play_kernel's reason, so the stores of a move are slot-major and whole: a wavefront writes 1 KiB contiguous of
+// `after`, 512 B of `gain` and 64 B of `flag`.  First the carry: slot 0 takes the three entries slot M held, each lane its own
+// board's (M >= 1: the two slots differ, and no lane reads what another writes).  Slot bases are formed in 64 bits:
+// (M + 1) * n * 16 bytes exceeds 2^32.  The weights are read with plain loads; nothing in the launch writes them.
+template <uint32_t T, class Shape>
+__global__ void __launch_bounds__(kBlock) ntuple_play_log_kernel(const StepArgs p, const Shape sh, uint32_t frac_bits,
+                                                                 const int32_t *__restrict__ weights, const NtupleLog log)
+{
+    __shared__ WaveTables s_tables[kBlock / 64];
+    const Lane ln = lane_of<kBlock, false>(p.n);
+    Board rec = load_board(p.st.boards, ln.i);
+    const LdsTables tb = stage_tables(s_tables, load_tables_piece());
+    const EpisodeCounters counters = load_episode_counters(p, ln.i_raw);
+    if (ln.valid) { // the carry
+        const uint64_t last = static_cast<uint64_t>(log.depth) * p.n;
+        store_board(log.after, ln.i, load_board(log.after + last, ln.i));
+        log.gain[ln.i] = log.gain[last + ln.i];
+        log.flag[ln.i] = log.flag[last + ln.i];
+    }
+    uint64_t t = (static_cast<uint64_t>(p.t_hi) << 32) | p.t_lo; // transaction of the first move
+    uint32_t episodes = 0, illegal_ends = 0, gained32 = 0;
+    unsigned long long gained = 0; // as in ntuple_play_kernel: 32-bit adds, folded into 64 bits every kGainFold moves
+    for (uint32_t m = 1; m <= log.depth; ++m, ++t) {
+        Words w;
+        NtupleLogEntry e;
+        const StepOut o = ntuple_play_log_step<T>(rec, t, p.board_offset + ln.i, p.seed_lo, p.seed_hi, sh, frac_bits, weights, p.max_exp,
+                                                  tb, w, e);
+        if (ln.valid) {
+            const uint64_t slot = static_cast<uint64_t>(m) * p.n;
+            store_board(log.after + slot, ln.i, e.after);
+            log.gain[slot + ln.i] = e.gain;
+            log.flag[slot + ln.i] = static_cast<uint8_t>(e.flag);
+        }
+        gained32 += o.gain;
+        const bool fin = o.terminated && ln.valid;
+        record_episode_ends(p, ln.i, fin, !o.legal, rec, episodes, illegal_ends);
+        if (o.terminated)
+            reset_record(rec, o, w, tb);
+        if (m % kGainFold == 0u) {
+            gained += gained32;
+            gained32 = 0;
+        }
+    }
+    gained += gained32;
+    if (ln.valid)
+        store_board(p.st.boards, ln.i, rec);
+    flush_episode_counts(counters, episodes, illegal_ends, wave_sum64_lane63(ln.valid ? gained : 0ull), 0ull);
+}
+
+// g2048_ntuple_log_delta: the backward error of slot m (ntuple_log_delta of g2048_device.h), one board per lane as
+// ntuple_values_kernel, whose V this is (ntuple_value on the packed board).  Up to two evaluations per board, 16T gathers; each
+// sits behind the flags that ask for it, so a wavefront whose boards all ended, or all have no successor, skips the second,
+// and one whose boards are all empty skips both.  The four-lanes-per-board layout of ntuple_eval_kernel is for the four
+// directions of one board; here there are two boards and no move to make, and one lane per board keeps the loads of a slot
+// contiguous over the wave (1 KiB of `after`, 512 B of `gain`, 64 B of `flag`) and the stores of delta whole.  A lane reads
+// flag[m], flag[m + 1], and what they ask for; it writes delta[i] only -- nothing it reads is written in the launch.
+// The two evaluations are straight-line code.  As one body in a two-trip loop (#pragma nounroll) the kernel holds 35 to 150
+// VGPRs in every shape where this form holds up to 243 (staged, T = 3..5), but it spills up to 634 SGPRs to VGPR lanes and
+// was slower in 11 of the 12 rows timed, by 1 to 5 us per launch (profiles/r28_ntuple_log_resource_usage.txt).
+template <uint32_t T, class Shape>
+__global__ void __launch_bounds__(kBlock) ntuple_log_delta_kernel(const NtupleLog log, uint32_t n, uint32_t m, const Shape sh,
+                                                                  const int32_t *__restrict__ weights, int64_t *__restrict__ delta)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint64_t self = static_cast<uint64_t>(m) * n, next = self + n;
+    const uint32_t f = log.flag[self + i], f1 = log.flag[next + i];
+    int64_t v0 = 0, v1 = 0, gain1 = 0;
+    if (ntuple_log_reads_self(f, f1))
+        v0 = ntuple_value<T>(ntuple_pack(load_board(log.after + self, i)), sh, weights);
+    if (ntuple_log_reads_next(f, f1)) {
+        gain1 = log.gain[next + i];
+        v1 = ntuple_value<T>(ntuple_pack(load_board(log.after + next, i)), sh, weights);
+    }
+    delta[i] = ntuple_log_delta(f, f1, gain1, v1, v0);
+}
+
 // The nine updates (g2048_ntuple_update_plain, g2048_ntuple_tc_update_plain, g2048_ntuple_trace_update,
 // g2048_ntuple_tc_trace_update, g2048_ntuple_delay_update, g2048_ntuple_tc_delay_update; the definitions of g2048_device.h,
 // "n-tuple network value function", "Temporal-coherence learning", "n-tuple traces" and "n-tuple delay") are three kernels,
@@ -2992,6 +3076,21 @@ hipError_t launch_ntuple_td_step(const StepArgs &a, const NtupleNet &net, const 
 {
     return dispatch_tuples(net, [&](auto tc, auto sh) {
         return launch_1d(ntuple_td_step_kernel<tc, decltype(sh)>, a.n, 0, s, a, sh, net.frac_bits, static_cast<const int32_t *>(net.weights), io);
+    });
+}
+
+hipError_t launch_ntuple_play_log(const StepArgs &a, const NtupleNet &net, const NtupleLog &log, hipStream_t s)
+{
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        return launch_1d(ntuple_play_log_kernel<tc, decltype(sh)>, a.n, 0, s, a, sh, net.frac_bits, static_cast<const int32_t *>(net.weights),
+                         log);
+    });
+}
+
+hipError_t launch_ntuple_log_delta(uint32_t n, const NtupleNet &net, const NtupleLog &log, uint32_t m, int64_t *delta, hipStream_t s)
+{
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        return launch_1d(ntuple_log_delta_kernel<tc, decltype(sh)>, n, 0, s, log, n, m, sh, static_cast<const int32_t *>(net.weights), delta);
     });
 }
 

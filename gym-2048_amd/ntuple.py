@@ -41,6 +41,10 @@ composition is the faster form, so ``fused=False`` is the default.
 ``NTupleMean`` and ``mean_step`` / ``mean_train`` / ``mean_tdl_step`` / ``mean_tdl_train`` are the batch-mean learners: every
 table entry a batch reaches moves once, by the mean of the errors that reached it, so its learning rate does not grow with the
 batch (``g2048_ntuple_mean_update_plain``, ``g2048_ntuple_mean_trace_update``).  Opt-in.
+``NTupleLog``, ``Batched2048.ntuple_play_log``, ``NTupleNet.log_delta``, :func:`log_sweep` and :func:`backward_train` are backward
+learning over logged segments (Matsuzaki 2017): M moves of every board played and kept in one launch, then updated from the
+last to the first (``g2048_ntuple_play_log``, ``g2048_ntuple_log_delta``, ``g2048_ntuple_log_sweep``, ``g2048_ntuple_log_train``,
+INTEGRATION.md §24).  A learner of its own.  Opt-in.
 """
 from __future__ import annotations
 
@@ -65,6 +69,7 @@ TRACE_MAX = 8                                                     # G2048_NTUPLE
 DELAY_STEP, DELAY_FLUSH = 0, 1                                    # G2048_NTUPLE_DELAY_STEP, G2048_NTUPLE_DELAY_FLUSH
 MAX_STAGES = 8                                                    # G2048_NTUPLE_MAX_STAGES
 CAROUSEL_MAX_CAPACITY = 65536                                     # G2048_CAROUSEL_MAX_CAPACITY
+LOG_MAX_DEPTH, LOG_VALID, LOG_ENDED = 1024, 1, 2                  # G2048_NTUPLE_LOG_MAX_DEPTH, G2048_NTUPLE_LOG_VALID, G2048_NTUPLE_LOG_ENDED
 NTUPLE_END = 0xff                                                 # G2048_NTUPLE_END: pads a cell list shorter than tuple_len
 SEEN_UNKNOWN = 0xff                                               # Carousel.seen: the stage of the episode is not known yet
 
@@ -549,6 +554,22 @@ class NTupleNet:
         self._own_mean(mean)
         _on_stream(self._fn("mean_trace_update"), trace.device, trace.n, delta.data_ptr(), shift, phases, net, C.byref(mean._c),
                    C.byref(trace._c), trace.slot)
+
+    def log_delta(self, log, m, out=None) -> torch.Tensor:
+        """The backward error of slot ``m`` (0..M-1) of ``log`` (an :class:`NTupleLog`; ``g2048_ntuple_log_delta``, INTEGRATION.md
+        §24), int64 ``[n]``, one launch on the current stream: 0 where slot ``m`` holds nothing; ``-V(after[m])`` where its move
+        ended the episode; 0 where slot ``m + 1`` holds nothing; else ``gain[m+1] + V(after[m+1]) - V(after[m])``.  Reads the log
+        and the weights only; ``V`` is :meth:`values` of the slot.  ``out``: a preallocated tensor."""
+        if not isinstance(log, NTupleLog):
+            raise ValueError("log must be an NTupleLog")
+        net = self._ref(log.device)
+        m = _int_arg("m", m, 0, log.depth - 1)
+        if out is None:
+            out = torch.empty(log.n, dtype=torch.int64, device=log.device)
+        else:
+            _check_tensor("out", out, (torch.int64,), (log.n,), log.device)
+        _on_stream(self._fn("log_delta"), log.device, log.n, net, C.byref(log._c), m, out.data_ptr())
+        return out
 
     def _delay_args(self, delay, lr_shift, flush):
         """(net, lr_shift, mode) for a delay update: ``delay`` checked as :meth:`trace_update` checks its trace."""
@@ -1127,6 +1148,124 @@ def delayed_tcl_train(engine, net, tc, delay, n_steps, lr_shift, carousel=None, 
         delayed_tcl_step(engine, net, tc, delay, lr_shift, work, carousel, fused)
     net.tc_delay_update(delay, lr_shift, tc, flush=True)
     delay.reset()
+    return net
+
+
+class NTupleLog:
+    """The move log of backward learning for ``n`` boards (``g2048_ntuple_log``): ``depth`` (M, 1..1024)
+    moves per segment in ``M + 1`` slots, slot-major -- ``after`` uint8 ``[M+1, n, 16]``, the afterstates played, ``gain`` int64
+    ``[M+1, n]``, the merge gain of each move ``<< frac_bits``, and ``flag`` uint8 ``[M+1, n]``: 0 (nothing played: the board had
+    no legal move, or the slot is still empty), ``LOG_VALID``, or ``LOG_VALID | LOG_ENDED`` (the move ended the episode).
+    ``Batched2048.ntuple_play_log`` writes slots 1..M and carries slot M into slot 0; :func:`log_sweep` learns from slots
+    M-1..0.  Zero-initialised; one per engine or shard; :meth:`reset` after ``engine.reset()``.
+
+    Memory: 25 (M + 1) bytes per board."""
+
+    def __init__(self, n, depth=16, device="cuda:0"):
+        self.n = _int_arg("n", n, 1, 0xffffff00)
+        self.depth = _int_arg("depth", depth, 1, LOG_MAX_DEPTH)
+        self.device = torch.device(device)
+        slots = self.depth + 1
+        self.after = torch.zeros((slots, self.n, 16), dtype=torch.uint8, device=self.device)
+        self.gain = torch.zeros((slots, self.n), dtype=torch.int64, device=self.device)
+        self.flag = torch.zeros((slots, self.n), dtype=torch.uint8, device=self.device)
+        self._c = _lib.NTupleLogC(self.depth, self.after.data_ptr(), self.gain.data_ptr(), self.flag.data_ptr())
+
+    def reset(self):
+        """Empty every slot on the current stream: the next segment has no predecessor (slot 0 carries nothing)."""
+        self.after.zero_()
+        self.gain.zero_()
+        self.flag.zero_()
+
+    def slot(self, m) -> torch.Tensor:
+        """Slot ``m`` (0..M) of ``after`` as a uint8 ``[n, 16]`` view: a plain-board batch for ``values`` and the updates."""
+        return self.after[_int_arg("m", m, 0, self.depth)]
+
+    def state_dict(self):
+        return {"depth": self.depth, "after": self.after.clone(), "gain": self.gain.clone(), "flag": self.flag.clone()}
+
+    def load_state_dict(self, state):
+        """Copy the tensors of a ``state_dict()`` of a log of the same shape into this one (in place)."""
+        if int(state["depth"]) != self.depth:
+            raise ValueError(f"state_dict is of a log of depth {state['depth']}, this one has {self.depth}")
+        new = {name: torch.as_tensor(state[name]) for name in ("after", "gain", "flag")}
+        for name, t in new.items():
+            mine = getattr(self, name)
+            if t.dtype != mine.dtype or t.shape != mine.shape:
+                raise ValueError(f"state_dict {name} must be {str(mine.dtype).replace('torch.', '')} {tuple(mine.shape)}")
+        for name, t in new.items():
+            getattr(self, name).copy_(t)
+
+
+def _log_of(engine, log):
+    if not isinstance(log, NTupleLog) or log.n != engine.n_envs or log.device != engine.device:
+        raise ValueError(f"log must be an NTupleLog of {engine.n_envs} boards on {engine.device}")
+    return log
+
+
+def _log_delta_buffer(log, delta):
+    """``delta`` checked as the int64 ``[log.n]`` work buffer of a sweep, or a fresh one."""
+    if delta is None:
+        return torch.empty(log.n, dtype=torch.int64, device=log.device)
+    _check_tensor("delta", delta, (torch.int64,), (log.n,), log.device)
+    return delta
+
+
+def log_sweep(net, log, lr_shift, tc=None, mean=None, delta=None) -> torch.Tensor:
+    """The backward sweep over ``log`` (an :class:`NTupleLog`): for ``m`` = M-1 down to 0, ``net.log_delta``
+    of slot ``m`` into ``delta`` and then the update of ``log.slot(m)`` by it, so that the target of slot ``m`` is formed with
+    the value slot ``m + 1`` has after its own update.  ``tc`` and ``mean`` None: ``net.update``, ``tc`` (an :class:`NTupleTC` of
+    ``net``): ``net.tc_update`` with ``phases=3`` -- both ONE library call, 2M or 3M plain launches
+    (``g2048_ntuple_log_sweep``); ``mean`` (an :class:`NTupleMean` of ``net``): ``net.mean_update``, composed here launch by
+    launch.  Slot M is not updated: it is slot 0 of the next segment.  ``delta``: the int64 ``[n]`` work buffer, returned (the
+    errors of slot 0 afterwards).  No host synchronisation.  Shards that share ``net`` do not call this: per ``m`` they run
+    ``net.log_delta`` on every shard, then the update on every shard."""
+    if not isinstance(net, NTupleNet):
+        raise ValueError("net must be an NTupleNet")
+    if not isinstance(log, NTupleLog):
+        raise ValueError("log must be an NTupleLog")
+    if tc is not None and mean is not None:
+        raise ValueError("log_sweep takes tc or mean, not both")
+    ref = net._ref(log.device)
+    shift = _int_arg("lr_shift", lr_shift, 0, MAX_LR_SHIFT)
+    delta = _log_delta_buffer(log, delta)
+    if mean is not None:
+        net._own_mean(mean)
+        for m in range(log.depth - 1, -1, -1):
+            net.log_delta(log, m, out=delta)
+            net.mean_update(log.slot(m), delta, shift, mean)
+        return delta
+    if tc is not None:
+        net._own_tc(tc)
+    _on_stream(net._fn("log_sweep"), log.device, log.n, ref, C.byref(log._c), shift, delta.data_ptr(),
+               None if tc is None else C.byref(tc._c))
+    return delta
+
+
+def backward_train(engine, net, log, rounds, lr_shift, tc=None, mean=None, carousel=None):
+    """Backward learning over logged segments (Matsuzaki 2017): ``rounds`` times
+    { ``engine.ntuple_play_log(net, log)``; :func:`log_sweep` } -- play ``log.depth`` moves of every board under frozen weights
+    in one launch, then update the logged afterstates from the last to the first.  ``tc`` and ``mean`` None (TD) or ``tc``: ONE
+    library call for all rounds (``Batched2048.ntuple_log_train``, ``g2048_ntuple_log_train``); ``mean``: the same loop in
+    Python.  The afterstates of slot M are updated by the next round, those of the last round never.  A learner of its own, not
+    :func:`train` at ``depth=1``.  ``carousel`` is not offered (ValueError): its launches sit between a step and the next
+    evaluate, and the moves of a segment are one launch.  A spawn-stream engine only."""
+    if carousel is not None:
+        raise ValueError("backward_train cannot run a carousel: its launches sit between a step and the next evaluate, and the "
+                         "moves of a segment are one launch (use the forward trainers)")
+    if tc is not None and mean is not None:
+        raise ValueError("backward_train takes tc or mean, not both")
+    _log_of(engine, log)
+    if mean is None:
+        engine.ntuple_log_train(net, log, rounds, lr_shift, _log_delta_buffer(log, None), tc)
+        return net
+    if not isinstance(net, NTupleNet):
+        raise ValueError("net must be an NTupleNet")
+    net._own_mean(mean)
+    delta = _log_delta_buffer(log, None)
+    for _ in range(_int_arg("rounds", rounds, 0, (1 << 32) - 1)):
+        engine.ntuple_play_log(net, log)
+        log_sweep(net, log, lr_shift, mean=mean, delta=delta)
     return net
 
 

@@ -968,6 +968,78 @@ int g2048_ntuple_td_train(g2048_engine *e, const g2048_ntuple_net *net, uint32_t
 int g2048_ntuple_staged_td_train(g2048_engine *e, const g2048_ntuple_staged_net *net, uint32_t k_steps, uint32_t lr_shift,
                                  const g2048_ntuple_td_io *work, const g2048_ntuple_tc *tc, void *stream);
 
+/* N-tuple move log and backward learning (K. Matsuzaki, "Developing a 2048 player with backward temporal
+ * coherence learning and restart", ACG 2017): play M moves of every board in one launch and keep them, then update the logged
+ * afterstates from the last to the first, each target formed with the value its successor has AFTER the successor's own
+ * update -- one error at the end of a segment reaches every logged move in one sweep, at full size.  Notation of the n-tuple
+ * block: V(a), F = frac_bits, and evaluate with its `action`, `best`, `after`, `after_value`.
+ *
+ * The log: caller-owned device memory, zero-initialised, one per engine or shard, M + 1 slots of n entries, slot-major.
+ *
+ * play_log (one launch), for every board i:
+ *   1. Carry: slot 0 takes the three entries that slot M held before the call; each lane moves only its own board's entry.  A
+ *      zeroed log therefore starts with slot 0 empty.
+ *   2. For m = 1..M in order: E = evaluate(board), then g2048_step(E.action, auto_reset = 1), and
+ *        after[m][i] = E.after;
+ *        gain[m][i]  = E.best - E.after_value, which is g << F for the merge gain g of the move (0 when no move is legal);
+ *        flag[m][i]  = 0 when the board had no legal move, else VALID | (terminated ? ENDED : 0).
+ *   3. The contract in one sentence: the engine ends in the bits of g2048_ntuple_play(e, net, M, NULL) -- the records, the
+ *      clock, the episode slots and the terminal records -- and slot m holds the outputs of the m-th round of
+ *      g2048_ntuple_evaluate -> g2048_step.  max_tile is honoured; the weights are only read.
+ * G2048_ERR_INVALID, before any HIP call, whichever is found first: what g2048_ntuple_play refuses, the numpy-RNG engine
+ * included; a NULL log or a NULL member; a depth outside 1..1024; `after` not 16-byte or `gain` not 8-byte aligned.
+ *
+ * log_delta(m), 0 <= m < M (one launch, no engine: n boards on the current device), writes delta[i] for every board:
+ *   f = flag[m][i], f1 = flag[m+1][i]
+ *   !(f & VALID)   -> 0
+ *   f & ENDED      -> 0 - V(after[m][i])
+ *   !(f1 & VALID)  -> 0
+ *   otherwise      -> gain[m+1][i] + V(after[m+1][i]) - V(after[m][i])      (int64, wraps)
+ * Total for any byte in flag (only bits 0 and 1 are read); reads the log and the weights only; V is exactly what
+ * g2048_ntuple_values_plain returns for that slot.  Refuses m >= M, a NULL or misaligned delta, n outside 1..2^32 - 256.
+ *
+ * log_sweep (no engine): for m = M-1 down to 0, log_delta(m) into the caller's `delta`, then the update of slot m --
+ * g2048_ntuple_update_plain(after + m*n*16, n, delta, lr_shift, net) when tc == NULL, otherwise
+ * g2048_ntuple_tc_update_plain(..., phases = 3, net, tc).  Plain launches on `stream`, no host synchronisation; the result is
+ * the bits of those 2M calls made by hand.  `delta` holds the errors of slot 0 afterwards.
+ *   - Slot M is never updated in the round that wrote it: it is updated as slot 0 of the next round.  So every logged
+ *     afterstate is updated exactly once, whether it ended an episode or not.
+ *   - The afterstates in slot M when training stops are not learned from.
+ *   - A delta launch reads no entry that its launch writes, and the updates are sums of integer adds: the weights do not
+ *     depend on lane, wave, block or launch geometry.
+ *   - Shards that share a network each own a log.  They run play_log everywhere; then, per m, log_delta on every shard,
+ *     followed by the update on every shard (for TC: W everywhere, then A everywhere): the bits of the unsharded run.
+ *   - A learner of its own, not TD(0) at M = 1: the move of round r is chosen under the weights before the update of round
+ *     r-1's afterstate.
+ *
+ * log_train: rounds x { play_log; log_sweep } on the engine's n boards.  rounds == 0 is G2048_OK and changes nothing.
+ * Refuses, before any HIP call, what play_log refuses, lr_shift > 40, a NULL or misaligned delta, and a tc
+ * g2048_ntuple_tc_update_plain refuses. */
+#define G2048_NTUPLE_LOG_MAX_DEPTH 1024
+#define G2048_NTUPLE_LOG_VALID 1u   /* the slot holds an afterstate that was played */
+#define G2048_NTUPLE_LOG_ENDED 2u   /* the step that played it ended the episode    */
+typedef struct g2048_ntuple_log {
+    uint32_t depth;   /* M, 1..1024 moves per segment; the log has M + 1 slots                    */
+    uint8_t *after;   /* uint8 [M+1][n][16] slot-major, 16-byte aligned: slot m is a plain-board batch */
+    int64_t *gain;    /* int64 [M+1][n], 8-byte aligned: (merge gain of the move played) << F          */
+    uint8_t *flag;    /* uint8 [M+1][n]: 0, VALID, or VALID | ENDED                                    */
+} g2048_ntuple_log;   /* caller-owned device memory, zero-initialised, one per engine or shard */
+int g2048_ntuple_play_log(g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_log *log, void *stream);
+int g2048_ntuple_staged_play_log(g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_log *log, void *stream);
+int g2048_ntuple_log_delta(uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_log *log, uint32_t m, int64_t *delta,
+                           void *stream);
+int g2048_ntuple_staged_log_delta(uint64_t n, const g2048_ntuple_staged_net *net, const g2048_ntuple_log *log, uint32_t m,
+                                  int64_t *delta, void *stream);
+int g2048_ntuple_log_sweep(uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_log *log, uint32_t lr_shift, int64_t *delta,
+                           const g2048_ntuple_tc *tc /* NULL: the TD update */, void *stream);
+int g2048_ntuple_staged_log_sweep(uint64_t n, const g2048_ntuple_staged_net *net, const g2048_ntuple_log *log, uint32_t lr_shift,
+                                  int64_t *delta, const g2048_ntuple_tc *tc, void *stream);
+int g2048_ntuple_log_train(g2048_engine *e, const g2048_ntuple_net *net, uint32_t rounds, uint32_t lr_shift,
+                           const g2048_ntuple_log *log, int64_t *delta, const g2048_ntuple_tc *tc /* NULL: the TD update */,
+                           void *stream);
+int g2048_ntuple_staged_log_train(g2048_engine *e, const g2048_ntuple_staged_net *net, uint32_t rounds, uint32_t lr_shift,
+                                  const g2048_ntuple_log *log, int64_t *delta, const g2048_ntuple_tc *tc, void *stream);
+
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream);
