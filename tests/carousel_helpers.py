@@ -8,29 +8,21 @@ import subprocess
 import numpy as np
 
 import carousel_ref as cref
+from host_build import TESTS, build_host, stale
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "tests", "host_carousel")
+HOST_DIR = os.path.join(TESTS, "host_carousel")
 SRC = os.path.join(HOST_DIR, "carousel_check.cpp")
-DEPS = [SRC, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-
-
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in DEPS)
 
 
 def build_host_carousel(force=False):
     """g++ build of tests/host_carousel as a shared library (the device header's carousel code compiled for the host)."""
-    so = os.path.join(HOST_DIR, "libcarousel_check.so")
-    if force or _stale(so):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, SRC])
-    return so
+    return build_host("host_carousel", "carousel_check.cpp", "libcarousel_check.so", force)
 
 
 def build_sanitized_driver(force=False):
     """The same file as a stand-alone program (its own main) under AddressSanitizer and UBSan."""
     exe = os.path.join(HOST_DIR, "carousel_driver_asan")
-    if force or _stale(exe):
+    if force or stale(exe, SRC):
         subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                                "-DCAROUSEL_CHECK_MAIN", "-Wall", "-Wno-unknown-pragmas", "-o", exe, SRC])
     return exe

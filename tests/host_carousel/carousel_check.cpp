@@ -4,23 +4,12 @@
 // scatter by rank) for any range size.  tests/test_carousel_host.py compares it with the pure-Python reference
 // (tests/carousel_ref.py); the GPU tests compare the kernels with that reference too.  With -DCAROUSEL_CHECK_MAIN the file is
 // a stand-alone program that drives the same code over random batches, for a sanitizer build.  Not part of the product.
-#define G2048_HOST_CHECK 1
-#include "../../gym-2048_amd/csrc/g2048_device.h"
+#include "../host_common/ntuple_host.h"
 
 #include <cstdio>
-#include <cstring>
 #include <vector>
 
-using namespace g2048;
-
 namespace {
-
-Board load_raw(const uint8_t *p)
-{
-    Board b;
-    memcpy(b.r, p, 16);
-    return b;
-}
 
 bool shape_ok(uint32_t S, const uint16_t *thr, uint32_t C)
 {

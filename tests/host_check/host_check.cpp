@@ -3,27 +3,12 @@
 // unit-tested against the oracle in a container that has no GPU.  It mirrors the bodies of
 // step_kernel / reset_kernel (g2048_kernels.hip) one board at a time; the last two sections do the same for the
 // expectimax and Monte-Carlo search.  Not part of the product.
-#define G2048_HOST_CHECK 1
-#include "../../gym-2048_amd/csrc/g2048_device.h"
+#include "../host_common/ntuple_host.h" // g2048_device.h for the host, HostTables, load_raw, load_cells
+
 #include "../../gym-2048_amd/csrc/g2048_pcg64.h"
 #include "../../oracle/g2048_oracle.h"
 
-#include <cstring>
-
-using namespace g2048;
-
-static Board load_board(const uint8_t *b)
-{
-    Board bd;
-    std::memcpy(bd.r, b, 16);
-    return bd;
-}
 static void store_board(uint8_t *b, const Board &bd) { std::memcpy(b, bd.r, 16); }
-static Board load_cells(const uint8_t *b) // exponents mod 32, as the plain kernels read them
-{
-    const Board bd = load_board(b);
-    return Board{{bd.r[0] & kCellBits, bd.r[1] & kCellBits, bd.r[2] & kCellBits, bd.r[3] & kCellBits}};
-}
 
 extern "C" {
 
@@ -57,19 +42,19 @@ uint32_t hostcheck_shift(const uint8_t row[4], uint8_t out[4], int lane, const u
 
 int hostcheck_move(const uint8_t in[16], uint32_t action, uint8_t out[16], uint32_t *score)
 {
-    Board bd = load_board(in);
+    Board bd = load_raw(in);
     const bool legal = move(bd, action, *score);
     store_board(out, bd);
     return legal;
 }
 
-uint32_t hostcheck_highest(const uint8_t in[16]) { return highest(load_board(in)); }
-uint32_t hostcheck_count_empty(const uint8_t in[16]) { return count_empty(load_board(in)); }
-int hostcheck_has_equal_neighbours(const uint8_t in[16]) { return has_equal_neighbours(load_board(in)); }
+uint32_t hostcheck_highest(const uint8_t in[16]) { return highest(load_raw(in)); }
+uint32_t hostcheck_count_empty(const uint8_t in[16]) { return count_empty(load_raw(in)); }
+int hostcheck_has_equal_neighbours(const uint8_t in[16]) { return has_equal_neighbours(load_raw(in)); }
 
 void hostcheck_add_tile(uint8_t b[16], uint32_t w)
 {
-    Board bd = load_board(b);
+    Board bd = load_raw(b);
     add_tile(bd, w);
     store_board(b, bd);
 }
@@ -99,7 +84,7 @@ void hostcheck_step_batch(g2048o_batch *s, uint64_t n, uint64_t seed, uint64_t t
                           float illegal_move_reward, int max_exp, int auto_reset, int)
 {
     for (uint64_t i = 0; i < n; ++i) {
-        Board bd = load_board(s->boards + 16 * i);
+        Board bd = load_raw(s->boards + 16 * i);
         int32_t score = s->score[i];
         const Words w = philox4x32_10((uint32_t)t, (uint32_t)(t >> 32), (uint32_t)(board_offset + i), 0u,
                                       (uint32_t)seed, (uint32_t)(seed >> 32));
@@ -124,14 +109,6 @@ void hostcheck_step_batch(g2048o_batch *s, uint64_t n, uint64_t seed, uint64_t t
 // ---- the RECORD layout and the per-step kernel's flow (step_kernel in g2048_kernels.hip), one board
 // at a time: state lives in `records` (16 B per board: cells + packed score deficit); the plain boards /
 // scores of the batch struct are exported after every call so the test can compare them with the oracle's.
-static const uint32_t kLutHost[32] = {G2048_MOVE_LUT_WORDS};
-
-static MoveSel host_move_sel(uint32_t action)
-{
-    const uint32_t *r = kLutHost + 8 * (action & 3u);
-    return MoveSel{r[0], r[1], r[2], r[3], r[4], r[5]};
-}
-
 static void export_record(g2048o_batch *s, uint64_t i, const Board &rec)
 {
     store_board(s->boards + 16 * i, record_cells(rec));
@@ -140,26 +117,26 @@ static void export_record(g2048o_batch *s, uint64_t i, const Board &rec)
 
 int hostcheck_move_sel(const uint8_t in[16], uint32_t action, uint8_t out[16], uint32_t *score)
 {
-    Board bd = load_board(in);
-    const bool legal = move_sel(bd, host_move_sel(action), *score);
+    Board bd = load_raw(in);
+    const bool legal = move_sel(bd, HostTables().move_sel(action), *score);
     store_board(out, bd);
     return legal;
 }
 
-uint32_t hostcheck_potential(const uint8_t in[16]) { return potential(load_board(in)); }
+uint32_t hostcheck_potential(const uint8_t in[16]) { return potential(load_raw(in)); }
 
 void hostcheck_make_record(const uint8_t cells[16], uint32_t score, uint8_t rec[16])
 {
-    store_board(rec, make_record(load_board(cells), score));
+    store_board(rec, make_record(load_raw(cells), score));
 }
 
-uint32_t hostcheck_record_score(const uint8_t rec[16]) { return record_score(load_board(rec)); }
-uint32_t hostcheck_record_deficit(const uint8_t rec[16]) { return record_deficit(load_board(rec)); }
+uint32_t hostcheck_record_score(const uint8_t rec[16]) { return record_score(load_raw(rec)); }
+uint32_t hostcheck_record_deficit(const uint8_t rec[16]) { return record_deficit(load_raw(rec)); }
 
 // record_update with an arbitrary number of "+4" carries (exercises the ripple through the cell bits)
 void hostcheck_record_bump(uint8_t rec[16], uint32_t times)
 {
-    Board raw = load_board(rec);
+    Board raw = load_raw(rec);
     for (uint32_t k = 0; k < times; ++k)
         record_update(raw, record_cells(raw), 0x80u);
     store_board(rec, raw);
@@ -187,14 +164,6 @@ void hostcheck_reset_records(g2048o_batch *s, uint8_t *records, uint64_t n, uint
     }
 }
 
-struct HostTables { // what LdsTables is on the device (g2048_kernels.hip)
-    MoveSel move_sel(uint32_t action) const { return host_move_sel(action); }
-    Board onehot_cell(uint32_t p) const
-    {
-        return Board{{onehot_cell_word(p, 0), onehot_cell_word(p, 1), onehot_cell_word(p, 2), onehot_cell_word(p, 3)}};
-    }
-};
-
 void hostcheck_fresh_record_lut(uint32_t w1, uint32_t w2, uint8_t out_lut[16], uint8_t out_ref[16])
 {
     store_board(out_lut, fresh_record_lut(w1, w2, HostTables{}));
@@ -207,7 +176,7 @@ void hostcheck_step_records(g2048o_batch *s, uint8_t *records, uint8_t *last_rec
                             uint64_t board_offset, float illegal_move_reward, int max_exp, int auto_reset)
 {
     for (uint64_t i = 0; i < n; ++i) {
-        Board rec = load_board(records + 16 * i);
+        Board rec = load_raw(records + 16 * i);
         const Words w = philox4x32_10((uint32_t)t, (uint32_t)(t >> 32), (uint32_t)(board_offset + i), 0u,
                                       (uint32_t)seed, (uint32_t)(seed >> 32));
         const uint32_t action = s->actions ? (s->actions[i] & 3u) : (w.w[3] >> 30);
@@ -220,7 +189,7 @@ void hostcheck_step_records(g2048o_batch *s, uint8_t *records, uint8_t *last_rec
         if (o.terminated) {
             store_board(last_records + 16 * i, o.terminal);
             if (s->terminal_boards) store_board(s->terminal_boards + 16 * i, record_cells(o.terminal));
-            s->last_score[i] = (int32_t)record_score(load_board(last_records + 16 * i)); // g2048_get_last_scores
+            s->last_score[i] = (int32_t)record_score(load_raw(last_records + 16 * i)); // g2048_get_last_scores
             s->last_len[i] = (int32_t)((uint32_t)t - s->ep_start[i]);
             s->ep_count[i] += 1;
             if (auto_reset) s->ep_start[i] = (uint32_t)t;
@@ -234,7 +203,7 @@ void hostcheck_step_records_unpacked(g2048o_batch *s, uint8_t *records, uint8_t 
                                      uint64_t board_offset, float illegal_move_reward, int max_exp, int auto_reset)
 {
     for (uint64_t i = 0; i < n; ++i) {
-        const Board raw = load_board(records + 16 * i);
+        const Board raw = load_raw(records + 16 * i);
         Board bd = record_cells(raw);
         int32_t score = (int32_t)record_score(raw);
         const Words w = philox4x32_10((uint32_t)t, (uint32_t)(t >> 32), (uint32_t)(board_offset + i), 0u,
@@ -272,7 +241,7 @@ void hostcheck_onehot_wave(const uint8_t *records, int obs_dtype, uint8_t *out)
 {
     Cells16 recs[64];
     for (int l = 0; l < 64; ++l) {
-        const Board cells = record_cells(load_board(records + 16 * l));
+        const Board cells = record_cells(load_raw(records + 16 * l));
         for (int k = 0; k < 4; ++k)
             recs[l].r[k] = cells.r[k];
     }
@@ -290,7 +259,7 @@ uint64_t hostcheck_pcg64_next64(g2048o_pcg64 *r) { Pcg64 p = load_rng(r); const 
 uint32_t hostcheck_pcg64_next32(g2048o_pcg64 *r) { Pcg64 p = load_rng(r); const uint32_t v = pcg64_next32(p); store_rng(r, p); return v; }
 uint32_t hostcheck_pcg64_interval(g2048o_pcg64 *r, uint32_t mx) { Pcg64 p = load_rng(r); const uint32_t v = pcg64_interval(p, mx); store_rng(r, p); return v; }
 void hostcheck_pcg64_from_seed(uint64_t entropy, g2048o_pcg64 *out) { store_rng(out, pcg64_from_seed(entropy)); }
-uint32_t hostcheck_empty_mask16(const uint8_t b[16]) { return empty_mask16(load_board(b)); }
+uint32_t hostcheck_empty_mask16(const uint8_t b[16]) { return empty_mask16(load_raw(b)); }
 
 void hostcheck_reset_batch_numpy(g2048o_batch *s, g2048o_pcg64 *rng, uint64_t n, uint64_t t, int)
 {
@@ -308,7 +277,7 @@ void hostcheck_step_batch_numpy(g2048o_batch *s, g2048o_pcg64 *rng, uint64_t n, 
                                 uint64_t board_offset, float illegal_move_reward, int max_exp, int auto_reset, int)
 {
     for (uint64_t i = 0; i < n; ++i) {
-        Board bd = load_board(s->boards + 16 * i);
+        Board bd = load_raw(s->boards + 16 * i);
         int32_t score = s->score[i];
         Pcg64 p = load_rng(&rng[i]);
         uint32_t action;

@@ -3,77 +3,13 @@
 // updates run the header's item sources, item loop and per-item operations -- what the update kernels run -- with
 // wrapping adds for the atomic ones.  tests/test_ntuple*_host.py compare it with the pure-Python references
 // (tests/ntuple*_ref.py); the GPU tests compare the kernels with those references too.  Not part of the product.
-#define G2048_HOST_CHECK 1
-#include "../../gym-2048_amd/csrc/g2048_device.h"
-
-#include <cstring>
-#include <type_traits>
-
-using namespace g2048;
+#include "../host_common/ntuple_host.h"
 
 namespace {
 
-const uint32_t kLut[32] = {G2048_MOVE_LUT_WORDS};
-
-struct HostTables { // what LdsTables is on the device (g2048_kernels.hip)
-    MoveSel move_sel(uint32_t action) const
-    {
-        const uint32_t *r = kLut + 8 * (action & 3u);
-        return MoveSel{r[0], r[1], r[2], r[3], r[4], r[5]};
-    }
-};
-
-// the 16 bytes as they are: what ntuple_pack sees of an engine record (score-deficit bits in bits 5..7 of bytes 8..15)
-Board load_raw(const uint8_t *p)
-{
-    Board b;
-    memcpy(b.r, p, 16);
-    return b;
-}
-
-// plain cells, taken mod 32 as input_cells<true> takes them on the device
-Board load_cells(const uint8_t *p)
-{
-    Board b = load_raw(p);
-    for (uint32_t &r : b.r)
-        r &= 0x1f1f1f1fu;
-    return b;
-}
-
-// the network a test describes (ctypes: ntuple_helpers.Desc)
-struct Desc {
-    uint32_t T, L, F, S;
-    uint32_t staged; // 0: the calls instantiate NtupleShape (S == 1); 1: NtupleStagedShape, S = 1 included
-    uint16_t thr[8]; // the first S - 1 used
-    uint8_t cells[8][6];
-};
-
-bool desc_ok(const Desc *d)
-{
-    return d && d->T >= 1 && d->T <= kNtupleMaxTuples && d->L >= 1 && d->L <= kNtupleMaxLen && d->F <= kNtupleMaxFrac && d->S >= 1 &&
-           d->S <= kNtupleMaxStages && d->staged <= 1 && (d->staged || d->S == 1);
-}
+constexpr uint32_t kMaxKind = 1; // the calls instantiate NtupleShape (S == 1) and NtupleStagedShape, S = 1 included
 
 NtupleStagedShape staged_shape_of(const Desc *d) { return ntuple_staged_shape(ntuple_shape(d->T, d->L, d->cells), d->S, d->thr); }
-
-template <uint32_t T = 1, class Shape, class F> void with_tuple_count(uint32_t n_tuples, const Shape &sh, F &&f)
-{
-    if constexpr (T <= kNtupleMaxTuples) {
-        if (n_tuples == T)
-            f(std::integral_constant<uint32_t, T>(), sh);
-        else
-            with_tuple_count<T + 1>(n_tuples, sh, f);
-    }
-}
-
-// f(std::integral_constant<uint32_t, T>(), shape) for the description's T in 1..8 and its shape type
-template <class F> void with_tuples(const Desc *d, F &&f)
-{
-    if (d->staged)
-        with_tuple_count(d->T, staged_shape_of(d), f);
-    else
-        with_tuple_count(d->T, ntuple_shape(d->T, d->L, d->cells), f);
-}
 
 // The update of every item of a source, in place on weights / err / mag.  mode 0: the TD update; mode 1..3: the TC update
 // with phases = mode, phase W over every item, then phase A over every item.
@@ -81,7 +17,7 @@ template <class Items>
 int update_items(const Items &items, const int64_t *delta, uint32_t lr_shift, uint32_t mode, const Desc *d, int32_t *weights, int64_t *err,
                  int64_t *mag)
 {
-    if (!desc_ok(d) || lr_shift > kNtupleMaxShift || mode > 3)
+    if (!desc_ok(d, kMaxKind) || lr_shift > kNtupleMaxShift || mode > 3)
         return -1;
     uint32_t *w = reinterpret_cast<uint32_t *>(weights);
     uint64_t *e = reinterpret_cast<uint64_t *>(err), *a = reinterpret_cast<uint64_t *>(mag);
@@ -160,7 +96,7 @@ void ntuple_check_mask(const uint8_t *boards, uint64_t n, uint32_t *out)
 // stage of n boards given as raw bytes; -1 for a description out of range
 int ntuple_check_stage(const uint8_t *boards, uint64_t n, const Desc *d, uint8_t *out)
 {
-    if (!desc_ok(d))
+    if (!desc_ok(d, kMaxKind))
         return -1;
     const NtupleStagedShape sh = staged_shape_of(d);
     for (uint64_t i = 0; i < n; ++i)
@@ -171,7 +107,7 @@ int ntuple_check_stage(const uint8_t *boards, uint64_t n, const Desc *d, uint8_t
 // element offset of the weight set of n plain boards (ntuple_stage_base): what the look-ups add
 int ntuple_check_base(const uint8_t *boards, uint64_t n, const Desc *d, uint32_t *out)
 {
-    if (!desc_ok(d))
+    if (!desc_ok(d, kMaxKind))
         return -1;
     with_tuples(d, [&](auto, const auto &sh) {
         for (uint64_t i = 0; i < n; ++i)
@@ -185,7 +121,7 @@ int ntuple_check_base(const uint8_t *boards, uint64_t n, const Desc *d, uint32_t
 int ntuple_check_evaluate(const uint8_t *boards, uint64_t n, const Desc *d, const int32_t *weights, int64_t *value, uint8_t *action,
                           int64_t *best, uint8_t *after, int64_t *after_value)
 {
-    if (!desc_ok(d))
+    if (!desc_ok(d, kMaxKind))
         return -1;
     with_tuples(d, [&](auto tc, const auto &sh) {
         for (uint64_t i = 0; i < n; ++i) {
@@ -202,7 +138,7 @@ int ntuple_check_evaluate(const uint8_t *boards, uint64_t n, const Desc *d, cons
 
 int ntuple_check_values(const uint8_t *boards, uint64_t n, const Desc *d, const int32_t *weights, int64_t *v)
 {
-    if (!desc_ok(d))
+    if (!desc_ok(d, kMaxKind))
         return -1;
     with_tuples(d, [&](auto tc, const auto &sh) {
         for (uint64_t i = 0; i < n; ++i)
@@ -215,7 +151,7 @@ int ntuple_check_values(const uint8_t *boards, uint64_t n, const Desc *d, const 
 int ntuple_check_search(const uint8_t *boards, uint64_t n, uint32_t depth, const Desc *d, const int32_t *weights, uint8_t *action,
                         int64_t *value)
 {
-    if (!desc_ok(d) || depth < 1 || depth > kNtupleSearchMaxDepth)
+    if (!desc_ok(d, kMaxKind) || depth < 1 || depth > kNtupleSearchMaxDepth)
         return -1;
     with_tuples(d, [&](auto tc, const auto &sh) {
         constexpr uint32_t T = decltype(tc)::value;
@@ -233,7 +169,7 @@ int ntuple_check_search(const uint8_t *boards, uint64_t n, uint32_t depth, const
 int ntuple_check_chance_split(const uint8_t *boards, uint64_t n, uint32_t depth, const Desc *d, const int32_t *weights, uint32_t K,
                               int64_t *sum)
 {
-    if (!desc_ok(d) || depth < 1 || depth > kNtupleSearchMaxDepth || K < 1)
+    if (!desc_ok(d, kMaxKind) || depth < 1 || depth > kNtupleSearchMaxDepth || K < 1)
         return -1;
     const HostTables tb;
     with_tuples(d, [&](auto tc, const auto &sh) {

@@ -5,71 +5,9 @@
 // before the next step begins (the kernel's barriers), with plain adds where the kernel uses LDS atomics.  For uniform, staged
 // and mixed-length networks.  tests/test_ntuple_adaptive_host.py compares both with the pure-Python reference, with the
 // composition by definition and with each other.  Not part of the product.
-#define G2048_HOST_CHECK 1
-#include "../../gym-2048_amd/csrc/g2048_device.h"
-
-#include <cstring>
-#include <type_traits>
-
-using namespace g2048;
+#include "../host_common/ntuple_host.h"
 
 namespace {
-
-const uint32_t kLut[32] = {G2048_MOVE_LUT_WORDS};
-
-struct HostTables { // what LdsTables is on the device (g2048_kernels.hip)
-    MoveSel move_sel(uint32_t action) const
-    {
-        const uint32_t *r = kLut + 8 * (action & 3u);
-        return MoveSel{r[0], r[1], r[2], r[3], r[4], r[5]};
-    }
-};
-
-// plain cells, taken mod 32 as input_cells<true> takes them on the device
-Board load_cells(const uint8_t *p)
-{
-    Board b;
-    memcpy(b.r, p, 16);
-    for (uint32_t &r : b.r)
-        r &= 0x1f1f1f1fu;
-    return b;
-}
-
-// the network a test describes (ctypes: ntuple_deep_helpers.Desc)
-struct Desc {
-    uint32_t T, L, F, S;
-    uint32_t kind;   // the shape type the call instantiates: 0 NtupleShape (S == 1), 1 NtupleStagedShape, 2 NtupleMixedShape
-    uint16_t thr[8]; // the first S - 1 used
-    uint8_t cells[8][6];
-};
-
-bool desc_ok(const Desc *d)
-{
-    return d && d->T >= 1 && d->T <= kNtupleMaxTuples && d->L >= 1 && d->L <= kNtupleMaxLen && d->F <= kNtupleMaxFrac && d->S >= 1 &&
-           d->S <= kNtupleMaxStages && d->kind <= 2 && (d->kind != 0 || d->S == 1);
-}
-
-template <uint32_t T = 1, class Shape, class F> void with_tuple_count(uint32_t n_tuples, const Shape &sh, F &&f)
-{
-    if constexpr (T <= kNtupleMaxTuples) {
-        if (n_tuples == T)
-            f(std::integral_constant<uint32_t, T>(), sh);
-        else
-            with_tuple_count<T + 1>(n_tuples, sh, f);
-    }
-}
-
-// f(std::integral_constant<uint32_t, T>(), shape) for the description's T in 1..8 and its shape type
-template <class F> void with_tuples(const Desc *d, F &&f)
-{
-    const NtupleShape sh = ntuple_shape(d->T, d->L, d->cells);
-    if (d->kind == 2)
-        with_tuple_count(d->T, ntuple_mixed_shape(d->T, d->L, d->cells, d->S, d->thr), f);
-    else if (d->kind == 1)
-        with_tuple_count(d->T, ntuple_staged_shape(sh, d->S, d->thr), f);
-    else
-        with_tuple_count(d->T, sh, f);
-}
 
 // evaluate's definition on one thread: q[4] and the action
 template <uint32_t T, class Shape>
@@ -126,7 +64,7 @@ extern "C" {
 int adaptive_check_root(const uint8_t *boards, uint64_t n, uint32_t depth, const Desc *d, const int32_t *weights, uint8_t *action,
                         int64_t *value)
 {
-    if (!desc_ok(d) || depth > kNtupleAdaptiveMaxDepth)
+    if (!desc_ok(d, 2) || depth > kNtupleAdaptiveMaxDepth)
         return -1;
     with_tuples(d, [&](auto tc, const auto &sh) {
         constexpr uint32_t T = decltype(tc)::value;
@@ -149,7 +87,7 @@ int adaptive_check_root(const uint8_t *boards, uint64_t n, uint32_t depth, const
 int adaptive_check_split(const uint8_t *boards, uint64_t n, const uint8_t *schedule, const Desc *d, const int32_t *weights, uint32_t P,
                          const uint32_t *active, uint8_t *action, int64_t *value, uint8_t *depth)
 {
-    if (!desc_ok(d) || !schedule || P < 1)
+    if (!desc_ok(d, 2) || !schedule || P < 1)
         return -1;
     for (uint32_t e = 0; e < 17u; ++e)
         if (schedule[e] > kNtupleAdaptiveMaxDepth)

@@ -5,71 +5,9 @@
 // mixed-length networks.  tests/test_ntuple_deep_host.py compares both with tests/ntuple_search_ref.py and with each other.
 // -DDEEP_CHECK_MAIN adds a stand-alone main() that runs the split against the one-thread root on a fixed board set (the
 // form a sanitizer build runs).  Not part of the product.
-#define G2048_HOST_CHECK 1
-#include "../../gym-2048_amd/csrc/g2048_device.h"
-
-#include <cstring>
-#include <type_traits>
-
-using namespace g2048;
+#include "../host_common/ntuple_host.h"
 
 namespace {
-
-const uint32_t kLut[32] = {G2048_MOVE_LUT_WORDS};
-
-struct HostTables { // what LdsTables is on the device (g2048_kernels.hip)
-    MoveSel move_sel(uint32_t action) const
-    {
-        const uint32_t *r = kLut + 8 * (action & 3u);
-        return MoveSel{r[0], r[1], r[2], r[3], r[4], r[5]};
-    }
-};
-
-// plain cells, taken mod 32 as input_cells<true> takes them on the device
-Board load_cells(const uint8_t *p)
-{
-    Board b;
-    memcpy(b.r, p, 16);
-    for (uint32_t &r : b.r)
-        r &= 0x1f1f1f1fu;
-    return b;
-}
-
-// the network a test describes (ctypes: ntuple_deep_helpers.Desc)
-struct Desc {
-    uint32_t T, L, F, S;
-    uint32_t kind;   // the shape type the call instantiates: 0 NtupleShape (S == 1), 1 NtupleStagedShape, 2 NtupleMixedShape
-    uint16_t thr[8]; // the first S - 1 used
-    uint8_t cells[8][6];
-};
-
-bool desc_ok(const Desc *d)
-{
-    return d && d->T >= 1 && d->T <= kNtupleMaxTuples && d->L >= 1 && d->L <= kNtupleMaxLen && d->F <= kNtupleMaxFrac && d->S >= 1 &&
-           d->S <= kNtupleMaxStages && d->kind <= 2 && (d->kind != 0 || d->S == 1);
-}
-
-template <uint32_t T = 1, class Shape, class F> void with_tuple_count(uint32_t n_tuples, const Shape &sh, F &&f)
-{
-    if constexpr (T <= kNtupleMaxTuples) {
-        if (n_tuples == T)
-            f(std::integral_constant<uint32_t, T>(), sh);
-        else
-            with_tuple_count<T + 1>(n_tuples, sh, f);
-    }
-}
-
-// f(std::integral_constant<uint32_t, T>(), shape) for the description's T in 1..8 and its shape type
-template <class F> void with_tuples(const Desc *d, F &&f)
-{
-    const NtupleShape sh = ntuple_shape(d->T, d->L, d->cells);
-    if (d->kind == 2)
-        with_tuple_count(d->T, ntuple_mixed_shape(d->T, d->L, d->cells, d->S, d->thr), f);
-    else if (d->kind == 1)
-        with_tuple_count(d->T, ntuple_staged_shape(sh, d->S, d->thr), f);
-    else
-        with_tuple_count(d->T, sh, f);
-}
 
 // One board through the kernel's steps with P lanes; the table is the caller's (the kernel reuses its LDS from board to board)
 template <int D, uint32_t T, class Shape>
@@ -105,7 +43,7 @@ extern "C" {
 int deep_check_root(const uint8_t *boards, uint64_t n, uint32_t depth, const Desc *d, const int32_t *weights, uint8_t *action,
                     int64_t *value)
 {
-    if (!desc_ok(d) || depth < 1 || depth > kNtupleDeepMaxDepth)
+    if (!desc_ok(d, 2) || depth < 1 || depth > kNtupleDeepMaxDepth)
         return -1;
     with_tuples(d, [&](auto tc, const auto &sh) {
         constexpr uint32_t T = decltype(tc)::value;
@@ -127,7 +65,7 @@ int deep_check_root(const uint8_t *boards, uint64_t n, uint32_t depth, const Des
 int deep_check_split(const uint8_t *boards, uint64_t n, uint32_t depth, const Desc *d, const int32_t *weights, uint32_t P,
                      const uint32_t *active, uint8_t *action, int64_t *value, uint32_t *items, uint32_t *units)
 {
-    if (!desc_ok(d) || depth < kNtupleDeepMinDepth || depth > kNtupleDeepMaxDepth || P < 1)
+    if (!desc_ok(d, 2) || depth < kNtupleDeepMinDepth || depth > kNtupleDeepMaxDepth || P < 1)
         return -1;
     with_tuples(d, [&](auto tc, const auto &sh) {
         constexpr uint32_t T = decltype(tc)::value;

@@ -5,50 +5,9 @@
 // tests/test_ntuple_delay_host.py compares it bit for bit with tests/ntuple_delay_ref.py.  With -DDELAY_CHECK_MAIN the file
 // is a stand-alone program that runs the same code on generated pushes (for a sanitizer build) and checks what can be
 // checked without the reference: the three orders agree, and lambda = 0 equals the plain updates.  Not part of the product.
-#define G2048_HOST_CHECK 1
-#include "../../gym-2048_amd/csrc/g2048_device.h"
-
-#include <cstring>
-#include <type_traits>
-
-using namespace g2048;
+#include "../host_common/ntuple_host.h"
 
 namespace {
-
-// the network a test describes (ctypes: test_ntuple_delay_host.Desc)
-struct Desc {
-    uint32_t T, L, F, S; // L = tuple_len; a list of a mixed network may end early with kNtupleEnd
-    uint32_t kind;       // 0: NtupleShape (S == 1), 1: NtupleStagedShape, 2: NtupleMixedShape
-    uint16_t thr[8];     // the first S - 1 used
-    uint8_t cells[8][6];
-};
-
-bool desc_ok(const Desc *d)
-{
-    return d && d->T >= 1 && d->T <= kNtupleMaxTuples && d->L >= 1 && d->L <= kNtupleMaxLen && d->F <= kNtupleMaxFrac && d->S >= 1 &&
-           d->S <= kNtupleMaxStages && d->kind <= 2 && (d->kind != 0 || d->S == 1);
-}
-
-template <uint32_t T = 1, class Shape, class F> void with_tuple_count(uint32_t n_tuples, const Shape &sh, F &&f)
-{
-    if constexpr (T <= kNtupleMaxTuples) {
-        if (n_tuples == T)
-            f(std::integral_constant<uint32_t, T>(), sh);
-        else
-            with_tuple_count<T + 1>(n_tuples, sh, f);
-    }
-}
-
-// f(std::integral_constant<uint32_t, T>(), shape) for the description's T and its shape type
-template <class F> void with_tuples(const Desc *d, F &&f)
-{
-    if (d->kind == 2)
-        with_tuple_count(d->T, ntuple_mixed_shape(d->T, d->L, d->cells, d->S, d->thr), f);
-    else if (d->kind == 1)
-        with_tuple_count(d->T, ntuple_staged_shape(ntuple_shape(d->T, d->L, d->cells), d->S, d->thr), f);
-    else
-        with_tuple_count(d->T, ntuple_shape(d->T, d->L, d->cells), f);
-}
 
 // f(item) for every item of a source.  order 0: ascending, through the header's loop; 1: descending; 2: the residues mod 7
 // one after the other, each through the header's loop with stride 7 -- a lane's walk with a grid of 7
@@ -70,7 +29,7 @@ template <class Items>
 int update_items(const Items &items, const int64_t *delta, uint32_t lr_shift, uint32_t form, uint32_t order, const Desc *d, int32_t *weights,
                  int64_t *err, int64_t *mag)
 {
-    if (!desc_ok(d) || lr_shift > kNtupleMaxShift || form > 3 || order > 2)
+    if (!desc_ok(d, 2) || lr_shift > kNtupleMaxShift || form > 3 || order > 2)
         return -1;
     uint32_t *w = reinterpret_cast<uint32_t *>(weights);
     uint64_t *e = reinterpret_cast<uint64_t *>(err), *a = reinterpret_cast<uint64_t *>(mag);

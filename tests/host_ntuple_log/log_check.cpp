@@ -4,70 +4,7 @@
 // carry before its first move, the record kept over the M moves and stored once, the episode counts per launch; in log_delta
 // one lane per board, the values behind the flags that ask for them.  All three shape types.
 // tests/test_ntuple_log_host.py compares both with tests/ntuple_log_ref.py.  Not part of the product.
-#define G2048_HOST_CHECK 1
-#include "../../gym-2048_amd/csrc/g2048_device.h"
-
-#include <cstring>
-#include <type_traits>
-#include <vector>
-
-using namespace g2048;
-
-namespace {
-
-const uint32_t kLut[32] = {G2048_MOVE_LUT_WORDS};
-
-struct HostTables { // what LdsTables is on the device (g2048_kernels.hip)
-    MoveSel move_sel(uint32_t action) const
-    {
-        const uint32_t *r = kLut + 8 * (action & 3u);
-        return MoveSel{r[0], r[1], r[2], r[3], r[4], r[5]};
-    }
-    Board onehot_cell(uint32_t p) const
-    {
-        return Board{{onehot_cell_word(p, 0), onehot_cell_word(p, 1), onehot_cell_word(p, 2), onehot_cell_word(p, 3)}};
-    }
-};
-
-// the network a test describes (ctypes: ntuple_play_helpers.Desc, the struct of tests/host_ntuple_play)
-struct Desc {
-    uint32_t T, L, F, S, kind;
-    uint16_t thr[8]; // the first S - 1 used
-    uint8_t cells[8][6];
-};
-
-bool desc_ok(const Desc *d)
-{
-    return d && d->T >= 1 && d->T <= kNtupleMaxTuples && d->L >= 1 && d->L <= kNtupleMaxLen && d->F <= kNtupleMaxFrac && d->S >= 1 &&
-           d->S <= kNtupleMaxStages && d->kind <= 2 && (d->kind != 0 || d->S == 1);
-}
-
-template <uint32_t T = 1, class F> void with_tuples(const Desc *d, F &&f)
-{
-    if constexpr (T <= kNtupleMaxTuples) {
-        if (d->T != T)
-            return with_tuples<T + 1>(d, f);
-        const std::integral_constant<uint32_t, T> tc;
-        const NtupleShape sh = ntuple_shape(d->T, d->L, d->cells);
-        if (d->kind == 0)
-            f(tc, sh);
-        else if (d->kind == 1)
-            f(tc, ntuple_staged_shape(sh, d->S, d->thr));
-        else
-            f(tc, ntuple_mixed_shape(d->T, d->L, d->cells, d->S, d->thr));
-    }
-}
-
-Board load16(const uint8_t *p)
-{
-    Board b;
-    memcpy(b.r, p, 16);
-    return b;
-}
-
-constexpr uint64_t kBlockLanes = 256; // kBlock of g2048_kernels.h
-
-} // namespace
+#include "../host_common/ntuple_host.h"
 
 extern "C" {
 
@@ -86,7 +23,7 @@ bool log_ok(const HostLog *lg) { return lg && lg->depth >= 1 && lg->depth <= kNt
 int64_t log_check_play(uint8_t *records, uint64_t n, uint64_t seed, uint64_t t_first, uint64_t board_offset, uint32_t max_exp, const Desc *d,
                        const int32_t *weights, const HostLog *lg, uint8_t *last_records, uint64_t *counts)
 {
-    if (!desc_ok(d) || n == 0 || !log_ok(lg) || !last_records || !counts)
+    if (!desc_ok(d, 2) || n == 0 || !log_ok(lg) || !last_records || !counts)
         return -1;
     const HostTables tb;
     const uint64_t lanes = (n + kBlockLanes - 1) / kBlockLanes * kBlockLanes;
@@ -96,7 +33,7 @@ int64_t log_check_play(uint8_t *records, uint64_t n, uint64_t seed, uint64_t t_f
         for (uint64_t i_raw = 0; i_raw < lanes; ++i_raw) {
             const bool valid = i_raw < n;
             const uint64_t i = valid ? i_raw : n - 1; // lane_of
-            Board rec = load16(records + 16 * i);
+            Board rec = load_raw(records + 16 * i);
             // (a lane past the end works on board n - 1 as that board's own lane left it or will find it: it must write nothing.
             //  The record it loads may already be the stepped one here, where lanes run one after the other; it is dropped.)
             if (!valid)
@@ -133,7 +70,7 @@ int64_t log_check_play(uint8_t *records, uint64_t n, uint64_t seed, uint64_t t_f
 // NULL, += the ntuple_value calls made: what the flags skip is not evaluated.
 int64_t log_check_delta(uint64_t n, const Desc *d, const int32_t *weights, const HostLog *lg, uint32_t m, int64_t *delta, uint64_t *evaluations)
 {
-    if (!desc_ok(d) || n == 0 || !log_ok(lg) || m >= lg->depth || !delta)
+    if (!desc_ok(d, 2) || n == 0 || !log_ok(lg) || m >= lg->depth || !delta)
         return -1;
     const uint64_t lanes = (n + kBlockLanes - 1) / kBlockLanes * kBlockLanes;
     with_tuples(d, [&](auto tc, const auto &sh) {
@@ -145,13 +82,13 @@ int64_t log_check_delta(uint64_t n, const Desc *d, const int32_t *weights, const
             const uint32_t f = lg->flag[self + i], f1 = lg->flag[next + i];
             int64_t v0 = 0, v1 = 0, gain1 = 0;
             if (ntuple_log_reads_self(f, f1)) {
-                v0 = ntuple_value<T>(ntuple_pack(load16(lg->after + 16 * (self + i))), sh, weights);
+                v0 = ntuple_value<T>(ntuple_pack(load_raw(lg->after + 16 * (self + i))), sh, weights);
                 if (evaluations)
                     *evaluations += 1;
             }
             if (ntuple_log_reads_next(f, f1)) {
                 gain1 = lg->gain[next + i];
-                v1 = ntuple_value<T>(ntuple_pack(load16(lg->after + 16 * (next + i))), sh, weights);
+                v1 = ntuple_value<T>(ntuple_pack(load_raw(lg->after + 16 * (next + i))), sh, weights);
                 if (evaluations)
                     *evaluations += 1;
             }

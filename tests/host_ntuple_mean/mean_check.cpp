@@ -3,48 +3,9 @@
 // ntuple_item_mean_apply -- what the two kernels run -- with plain adds for the atomic adds and a plain read-then-zero for the
 // atomic exchanges, over any of the three shape types and in any item order.
 // tests/test_ntuple_mean_host.py compares it with tests/ntuple_mean_ref.py.  Not part of the product.
-#define G2048_HOST_CHECK 1
-#include "../../gym-2048_amd/csrc/g2048_device.h"
-
-#include <type_traits>
-
-using namespace g2048;
+#include "../host_common/ntuple_host.h"
 
 namespace {
-
-// the network a test describes (ctypes: ntuple_mean_helpers.Desc): a g2048_ntuple_staged_net without its pointers
-struct Desc {
-    uint32_t T, L, F, S; // L = tuple_len: how many entries of cells[t][] are read; a list may end early with kNtupleEnd
-    uint32_t kind;       // 0: NtupleShape (S == 1), 1: NtupleStagedShape, 2: NtupleMixedShape
-    uint16_t thr[8];     // the first S - 1 used
-    uint8_t cells[8][6];
-};
-
-bool desc_ok(const Desc *d)
-{
-    return d && d->T >= 1 && d->T <= kNtupleMaxTuples && d->L >= 1 && d->L <= kNtupleMaxLen && d->F <= kNtupleMaxFrac && d->S >= 1 &&
-           d->S <= kNtupleMaxStages && d->kind <= 2 && (d->kind != 0 || d->S == 1);
-}
-
-template <uint32_t T = 1, class Shape, class F> void with_tuple_count(uint32_t n_tuples, const Shape &sh, F &&f)
-{
-    if constexpr (T <= kNtupleMaxTuples) {
-        if (n_tuples == T)
-            f(std::integral_constant<uint32_t, T>(), sh);
-        else
-            with_tuple_count<T + 1>(n_tuples, sh, f);
-    }
-}
-
-template <class F> void with_tuples(const Desc *d, F &&f)
-{
-    if (d->kind == 2)
-        with_tuple_count(d->T, ntuple_mixed_shape(d->T, d->L, d->cells, d->S, d->thr), f);
-    else if (d->kind == 1)
-        with_tuple_count(d->T, ntuple_staged_shape(ntuple_shape(d->T, d->L, d->cells), d->S, d->thr), f);
-    else
-        with_tuple_count(d->T, ntuple_shape(d->T, d->L, d->cells), f);
-}
 
 // f(item) for every item of a source: through the header's loop, or in the caller's order (a permutation of 0..size-1)
 template <class Items, class F> bool visit(const Items &items, const uint64_t *order, uint64_t n_order, F f)
@@ -67,7 +28,7 @@ template <class Items>
 int update_items(const Items &items, const int64_t *delta, uint32_t lr_shift, uint32_t phases, const Desc *d, int32_t *weights, int64_t *sum,
                  uint32_t *count, const uint64_t *order, uint64_t n_order)
 {
-    if (!desc_ok(d) || lr_shift > kNtupleMaxShift || phases < 1 || phases > 3 || items.size() >= (1ull << 29))
+    if (!desc_ok(d, 2) || lr_shift > kNtupleMaxShift || phases < 1 || phases > 3 || items.size() >= (1ull << 29))
         return -1;
     uint32_t *w = reinterpret_cast<uint32_t *>(weights);
     uint64_t *s = reinterpret_cast<uint64_t *>(sum);

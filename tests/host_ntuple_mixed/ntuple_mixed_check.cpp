@@ -3,66 +3,20 @@
 // updates, staged or not, and the offsets of every look-up.  The updates run the header's item sources, item loop and
 // per-item operations -- what the update kernels run -- with wrapping adds for the atomic ones.
 // tests/test_ntuple_mixed_host.py compares it with tests/ntuple_mixed_ref.py.  Not part of the product.
-#define G2048_HOST_CHECK 1
-#include "../../gym-2048_amd/csrc/g2048_device.h"
-
-#include <cstring>
-#include <type_traits>
-
-using namespace g2048;
+#include "../host_common/ntuple_host.h"
 
 namespace {
 
-const uint32_t kLut[32] = {G2048_MOVE_LUT_WORDS};
-
-struct HostTables { // what LdsTables is on the device (g2048_kernels.hip)
-    MoveSel move_sel(uint32_t action) const
-    {
-        const uint32_t *r = kLut + 8 * (action & 3u);
-        return MoveSel{r[0], r[1], r[2], r[3], r[4], r[5]};
-    }
-};
-
-// plain cells, taken mod 32 as input_cells<true> takes them on the device
-Board load_cells(const uint8_t *p)
-{
-    Board b;
-    memcpy(b.r, p, 16);
-    for (uint32_t &r : b.r)
-        r &= 0x1f1f1f1fu;
-    return b;
-}
-
-// the network a test describes (ctypes: test_ntuple_mixed_host.Desc): a g2048_ntuple_staged_net without its pointers
-struct Desc {
-    uint32_t T, L, F, S; // L = tuple_len: how many entries of cells[t][] are read; a list may end early with kNtupleEnd
-    uint16_t thr[8];     // the first S - 1 used
-    uint8_t cells[8][6];
-};
-
-bool desc_ok(const Desc *d)
-{
-    return d && d->T >= 1 && d->T <= kNtupleMaxTuples && d->L >= 1 && d->L <= kNtupleMaxLen && d->F <= kNtupleMaxFrac && d->S >= 1 &&
-           d->S <= kNtupleMaxStages;
-}
+// every call here instantiates NtupleMixedShape, whatever the lengths of the lists: kind 2 alone
+bool mixed_ok(const Desc *d) { return desc_ok(d, 2) && d->kind == 2; }
 
 NtupleMixedShape shape_of(const Desc *d) { return ntuple_mixed_shape(d->T, d->L, d->cells, d->S, d->thr); }
-
-template <uint32_t T = 1, class F> void with_tuples(const Desc *d, F &&f)
-{
-    if constexpr (T <= kNtupleMaxTuples) {
-        if (d->T == T)
-            f(std::integral_constant<uint32_t, T>(), shape_of(d));
-        else
-            with_tuples<T + 1>(d, f);
-    }
-}
 
 template <class Items>
 int update_items(const Items &items, const int64_t *delta, uint32_t lr_shift, uint32_t mode, const Desc *d, int32_t *weights, int64_t *err,
                  int64_t *mag)
 {
-    if (!desc_ok(d) || lr_shift > kNtupleMaxShift || mode > 3)
+    if (!mixed_ok(d) || lr_shift > kNtupleMaxShift || mode > 3)
         return -1;
     uint32_t *w = reinterpret_cast<uint32_t *>(weights);
     uint64_t *e = reinterpret_cast<uint64_t *>(err), *a = reinterpret_cast<uint64_t *>(mag);
@@ -72,7 +26,7 @@ int update_items(const Items &items, const int64_t *delta, uint32_t lr_shift, ui
         a[off] += m;
     };
     using Item = typename Items::Item;
-    with_tuples(d, [&](auto tc, const NtupleMixedShape &sh) {
+    with_tuples(d, [&](auto tc, const auto &sh) {
         constexpr uint32_t T = decltype(tc)::value;
         if (mode == 0)
             ntuple_for_items(items, 0, 1, [&](Item it) { ntuple_item_update<T>(items, delta, it, lr_shift, sh, add); });
@@ -93,7 +47,7 @@ extern "C" {
 // the shape's own numbers: is_mixed, W, len[8] (from the list words' top byte), base[8]
 int ntuple_mixed_check_shape(const Desc *d, uint32_t *is_mixed, uint32_t *n_weights, uint32_t *len, uint32_t *base)
 {
-    if (!desc_ok(d))
+    if (!mixed_ok(d))
         return -1;
     const NtupleMixedShape sh = shape_of(d);
     *is_mixed = ntuple_is_mixed(d->T, d->L, d->cells) ? 1u : 0u;
@@ -108,7 +62,7 @@ int ntuple_mixed_check_shape(const Desc *d, uint32_t *is_mixed, uint32_t *n_weig
 // the element every look-up reads: out[n][8][T] = ntuple_offset(packed, sh, s, t, ntuple_stage_base(packed, sh))
 int ntuple_mixed_check_offsets(const uint8_t *boards, uint64_t n, const Desc *d, uint32_t *out)
 {
-    if (!desc_ok(d))
+    if (!mixed_ok(d))
         return -1;
     const NtupleMixedShape sh = shape_of(d);
     for (uint64_t i = 0; i < n; ++i) {
@@ -123,9 +77,9 @@ int ntuple_mixed_check_offsets(const uint8_t *boards, uint64_t n, const Desc *d,
 
 int ntuple_mixed_check_values(const uint8_t *boards, uint64_t n, const Desc *d, const int32_t *weights, int64_t *v)
 {
-    if (!desc_ok(d))
+    if (!mixed_ok(d))
         return -1;
-    with_tuples(d, [&](auto tc, const NtupleMixedShape &sh) {
+    with_tuples(d, [&](auto tc, const auto &sh) {
         for (uint64_t i = 0; i < n; ++i)
             v[i] = ntuple_value<decltype(tc)::value>(ntuple_pack(load_cells(boards + 16 * i)), sh, weights);
     });
@@ -135,9 +89,9 @@ int ntuple_mixed_check_values(const uint8_t *boards, uint64_t n, const Desc *d, 
 int ntuple_mixed_check_evaluate(const uint8_t *boards, uint64_t n, const Desc *d, const int32_t *weights, int64_t *value, uint8_t *action,
                                 int64_t *best, uint8_t *after, int64_t *after_value)
 {
-    if (!desc_ok(d))
+    if (!mixed_ok(d))
         return -1;
-    with_tuples(d, [&](auto tc, const NtupleMixedShape &sh) {
+    with_tuples(d, [&](auto tc, const auto &sh) {
         for (uint64_t i = 0; i < n; ++i) {
             const NtupleRoot r = ntuple_root<decltype(tc)::value>(load_cells(boards + 16 * i), sh, d->F, weights, HostTables());
             memcpy(value + 4 * i, r.q, sizeof(r.q));
@@ -153,9 +107,9 @@ int ntuple_mixed_check_evaluate(const uint8_t *boards, uint64_t n, const Desc *d
 int ntuple_mixed_check_search(const uint8_t *boards, uint64_t n, uint32_t depth, const Desc *d, const int32_t *weights, uint8_t *action,
                               int64_t *value)
 {
-    if (!desc_ok(d) || depth < 1 || depth > kNtupleSearchMaxDepth)
+    if (!mixed_ok(d) || depth < 1 || depth > kNtupleSearchMaxDepth)
         return -1;
-    with_tuples(d, [&](auto tc, const NtupleMixedShape &sh) {
+    with_tuples(d, [&](auto tc, const auto &sh) {
         constexpr uint32_t T = decltype(tc)::value;
         for (uint64_t i = 0; i < n; ++i) {
             const Board b = load_cells(boards + 16 * i);

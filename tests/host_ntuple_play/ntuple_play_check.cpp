@@ -2,68 +2,7 @@
 // (-DG2048_HOST_CHECK) on one thread, inside the loop ntuple_play_kernel runs around it: the budget test, the step, the
 // episode end (terminal record, histogram), reset_record, the budget's decrement.  All three shape types.
 // tests/test_ntuple_play_host.py compares it with tests/ntuple_play_ref.py.  Not part of the product.
-#define G2048_HOST_CHECK 1
-#include "../../gym-2048_amd/csrc/g2048_device.h"
-
-#include <cstring>
-#include <type_traits>
-
-using namespace g2048;
-
-namespace {
-
-const uint32_t kLut[32] = {G2048_MOVE_LUT_WORDS};
-
-struct HostTables { // what LdsTables is on the device (g2048_kernels.hip)
-    MoveSel move_sel(uint32_t action) const
-    {
-        const uint32_t *r = kLut + 8 * (action & 3u);
-        return MoveSel{r[0], r[1], r[2], r[3], r[4], r[5]};
-    }
-    Board onehot_cell(uint32_t p) const
-    {
-        return Board{{onehot_cell_word(p, 0), onehot_cell_word(p, 1), onehot_cell_word(p, 2), onehot_cell_word(p, 3)}};
-    }
-};
-
-// the network a test describes (ctypes: ntuple_play_helpers.Desc): a g2048_ntuple_staged_net without its pointers, and the
-// shape type to instantiate: 0 NtupleShape, 1 NtupleStagedShape, 2 NtupleMixedShape
-struct Desc {
-    uint32_t T, L, F, S, kind;
-    uint16_t thr[8]; // the first S - 1 used
-    uint8_t cells[8][6];
-};
-
-bool desc_ok(const Desc *d)
-{
-    return d && d->T >= 1 && d->T <= kNtupleMaxTuples && d->L >= 1 && d->L <= kNtupleMaxLen && d->F <= kNtupleMaxFrac && d->S >= 1 &&
-           d->S <= kNtupleMaxStages && d->kind <= 2 && (d->kind != 0 || d->S == 1);
-}
-
-template <uint32_t T = 1, class F> void with_tuples(const Desc *d, F &&f)
-{
-    if constexpr (T <= kNtupleMaxTuples) {
-        if (d->T != T)
-            return with_tuples<T + 1>(d, f);
-        const std::integral_constant<uint32_t, T> tc;
-        const NtupleShape sh = ntuple_shape(d->T, d->L, d->cells);
-        if (d->kind == 0)
-            f(tc, sh);
-        else if (d->kind == 1)
-            f(tc, ntuple_staged_shape(sh, d->S, d->thr));
-        else
-            f(tc, ntuple_mixed_shape(d->T, d->L, d->cells, d->S, d->thr));
-    }
-}
-
-Board load_record(const uint8_t *p)
-{
-    Board b;
-    memcpy(b.r, p, 16);
-    return b;
-}
-
-} // namespace
+#include "../host_common/ntuple_host.h"
 
 extern "C" {
 
@@ -75,13 +14,13 @@ int ntuple_play_check_run(uint8_t *records, uint64_t n, uint64_t seed, uint64_t 
                           uint8_t *action, uint8_t *last_records, uint64_t *episodes, uint64_t *return_sum, uint64_t *gain_sum,
                           uint64_t *hist, uint64_t *moves)
 {
-    if (!desc_ok(d))
+    if (!desc_ok(d, 2))
         return -1;
     const HostTables tb;
     with_tuples(d, [&](auto tc, const auto &sh) {
         constexpr uint32_t T = decltype(tc)::value;
         for (uint64_t i = 0; i < n; ++i) {
-            Board rec = load_record(records + 16 * i);
+            Board rec = load_raw(records + 16 * i);
             uint32_t left = games_left ? games_left[i] : 1u;
             uint64_t t = t_first;
             for (uint32_t j = 0; j < k_steps; ++j, ++t) {

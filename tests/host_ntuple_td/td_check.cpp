@@ -3,72 +3,9 @@
 // lanes past the end on board n - 1 and writing nothing, the episode counts per launch), and, as its check, the same step
 // composed by hand of ntuple_root, ntuple_play_step, reset_record and ntuple_root.  All three shape types.
 // tests/test_ntuple_td_host.py compares the two with each other and with tests/ntuple_play_ref.py.  Not part of the product.
-#define G2048_HOST_CHECK 1
-#include "../../gym-2048_amd/csrc/g2048_device.h"
+#include "../host_common/ntuple_host.h"
 
-#include <cstring>
-#include <type_traits>
 #include <vector>
-
-using namespace g2048;
-
-namespace {
-
-const uint32_t kLut[32] = {G2048_MOVE_LUT_WORDS};
-
-struct HostTables { // what LdsTables is on the device (g2048_kernels.hip)
-    MoveSel move_sel(uint32_t action) const
-    {
-        const uint32_t *r = kLut + 8 * (action & 3u);
-        return MoveSel{r[0], r[1], r[2], r[3], r[4], r[5]};
-    }
-    Board onehot_cell(uint32_t p) const
-    {
-        return Board{{onehot_cell_word(p, 0), onehot_cell_word(p, 1), onehot_cell_word(p, 2), onehot_cell_word(p, 3)}};
-    }
-};
-
-// the network a test describes (ctypes: ntuple_play_helpers.Desc, the struct of tests/host_ntuple_play): a
-// g2048_ntuple_staged_net without its pointers, and the shape type to instantiate: 0 NtupleShape, 1 NtupleStagedShape,
-// 2 NtupleMixedShape
-struct Desc {
-    uint32_t T, L, F, S, kind;
-    uint16_t thr[8]; // the first S - 1 used
-    uint8_t cells[8][6];
-};
-
-bool desc_ok(const Desc *d)
-{
-    return d && d->T >= 1 && d->T <= kNtupleMaxTuples && d->L >= 1 && d->L <= kNtupleMaxLen && d->F <= kNtupleMaxFrac && d->S >= 1 &&
-           d->S <= kNtupleMaxStages && d->kind <= 2 && (d->kind != 0 || d->S == 1);
-}
-
-template <uint32_t T = 1, class F> void with_tuples(const Desc *d, F &&f)
-{
-    if constexpr (T <= kNtupleMaxTuples) {
-        if (d->T != T)
-            return with_tuples<T + 1>(d, f);
-        const std::integral_constant<uint32_t, T> tc;
-        const NtupleShape sh = ntuple_shape(d->T, d->L, d->cells);
-        if (d->kind == 0)
-            f(tc, sh);
-        else if (d->kind == 1)
-            f(tc, ntuple_staged_shape(sh, d->S, d->thr));
-        else
-            f(tc, ntuple_mixed_shape(d->T, d->L, d->cells, d->S, d->thr));
-    }
-}
-
-Board load_record(const uint8_t *p)
-{
-    Board b;
-    memcpy(b.r, p, 16);
-    return b;
-}
-
-constexpr uint64_t kBlockLanes = 256; // kBlock of g2048_kernels.h
-
-} // namespace
 
 extern "C" {
 
@@ -88,7 +25,7 @@ struct TdOut {
 int64_t td_check_fused(uint8_t *records, uint64_t n, uint64_t seed, uint64_t t, uint64_t board_offset, uint32_t max_exp, const Desc *d,
                        const int32_t *weights, const TdOut *out)
 {
-    if (!desc_ok(d) || n == 0 || !out)
+    if (!desc_ok(d, 2) || n == 0 || !out)
         return -1;
     const HostTables tb;
     const std::vector<uint8_t> loaded(records, records + 16 * n); // every lane loads before any lane stores
@@ -98,7 +35,7 @@ int64_t td_check_fused(uint8_t *records, uint64_t n, uint64_t seed, uint64_t t, 
         for (uint64_t i_raw = 0; i_raw < lanes; ++i_raw) {
             const bool valid = i_raw < n;
             const uint64_t i = valid ? i_raw : n - 1; // lane_of
-            Board rec = load_record(loaded.data() + 16 * i);
+            Board rec = load_raw(loaded.data() + 16 * i);
             const NtupleTdOut o =
                 ntuple_td_step<T>(rec, t, static_cast<uint32_t>(board_offset + i), static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32),
                                   sh, d->F, weights, max_exp, tb, [&](const StepOut &st, const Board &terminal) {
@@ -128,14 +65,14 @@ int64_t td_check_fused(uint8_t *records, uint64_t n, uint64_t seed, uint64_t t, 
 int64_t td_check_composed(uint8_t *records, uint64_t n, uint64_t seed, uint64_t t, uint64_t board_offset, uint32_t max_exp, const Desc *d,
                           const int32_t *weights, const TdOut *out)
 {
-    if (!desc_ok(d) || n == 0 || !out)
+    if (!desc_ok(d, 2) || n == 0 || !out)
         return -1;
     const HostTables tb;
     int64_t rc = static_cast<int64_t>(n);
     with_tuples(d, [&](auto tc, const auto &sh) {
         constexpr uint32_t T = decltype(tc)::value;
         for (uint64_t i = 0; i < n; ++i) {
-            Board rec = load_record(records + 16 * i);
+            Board rec = load_raw(records + 16 * i);
             const Board before = rec;
             const NtupleRoot r0 = ntuple_root<T>(record_cells(rec), sh, d->F, weights, tb);
             Words w;

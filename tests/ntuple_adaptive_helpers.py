@@ -3,8 +3,6 @@ adaptive search code (tests/host_ntuple_adaptive/adaptive_check.cpp, g++) behind
 GPU tests share (computed once), the composition "depth k + 1 from depth-k values", the 17 boards with 0..16 empty cells and
 their mixed schedule, and the per-move composition of an AdaptivePlayer game.  A plain module, like ntuple_deep_helpers."""
 import ctypes as C
-import os
-import subprocess
 import types
 
 import numpy as np
@@ -12,11 +10,11 @@ import numpy as np
 import ntuple_ref as ref
 import ntuple_search_ref as sref
 from analysis_helpers import ONE_LEGAL, TERMINAL
-from ntuple_deep_helpers import Desc, ROOT, cached, compose_depth3, desc_of, near_full, w32_of
+from host_build import Desc, build_host
+from ntuple_deep_helpers import cached, compose_depth3, desc_of, near_full, w32_of
 from ntuple_helpers import TUPLES_8x4, random_net
 from ntuple_search_helpers import PAIR_ONLY
 
-HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple_adaptive")
 ILLEGAL = ref.ILLEGAL
 MAX_DEPTH, SKIPPED = 4, 0xff
 
@@ -76,11 +74,7 @@ def rows_at(schedule, boards):
 # ------------------------------------------------------------------------------------------------ the host build
 def build_host_adaptive(force=False):
     """g++ build of tests/host_ntuple_adaptive (the device header's adaptive search code compiled for the host; tests only)."""
-    so, src = os.path.join(HOST_DIR, "libadaptive_check.so"), os.path.join(HOST_DIR, "adaptive_check.cpp")
-    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
-    return so
+    return build_host("host_ntuple_adaptive", "adaptive_check.cpp", "libadaptive_check.so", force)
 
 
 def load_host_adaptive():

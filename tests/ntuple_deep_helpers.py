@@ -3,22 +3,20 @@ search code (tests/host_ntuple_deep/deep_check.cpp, g++) behind ctypes, the refe
 (computed once), the composition of depth 3 from depth-2 calls, the boards, networks and anchored composition of the value-extremes
 tests, and the per-move composition of a DeepPlayer game.  A plain module, like ntuple_helpers."""
 import ctypes as C
-import os
-import subprocess
 import types
 
 import numpy as np
 
+import host_build
 import ntuple_mixed_ref as mref
 import ntuple_ref as ref
 import ntuple_search_ref as sref
 import ntuple_staged_ref as stref
 from analysis_helpers import mid_game
+from host_build import Desc, raw_desc
 from ntuple_helpers import TUPLES_2x6, TUPLES_8x4, random_net
 from ntuple_staged_helpers import LOW_THR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple_deep")
 ILLEGAL = ref.ILLEGAL
 _cache = {}
 
@@ -324,35 +322,13 @@ def engine_with(g, boards, seed=3):
 
 
 # ------------------------------------------------------------------------------------------------ the host build
-class Desc(C.Structure):
-    """struct Desc of deep_check.cpp."""
-    _fields_ = [("T", C.c_uint32), ("L", C.c_uint32), ("F", C.c_uint32), ("S", C.c_uint32), ("kind", C.c_uint32),
-                ("thr", C.c_uint16 * 8), ("cells", (C.c_uint8 * 6) * 8)]
-
-
 def desc_of(net):
-    thr, kind = tuple(getattr(net, "thr", ())), kind_of(net)
-    d = Desc(len(net.tuples), max(mref.lens(net.tuples)), net.frac_bits, len(thr) + 1, kind)
-    d.thr[:len(thr)] = thr
-    cells = mref.cells_of(net.tuples)
-    for t in range(8):
-        for k in range(6):
-            d.cells[t][k] = int(cells[t, k])
-    return C.byref(d)
-
-
-def raw_desc(T, L, F=10, S=1, kind=0):
-    """A description by its numbers alone, in or out of range (no cells: for calls that must be refused)."""
-    return C.byref(Desc(T, L, F, S, kind))
+    return host_build.desc_of(net, kind_of(net))
 
 
 def build_host_deep(force=False):
     """g++ build of tests/host_ntuple_deep (the device header's deep search code compiled for the host; tests only)."""
-    so, src = os.path.join(HOST_DIR, "libdeep_check.so"), os.path.join(HOST_DIR, "deep_check.cpp")
-    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
-    return so
+    return host_build.build_host("host_ntuple_deep", "deep_check.cpp", "libdeep_check.so", force)
 
 
 def load_host_deep():

@@ -2,42 +2,17 @@
 g++) behind ctypes -- the push and the item loop over NtupleDelayItems on a copy of a reference ring.  A plain module, like
 ntuple_helpers."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import ntuple_mixed_ref as mref
+from host_build import Desc, build_host, desc_of
 from ntuple_mixed_helpers import _tables
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple_delay")
 ORDERS = {"ascending": 0, "descending": 1, "stride 7": 2}
 
 
-class Desc(C.Structure):
-    """struct Desc of delay_check.cpp."""
-    _fields_ = [("T", C.c_uint32), ("L", C.c_uint32), ("F", C.c_uint32), ("S", C.c_uint32), ("kind", C.c_uint32),
-                ("thr", C.c_uint16 * 8), ("cells", (C.c_uint8 * 6) * 8)]
-
-
-def desc_of(net, kind):
-    """The description of a reference network; kind 0 / 1 / 2 = NtupleShape (S = 1) / NtupleStagedShape / NtupleMixedShape."""
-    d = Desc(len(net.tuples), max(mref.lens(net.tuples)), net.frac_bits, len(net.thr) + 1, kind)
-    d.thr[:len(net.thr)] = net.thr
-    cells = mref.cells_of(net.tuples)
-    for t in range(8):
-        for k in range(6):
-            d.cells[t][k] = int(cells[t, k])
-    return C.byref(d)
-
-
 def load_host_delay():
-    so, src = os.path.join(HOST_DIR, "libdelay_check.so"), os.path.join(HOST_DIR, "delay_check.cpp")
-    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
-    lib = C.CDLL(so)
+    lib = C.CDLL(build_host("host_ntuple_delay", "delay_check.cpp", "libdelay_check.so"))
     P, u32, u64, D = C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(Desc)
     lib.delay_check_due.restype, lib.delay_check_due.argtypes = u32, [u32, u32, u32, u32]
     lib.delay_check_push.restype, lib.delay_check_push.argtypes = C.c_int, [P, P, P, P, u64, u32, u32, P, P, P, u32, P]

@@ -2,15 +2,11 @@
 behind ctypes -- network, search, TD, TC and trace updates, stages -- the network shapes the tests use, and random weights.
 A plain module, like analysis_helpers."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import ntuple_ref as ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple")
+from host_build import Desc, build_host, desc_of, raw_desc
 
 TUPLES_17x4 = ((0, 1, 2, 3), (4, 5, 6, 7), (0, 1, 4, 5), (1, 2, 5, 6), (5, 6, 9, 10))
 TUPLES_4x6 = ((0, 1, 2, 3, 4, 5), (4, 5, 6, 7, 8, 9), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10))
@@ -35,36 +31,9 @@ def symmetry_images(cells):
     return out
 
 
-class Desc(C.Structure):
-    """struct Desc of ntuple_check.cpp: the network of a call, and the shape type the call instantiates."""
-    _fields_ = [("T", C.c_uint32), ("L", C.c_uint32), ("F", C.c_uint32), ("S", C.c_uint32), ("staged", C.c_uint32),
-                ("thr", C.c_uint16 * 8), ("cells", (C.c_uint8 * 6) * 8)]
-
-
-def desc_of(net):
-    """The description of an ntuple_ref.Net (the NtupleShape code) or an ntuple_staged_ref.StagedNet (the NtupleStagedShape
-    code, S = 1 included)."""
-    thr = getattr(net, "thr", None)
-    d = Desc(len(net.tuples), len(net.tuples[0]), net.frac_bits, 1 if thr is None else len(thr) + 1, 0 if thr is None else 1)
-    d.thr[:len(thr or ())] = thr or ()
-    for t, cells in enumerate(net.tuples):
-        for k, c in enumerate(cells):
-            d.cells[t][k] = c
-    return C.byref(d)
-
-
-def raw_desc(T, L, F=10, S=1, staged=0):
-    """A description by its numbers alone, in or out of range (no cells: for calls that must be refused)."""
-    return C.byref(Desc(T, L, F, S, staged))
-
-
 def build_host_ntuple(force=False):
     """g++ build of tests/host_ntuple (the device header's n-tuple code compiled for the host; tests only)."""
-    so, src = os.path.join(HOST_DIR, "libntuple_check.so"), os.path.join(HOST_DIR, "ntuple_check.cpp")
-    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
-    return so
+    return build_host("host_ntuple", "ntuple_check.cpp", "libntuple_check.so", force)
 
 
 def load_host_ntuple():

@@ -3,18 +3,15 @@ g2048_ntuple_log_train): the host build of the device heade
 lane structure (tests/host_ntuple_log, g++) behind ctypes, and what the tests assert from the reference alone before they
 compare anything.  A plain module, like ntuple_td_helpers, whose boards and networks it reuses."""
 import ctypes as C
-import os
-import subprocess
 import types
 
 import numpy as np
 
 import late_game as lg
 import ntuple_log_ref as lref
-from ntuple_play_helpers import ENGINEERED_CLOCK, Desc
+from host_build import Desc, build_host
+from ntuple_play_helpers import ENGINEERED_CLOCK
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple_log")
 K_BLOCK = 256
 
 
@@ -25,11 +22,7 @@ class HostLog(C.Structure):
 
 def build_host_log(force=False):
     """g++ build of tests/host_ntuple_log (the device header's play_log step and delta rule compiled for the host; tests only)."""
-    so, src = os.path.join(HOST_DIR, "liblog_check.so"), os.path.join(HOST_DIR, "log_check.cpp")
-    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
-    return so
+    return build_host("host_ntuple_log", "log_check.cpp", "liblog_check.so", force)
 
 
 def load_host_log():

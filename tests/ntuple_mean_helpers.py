@@ -2,50 +2,31 @@
 behind ctypes, the comparison of the three tables, a vectorised numpy form of the reference for batches of thousands of boards,
 and the device's side of a reference network.  A plain module, like ntuple_mixed_helpers."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import host_build
 import ntuple_mean_ref as meanref
 import ntuple_mixed_ref as mref
 import ntuple_staged_ref as sref
 import ntuple_tc_ref as tcref
 import ntuple_trace_ref as tref
+from host_build import Desc
 from ntuple_tc_helpers import assert_tables_equal
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple_mean")
 NAMES = ("weights", "sum", "count")
 KIND = {"uniform": 0, "staged": 1, "mixed": 2}
-
-
-class Desc(C.Structure):
-    """struct Desc of mean_check.cpp."""
-    _fields_ = [("T", C.c_uint32), ("L", C.c_uint32), ("F", C.c_uint32), ("S", C.c_uint32), ("kind", C.c_uint32), ("thr", C.c_uint16 * 8),
-                ("cells", (C.c_uint8 * 6) * 8)]
 
 
 def desc_of(net, kind=2):
     """The description of a reference network (ntuple_mixed_ref.mixed_net): END-padded lists up to the longest one.  kind 0 / 1
     (NtupleShape / NtupleStagedShape) are for lists of one length only: there [S][T][16^L] is the compact layout."""
-    lens = mref.lens(net.tuples)
-    assert kind == 2 or len(set(lens)) == 1
-    d = Desc(len(net.tuples), max(lens), net.frac_bits, len(net.thr) + 1, kind)
-    d.thr[:len(net.thr)] = net.thr
-    cells = mref.cells_of(net.tuples)
-    for t in range(8):
-        for k in range(6):
-            d.cells[t][k] = int(cells[t, k])
-    return C.byref(d)
+    assert kind == 2 or len(set(mref.lens(net.tuples))) == 1
+    return host_build.desc_of(net, kind)
 
 
 def build_host_mean(force=False):
-    so, src = os.path.join(HOST_DIR, "libmean_check.so"), os.path.join(HOST_DIR, "mean_check.cpp")
-    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
-    return so
+    return host_build.build_host("host_ntuple_mean", "mean_check.cpp", "libmean_check.so", force)
 
 
 def load_host_mean():

@@ -1,23 +1,21 @@
 """Shared by the mixed-length n-tuple tests: the host build of the header's mixed code (tests/host_ntuple_mixed, g++) behind
 ctypes, and the boards the tests use.  A plain module, like ntuple_helpers."""
 import ctypes as C
-import os
-import subprocess
 import types
 
 import numpy as np
 
+import host_build
 import ntuple_mixed_ref as mref
 import ntuple_staged_ref as sref
 import ntuple_trace_ref as tref
 from analysis_helpers import ONE_LEGAL, TERMINAL, mid_game, mixed_boards
+from host_build import Desc
 from ntuple_search_helpers import PAIR_ONLY
 from ntuple_staged_helpers import small_boards
 from ntuple_tc_helpers import preload
 from ntuple_trace_helpers import push_inputs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple_mixed")
 TIE = np.array([[0] * 5 + [3] + [0] * 10], np.uint8)    # the four afterstates are images of one another: four equal values
 _cache = {}
 
@@ -39,30 +37,14 @@ def near_full_12():
     return cached("near full", lambda: np.concatenate([mid_game(10, 82, max_empty=2), PAIR_ONLY, TERMINAL]))
 
 
-class Desc(C.Structure):
-    """struct Desc of ntuple_mixed_check.cpp."""
-    _fields_ = [("T", C.c_uint32), ("L", C.c_uint32), ("F", C.c_uint32), ("S", C.c_uint32), ("thr", C.c_uint16 * 8),
-                ("cells", (C.c_uint8 * 6) * 8)]
-
-
 def desc_of(net, tuple_len=None):
-    """The description of a reference network (ntuple_mixed_ref.mixed_net): END-padded lists up to tuple_len."""
-    L = max(mref.lens(net.tuples)) if tuple_len is None else tuple_len
-    d = Desc(len(net.tuples), L, net.frac_bits, len(net.thr) + 1)
-    d.thr[:len(net.thr)] = net.thr
-    cells = mref.cells_of(net.tuples, L)
-    for t in range(8):
-        for k in range(6):
-            d.cells[t][k] = int(cells[t, k])
-    return C.byref(d)
+    """The description of a reference network (ntuple_mixed_ref.mixed_net): END-padded lists up to tuple_len, the
+    NtupleMixedShape code."""
+    return host_build.desc_of(net, 2, tuple_len)
 
 
 def build_host_mixed(force=False):
-    so, src = os.path.join(HOST_DIR, "libntuple_mixed_check.so"), os.path.join(HOST_DIR, "ntuple_mixed_check.cpp")
-    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
-    return so
+    return host_build.build_host("host_ntuple_mixed", "ntuple_mixed_check.cpp", "libntuple_mixed_check.so", force)
 
 
 def load_host_mixed():

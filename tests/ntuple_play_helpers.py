@@ -2,8 +2,6 @@
 g++) behind ctypes, the networks the tests play -- each as a reference network, a flat int32 weight array and what an
 ``NTupleNet`` needs -- and the reference traces, computed once.  A plain module, like ntuple_helpers."""
 import ctypes as C
-import os
-import subprocess
 import types
 
 import numpy as np
@@ -13,10 +11,9 @@ import ntuple_mixed_ref as mref
 import ntuple_play_ref as pref
 import ntuple_ref as ref
 import ntuple_staged_ref as sref
+from host_build import Desc, build_host, make_desc
 from ntuple_helpers import TUPLES_8x4, TUPLES_17x4
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple_play")
 THR_3 = (sref.stage_mask(8), sref.stage_mask(32))       # S = 3, low enough that boards cross both inside a short game
 _cache = {}
 
@@ -27,19 +24,9 @@ def cached(key, make):
     return _cache[key]
 
 
-class Desc(C.Structure):
-    """struct Desc of ntuple_play_check.cpp; kind 0 / 1 / 2 = NtupleShape / NtupleStagedShape / NtupleMixedShape."""
-    _fields_ = [("T", C.c_uint32), ("L", C.c_uint32), ("F", C.c_uint32), ("S", C.c_uint32), ("kind", C.c_uint32),
-                ("thr", C.c_uint16 * 8), ("cells", (C.c_uint8 * 6) * 8)]
-
-
 def build_host_play(force=False):
     """g++ build of tests/host_ntuple_play (the device header's fused player compiled for the host; tests only)."""
-    so, src = os.path.join(HOST_DIR, "libntuple_play_check.so"), os.path.join(HOST_DIR, "ntuple_play_check.cpp")
-    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
-    return so
+    return build_host("host_ntuple_play", "ntuple_play_check.cpp", "libntuple_play_check.so", force)
 
 
 def load_host_play():
@@ -52,15 +39,8 @@ def load_host_play():
 
 # ------------------------------------------------------------------------------------------------ the networks
 def _case(name, rnet, w32, tuples, stages, kind):
-    L = max(len(t) for t in tuples)
-    d = Desc(len(tuples), L, rnet.frac_bits, len(stages) + 1, kind)
-    d.thr[:len(stages)] = stages
-    cells = mref.cells_of(tuples, L)
-    for t in range(8):
-        for k in range(6):
-            d.cells[t][k] = int(cells[t, k])
     return types.SimpleNamespace(name=name, rnet=rnet, w32=np.ascontiguousarray(w32.reshape(-1)), tuples=tuples,
-                                 stages=stages if kind else None, desc=d)
+                                 stages=stages if kind else None, desc=make_desc(tuples, rnet.frac_bits, stages, kind))
 
 
 def uniform_case(T=5, seed=301, zero=False):

@@ -3,19 +3,17 @@ reduced search code (tests/host_ntuple_reduced/reduced_check.cpp, g++) behind ct
 with a root tie, the one-level composition with two child depths, the evaluations a search costs counted from the definition,
 and the per-move composition of a ReducedPlayer game.  A plain module, like ntuple_adaptive_helpers."""
 import ctypes as C
-import os
-import subprocess
 import types
 
 import numpy as np
 
 import ntuple_ref as ref
 from analysis_helpers import ONE_LEGAL, TERMINAL, mixed_boards
+from host_build import Desc, build_host
 from ntuple_adaptive_helpers import CRAFTED, named_boards
-from ntuple_deep_helpers import Desc, LOW_STAGE, ROOT, desc_of, w32_of
+from ntuple_deep_helpers import LOW_STAGE, desc_of, w32_of
 from ntuple_search_helpers import PAIR_ONLY, WIDE_FANS
 
-HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple_reduced")
 ILLEGAL = ref.ILLEGAL
 REDUCE4 = (1, 2)
 
@@ -113,11 +111,7 @@ def evaluations(board, depth, R):
 # ------------------------------------------------------------------------------------------------ the host build
 def build_host_reduced(force=False):
     """g++ build of tests/host_ntuple_reduced (the device header's reduced search code compiled for the host; tests only)."""
-    so, src = os.path.join(HOST_DIR, "libreduced_check.so"), os.path.join(HOST_DIR, "reduced_check.cpp")
-    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
-    return so
+    return build_host("host_ntuple_reduced", "reduced_check.cpp", "libreduced_check.so", force)
 
 
 def load_host_reduced():

@@ -3,8 +3,6 @@ fused body in the kernel's lane structure and of the step composed by hand (test
 boards the tests start from, the networks, and the reference: the oracle's step under the pure-Python references' evaluate,
 computed once.  A plain module, like ntuple_play_helpers, whose networks, engineered boards and network description it reuses."""
 import ctypes as C
-import os
-import subprocess
 import types
 
 import numpy as np
@@ -13,11 +11,10 @@ import late_game as lg
 import ntuple_play_ref as pref
 import ntuple_ref as ref
 import ntuple_staged_ref as sref
+from host_build import Desc, build_host
 from ntuple_helpers import TUPLES_17x4
-from ntuple_play_helpers import ENGINEERED_CLOCK, Desc, _case, cached, engineered, mixed_case, staged_case, trace_of, uniform_case
+from ntuple_play_helpers import ENGINEERED_CLOCK, _case, cached, engineered, mixed_case, staged_case, trace_of, uniform_case
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "tests", "host_ntuple_td")
 K_BLOCK = 256
 FIELDS = ("action", "after", "after_value", "best_next", "terminated", "delta")
 
@@ -29,11 +26,7 @@ class TdOut(C.Structure):
 
 def build_host_td(force=False):
     """g++ build of tests/host_ntuple_td (the device header's fused TD step compiled for the host; tests only)."""
-    so, src = os.path.join(HOST_DIR, "libtd_check.so"), os.path.join(HOST_DIR, "td_check.cpp")
-    deps = [src, os.path.join(ROOT, "gym-2048_amd", "csrc", "g2048_device.h")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", so, src])
-    return so
+    return build_host("host_ntuple_td", "td_check.cpp", "libtd_check.so", force)
 
 
 def load_host_td():
