@@ -249,6 +249,21 @@ class CarouselC(C.Structure):
     ]
 
 
+class RestartC(C.Structure):
+    """g2048_restart (include/g2048.h): the rule (stride_log2, capacity, min_span, max_restarts) and the device state of a midpoint
+    restart."""
+    _fields_ = [
+        ("stride_log2", C.c_uint32),
+        ("capacity", C.c_uint32),
+        ("min_span", C.c_uint32),
+        ("max_restarts", C.c_uint32),
+        ("snap", C.c_void_p),
+        ("pos", C.c_void_p),
+        ("start", C.c_void_p),
+        ("restarts", C.c_void_p),
+    ]
+
+
 class Stats(C.Structure):
     """g2048_stats (include/g2048.h)."""
     _fields_ = [
@@ -383,6 +398,14 @@ SIGNATURES = {
     "g2048_carousel_scratch_bytes": (_u64, [_u64]),
     "g2048_carousel_step": (C.c_int, [_E, C.POINTER(CarouselC), C.c_void_p, _S]),
     "g2048_carousel_step_plain": (C.c_int, [C.c_void_p, _u64, _u64, C.c_void_p, C.POINTER(CarouselC), _S]),
+    "g2048_restart_step": (C.c_int, [_E, C.POINTER(RestartC), C.c_void_p, _S]),
+    "g2048_restart_step_plain": (C.c_int, [C.c_void_p, _u64, C.c_void_p, C.POINTER(RestartC), _S]),
+    "g2048_ntuple_play_log_restart": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleLogC), C.POINTER(RestartC), _S]),
+    "g2048_ntuple_staged_play_log_restart": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleLogC), C.POINTER(RestartC), _S]),
+    "g2048_ntuple_log_train_restart": (C.c_int, [_E, C.POINTER(NTupleNetC), _u32, _u32, C.POINTER(NTupleLogC), C.c_void_p,
+                                                C.POINTER(NTupleTCC), C.POINTER(RestartC), _S]),
+    "g2048_ntuple_staged_log_train_restart": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), _u32, _u32, C.POINTER(NTupleLogC), C.c_void_p,
+                                                       C.POINTER(NTupleTCC), C.POINTER(RestartC), _S]),
     "g2048_add_tile": (C.c_int, [_E, _u32, _S]),
     "g2048_fill_random_actions": (C.c_int, [_E, _u64, _u32, C.c_void_p, _S]),
     "g2048_onehot": (C.c_int, [_E, C.c_void_p, _i32, _S]),

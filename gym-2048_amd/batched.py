@@ -33,6 +33,7 @@ from .ntuple import AdaptivePlayer, NTupleAdaptive, ReducedPlayer, _adaptive_io 
 from .ntuple import PlayReport, play_games, _check_tensor, _play_io  # noqa: F401
 from .ntuple import TDWork, td_evaluate, td_update, td_work, _td_io  # noqa: F401
 from .ntuple import NTupleLog, backward_train, log_sweep, _log_of  # noqa: F401
+from .ntuple import Restart, _restart_of  # noqa: F401
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}
 
@@ -807,24 +808,30 @@ class Batched2048:
         if n_steps:
             self._fresh = False
 
-    def ntuple_play_log(self, net, log):
+    def ntuple_play_log(self, net, log, restart=None):
         """``log.depth`` moves of the greedy player on every board in ONE launch that also keeps them
         (``g2048_ntuple_play_log``), on the engine's stream: the engine ends up as after
         ``ntuple_play(net, log.depth)``, bit for bit, slot ``m`` = 1..M of ``log`` (an :class:`NTupleLog` of this engine)
         holds the afterstate, the shifted merge gain and the flag of move ``m``, and slot 0 what slot M held before the call.
-        The weights are only read.  A spawn-stream engine only (``rng="philox"``)."""
+        The weights are only read.  A spawn-stream engine only (``rng="philox"``).  ``restart`` (a :class:`Restart` of this
+        engine): ``restart.step`` behind every move, inside the same launch (``g2048_ntuple_play_log_restart``, INTEGRATION.md
+        §25) -- the bits of M rounds of ``ntuple_evaluate``, ``step(auto_reset=True)``, ``restart.step(engine)``."""
         if not isinstance(net, NTupleNet):
             raise ValueError("net must be an NTupleNet")
         ref = net._ref(self.device)
-        check(net._fn("play_log")(self._h, ref, C.byref(_log_of(self, log)._c), self._stream()))
+        if restart is None:
+            check(net._fn("play_log")(self._h, ref, C.byref(_log_of(self, log)._c), self._stream()))
+        else:
+            check(net._fn("play_log_restart")(self._h, ref, C.byref(_log_of(self, log)._c), C.byref(_restart_of(self, restart)._c),
+                                              self._stream()))
         self._fresh = False
 
-    def ntuple_log_train(self, net, log, rounds, lr_shift, delta, tc=None):
+    def ntuple_log_train(self, net, log, rounds, lr_shift, delta, tc=None, restart=None):
         """``rounds`` times { :meth:`ntuple_play_log`; the backward sweep of ``log`` } in ONE library call
         (``g2048_ntuple_log_train``): plain launches on the engine's stream, no Python between them.
         ``delta``: int64 ``[n]`` work buffer (the errors of slot 0 of the last round afterwards).  ``tc`` None: ``net.update``
         per slot; an :class:`NTupleTC` of ``net``: ``net.tc_update`` with ``phases=3``.  The bits of
-        :func:`backward_train`'s Python loop."""
+        :func:`backward_train`'s Python loop.  ``restart``: every round's play_log with it (``g2048_ntuple_log_train_restart``)."""
         if not isinstance(net, NTupleNet):
             raise ValueError("net must be an NTupleNet")
         ref = net._ref(self.device)
@@ -834,8 +841,12 @@ class Batched2048:
             net._own_tc(tc)
         log = _log_of(self, log)
         _check_tensor("delta", delta, (torch.int64,), (self.n_envs,), self.device)
-        check(net._fn("log_train")(self._h, ref, rounds, lr_shift, C.byref(log._c), delta.data_ptr(),
-                                   None if tc is None else C.byref(tc._c), self._stream()))
+        tc_ref = None if tc is None else C.byref(tc._c)
+        if restart is None:
+            check(net._fn("log_train")(self._h, ref, rounds, lr_shift, C.byref(log._c), delta.data_ptr(), tc_ref, self._stream()))
+        else:
+            check(net._fn("log_train_restart")(self._h, ref, rounds, lr_shift, C.byref(log._c), delta.data_ptr(), tc_ref,
+                                               C.byref(_restart_of(self, restart)._c), self._stream()))
         if rounds:
             self._fresh = False
 

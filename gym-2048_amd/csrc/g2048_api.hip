@@ -1637,6 +1637,51 @@ static int ntuple_td_train(g2048_engine *e, const Net *net, uint32_t k_steps, ui
     return G2048_OK;
 }
 
+// g2048_restart -> the launchers' arguments, or G2048_ERR_INVALID (before any HIP call: works without a device): the rule, then
+// NULL members, then alignment.  The records, terminated and n of a step are restart_records'.
+static int restart_args(const g2048_restart *r, g2048::RestartArgs *a)
+{
+    if (!r)
+        return fail(G2048_ERR_INVALID, "restart is NULL");
+    if (r->stride_log2 > G2048_RESTART_MAX_STRIDE_LOG2)
+        return fail(G2048_ERR_INVALID, "stride_log2=%u: need stride_log2 <= %d", r->stride_log2, G2048_RESTART_MAX_STRIDE_LOG2);
+    if (r->capacity < 1 || r->capacity > G2048_RESTART_MAX_CAPACITY)
+        return fail(G2048_ERR_INVALID, "capacity=%u: need 1 <= capacity <= %d", r->capacity, G2048_RESTART_MAX_CAPACITY);
+    if (r->min_span < 2 || r->min_span > 0x80000000u)
+        return fail(G2048_ERR_INVALID, "min_span=%u: need 2 <= min_span <= 2^31", r->min_span);
+    if (r->max_restarts < 1)
+        return fail(G2048_ERR_INVALID, "max_restarts=0: need max_restarts >= 1");
+    if (!r->snap)
+        return fail(G2048_ERR_INVALID, "restart snap is NULL");
+    if (!r->pos)
+        return fail(G2048_ERR_INVALID, "restart pos is NULL");
+    if (!r->start)
+        return fail(G2048_ERR_INVALID, "restart start is NULL");
+    if (!r->restarts)
+        return fail(G2048_ERR_INVALID, "restart restarts is NULL");
+    if (reinterpret_cast<uintptr_t>(r->snap) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: restart snap needs 16 bytes");
+    if ((reinterpret_cast<uintptr_t>(r->pos) | reinterpret_cast<uintptr_t>(r->start) | reinterpret_cast<uintptr_t>(r->restarts)) & 3u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: restart pos, start and restarts need 4 bytes");
+    *a = g2048::RestartArgs{r->stride_log2, r->capacity, r->min_span, r->max_restarts, reinterpret_cast<uint4 *>(r->snap),
+                            r->pos,         r->start,    r->restarts};
+    return G2048_OK;
+}
+
+// the records, terminated and n of a restart step
+static int restart_records(const uint8_t *records, uint64_t n, const uint8_t *terminated)
+{
+    if (!records)
+        return fail(G2048_ERR_INVALID, "records is NULL");
+    if (!terminated)
+        return fail(G2048_ERR_INVALID, "terminated is NULL");
+    if (reinterpret_cast<uintptr_t>(records) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: records need 16 bytes");
+    if (n == 0 || n > 0xffffff00ull) // (the cap of g2048_create)
+        return fail(G2048_ERR_INVALID, "n=%llu: need 1 <= n <= 2^32 - 256", (unsigned long long)n);
+    return G2048_OK;
+}
+
 // g2048_ntuple_log -> the launchers' log, or G2048_ERR_INVALID (before any HIP call: works without a device)
 static int ntuple_log(const g2048_ntuple_log *log, g2048::NtupleLog *out)
 {
@@ -1658,14 +1703,17 @@ static int ntuple_log(const g2048_ntuple_log *log, g2048::NtupleLog *out)
     return G2048_OK;
 }
 
-// log.depth transactions of the clock and one launch, as g2048_ntuple_play with k_steps == log.depth
-static hipError_t ntuple_play_log_launch(g2048_engine *e, const g2048::NtupleNet &nn, const g2048::NtupleLog &lg, void *stream)
+// log.depth transactions of the clock and one launch, as g2048_ntuple_play with k_steps == log.depth; rs: NULL, or the restart
+// whose step runs behind every move in that launch
+static hipError_t ntuple_play_log_launch(g2048_engine *e, const g2048::NtupleNet &nn, const g2048::NtupleLog &lg, const g2048::RestartArgs *rs,
+                                         void *stream)
 {
     e->t += 1; // transaction of the first move
     e->fresh = 0;
     g2048::StepArgs a = make_args(e, nullptr, 1);
     a.k_steps = lg.depth;
-    const hipError_t err = g2048::launch_ntuple_play_log(a, nn, lg, static_cast<hipStream_t>(stream));
+    const hipError_t err = rs ? g2048::launch_ntuple_play_log_restart(a, nn, lg, *rs, static_cast<hipStream_t>(stream))
+                              : g2048::launch_ntuple_play_log(a, nn, lg, static_cast<hipStream_t>(stream));
     if (err == hipSuccess)
         e->t += lg.depth - 1;
     return err;
@@ -1686,7 +1734,15 @@ static hipError_t ntuple_log_sweep_launch(uint32_t n, const g2048::NtupleNet &nn
     return hipSuccess;
 }
 
-template <class Net> static int ntuple_play_log(g2048_engine *e, const Net *net, const g2048_ntuple_log *log, void *stream)
+// The optional restart of a play_log or log_train call: absent (today's entry points), or a g2048_restart that must be valid
+struct RestartOpt {
+    bool wanted;
+    const g2048_restart *restart;
+};
+static int restart_opt(const RestartOpt &opt, g2048::RestartArgs *a) { return opt.wanted ? restart_args(opt.restart, a) : G2048_OK; }
+
+template <class Net>
+static int ntuple_play_log(g2048_engine *e, const Net *net, const g2048_ntuple_log *log, const RestartOpt &restart, void *stream)
 {
     g2048::NtupleNet nn;
     if (int rc = ntuple_net(net, &nn))
@@ -1694,10 +1750,13 @@ template <class Net> static int ntuple_play_log(g2048_engine *e, const Net *net,
     g2048::NtupleLog lg;
     if (int rc = ntuple_log(log, &lg))
         return rc;
-    if (int rc = ntuple_td_engine(e, "g2048_ntuple_play_log"))
+    g2048::RestartArgs rs{};
+    if (int rc = restart_opt(restart, &rs))
+        return rc;
+    if (int rc = ntuple_td_engine(e, restart.wanted ? "g2048_ntuple_play_log_restart" : "g2048_ntuple_play_log"))
         return rc;
     G2048_HIP(hipSetDevice(e->device));
-    G2048_HIP(ntuple_play_log_launch(e, nn, lg, stream));
+    G2048_HIP(ntuple_play_log_launch(e, nn, lg, restart.wanted ? &rs : nullptr, stream));
     return G2048_OK;
 }
 
@@ -1752,7 +1811,7 @@ static int ntuple_log_sweep(uint64_t n, const Net *net, const g2048_ntuple_log *
 // rounds times { play_log; sweep }, plain launches on one stream
 template <class Net>
 static int ntuple_log_train(g2048_engine *e, const Net *net, uint32_t rounds, uint32_t lr_shift, const g2048_ntuple_log *log, int64_t *delta,
-                            const g2048_ntuple_tc *tc, void *stream)
+                            const g2048_ntuple_tc *tc, const RestartOpt &restart, void *stream)
 {
     g2048::NtupleNet nn;
     if (int rc = ntuple_net(net, &nn))
@@ -1761,13 +1820,16 @@ static int ntuple_log_train(g2048_engine *e, const Net *net, uint32_t rounds, ui
     g2048::NtupleTc t{};
     if (int rc = ntuple_log_sweep_args(log, lr_shift, delta, tc, &lg, &t))
         return rc;
-    if (int rc = ntuple_td_engine(e, "g2048_ntuple_log_train"))
+    g2048::RestartArgs rs{};
+    if (int rc = restart_opt(restart, &rs))
+        return rc;
+    if (int rc = ntuple_td_engine(e, restart.wanted ? "g2048_ntuple_log_train_restart" : "g2048_ntuple_log_train"))
         return rc;
     if (rounds == 0)
         return G2048_OK;
     G2048_HIP(hipSetDevice(e->device));
     for (uint32_t r = 0; r < rounds; ++r) {
-        G2048_HIP(ntuple_play_log_launch(e, nn, lg, stream));
+        G2048_HIP(ntuple_play_log_launch(e, nn, lg, restart.wanted ? &rs : nullptr, stream));
         G2048_HIP(ntuple_log_sweep_launch(static_cast<uint32_t>(e->n), nn, lg, lr_shift, delta, tc ? &t : nullptr, stream));
     }
     return G2048_OK;
@@ -2074,12 +2136,24 @@ int g2048_ntuple_staged_td_train(g2048_engine *e, const g2048_ntuple_staged_net 
 
 int g2048_ntuple_play_log(g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_log *log, void *stream)
 {
-    return ntuple_play_log(e, net, log, stream);
+    return ntuple_play_log(e, net, log, RestartOpt{false, nullptr}, stream);
 }
 
 int g2048_ntuple_staged_play_log(g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_log *log, void *stream)
 {
-    return ntuple_play_log(e, net, log, stream);
+    return ntuple_play_log(e, net, log, RestartOpt{false, nullptr}, stream);
+}
+
+int g2048_ntuple_play_log_restart(g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_log *log, const g2048_restart *restart,
+                                  void *stream)
+{
+    return ntuple_play_log(e, net, log, RestartOpt{true, restart}, stream);
+}
+
+int g2048_ntuple_staged_play_log_restart(g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_log *log,
+                                         const g2048_restart *restart, void *stream)
+{
+    return ntuple_play_log(e, net, log, RestartOpt{true, restart}, stream);
 }
 
 int g2048_ntuple_log_delta(uint64_t n, const g2048_ntuple_net *net, const g2048_ntuple_log *log, uint32_t m, int64_t *delta, void *stream)
@@ -2108,13 +2182,27 @@ int g2048_ntuple_staged_log_sweep(uint64_t n, const g2048_ntuple_staged_net *net
 int g2048_ntuple_log_train(g2048_engine *e, const g2048_ntuple_net *net, uint32_t rounds, uint32_t lr_shift, const g2048_ntuple_log *log,
                            int64_t *delta, const g2048_ntuple_tc *tc, void *stream)
 {
-    return ntuple_log_train(e, net, rounds, lr_shift, log, delta, tc, stream);
+    return ntuple_log_train(e, net, rounds, lr_shift, log, delta, tc, RestartOpt{false, nullptr}, stream);
 }
 
 int g2048_ntuple_staged_log_train(g2048_engine *e, const g2048_ntuple_staged_net *net, uint32_t rounds, uint32_t lr_shift,
                                   const g2048_ntuple_log *log, int64_t *delta, const g2048_ntuple_tc *tc, void *stream)
 {
-    return ntuple_log_train(e, net, rounds, lr_shift, log, delta, tc, stream);
+    return ntuple_log_train(e, net, rounds, lr_shift, log, delta, tc, RestartOpt{false, nullptr}, stream);
+}
+
+int g2048_ntuple_log_train_restart(g2048_engine *e, const g2048_ntuple_net *net, uint32_t rounds, uint32_t lr_shift,
+                                   const g2048_ntuple_log *log, int64_t *delta, const g2048_ntuple_tc *tc, const g2048_restart *restart,
+                                   void *stream)
+{
+    return ntuple_log_train(e, net, rounds, lr_shift, log, delta, tc, RestartOpt{true, restart}, stream);
+}
+
+int g2048_ntuple_staged_log_train_restart(g2048_engine *e, const g2048_ntuple_staged_net *net, uint32_t rounds, uint32_t lr_shift,
+                                          const g2048_ntuple_log *log, int64_t *delta, const g2048_ntuple_tc *tc,
+                                          const g2048_restart *restart, void *stream)
+{
+    return ntuple_log_train(e, net, rounds, lr_shift, log, delta, tc, RestartOpt{true, restart}, stream);
 }
 
 // One budgeted step with the caller's actions: g2048_ntuple_play's contract and clock at k_steps == 1, g2048_step's checks of
@@ -2488,6 +2576,32 @@ int g2048_carousel_step_plain(uint8_t *records, uint64_t n, uint64_t index_offse
     if (int rc = carousel_args(c, records, n, index_offset, terminated, &a))
         return rc;
     G2048_HIP(g2048::launch_carousel_step(a, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_restart_step(g2048_engine *e, const g2048_restart *r, const uint8_t *terminated, void *stream)
+{
+    if (int rc = usable(e))
+        return rc;
+    g2048::RestartArgs a;
+    if (int rc = restart_args(r, &a))
+        return rc;
+    if (int rc = restart_records(reinterpret_cast<const uint8_t *>(e->st.boards), e->n, terminated))
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(g2048::launch_restart_step(e->st.boards, terminated, static_cast<uint32_t>(e->n), a, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_restart_step_plain(uint8_t *records, uint64_t n, const uint8_t *terminated, const g2048_restart *r, void *stream)
+{
+    g2048::RestartArgs a;
+    if (int rc = restart_args(r, &a))
+        return rc;
+    if (int rc = restart_records(records, n, terminated))
+        return rc;
+    G2048_HIP(g2048::launch_restart_step(reinterpret_cast<uint4 *>(records), terminated, static_cast<uint32_t>(n), a,
+                                         static_cast<hipStream_t>(stream)));
     return G2048_OK;
 }
 

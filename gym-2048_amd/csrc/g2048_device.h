@@ -2432,6 +2432,89 @@ G2048_DEV int64_t ntuple_log_delta(uint32_t f, uint32_t f1, int64_t gain1, int64
     return static_cast<int64_t>(target - static_cast<uint64_t>(v0));
 }
 
+// ------------------------------------------------------------------- midpoint restart
+// A board whose episode has just ended goes back to the middle of the run that ended, so that late-game positions are met
+// more often (g2048_restart_step, include/g2048.h; the restart of Matsuzaki 2017, with snapshots every
+// s = 2^k positions in place of whole recorded games).  Any network, no stage, no pool, no batch-wide rank: everything is a
+// function of the one board's own history, so the bits are those of any launch geometry and of any sharding.  Integers only.
+//   snap      [C][n] engine records, slot-major: slot j of board i = the record at position (j + 1) * s of the current lineage
+//   pos       p: non-terminating steps since the lineage's empty board;  start  S: where the current run began (0: a fresh game)
+//   restarts  restarts made so far in the lineage
+// One operation, restart_board, after a step with auto-reset on:
+//   terminated == 0:  pos == 2^32 - 1 -> nothing.  Else p = pos + 1; pos = p; if p & (s - 1) == 0 and 1 <= q = p >> k <= C:
+//                     snap[q - 1][i] = record
+//   terminated != 0 (the record is already the fresh auto-reset board):
+//                     L = pos, R = L - S, m = S + (R >> 1), q = min(m >> k, C), S' = q << k
+//                     if R >= min_span, restarts < max_restarts, q >= 1 and S' > S:
+//                         record = snap[q - 1][i]; start = pos = S'; restarts += 1
+//                     else the fresh board stays and start = pos = restarts = 0
+// S' > S and S' <= m <= L: slot q - 1 was written by the current run; the slots at or below S belong to the shared prefix.  No
+// slot is read that this lineage did not write, and no lane touches another board's state.
+constexpr uint32_t kRestartMaxStrideLog2 = 16, kRestartMaxCapacity = 4096; // = G2048_RESTART_MAX_STRIDE_LOG2, _MAX_CAPACITY
+constexpr uint32_t kRestartMinSpan = 2, kRestartMaxSpan = 0x80000000u;     // min_span in 2..2^31
+
+struct RestartRule {
+    uint32_t stride_log2, capacity, min_span, max_restarts; // k, C, min_span, max_restarts
+};
+// g2048_restart, checked by the caller: the rule and the state of n boards
+struct Restart {
+    RestartRule rule;
+    uint4 *snap;                    // [C][n] records
+    uint32_t *pos, *start, *restarts; // [n] each
+};
+// pos, start and restarts of one board, in registers
+struct RestartBoard {
+    uint32_t pos, start, restarts;
+};
+
+// one 16-byte record of a slot: one global_store_dwordx4 per lane, contiguous over the wave
+#if defined(G2048_HOST_CHECK)
+G2048_DEV void restart_store(uint4 *slot, uint32_t i, const Board &b) { __builtin_memcpy(slot + i, b.r, 16); }
+#else
+G2048_DEV void restart_store(uint4 *slot, uint32_t i, const Board &b) { slot[i] = make_uint4(b.r[0], b.r[1], b.r[2], b.r[3]); }
+#endif
+
+// Where restart_board finds the live record of its board: in the registers of a kernel that plays on (RestartRecordHeld), or in
+// memory, read and written only where the rule asks for it (RestartRecordStored)
+struct RestartRecordHeld {
+    Board &rec;
+    G2048_MEMBER Board get() const { return rec; }
+    G2048_MEMBER void set(const Board &b) const { rec = b; }
+};
+struct RestartRecordStored {
+    uint4 *records;
+    uint32_t i;
+    G2048_MEMBER Board get() const { return load_board(records, i); }
+    G2048_MEMBER void set(const Board &b) const { restart_store(records, i, b); }
+};
+
+// The restart step of board i of n (the rule above).  When terminated == false only b.pos is read and written.
+template <class Record>
+G2048_HOST_DEV void restart_board(const Record &record, bool terminated, const RestartRule &r, uint4 *snap, uint32_t n, uint32_t i,
+                                  RestartBoard &b)
+{
+    const uint32_t k = r.stride_log2;
+    if (!terminated) {
+        if (b.pos == 0xffffffffu)
+            return;
+        const uint32_t p = b.pos + 1u, q = p >> k;
+        b.pos = p;
+        if ((p & ((1u << k) - 1u)) == 0u && q >= 1u && q <= r.capacity)
+            restart_store(snap + static_cast<uint64_t>(q - 1u) * n, i, record.get());
+        return;
+    }
+    const uint32_t S = b.start, R = b.pos - S, m = S + (R >> 1);
+    const uint32_t q = (m >> k) < r.capacity ? (m >> k) : r.capacity;
+    const uint32_t S1 = q << k; // q <= 4096, k <= 16: below 2^29
+    if (R >= r.min_span && b.restarts < r.max_restarts && q >= 1u && S1 > S) {
+        record.set(load_board(snap + static_cast<uint64_t>(q - 1u) * n, i));
+        b.start = b.pos = S1;
+        b.restarts += 1u;
+    } else {
+        b.start = b.pos = b.restarts = 0u;
+    }
+}
+
 // ------------------------------------------------------------------------------ one env step
 struct StepResult {
     float reward;

@@ -259,6 +259,19 @@ constexpr uint32_t kCarouselMaxGroups = 1024;
 constexpr size_t kCarouselScratchBytes = (2 * 8 * kCarouselMaxGroups + 16) * sizeof(uint32_t);
 // three launches on s: restart (reads the pool), scan, scatter (writes the pool)
 hipError_t launch_carousel_step(const CarouselArgs &a, hipStream_t s);
+// g2048_restart_step and g2048_ntuple_play_log_restart: the midpoint restart (g2048_restart, checked by the caller)
+struct RestartArgs {
+    uint32_t stride_log2, capacity; // k in 0..16, C in 1..4096
+    uint32_t min_span, max_restarts;
+    uint4 *snap;                    // [C][n] engine records, slot-major
+    uint32_t *pos, *start, *restarts; // [n] each
+};
+// restart_step_kernel strides over the boards: the cap on its workgroups
+constexpr uint32_t kRestartMaxGroups = 1024;
+// one launch on s: the restart step on n records in place
+hipError_t launch_restart_step(uint4 *records, const uint8_t *terminated, uint32_t n, const RestartArgs &rs, hipStream_t s);
+// launch_ntuple_play_log with the restart step behind every move, in the same launch
+hipError_t launch_ntuple_play_log_restart(const StepArgs &a, const NtupleNet &net, const NtupleLog &log, const RestartArgs &rs, hipStream_t s);
 hipError_t launch_add_tile(const StepArgs &a, uint32_t slot, hipStream_t s);
 // numpy-RNG mode: every board's PCG64 generator, seeded as numpy seeds it, into the DeviceState::rng planes
 hipError_t launch_seed_numpy(uint64_t *planes, uint32_t n, uint64_t first_seed, hipStream_t s);

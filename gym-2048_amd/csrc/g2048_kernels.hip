@@ -2015,11 +2015,15 @@ __global__ void __launch_bounds__(kBlock) ntuple_td_step_kernel(const StepArgs p
 // `after`, 512 B of `gain` and 64 B of `flag`.  First the carry: slot 0 takes the three entries slot M held, each lane its own
 // board's (M >= 1: the two slots differ, and no lane reads what another writes).  Slot bases are formed in 64 bits:
 // (M + 1) * n * 16 bytes exceeds 2^32.  The weights are read with plain loads; nothing in the launch writes them.
-template <uint32_t T, class Shape>
-__global__ void __launch_bounds__(kBlock) ntuple_play_log_kernel(const StepArgs p, const Shape sh, uint32_t frac_bits,
-                                                                 const int32_t *__restrict__ weights, const NtupleLog log)
+// RESTART (g2048_ntuple_play_log_restart): restart_board of g2048_device.h behind every move, on the record in registers, with
+// pos, start and restarts of the board held in registers over the M moves and stored once -- the bits of M rounds of
+// evaluate -> step -> g2048_restart_step.  A lane past the end neither reads nor writes the snapshots.  A compile-time option:
+// without it the body is what ntuple_play_log_kernel was, and `rs` is not looked at.
+struct NoRestart {};
+template <uint32_t T, bool RESTART, class Shape, class Rs>
+__device__ __forceinline__ void ntuple_play_log_body(WaveTables *s_tables, const StepArgs &p, const Shape &sh, uint32_t frac_bits,
+                                                     const int32_t *__restrict__ weights, const NtupleLog &log, const Rs &rs)
 {
-    __shared__ WaveTables s_tables[kBlock / 64];
     const Lane ln = lane_of<kBlock, false>(p.n);
     Board rec = load_board(p.st.boards, ln.i);
     const LdsTables tb = stage_tables(s_tables, load_tables_piece());
@@ -2030,6 +2034,9 @@ __global__ void __launch_bounds__(kBlock) ntuple_play_log_kernel(const StepArgs 
         log.gain[ln.i] = log.gain[last + ln.i];
         log.flag[ln.i] = log.flag[last + ln.i];
     }
+    RestartBoard rb{};
+    if constexpr (RESTART)
+        rb = RestartBoard{rs.pos[ln.i], rs.start[ln.i], rs.restarts[ln.i]};
     uint64_t t = (static_cast<uint64_t>(p.t_hi) << 32) | p.t_lo; // transaction of the first move
     uint32_t episodes = 0, illegal_ends = 0, gained32 = 0;
     unsigned long long gained = 0; // as in ntuple_play_kernel: 32-bit adds, folded into 64 bits every kGainFold moves
@@ -2049,15 +2056,70 @@ __global__ void __launch_bounds__(kBlock) ntuple_play_log_kernel(const StepArgs 
         record_episode_ends(p, ln.i, fin, !o.legal, rec, episodes, illegal_ends);
         if (o.terminated)
             reset_record(rec, o, w, tb);
+        if constexpr (RESTART) {
+            if (ln.valid)
+                restart_board(RestartRecordHeld{rec}, o.terminated, rs.rule, rs.snap, p.n, ln.i, rb);
+        }
         if (m % kGainFold == 0u) {
             gained += gained32;
             gained32 = 0;
         }
     }
     gained += gained32;
-    if (ln.valid)
+    if (ln.valid) {
         store_board(p.st.boards, ln.i, rec);
+        if constexpr (RESTART) {
+            rs.pos[ln.i] = rb.pos;
+            rs.start[ln.i] = rb.start;
+            rs.restarts[ln.i] = rb.restarts;
+        }
+    }
     flush_episode_counts(counters, episodes, illegal_ends, wave_sum64_lane63(ln.valid ? gained : 0ull), 0ull);
+}
+
+template <uint32_t T, class Shape>
+__global__ void __launch_bounds__(kBlock) ntuple_play_log_kernel(const StepArgs p, const Shape sh, uint32_t frac_bits,
+                                                                 const int32_t *__restrict__ weights, const NtupleLog log)
+{
+    __shared__ WaveTables s_tables[kBlock / 64];
+    ntuple_play_log_body<T, false>(s_tables, p, sh, frac_bits, weights, log, NoRestart{});
+}
+
+template <uint32_t T, class Shape>
+__global__ void __launch_bounds__(kBlock) ntuple_play_log_restart_kernel(const StepArgs p, const Shape sh, uint32_t frac_bits,
+                                                                         const int32_t *__restrict__ weights, const NtupleLog log,
+                                                                         const Restart rs)
+{
+    __shared__ WaveTables s_tables[kBlock / 64];
+    ntuple_play_log_body<T, true>(s_tables, p, sh, frac_bits, weights, log, rs);
+}
+
+// g2048_restart_step: restart_board of g2048_device.h, one board per lane in a grid-stride loop (at most kRestartMaxGroups
+// workgroups whatever n is), ONE launch.  A board whose episode goes on reads terminated[i] and pos[i] and writes pos[i]; on
+// one step in s it also reads its record and stores it in a slot -- slot-major, so a wavefront stores 1 KiB contiguous.  A
+// board whose episode ended reads start[i] and restarts[i] too and, when it restarts, loads one slot and stores its record.
+// Every lane touches its own board's state only: nothing a lane reads is written by another.
+__global__ void __launch_bounds__(kBlock) restart_step_kernel(uint4 *__restrict__ records, const uint8_t *__restrict__ terminated, uint32_t n,
+                                                              const Restart rs)
+{
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; g < n; g += stride) {
+        const uint32_t i = static_cast<uint32_t>(g);
+        const bool ended = terminated[i] != 0;
+        RestartBoard b{rs.pos[i], 0u, 0u};
+        const uint32_t pos = b.pos;
+        if (ended) {
+            b.start = rs.start[i];
+            b.restarts = rs.restarts[i];
+        }
+        restart_board(RestartRecordStored{records, i}, ended, rs.rule, rs.snap, n, i, b);
+        if (b.pos != pos)
+            rs.pos[i] = b.pos;
+        if (ended) {
+            rs.start[i] = b.start;
+            rs.restarts[i] = b.restarts;
+        }
+    }
 }
 
 // g2048_ntuple_log_delta: the backward error of slot m (ntuple_log_delta of g2048_device.h), one board per lane as
@@ -3085,6 +3147,29 @@ hipError_t launch_ntuple_play_log(const StepArgs &a, const NtupleNet &net, const
         return launch_1d(ntuple_play_log_kernel<tc, decltype(sh)>, a.n, 0, s, a, sh, net.frac_bits, static_cast<const int32_t *>(net.weights),
                          log);
     });
+}
+
+static Restart restart_of(const RestartArgs &a)
+{
+    return Restart{RestartRule{a.stride_log2, a.capacity, a.min_span, a.max_restarts}, a.snap, a.pos, a.start, a.restarts};
+}
+
+hipError_t launch_ntuple_play_log_restart(const StepArgs &a, const NtupleNet &net, const NtupleLog &log, const RestartArgs &ra, hipStream_t s)
+{
+    const Restart rs = restart_of(ra);
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        return launch_1d(ntuple_play_log_restart_kernel<tc, decltype(sh)>, a.n, 0, s, a, sh, net.frac_bits,
+                         static_cast<const int32_t *>(net.weights), log, rs);
+    });
+}
+
+hipError_t launch_restart_step(uint4 *records, const uint8_t *terminated, uint32_t n, const RestartArgs &ra, hipStream_t s)
+{
+    const Restart rs = restart_of(ra);
+    const uint64_t groups = (static_cast<uint64_t>(n) + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(restart_step_kernel, dim3(static_cast<uint32_t>(groups < kRestartMaxGroups ? groups : kRestartMaxGroups)), dim3(kBlock), 0,
+                       s, records, terminated, n, rs);
+    return hipGetLastError();
 }
 
 hipError_t launch_ntuple_log_delta(uint32_t n, const NtupleNet &net, const NtupleLog &log, uint32_t m, int64_t *delta, hipStream_t s)

@@ -45,16 +45,23 @@ batch (``g2048_ntuple_mean_update_plain``, ``g2048_ntuple_mean_trace_update``, I
 learning over logged segments (Matsuzaki 2017): M moves of every board played and kept in one launch, then updated from the
 last to the first (``g2048_ntuple_play_log``, ``g2048_ntuple_log_delta``, ``g2048_ntuple_log_sweep``, ``g2048_ntuple_log_train``,
 INTEGRATION.md §24).  A learner of its own.  Opt-in.
+``Restart`` is the midpoint restart of the same paper (``g2048_restart_*``): a finished episode goes back to
+the last snapshot at or below the middle of the run that ended -- per board, integers only, for any network, the same bits
+across shards; every trainer takes it as ``restart=`` (keyword only) where it takes ``carousel=``, and ``Batched2048.ntuple_play_log`` and
+:func:`backward_train` run it inside the play-log launch (``g2048_ntuple_play_log_restart``,
+``g2048_ntuple_log_train_restart``).  Opt-in.
 """
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import inspect
 from typing import NamedTuple, Optional
 
 import torch
 
 from . import _lib
-from ._lib import CarouselC, NTupleAdaptiveIO, NTupleDeepIO, NTupleReducedIO, NTupleDelayC, NTupleIO, NTupleMeanC, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTDIO, NTupleTraceC, check
+from ._lib import CarouselC, RestartC, NTupleAdaptiveIO, NTupleDeepIO, NTupleReducedIO, NTupleDelayC, NTupleIO, NTupleMeanC, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTDIO, NTupleTraceC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
@@ -69,6 +76,8 @@ TRACE_MAX = 8                                                     # G2048_NTUPLE
 DELAY_STEP, DELAY_FLUSH = 0, 1                                    # G2048_NTUPLE_DELAY_STEP, G2048_NTUPLE_DELAY_FLUSH
 MAX_STAGES = 8                                                    # G2048_NTUPLE_MAX_STAGES
 CAROUSEL_MAX_CAPACITY = 65536                                     # G2048_CAROUSEL_MAX_CAPACITY
+RESTART_MAX_STRIDE_LOG2, RESTART_MAX_CAPACITY = 16, 4096          # G2048_RESTART_MAX_STRIDE_LOG2, G2048_RESTART_MAX_CAPACITY
+RESTART_MAX_RESTARTS = 2**32 - 1                                  # g2048_restart.max_restarts: 1..2^32 - 1
 LOG_MAX_DEPTH, LOG_VALID, LOG_ENDED = 1024, 1, 2                  # G2048_NTUPLE_LOG_MAX_DEPTH, G2048_NTUPLE_LOG_VALID, G2048_NTUPLE_LOG_ENDED
 NTUPLE_END = 0xff                                                 # G2048_NTUPLE_END: pads a cell list shorter than tuple_len
 SEEN_UNKNOWN = 0xff                                               # Carousel.seen: the stage of the episode is not known yet
@@ -858,10 +867,101 @@ class Carousel:
             mine.copy_(new[name])
 
 
+class _Rides:
+    """A :class:`Restart` given as ``restart=``, on its way through the ``carousel`` argument of the trainers (``_restart_keyword``)."""
+
+    def __init__(self, restart):
+        self.restart = restart
+
+
 def _carousel_of(engine, carousel):
+    """``carousel`` checked against the engine: the object whose ``step(engine)`` runs right behind the step."""
+    if isinstance(carousel, _Rides):
+        return _restart_of(engine, carousel.restart)
     if not isinstance(carousel, Carousel) or carousel.n != engine.n_envs or carousel.device != engine.device:
         raise ValueError(f"carousel must be a Carousel of {engine.n_envs} boards on {engine.device}")
     return carousel
+
+
+class Restart:
+    """Midpoint restart for ``n`` boards (``g2048_restart``; the restart of Matsuzaki 2017): a board whose
+    episode has just ended goes back to the middle of the run that ended, so that late-game positions -- where the value function
+    is worst -- are met more often.  For any network: no stages, no pool, no batch-wide rank.
+
+    Every ``stride`` (a power of two, 1..65536) positions the board's engine record is kept in the next of ``capacity`` (1..4096)
+    slots, ``snap`` uint8 ``[capacity, n, 16]`` (records, verbatim: cells and packed score).  :meth:`step`, run right after a step
+    with auto-reset on, counts the position of every board that goes on (``pos``) and, where an episode ended after a run of
+    ``R = pos - start`` positions, restarts it from the last snapshot at or below ``start + R // 2`` -- if ``R >= min_span``, the
+    lineage has made fewer than ``max_restarts`` restarts and that snapshot lies beyond ``start``; otherwise the fresh board stays
+    and ``pos``, ``start`` and ``restarts`` (int32 ``[n]`` each, read as unsigned) return to 0.  Everything is integers and a
+    function of the board's own history: the same bits whatever the launch geometry, and -- unlike :class:`Carousel` -- the
+    shards of a batch reproduce the unsharded run.  The paper records whole games and restarts exactly at the middle; here the
+    restart point is up to ``stride - 1`` positions earlier, and earlier still once the middle lies beyond ``capacity * stride``.
+    A restarted board carries the score it was recorded with: ``engine.scores()`` and the episode statistics then describe
+    composite episodes.  One per engine or shard; call :meth:`reset` after ``engine.reset()``.
+
+    Memory: 16 capacity + 12 bytes per board."""
+
+    def __init__(self, n, stride=16, capacity=256, min_span=64, max_restarts=RESTART_MAX_RESTARTS, device="cuda:0"):
+        self.n = _int_arg("n", n, 1, 0xffffff00)
+        self.stride = _int_arg("stride", stride, 1, 1 << RESTART_MAX_STRIDE_LOG2)
+        if self.stride & (self.stride - 1):
+            raise ValueError(f"stride={stride}: need a power of two")
+        self.capacity = _int_arg("capacity", capacity, 1, RESTART_MAX_CAPACITY)
+        self.min_span = _int_arg("min_span", min_span, 2, 1 << 31)
+        self.max_restarts = _int_arg("max_restarts", max_restarts, 1, RESTART_MAX_RESTARTS)
+        self.device = torch.device(device)
+        self.snap = torch.zeros((self.capacity, self.n, 16), dtype=torch.uint8, device=self.device)
+        self.pos = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self.start = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self.restarts = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self._c = RestartC(self.stride.bit_length() - 1, self.capacity, self.min_span, self.max_restarts, self.snap.data_ptr(),
+                           self.pos.data_ptr(), self.start.data_ptr(), self.restarts.data_ptr())
+
+    def reset(self):
+        """Every board is at the start of a fresh game again (``pos`` = ``start`` = ``restarts`` = 0); no snapshot is read before
+        it is written again, so ``snap`` stays."""
+        self.pos.zero_()
+        self.start.zero_()
+        self.restarts.zero_()
+
+    def step(self, engine):
+        """The restart step on the live records of ``engine`` (``g2048_restart_step``) with ``engine.terminated`` of the step just
+        made (auto-reset on): one launch on the engine's stream, no host synchronisation."""
+        if engine.n_envs != self.n or engine.device != self.device:
+            raise ValueError(f"the restart is for {self.n} boards on {self.device}, the engine has {engine.n_envs} on {engine.device}")
+        check(_lib.load().g2048_restart_step(engine._h, C.byref(self._c), engine.terminated.data_ptr(), engine._stream()))
+
+    def step_plain(self, records, terminated):
+        """The same on any device uint8 ``[n, 16]`` tensor of engine records, updated in place (``g2048_restart_step_plain``);
+        ``terminated`` uint8 or bool ``[n]``."""
+        _check_tensor("records", records, (torch.uint8,), (self.n, 16), self.device)
+        _check_tensor("terminated", terminated, (torch.uint8, torch.bool), (self.n,), self.device)
+        _on_stream(_lib.load().g2048_restart_step_plain, self.device, records.data_ptr(), self.n, terminated.data_ptr(), C.byref(self._c))
+
+    def state_dict(self):
+        return {"stride": self.stride, "capacity": self.capacity, "snap": self.snap.clone(), "pos": self.pos.clone(),
+                "start": self.start.clone(), "restarts": self.restarts.clone()}
+
+    def load_state_dict(self, state):
+        """Copy the snapshots and the per-board counters of a ``state_dict()`` of a restart of the same shape into this one (in
+        place)."""
+        if int(state["stride"]) != self.stride or int(state["capacity"]) != self.capacity:
+            raise ValueError("state_dict is of a restart with another stride or another capacity")
+        new = {}
+        for name in ("snap", "pos", "start", "restarts"):
+            t, mine = torch.as_tensor(state[name]), getattr(self, name)
+            if t.dtype != mine.dtype or t.shape != mine.shape:
+                raise ValueError(f"state_dict {name} must be {str(mine.dtype).replace('torch.', '')} {tuple(mine.shape)}")
+            new[name] = t
+        for name, t in new.items():
+            getattr(self, name).copy_(t)
+
+
+def _restart_of(engine, restart):
+    if not isinstance(restart, Restart) or restart.n != engine.n_envs or restart.device != engine.device:
+        raise ValueError(f"restart must be a Restart of {engine.n_envs} boards on {engine.device}")
+    return restart
 
 
 class TDWork(NamedTuple):
@@ -896,6 +996,30 @@ def _td_io(engine, work, delta=True):
     return io
 
 
+def _restart_keyword(fn):
+    """``fn`` -- a function with ``carousel=None, fused=False`` -- with the keyword-only ``restart=`` (a :class:`Restart`,
+    INTEGRATION.md §25) added.  Positional arguments are ``fn``'s, unchanged.  ``restart=`` with ``carousel=`` is a ValueError,
+    and so is ``restart=`` with ``fused=True``, both raised before anything is looked at or launched; otherwise the restart
+    rides where a carousel rides (``_Rides``), and its ``step(engine)`` runs at exactly the place ``carousel.step(engine)``
+    runs."""
+    params = inspect.signature(fn)
+
+    @functools.wraps(fn)
+    def call(*args, restart=None, **kw):
+        if restart is None:
+            return fn(*args, **kw)
+        bound = params.bind(*args, **kw)
+        bound.apply_defaults()
+        if bound.arguments["carousel"] is not None:
+            raise ValueError("carousel= and restart= are two ways to restart a finished episode: give one of them")
+        if bound.arguments["fused"]:
+            raise ValueError("fused=True cannot run a restart: its launch sits between the step and the second evaluate and needs "
+                             "the whole batch's terminated (use fused=False)")
+        bound.arguments["carousel"] = _Rides(restart)
+        return fn(*bound.args, **bound.kwargs)
+    return call
+
+
 def _fused_args(fused, carousel):
     """``fused`` as a bool; ValueError for ``fused=True`` with a carousel."""
     if fused and carousel is not None:
@@ -904,6 +1028,7 @@ def _fused_args(fused, carousel):
     return bool(fused)
 
 
+@_restart_keyword
 def td_evaluate(engine, net, work, carousel=None, fused=False) -> TDWork:
     """Points 1-3 of the TD(0) step and the delta of point 4, leaving the weights alone: evaluate, play the greedy move
     (auto-reset on), evaluate the new boards, ``work.delta = (0 if terminated else best') - V(after)``.  Shards that share
@@ -911,6 +1036,9 @@ def td_evaluate(engine, net, work, carousel=None, fused=False) -> TDWork:
     ``carousel`` (a :class:`Carousel` of this engine): ``carousel.step(engine)`` right behind the step, so a finished
     episode restarts from the carousel's pool; the second evaluate sees the restarted board, and its ``best`` is masked by
     ``terminated`` as before.  None: exactly the launches above.
+    ``restart=`` (keyword only; a :class:`Restart` of this engine): ``restart.step(engine)`` at that same place -- the midpoint
+    restart, one launch, for any network.  Not together with ``carousel`` and not with ``fused=True`` (ValueError).  Every
+    ``*_evaluate``, ``*_step`` and ``*_train`` function below that takes ``carousel=`` takes ``restart=`` the same way.
     ``fused=True``: all seven launches as ONE (``Batched2048.ntuple_td_step``, ``g2048_ntuple_td_step``) --
     the same bits in ``work``, ``engine.terminated`` and the engine; ``engine.reward`` is not written.  A spawn-stream engine
     only, and not with a ``carousel`` (ValueError): the carousel's three launches sit between the step and the second
@@ -921,7 +1049,7 @@ def td_evaluate(engine, net, work, carousel=None, fused=False) -> TDWork:
     if _fused_args(fused, carousel):
         return engine.ntuple_td_step(net, work)
     if carousel is not None:
-        _carousel_of(engine, carousel)
+        carousel = _carousel_of(engine, carousel)
     engine.ntuple_evaluate(net, out=work.before)
     engine.step(work.before.action, auto_reset=True, want_info=False)
     if carousel is not None:
@@ -938,6 +1066,7 @@ def td_update(net, work, lr_shift):
     net.update(work.before.after, work.delta, lr_shift)
 
 
+@_restart_keyword
 def td_step(engine, net, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """One afterstate TD(0) step of every board of ``engine`` (a ``Batched2048``) under ``net``, on the engine's stream:
     evaluate, play the greedy move, evaluate the new boards, and move V of the afterstate just played towards what
@@ -948,6 +1077,7 @@ def td_step(engine, net, lr_shift, work=None, carousel=None, fused=False) -> TDW
     return work
 
 
+@_restart_keyword
 def train(engine, net, n_steps, lr_shift, carousel=None, fused=False):
     """``n_steps`` :func:`td_step` calls with one set of buffers.  ``fused=True``: ONE library call for all of them
     (``Batched2048.ntuple_td_train``, ``g2048_ntuple_td_train``) -- two launches per step and no Python
@@ -969,6 +1099,7 @@ def tc_update(net, tc, work, lr_shift, phases=3):
     net.tc_update(work.before.after, work.delta, lr_shift, tc, phases)
 
 
+@_restart_keyword
 def tc_step(engine, net, tc, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """:func:`td_step` with the temporal-coherence update in place of the TD(0) one: :func:`td_evaluate`, then
     :func:`tc_update` (two launches).  No host synchronisation; ``work`` (:func:`td_work`) is reused.  ``fused``: as in
@@ -978,6 +1109,7 @@ def tc_step(engine, net, tc, lr_shift, work=None, carousel=None, fused=False) ->
     return work
 
 
+@_restart_keyword
 def tc_train(engine, net, tc, n_steps, lr_shift, carousel=None, fused=False):
     """``n_steps`` :func:`tc_step` calls with one set of buffers.  ``fused=True``: ONE library call for all of them, as in
     :func:`train` (three launches per step); not with a ``carousel``."""
@@ -998,6 +1130,7 @@ def mean_update(net, mean, work, lr_shift, phases=3):
     net.mean_update(work.before.after, work.delta, lr_shift, mean, phases)
 
 
+@_restart_keyword
 def mean_step(engine, net, mean, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """:func:`td_step` with the batch-mean update in place of the summed one: :func:`td_evaluate`, then :func:`mean_update` (two
     launches).  Measured (profiles/r26_ntuple_mean_probe.txt): "4x6" with ``lr_shift`` 6 scores the same at
@@ -1009,6 +1142,7 @@ def mean_step(engine, net, mean, lr_shift, work=None, carousel=None, fused=False
     return work
 
 
+@_restart_keyword
 def mean_train(engine, net, mean, n_steps, lr_shift, carousel=None, fused=False):
     """``n_steps`` :func:`mean_step` calls with one set of buffers.  ``fused=True`` is the fused front half per step; there is no
     one-call trainer for this update."""
@@ -1020,6 +1154,7 @@ def mean_train(engine, net, mean, n_steps, lr_shift, carousel=None, fused=False)
     return net
 
 
+@_restart_keyword
 def tdl_evaluate(engine, net, trace, work, carousel=None, fused=False) -> TDWork:
     """:func:`td_evaluate` for the trace learners: evaluate, play the greedy move, evaluate the new boards, then one
     ``trace.push`` that stores the afterstate just played and forms ``work.delta`` in the same launch (in place of
@@ -1032,7 +1167,7 @@ def tdl_evaluate(engine, net, trace, work, carousel=None, fused=False) -> TDWork
         trace.push(work.before.after, work.before.after_value, work.after.best, engine.terminated, work.delta)
         return work
     if carousel is not None:
-        _carousel_of(engine, carousel)
+        carousel = _carousel_of(engine, carousel)
     engine.ntuple_evaluate(net, out=work.before)
     engine.step(work.before.action, auto_reset=True, want_info=False)
     if carousel is not None:
@@ -1048,6 +1183,7 @@ def _trace_of(engine, trace):
     return trace
 
 
+@_restart_keyword
 def tdl_step(engine, net, trace, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """One afterstate TD(lambda) step of every board of ``engine`` under ``net``: :func:`tdl_evaluate`, then
     ``net.trace_update``.  No host synchronisation; ``work`` (:func:`td_work`) is reused.  ``fused``: as in
@@ -1057,6 +1193,7 @@ def tdl_step(engine, net, trace, lr_shift, work=None, carousel=None, fused=False
     return work
 
 
+@_restart_keyword
 def tdl_train(engine, net, trace, n_steps, lr_shift, carousel=None, fused=False):
     """``n_steps`` :func:`tdl_step` calls with one set of buffers."""
     work = td_work(engine)
@@ -1065,6 +1202,7 @@ def tdl_train(engine, net, trace, n_steps, lr_shift, carousel=None, fused=False)
     return net
 
 
+@_restart_keyword
 def mean_tdl_step(engine, net, mean, trace, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """:func:`tdl_step` with the batch-mean trace update: :func:`tdl_evaluate`, then ``net.mean_trace_update`` (two launches, SUM
     then APPLY)."""
@@ -1073,6 +1211,7 @@ def mean_tdl_step(engine, net, mean, trace, lr_shift, work=None, carousel=None, 
     return work
 
 
+@_restart_keyword
 def mean_tdl_train(engine, net, mean, trace, n_steps, lr_shift, carousel=None, fused=False):
     """``n_steps`` :func:`mean_tdl_step` calls with one set of buffers."""
     work = td_work(engine)
@@ -1081,6 +1220,7 @@ def mean_tdl_train(engine, net, mean, trace, n_steps, lr_shift, carousel=None, f
     return net
 
 
+@_restart_keyword
 def tcl_step(engine, net, tc, trace, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """:func:`tdl_step` with the temporal-coherence trace update: :func:`tdl_evaluate`, then ``net.tc_trace_update`` (two
     launches, W then A)."""
@@ -1089,6 +1229,7 @@ def tcl_step(engine, net, tc, trace, lr_shift, work=None, carousel=None, fused=F
     return work
 
 
+@_restart_keyword
 def tcl_train(engine, net, tc, trace, n_steps, lr_shift, carousel=None, fused=False):
     """``n_steps`` :func:`tcl_step` calls with one set of buffers."""
     work = td_work(engine)
@@ -1103,6 +1244,7 @@ def _delay_of(engine, delay):
     return delay
 
 
+@_restart_keyword
 def delayed_evaluate(engine, net, delay, work, carousel=None, fused=False) -> TDWork:
     """:func:`tdl_evaluate` for the delayed learners: the same launches with ``delay.push`` (an :class:`NTupleDelay`) in place
     of ``trace.push``.  Shards that share one network run this on every shard before an update on any.  ``fused``: as in
@@ -1110,6 +1252,7 @@ def delayed_evaluate(engine, net, delay, work, carousel=None, fused=False) -> TD
     return tdl_evaluate(engine, net, _delay_of(engine, delay), work, carousel, fused)
 
 
+@_restart_keyword
 def delayed_tdl_step(engine, net, delay, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """One delayed TD(lambda) step of every board of ``engine`` under ``net``: :func:`delayed_evaluate`, then
     ``net.delay_update``.  No host synchronisation; ``work`` (:func:`td_work`) is reused.  Errors stay pending in ``delay``:
@@ -1119,6 +1262,7 @@ def delayed_tdl_step(engine, net, delay, lr_shift, work=None, carousel=None, fus
     return work
 
 
+@_restart_keyword
 def delayed_tdl_train(engine, net, delay, n_steps, lr_shift, carousel=None, fused=False):
     """``n_steps`` :func:`delayed_tdl_step` calls with one set of buffers, then the flush and ``delay.reset()``: no collected
     error is lost, and the next call starts every board's history anew."""
@@ -1131,6 +1275,7 @@ def delayed_tdl_train(engine, net, delay, n_steps, lr_shift, carousel=None, fuse
     return net
 
 
+@_restart_keyword
 def delayed_tcl_step(engine, net, tc, delay, lr_shift, work=None, carousel=None, fused=False) -> TDWork:
     """:func:`delayed_tdl_step` with the temporal-coherence update: :func:`delayed_evaluate`, then ``net.tc_delay_update``
     (two launches, W then A)."""
@@ -1139,6 +1284,7 @@ def delayed_tcl_step(engine, net, tc, delay, lr_shift, work=None, carousel=None,
     return work
 
 
+@_restart_keyword
 def delayed_tcl_train(engine, net, tc, delay, n_steps, lr_shift, carousel=None, fused=False):
     """``n_steps`` :func:`delayed_tcl_step` calls with one set of buffers, then the flush and ``delay.reset()``, as
     :func:`delayed_tdl_train`."""
@@ -1242,29 +1388,33 @@ def log_sweep(net, log, lr_shift, tc=None, mean=None, delta=None) -> torch.Tenso
     return delta
 
 
-def backward_train(engine, net, log, rounds, lr_shift, tc=None, mean=None, carousel=None):
+def backward_train(engine, net, log, rounds, lr_shift, tc=None, mean=None, carousel=None, restart=None):
     """Backward learning over logged segments (Matsuzaki 2017): ``rounds`` times
     { ``engine.ntuple_play_log(net, log)``; :func:`log_sweep` } -- play ``log.depth`` moves of every board under frozen weights
     in one launch, then update the logged afterstates from the last to the first.  ``tc`` and ``mean`` None (TD) or ``tc``: ONE
     library call for all rounds (``Batched2048.ntuple_log_train``, ``g2048_ntuple_log_train``); ``mean``: the same loop in
     Python.  The afterstates of slot M are updated by the next round, those of the last round never.  A learner of its own, not
     :func:`train` at ``depth=1``.  ``carousel`` is not offered (ValueError): its launches sit between a step and the next
-    evaluate, and the moves of a segment are one launch.  A spawn-stream engine only."""
+    evaluate, and the moves of a segment are one launch.  ``restart`` (a :class:`Restart` of this engine) is: its step is per
+    board and runs behind every move inside the play-log launch (``g2048_ntuple_play_log_restart``,
+    ``g2048_ntuple_log_train_restart``).  A spawn-stream engine only."""
     if carousel is not None:
         raise ValueError("backward_train cannot run a carousel: its launches sit between a step and the next evaluate, and the "
                          "moves of a segment are one launch (use the forward trainers)")
     if tc is not None and mean is not None:
         raise ValueError("backward_train takes tc or mean, not both")
     _log_of(engine, log)
+    if restart is not None:
+        _restart_of(engine, restart)
     if mean is None:
-        engine.ntuple_log_train(net, log, rounds, lr_shift, _log_delta_buffer(log, None), tc)
+        engine.ntuple_log_train(net, log, rounds, lr_shift, _log_delta_buffer(log, None), tc, restart=restart)
         return net
     if not isinstance(net, NTupleNet):
         raise ValueError("net must be an NTupleNet")
     net._own_mean(mean)
     delta = _log_delta_buffer(log, None)
     for _ in range(_int_arg("rounds", rounds, 0, (1 << 32) - 1)):
-        engine.ntuple_play_log(net, log)
+        engine.ntuple_play_log(net, log, restart=restart)
         log_sweep(net, log, lr_shift, mean=mean, delta=delta)
     return net
 

@@ -1040,6 +1040,84 @@ int g2048_ntuple_log_train(g2048_engine *e, const g2048_ntuple_net *net, uint32_
 int g2048_ntuple_staged_log_train(g2048_engine *e, const g2048_ntuple_staged_net *net, uint32_t rounds, uint32_t lr_shift,
                                   const g2048_ntuple_log *log, int64_t *delta, const g2048_ntuple_tc *tc, void *stream);
 
+/* Midpoint restart: a board whose episode has just ended goes back to the middle of the run that ended (INTEGRATION.md §25;
+ * the restart of K. Matsuzaki, "Developing a 2048 player with backward temporal coherence learning and restart", ACG 2017).
+ * Every episode starts from an empty board, and the last moves of a game, where the value function is worst, are seen once
+ * per few thousand steps.  Unlike the carousel above this needs no staged network, no pool and no batch-wide rank: the rule
+ * is a function of one board's own history.  Everything is integers and per board.
+ *
+ * The state of a restart for n boards, caller-owned device memory, zero-initialised, one per engine or shard:
+ *   stride_log2   k in 0..16: a snapshot every s = 2^k positions
+ *   capacity      C in 1..G2048_RESTART_MAX_CAPACITY (= 4096): snapshot slots per board
+ *   min_span      2..2^31: a run shorter than this is not restarted
+ *   max_restarts  1..2^32 - 1: restarts allowed in one lineage
+ *   snap          uint8 [C][n][16], slot-major, 16-byte aligned: slot j of board i holds the engine record, verbatim (cells and
+ *                 packed score), as it was at position (j + 1) * s of the board's current lineage
+ *   pos           uint32 [n]: position p, the non-terminating steps since the lineage's empty board
+ *   start         uint32 [n]: S, the position at which the current run began, 0 for a fresh game
+ *   restarts      uint32 [n]: restarts made so far in this lineage
+ * One operation, the restart step, after a step with auto-reset on.  Inputs: the live records and terminated[n] (uint8,
+ * non-zero = true).  For every board i:
+ *   terminated[i] == 0:
+ *     if pos[i] == 2^32 - 1 it stays, and nothing is stored.  Otherwise p = pos[i] + 1;  pos[i] = p
+ *     if p & (s - 1) == 0 and q = p >> k satisfies 1 <= q <= C:   snap[q - 1][i] = record[i]
+ *   terminated[i] != 0 (the record is already the fresh auto-reset board):
+ *     L = pos[i];  S = start[i];  R = L - S;  m = S + (R >> 1);  q = min(m >> k, C);  S' = q << k
+ *     if R >= min_span and restarts[i] < max_restarts and q >= 1 and S' > S:
+ *         record[i] = snap[q - 1][i];   start[i] = pos[i] = S';   restarts[i] += 1
+ *     otherwise the fresh board stays and start[i] = pos[i] = restarts[i] = 0
+ * The snapshot is always valid: S' > S and S' <= m <= L guarantee that slot q - 1 was written by the current run, and the slots
+ * at or below S belong to the prefix this run shares with the one before it.  So no slot is ever read that this lineage did not
+ * write, and no lane touches another board's state.
+ *   - The spawn stream is counter-based on the engine clock, so a restarted run does not replay the first one.
+ *   - The result depends on nothing but the board's own trajectory: the same bits for any launch geometry, and -- unlike the
+ *     carousel -- the shards of a batch reproduce the unsharded bits.
+ *   - A restarted board carries the score it was recorded with: g2048_get_scores, the last records and the statistics computed
+ *     from them then describe composite episodes; g2048_stats.return_sum, kept by conservation of the merge scores played, does
+ *     not see the recorded prefix of a restart (and has it subtracted while that episode runs): under a restart read the last
+ *     records instead.
+ *   - Against the paper: it records whole games and restarts exactly at the middle of the played part.  Here the restart point
+ *     is the last snapshot at or below that middle: up to s - 1 positions earlier, and earlier still once the middle lies beyond
+ *     C * s.  Memory is bounded at 16 C bytes per board (plus 12 of counters), however long a game gets.
+ * A call is ONE launch on `stream`, one board per lane in a grid-stride loop, no host synchronisation.  Every call validates
+ * before any HIP call, whichever is found first: k, C, min_span, max_restarts, NULL members, alignment (snap and the records 16
+ * bytes, the counters 4), n outside 1..2^32 - 256.  Each refusal is G2048_ERR_INVALID. */
+#define G2048_RESTART_MAX_STRIDE_LOG2 16
+#define G2048_RESTART_MAX_CAPACITY 4096
+typedef struct g2048_restart {
+    uint32_t stride_log2;   /* k, 0..16 */
+    uint32_t capacity;      /* C, 1..4096 */
+    uint32_t min_span;      /* 2..2^31 */
+    uint32_t max_restarts;  /* 1..2^32 - 1 */
+    uint8_t *snap;          /* [C][n][16] slot-major, 16-byte aligned */
+    uint32_t *pos;          /* [n] */
+    uint32_t *start;        /* [n] */
+    uint32_t *restarts;     /* [n] */
+} g2048_restart;
+/* The restart step on the engine's live records; `terminated` is the uint8[n] output of the step just made (device memory).
+ * Enqueued on `stream` and ordered against the engine's own launches the way g2048_carousel_step is.  Consumes no randomness
+ * and leaves the clock and the episode bookkeeping alone. */
+int g2048_restart_step(g2048_engine *e, const g2048_restart *restart, const uint8_t *terminated, void *stream);
+/* The same on any device array of n engine records (uint8[n][16], 16-byte aligned), updated in place.  Needs no engine; runs
+ * on the current device.  1 <= n <= 2^32 - 256. */
+int g2048_restart_step_plain(uint8_t *records, uint64_t n, const uint8_t *terminated, const g2048_restart *restart, void *stream);
+/* Restart inside the move log.  The contract in one sentence: after a call of depth M the engine, the restart state and the
+ * log hold the bits of M rounds of g2048_ntuple_evaluate -> g2048_step(auto_reset = 1) -> g2048_restart_step, slot m holding
+ * what play_log defines for round m.  The step that ends an episode is flagged ENDED exactly as in play_log, so log_delta and
+ * log_sweep do not change; the restart runs inside the one launch, which g2048_carousel_step cannot.  log_train_restart is
+ * log_train with this play_log.  Refuses what play_log (log_train) refuses and what g2048_restart_step refuses of `restart`,
+ * before any HIP call.  g2048_ntuple_play has no such form: a game report must not restart. */
+int g2048_ntuple_play_log_restart(g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_log *log,
+                                  const g2048_restart *restart, void *stream);
+int g2048_ntuple_staged_play_log_restart(g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_ntuple_log *log,
+                                         const g2048_restart *restart, void *stream);
+int g2048_ntuple_log_train_restart(g2048_engine *e, const g2048_ntuple_net *net, uint32_t rounds, uint32_t lr_shift,
+                                   const g2048_ntuple_log *log, int64_t *delta, const g2048_ntuple_tc *tc /* NULL: the TD update */,
+                                   const g2048_restart *restart, void *stream);
+int g2048_ntuple_staged_log_train_restart(g2048_engine *e, const g2048_ntuple_staged_net *net, uint32_t rounds, uint32_t lr_shift,
+                                          const g2048_ntuple_log *log, int64_t *delta, const g2048_ntuple_tc *tc,
+                                          const g2048_restart *restart, void *stream);
+
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream);
