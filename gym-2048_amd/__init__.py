@@ -21,7 +21,7 @@ def __getattr__(name):
                 "tcl_train", "NTupleDelay", "delayed_evaluate", "delayed_tdl_step", "delayed_tdl_train", "delayed_tcl_step",
                 "delayed_tcl_train", "Carousel", "PlayReport", "play_games", "DeepPlayer", "NTupleAdaptive",
                 "AdaptivePlayer", "ReducedPlayer", "TDWork", "td_work", "td_evaluate", "td_update", "NTupleLog", "log_sweep",
-                "backward_train", "Restart"):  # need torch + a GPU; imported on first use
+                "backward_train", "Restart", "Downgrade", "Downgraded", "DowngradedPlayer", "downgrade"):  # need torch + a GPU; imported on first use
         from . import batched
         return getattr(batched, name)
     raise AttributeError(name)

@@ -264,6 +264,14 @@ class RestartC(C.Structure):
     ]
 
 
+class DowngradeC(C.Structure):
+    """g2048_downgrade (include/g2048.h): the rule of tile-downgrading, in exponents."""
+    _fields_ = [
+        ("min_exp", C.c_uint32),
+        ("floor_exp", C.c_uint32),
+    ]
+
+
 class Stats(C.Structure):
     """g2048_stats (include/g2048.h)."""
     _fields_ = [
@@ -326,6 +334,11 @@ SIGNATURES = {
     "g2048_ntuple_play": (C.c_int, [_E, C.POINTER(NTupleNetC), _u32, C.POINTER(NTuplePlayIO), _S]),
     "g2048_ntuple_staged_play": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), _u32, C.POINTER(NTuplePlayIO), _S]),
     "g2048_play_step": (C.c_int, [_E, C.c_void_p, _i32, C.POINTER(NTuplePlayIO), _S]),
+    "g2048_downgrade_plain": (C.c_int, [C.c_void_p, _u64, C.POINTER(DowngradeC), C.c_void_p, C.c_void_p, _S]),
+    "g2048_downgrade_boards": (C.c_int, [_E, C.POINTER(DowngradeC), C.c_void_p, C.c_void_p, C.c_void_p, _S]),
+    "g2048_ntuple_play_downgraded": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(DowngradeC), _u32, C.POINTER(NTuplePlayIO), _S]),
+    "g2048_ntuple_staged_play_downgraded": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(DowngradeC), _u32,
+                                                     C.POINTER(NTuplePlayIO), _S]),
     "g2048_ntuple_td_step": (C.c_int, [_E, C.POINTER(NTupleNetC), C.POINTER(NTupleTDIO), _S]),
     "g2048_ntuple_staged_td_step": (C.c_int, [_E, C.POINTER(NTupleStagedNetC), C.POINTER(NTupleTDIO), _S]),
     "g2048_ntuple_td_train": (C.c_int, [_E, C.POINTER(NTupleNetC), _u32, _u32, C.POINTER(NTupleTDIO), C.POINTER(NTupleTCC), _S]),

@@ -34,6 +34,7 @@ from .ntuple import PlayReport, play_games, _check_tensor, _play_io  # noqa: F40
 from .ntuple import TDWork, td_evaluate, td_update, td_work, _td_io  # noqa: F401
 from .ntuple import NTupleLog, backward_train, log_sweep, _log_of  # noqa: F401
 from .ntuple import Restart, _restart_of  # noqa: F401
+from .ntuple import Downgrade, Downgraded, DowngradedPlayer, downgrade, _downgraded_out, _rule  # noqa: F401
 
 _ACTION_DTYPES = {torch.uint8: _lib.ACT_U8, torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}
 
@@ -738,7 +739,23 @@ class Batched2048:
         check(net._fn("evaluate")(self._h, ref, C.byref(io), self._stream()))
         return out
 
-    def ntuple_play(self, net, k_steps, games_left=None, hist=None, moves=None):
+    def downgraded_boards(self, rule, active=None, out=None) -> Downgraded:
+        """Tile-downgrading of the live boards (``g2048_downgrade_boards``): ``Downgraded(boards [n, 16]
+        uint8, missing [n] uint8)`` on the engine's stream, as :func:`downgrade` -- plain exponents, whatever the scores.
+        ``rule``: a :class:`Downgrade`.  ``active``: a uint32 ``[n]`` device tensor -- a board at 0 gets the all-empty board and
+        ``missing`` 0xff; every ``NTupleNet`` search of plain boards answers the empty board at once with action 0, so
+        ``downgraded_boards(rule, active=left)``, a plain search and :meth:`play_step` play budgeted games with look-ahead on
+        translated boards.  ``out``: a preallocated ``Downgraded`` (``missing`` may be None).  Either RNG mode.  Touches no
+        record, clock, statistic or randomness."""
+        ref = _rule(rule)
+        out = _downgraded_out(self.n_envs, self.device, out)
+        if active is not None:
+            _check_tensor("active", active, (torch.uint32,), (self.n_envs,), self.device)
+        check(self._lib.g2048_downgrade_boards(self._h, ref, None if active is None else active.data_ptr(), out.boards.data_ptr(),
+                                               None if out.missing is None else out.missing.data_ptr(), self._stream()))
+        return out
+
+    def ntuple_play(self, net, k_steps, games_left=None, hist=None, moves=None, downgrade=None):
         """``k_steps`` moves of the greedy player of an n-tuple network on every board in ONE launch (``g2048_ntuple_play``,
         INTEGRATION.md §16), on the engine's stream: the records, the clock, the statistics and the terminal records end up
         as after ``k_steps`` rounds of ``step(ntuple_evaluate(net).action)``, bit for bit; no per-step output is written.
@@ -747,13 +764,20 @@ class Batched2048:
         highest tile 2^k; ``moves`` uint64 ``[1]`` += the moves played.  A spawn-stream engine only (``rng="philox"``).
         Measured (profiles/r19_ntuple_play_probe.txt): per move this launch is NOT faster than the
         per-move loop at 1 024 boards (23 against 17 µs for "4x6") nor at 2^20 (15 % slower); it ties at 65 536.  What it
-        buys is the budgeted form -- exactly G games per board, :func:`play_games` -- and K moves without the host."""
+        buys is the budgeted form -- exactly G games per board, :func:`play_games` -- and K moves without the host.
+        ``downgrade`` (a :class:`Downgrade`; None: the call as it always was): every move is the greedy player's on the
+        TRANSLATED board (``g2048_ntuple_play_downgraded``; a staged network takes the stage of the
+        translated board) while the record is stepped, reset and counted as before -- the bits of ``k_steps`` rounds of
+        ``downgraded_boards``, ``net.evaluate`` of those boards and ``play_step`` of its action."""
         if not isinstance(net, NTupleNet):
             raise ValueError("net must be an NTupleNet")
         ref = net._ref(self.device)
         k_steps = _int_arg("k_steps", k_steps, 0, (1 << 32) - 1)
         io = _play_io(self.n_envs, self.device, games_left, hist, moves)
-        check(net._fn("play")(self._h, ref, k_steps, C.byref(io), self._stream()))
+        if downgrade is None:
+            check(net._fn("play")(self._h, ref, k_steps, C.byref(io), self._stream()))
+        else:
+            check(net._fn("play_downgraded")(self._h, ref, _rule(downgrade), k_steps, C.byref(io), self._stream()))
         if k_steps:
             self._fresh = False
 

@@ -1554,6 +1554,62 @@ template <class Net> static int ntuple_play(g2048_engine *e, const Net *net, uin
     return G2048_OK;
 }
 
+// g2048_downgrade -> the kernels' rule, or G2048_ERR_INVALID (before any HIP call: works without a device)
+static int downgrade_rule(const g2048_downgrade *rule, g2048::DowngradeArgs *out)
+{
+    if (!rule)
+        return fail(G2048_ERR_INVALID, "rule is NULL");
+    if (rule->min_exp < 1u || rule->min_exp > 31u)
+        return fail(G2048_ERR_INVALID, "downgrade min_exp=%u: need 1..31", rule->min_exp);
+    if (rule->floor_exp < G2048_DOWNGRADE_MIN_FLOOR || rule->floor_exp > 31u)
+        return fail(G2048_ERR_INVALID, "downgrade floor_exp=%u: need %d..31", rule->floor_exp, G2048_DOWNGRADE_MIN_FLOOR);
+    *out = g2048::DowngradeArgs{rule->min_exp, rule->floor_exp};
+    return G2048_OK;
+}
+
+// g2048_ntuple_play with every move chosen on the translated board: the same checks, clock and bookkeeping.  The engine is
+// looked at after everything that can be refused without it.
+template <class Net>
+static int ntuple_play_downgraded(g2048_engine *e, const Net *net, const g2048_downgrade *rule, uint32_t k_steps,
+                                  const g2048_ntuple_play_io *io, void *stream)
+{
+    g2048::NtupleNet nn;
+    if (int rc = ntuple_net(net, &nn))
+        return rc;
+    g2048::DowngradeArgs dr;
+    if (int rc = downgrade_rule(rule, &dr))
+        return rc;
+    g2048::NtuplePlayOut o;
+    if (int rc = ntuple_play_out(io, &o))
+        return rc;
+    if (int rc = usable(e))
+        return rc;
+    if (e->st.rng)
+        return fail(G2048_ERR_INVALID, "g2048_ntuple_play_downgraded needs the spawn stream: this engine is in numpy-RNG mode, whose "
+                                       "fused form is not offered (play it with g2048_downgrade_boards, g2048_ntuple_evaluate_plain "
+                                       "and g2048_step)");
+    if (k_steps == 0)
+        return G2048_OK;
+    G2048_HIP(hipSetDevice(e->device));
+    e->t += 1; // transaction of the first fused step
+    e->fresh = 0;
+    g2048::StepArgs a = make_args(e, nullptr, 1);
+    a.k_steps = k_steps;
+    G2048_HIP(g2048::launch_ntuple_play_downgraded(a, nn, dr, o, static_cast<hipStream_t>(stream)));
+    e->t += k_steps - 1;
+    return G2048_OK;
+}
+
+// The outputs of a translation: out [n][16], missing [n] or NULL
+static int downgrade_out(const uint8_t *out)
+{
+    if (!out)
+        return fail(G2048_ERR_INVALID, "out is NULL");
+    if (reinterpret_cast<uintptr_t>(out) & 15u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: downgrade out needs 16 bytes");
+    return G2048_OK;
+}
+
 // g2048_ntuple_td_io -> the kernel's outputs, or G2048_ERR_INVALID (before any HIP call: works without a device).  what: the
 // entry point, for the one message that names it; train: after and delta are what its update reads
 static int ntuple_td_out(const g2048_ntuple_td_io *io, const char *what, bool train, g2048::NtupleTdIo *o)
@@ -2132,6 +2188,50 @@ int g2048_ntuple_staged_td_train(g2048_engine *e, const g2048_ntuple_staged_net 
                                  const g2048_ntuple_td_io *work, const g2048_ntuple_tc *tc, void *stream)
 {
     return ntuple_td_train(e, net, k_steps, lr_shift, work, tc, stream);
+}
+
+int g2048_ntuple_play_downgraded(g2048_engine *e, const g2048_ntuple_net *net, const g2048_downgrade *rule, uint32_t k_steps,
+                                 const g2048_ntuple_play_io *io, void *stream)
+{
+    return ntuple_play_downgraded(e, net, rule, k_steps, io, stream);
+}
+
+int g2048_ntuple_staged_play_downgraded(g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_downgrade *rule,
+                                        uint32_t k_steps, const g2048_ntuple_play_io *io, void *stream)
+{
+    return ntuple_play_downgraded(e, net, rule, k_steps, io, stream);
+}
+
+int g2048_downgrade_plain(const uint8_t *boards, uint64_t n, const g2048_downgrade *rule, uint8_t *out, uint8_t *missing, void *stream)
+{
+    if (int rc = plain_boards(boards, n))
+        return rc;
+    g2048::DowngradeArgs dr;
+    if (int rc = downgrade_rule(rule, &dr))
+        return rc;
+    if (int rc = downgrade_out(out))
+        return rc;
+    G2048_HIP(g2048::launch_downgrade(reinterpret_cast<const uint4 *>(boards), static_cast<uint32_t>(n), dr, nullptr,
+                                      reinterpret_cast<uint4 *>(out), missing, static_cast<hipStream_t>(stream)));
+    return G2048_OK;
+}
+
+int g2048_downgrade_boards(const g2048_engine *e, const g2048_downgrade *rule, const uint32_t *active, uint8_t *out, uint8_t *missing,
+                           void *stream)
+{
+    g2048::DowngradeArgs dr;
+    if (int rc = downgrade_rule(rule, &dr))
+        return rc;
+    if (int rc = downgrade_out(out))
+        return rc;
+    if (reinterpret_cast<uintptr_t>(active) & 3u)
+        return fail(G2048_ERR_INVALID, "misaligned buffer: downgrade active needs 4 bytes");
+    if (int rc = usable(e)) // (after everything that can be refused without an engine)
+        return rc;
+    G2048_HIP(hipSetDevice(e->device));
+    G2048_HIP(g2048::launch_downgrade(e->st.boards, static_cast<uint32_t>(e->n), dr, active, reinterpret_cast<uint4 *>(out), missing,
+                                      static_cast<hipStream_t>(stream)));
+    return G2048_OK;
 }
 
 int g2048_ntuple_play_log(g2048_engine *e, const g2048_ntuple_net *net, const g2048_ntuple_log *log, void *stream)

@@ -2306,6 +2306,74 @@ G2048_DEV StepOut ntuple_play_step(Board &rec, uint64_t t, uint32_t board, uint3
     return play_record(rec, action, w, max_exp, tb);
 }
 
+// ------------------------------------------------------- tile-downgrading: a board of very large tiles, translated
+// g2048_downgrade_plain / _boards / g2048_ntuple_play_downgraded (include/g2048.h; after Guei, Chen & Wu
+// 2022 -- the choice of k and the guard below are this project's own).  In exponents e_c = byte & 0x1f of cell c, so the rule
+// reads an engine record as well as a plain board and the score bits of a record never reach the result:
+//   P = the exponents e >= 1 on the board, D = those held by two or more cells, m = max P (empty board: identity, k = 0)
+//   m < min_exp: identity, k = 0
+//   k = the LARGEST c with floor_exp <= c < m, c not in P and (c - 1) not in D; none: identity, k = 0
+//   out_c = e_c - 1 where e_c > k, else e_c
+// k is the "missing tile".  The guard on c - 1 keeps the translated board honest one move ahead: two tiles 2^(k-1) could merge
+// into a real 2^k, which would sit beside the halved 2^(k+1) and look mergeable with it (deeper collisions of this kind are
+// accepted).  The map is strictly increasing on the tiles of one board, so a move is legal on the translated board exactly
+// where it is legal on the board, and slides and merges the same cells; only the gains of halved tiles differ.  One
+// application.  Integers only, no table: P and D from 16 byte extracts, the subtraction SWAR on the four rows -- after masking
+// to 5 bits, ((row + (31 - k) * 0x01010101) >> 5) & 0x01010101 is 1 exactly where e > k, and no carry crosses a byte
+// (31 + 27 < 256: k >= kDowngradeMinFloor).
+constexpr uint32_t kDowngradeMinFloor = 4u;  // = G2048_DOWNGRADE_MIN_FLOOR: the spawn tiles and their first merge stay below k
+constexpr uint32_t kDowngradeSkipped = 0xffu; // = G2048_DOWNGRADE_SKIPPED
+
+struct DowngradeRule {
+    uint32_t min_exp;   // 1..31
+    uint32_t floor_exp; // kDowngradeMinFloor..31
+};
+
+struct Downgraded {
+    Board cells; // plain exponents: every byte below 32
+    uint32_t k;  // the missing tile's exponent; 0: the board came through unchanged
+};
+
+G2048_DEV Downgraded downgrade_cells(const Board &raw, const DowngradeRule &rule)
+{
+    Downgraded out;
+    uint32_t present = 0, twice = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        out.cells.r[i] = raw.r[i] & kCellBits;
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const uint32_t bit = 1u << ((out.cells.r[i] >> (8 * l)) & 0x1fu);
+            twice |= present & bit;
+            present |= bit;
+        }
+    }
+    present &= ~1u; // (empty cells are no tile)
+    twice &= ~1u;
+    const uint32_t m = 31u - g2048_clz(present | 1u); // 0 on the empty board: no candidate below it
+    uint32_t cand = ~present & ~(twice << 1) & ((1u << m) - 1u) & ~((1u << rule.floor_exp) - 1u);
+    cand = m < rule.min_exp ? 0u : cand;
+    out.k = cand != 0u ? 31u - g2048_clz(cand) : 0u;
+    const uint32_t add = (31u - out.k) * 0x01010101u, ones = out.k != 0u ? 0x01010101u : 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        out.cells.r[i] -= ((out.cells.r[i] + add) >> 5) & ones;
+    return out;
+}
+
+// One move of g2048_ntuple_play_downgraded on a record: ntuple_play_step with the action of ntuple_root on the TRANSLATED cells
+// of the record (a staged network so takes the stage of the translated board); the record itself is stepped as before, so the
+// gain, the spawn and the end of the episode are the real game's.
+template <uint32_t T, class Shape, class Tables>
+G2048_DEV StepOut ntuple_play_downgraded_step(Board &rec, uint64_t t, uint32_t board, uint32_t seed_lo, uint32_t seed_hi, const Shape &sh,
+                                              uint32_t F, const int32_t *weights, uint32_t max_exp, const DowngradeRule &rule,
+                                              const Tables &tb, Words &w)
+{
+    w = philox4x32_10(static_cast<uint32_t>(t), static_cast<uint32_t>(t >> 32), board, 0u, seed_lo, seed_hi);
+    const uint32_t action = ntuple_root<T>(downgrade_cells(rec, rule).cells, sh, F, weights, tb).action;
+    return play_record(rec, action, w, max_exp, tb);
+}
+
 // ------------------------------------------------------- one fused TD step of the greedy n-tuple player on a record
 // g2048_ntuple_td_step (include/g2048.h): the front half of every n-tuple learner on one record --
 // ntuple_root, the step g2048_step makes of its action (the Philox block (t, board), play_record), the auto-reset, and

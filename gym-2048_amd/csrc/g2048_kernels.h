@@ -166,6 +166,17 @@ struct NtuplePlayOut {
     unsigned long long *moves; // [1] += (board, step) pairs played
 };
 hipError_t launch_ntuple_play(const StepArgs &a, const NtupleNet &net, const NtuplePlayOut &io, hipStream_t s);
+// Tile-downgrading (g2048_downgrade, checked by the caller): min_exp in 1..31, floor_exp in 4..31
+struct DowngradeArgs {
+    uint32_t min_exp, floor_exp;
+};
+// g2048_ntuple_play_downgraded: launch_ntuple_play with every move chosen on the translated board
+hipError_t launch_ntuple_play_downgraded(const StepArgs &a, const NtupleNet &net, const DowngradeArgs &rule, const NtuplePlayOut &io,
+                                         hipStream_t s);
+// g2048_downgrade_plain / _boards: out[i] = the translation of boards[i] (plain boards or records; out may be boards),
+// missing[i] (or NULL) = its k; active (or NULL): a board at 0 gets the empty board and G2048_DOWNGRADE_SKIPPED
+hipError_t launch_downgrade(const uint4 *boards, uint32_t n, const DowngradeArgs &rule, const uint32_t *active, uint4 *out,
+                            uint8_t *missing, hipStream_t s);
 // g2048_play_step: one step of that launch with the actions of a.actions (action_dtype G2048_ACT_*, checked by the caller)
 hipError_t launch_play_step(const StepArgs &a, int action_dtype, const NtuplePlayOut &io, hipStream_t s);
 // g2048_ntuple_td_step: one greedy step with auto-reset and the evaluate on either side of it in one launch (spawn stream

@@ -1903,6 +1903,85 @@ __global__ void __launch_bounds__(kBlock) ntuple_play_kernel(const StepArgs p, c
     }
 }
 
+// g2048_ntuple_play_downgraded: ntuple_play_kernel with the action taken on the translated cells of the record
+// (ntuple_play_downgraded_step of g2048_device.h) -- the same lane layout, the same bookkeeping, the same side outputs, all of
+// them describing the real game.  The body is ntuple_play_kernel's, copied: a flag in that kernel, or its body shared as a
+// __device__ function, would move the register allocation of its 24 instantiations (what happened with play_step_kernel,
+// below), so that kernel stays as it was and this one has 24 of its own (profiles/r30_downgrade_resource_usage.txt).
+template <uint32_t T, class Shape>
+__global__ void __launch_bounds__(kBlock) ntuple_play_downgraded_kernel(const StepArgs p, const Shape sh, uint32_t frac_bits,
+                                                                        const int32_t *__restrict__ weights, const DowngradeRule rule,
+                                                                        const NtuplePlayOut io)
+{
+    __shared__ WaveTables s_tables[kBlock / 64];
+    const Lane ln = lane_of<kBlock, false>(p.n);
+    Board rec = load_board(p.st.boards, ln.i);
+    const LdsTables tb = stage_tables(s_tables, load_tables_piece());
+    const EpisodeCounters counters = load_episode_counters(p, ln.i_raw);
+    uint32_t left = io.games_left ? io.games_left[ln.i] : 1u; // (no limit: never decremented)
+    uint64_t t = (static_cast<uint64_t>(p.t_hi) << 32) | p.t_lo; // transaction of the first step
+    uint32_t episodes = 0, illegal_ends = 0, played = 0, gained32 = 0;
+    unsigned long long gained = 0; // as in ntuple_play_kernel: 32-bit adds, folded into 64 bits every kGainFold steps
+    for (uint32_t j = 0; j < p.k_steps; ++j, ++t) {
+        const bool go = left != 0u;
+        if (__builtin_amdgcn_ballot_w64(go) == 0ull)
+            break;
+        StepOut o{}; // a board that sits the step out: gain 0, not terminated
+        Words w{};
+        if (go)
+            o = ntuple_play_downgraded_step<T>(rec, t, p.board_offset + ln.i, p.seed_lo, p.seed_hi, sh, frac_bits, weights, p.max_exp,
+                                               rule, tb, w);
+        played += go ? 1u : 0u;
+        gained32 += o.gain;
+        const bool fin = o.terminated && ln.valid;
+        record_episode_ends(p, ln.i, fin, !o.legal, rec, episodes, illegal_ends);
+        if (o.terminated) {
+            if (fin && io.hist)
+                atomicAdd(io.hist + highest(record_cells(rec)), 1ull);
+            reset_record(rec, o, w, tb);
+            if (io.games_left)
+                left -= 1u;
+        }
+        if ((j + 1u) % kGainFold == 0u) {
+            gained += gained32;
+            gained32 = 0;
+        }
+    }
+    gained += gained32;
+    if (ln.valid) {
+        store_board(p.st.boards, ln.i, rec);
+        if (io.games_left)
+            io.games_left[ln.i] = left;
+    }
+    // a board that was stepped has been reset at every episode end; one that sat the whole launch out keeps its mark
+    const unsigned long long pending = ((static_cast<unsigned long long>(counters.pend_hi) << 32) | counters.pend_lo) &
+                                       ~__builtin_amdgcn_ballot_w64(played != 0u);
+    flush_episode_counts(counters, episodes, illegal_ends, wave_sum64_lane63(ln.valid ? gained : 0ull), pending);
+    if (io.moves) { // (wave-uniform)
+        const unsigned long long total = wave_sum64_lane63(ln.valid ? played : 0u);
+        if ((threadIdx.x & 63u) == 63u && total != 0ull)
+            atomicAdd(io.moves, total);
+    }
+}
+
+// g2048_downgrade_plain / g2048_downgrade_boards: downgrade_cells of every board, one board per lane, 16 B in and 16 (+ 1) B
+// out; no LDS, no table.  `boards` are plain boards or engine records (the rule masks every byte to its cell), and `out` may be
+// `boards`: a lane reads its board before it writes it, and no lane reads another's (so neither pointer is __restrict__).
+// active (NULL: every board): a board at 0 gets the all-empty board and kDowngradeSkipped.
+__global__ void __launch_bounds__(kBlock) downgrade_kernel(const uint4 *boards, uint32_t n, const DowngradeRule rule,
+                                                           const uint32_t *__restrict__ active, uint4 *out, uint8_t *__restrict__ missing)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    Downgraded d = downgrade_cells(load_board(boards, i), rule);
+    if (active && active[i] == 0u) // (active: wave-uniform)
+        d = Downgraded{Board{{0u, 0u, 0u, 0u}}, kDowngradeSkipped};
+    store_board(out, i, d.cells);
+    if (missing)
+        missing[i] = static_cast<uint8_t>(d.k);
+}
+
 // g2048_play_step: ONE step of every board under that contract with the action read from a buffer (ACT as in step_kernel: 0 =
 // the synthetic policy of the transaction, 1 / 2 / 3 = uint8 / int32 / int64) -- g2048_ntuple_play with k_steps == 1 for any
 // player.  The same lane layout for the same reason: one board per lane, the wavefront owns its episode slot.  The body is
@@ -3132,6 +3211,24 @@ hipError_t launch_ntuple_play(const StepArgs &a, const NtupleNet &net, const Ntu
     return dispatch_tuples(net, [&](auto tc, auto sh) {
         return launch_1d(ntuple_play_kernel<tc, decltype(sh)>, a.n, 0, s, a, sh, net.frac_bits, static_cast<const int32_t *>(net.weights), io);
     });
+}
+
+hipError_t launch_ntuple_play_downgraded(const StepArgs &a, const NtupleNet &net, const DowngradeArgs &rule, const NtuplePlayOut &io,
+                                         hipStream_t s)
+{
+    if (a.k_steps == 0)
+        return hipSuccess;
+    const DowngradeRule r{rule.min_exp, rule.floor_exp};
+    return dispatch_tuples(net, [&](auto tc, auto sh) {
+        return launch_1d(ntuple_play_downgraded_kernel<tc, decltype(sh)>, a.n, 0, s, a, sh, net.frac_bits,
+                         static_cast<const int32_t *>(net.weights), r, io);
+    });
+}
+
+hipError_t launch_downgrade(const uint4 *boards, uint32_t n, const DowngradeArgs &rule, const uint32_t *active, uint4 *out,
+                            uint8_t *missing, hipStream_t s)
+{
+    return launch_1d(downgrade_kernel, n, 0, s, boards, n, DowngradeRule{rule.min_exp, rule.floor_exp}, active, out, missing);
 }
 
 hipError_t launch_ntuple_td_step(const StepArgs &a, const NtupleNet &net, const NtupleTdIo &io, hipStream_t s)

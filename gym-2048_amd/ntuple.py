@@ -50,6 +50,10 @@ the last snapshot at or below the middle of the run that ended -- per board, int
 across shards; every trainer takes it as ``restart=`` (keyword only) where it takes ``carousel=``, and ``Batched2048.ntuple_play_log`` and
 :func:`backward_train` run it inside the play-log launch (``g2048_ntuple_play_log_restart``,
 ``g2048_ntuple_log_train_restart``).  Opt-in.
+``Downgrade``, :func:`downgrade`, ``Batched2048.downgraded_boards``, ``Batched2048.ntuple_play(..., downgrade=)``,
+``play_games(..., downgrade=)`` and ``DowngradedPlayer`` are tile-downgrading, and ``NTupleNet.fill_value`` /
+``NTupleNet(..., init_value=)`` optimistic initialisation -- the two ideas of Guei, Chen & Wu 2022 (``g2048_downgrade_*``,
+``g2048_ntuple_play_downgraded``).  Opt-in.
 """
 from __future__ import annotations
 
@@ -61,7 +65,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from ._lib import CarouselC, RestartC, NTupleAdaptiveIO, NTupleDeepIO, NTupleReducedIO, NTupleDelayC, NTupleIO, NTupleMeanC, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTDIO, NTupleTraceC, check
+from ._lib import CarouselC, DowngradeC, RestartC, NTupleAdaptiveIO, NTupleDeepIO, NTupleReducedIO, NTupleDelayC, NTupleIO, NTupleMeanC, NTupleNetC, NTuplePlayIO, NTupleSearchIO, NTupleStagedNetC, NTupleTCC, NTupleTDIO, NTupleTraceC, check
 from .analysis import _bind_out, _int_arg, _plain_boards
 
 MAX_TUPLES, MAX_LEN, MAX_FRAC_BITS, MAX_LR_SHIFT = 8, 6, 16, 40   # G2048_NTUPLE_MAX_* (include/g2048.h)
@@ -81,6 +85,7 @@ RESTART_MAX_RESTARTS = 2**32 - 1                                  # g2048_restar
 LOG_MAX_DEPTH, LOG_VALID, LOG_ENDED = 1024, 1, 2                  # G2048_NTUPLE_LOG_MAX_DEPTH, G2048_NTUPLE_LOG_VALID, G2048_NTUPLE_LOG_ENDED
 NTUPLE_END = 0xff                                                 # G2048_NTUPLE_END: pads a cell list shorter than tuple_len
 SEEN_UNKNOWN = 0xff                                               # Carousel.seen: the stage of the episode is not known yet
+DOWNGRADE_MIN_FLOOR, DOWNGRADE_SKIPPED = 4, 0xff                  # G2048_DOWNGRADE_MIN_FLOOR, G2048_DOWNGRADE_SKIPPED
 
 # Default shapes, as row-major cell indices (cell 4r + c).  The value sums every tuple over the eight symmetries of the
 # board, so a shape lists each tuple once, not once per placement.
@@ -272,6 +277,66 @@ def _play_io(n, device, games_left, hist, moves):
     return io
 
 
+def _tile_exp(name, tile, lo, hi):
+    """log2 of ``tile``, a power of two in 2^lo .. 2^hi."""
+    tile = _int_arg(name, tile, 1 << lo, 1 << hi)
+    if tile & (tile - 1):
+        raise ValueError(f"{name} must be a power of two, not {tile}")
+    return tile.bit_length() - 1
+
+
+class Downgrade:
+    """The rule of tile-downgrading (``g2048_downgrade``; after Guei, Chen & Wu 2022): at play time a board
+    whose largest tile is at least ``min_tile`` is translated into a board the network knows better -- the largest tile value
+    ``2^k >= floor_tile`` below its largest tile that is missing from the board, and not about to be made by two tiles
+    ``2^(k-1)``, is picked and every tile above it is halved -- and the move is chosen on the translated board.  ``min_tile``: a
+    power of two in 2..2^31; ``floor_tile``: one in 16..2^31.  The choice of the missing tile and its guard are this project's
+    own, and activation is a parameter here (the paper activates on the 32768 tile)."""
+
+    def __init__(self, min_tile=32768, floor_tile=16):
+        self._c = DowngradeC(_tile_exp("min_tile", min_tile, 1, 31), _tile_exp("floor_tile", floor_tile, DOWNGRADE_MIN_FLOOR, 31))
+        self.min_tile, self.floor_tile = int(min_tile), int(floor_tile)
+
+    def __repr__(self):
+        return f"Downgrade(min_tile={self.min_tile}, floor_tile={self.floor_tile})"
+
+
+def _rule(rule):
+    if not isinstance(rule, Downgrade):
+        raise ValueError("rule must be a Downgrade")
+    return C.byref(rule._c)
+
+
+class Downgraded(NamedTuple):
+    """Result of :func:`downgrade` / ``Batched2048.downgraded_boards``."""
+    boards: torch.Tensor              # uint8 [n, 16]: the translated boards, plain exponents
+    missing: Optional[torch.Tensor]   # uint8 [n]: the exponent k of the missing tile, 0 = unchanged, 0xff = masked out
+
+
+def _downgraded_out(n, device, out):
+    """(boards, missing) tensors of a translation: fresh ones, or those of ``out`` (missing may be None), checked."""
+    if out is None:
+        return Downgraded(torch.empty((n, 16), dtype=torch.uint8, device=device), torch.empty(n, dtype=torch.uint8, device=device))
+    boards, missing = out
+    _check_tensor("out.boards", boards, (torch.uint8,), (n, 16), device)
+    if missing is not None:
+        _check_tensor("out.missing", missing, (torch.uint8,), (n,), device)
+    return Downgraded(boards, missing)
+
+
+def downgrade(boards, rule, out=None) -> Downgraded:
+    """Tile-downgrading of plain boards (``g2048_downgrade_plain``): ``boards`` a device ``uint8``
+    ``[n, 16]`` or ``[n, 4, 4]`` tensor of exponents, ``rule`` a :class:`Downgrade`.  One launch on the current stream of the
+    boards' device.  ``out``: a preallocated :class:`Downgraded` (``missing`` may be None); ``out.boards`` may be ``boards``
+    itself (in place)."""
+    n, device = _plain_boards(boards)
+    ref = _rule(rule)
+    out = _downgraded_out(n, device, out)
+    _on_stream(_lib.load().g2048_downgrade_plain, device, boards.data_ptr(), n, ref, out.boards.data_ptr(),
+               None if out.missing is None else out.missing.data_ptr())
+    return out
+
+
 class NTupleNet:
     """T tuples of L cells with a table of 16^L int32 weights each; a weight is a score in units of 2^-``frac_bits``.
 
@@ -285,6 +350,8 @@ class NTupleNet:
     ``table_offsets[t]`` on, and ``weights`` is int32 ``[W]``, ``W = n_weights`` = the sum of the table sizes (``[S, W]``
     when staged); :meth:`table` views one table.  ``tuple_len`` is the longest length.
 
+    ``init_value``: None (zero weights), or a score for :meth:`fill_value` -- optimistic initialisation.
+
     ``stages``: None, or a sequence of at most 7 strictly ascending thresholds in 1..65535 (:func:`stage_mask`) for a
     multi-stage network of ``S = len(stages) + 1`` weight sets: ``weights`` is then ``[S, T, 16^L]``,
     a board reads and updates the set ``stage(board)`` = the number of thresholds its tile mask is not below, and every
@@ -292,7 +359,7 @@ class NTupleNet:
     board, the leaves of a search and the slots of a trace may all be in different stages.  Memory: S times the unstaged
     network's."""
 
-    def __init__(self, tuples="4x6", frac_bits=10, device="cuda:0", stages=None, mixed=False):
+    def __init__(self, tuples="4x6", frac_bits=10, device="cuda:0", stages=None, mixed=False, init_value=None):
         if isinstance(tuples, str):
             if tuples not in TUPLES:
                 raise ValueError(f"tuples must be one of {sorted(TUPLES)} or a sequence of cell lists, not {tuples!r}")
@@ -334,6 +401,23 @@ class NTupleNet:
             for k in range(length):
                 c_net.cells[t][k] = cells[k] if k < len(cells) else NTUPLE_END
         c_net.weights = self.weights.data_ptr()
+        if init_value is not None:
+            self.fill_value(init_value)
+
+    def fill_value(self, score):
+        """Optimistic initialisation (Guei, Chen & Wu 2022): every weight of every table and stage is set to
+        ``floor((score << frac_bits) / (8 * T))``, so that ``V(b)`` is that constant times ``8 T`` -- ``score``, to within the
+        rounding -- for every board, and an afterstate that was never tried looks as good as ``score`` until it is tried.
+        ``score``: an int, in points.  ValueError when the weight does not fit in int32.  On the current stream of the weights'
+        device; the accumulators of an :class:`NTupleTC` are not touched.  ``NTupleNet(..., init_value=score)`` is the same at
+        construction."""
+        score = _int_arg("score", score, -(1 << 62), 1 << 62)
+        weight = (score << self.frac_bits) // (8 * self.n_tuples)
+        if not -(1 << 31) <= weight < 1 << 31:
+            raise ValueError(f"fill_value: score {score} needs the weight {weight}, which does not fit in int32 "
+                             f"(frac_bits={self.frac_bits}, {self.n_tuples} tuples)")
+        self.weights.fill_(weight)
+        return self
 
     @property
     def n_tuples(self):
@@ -1483,6 +1567,103 @@ class ReducedPlayer:
         engine.ntuple_reduced_search(self.net, self.schedule, self.reduce4, out=NTupleAdaptive(actions, None, None), active=active)
 
 
+class DowngradedPlayer:
+    """A :class:`DeepPlayer`, :class:`AdaptivePlayer` or :class:`ReducedPlayer` searching translated boards (tile-downgrading,
+    INTEGRATION.md §26), for :func:`play_games`: per move ``engine.downgraded_boards(rule, active)`` and then the wrapped
+    player's search of its own network on those plain boards (``net.deep_search`` / ``adaptive_search`` / ``reduced_search``).
+    A board that rests comes out of the translation as the empty board, which every plain search answers at once with action
+    0, so resting boards are not searched and nothing is read by the host.  A callable ``player(engine, actions, active=None)``
+    with ``takes_active``."""
+    takes_active = True
+
+    def __init__(self, player, rule):
+        if not isinstance(player, (DeepPlayer, AdaptivePlayer, ReducedPlayer)):
+            raise ValueError("player must be a DeepPlayer, an AdaptivePlayer or a ReducedPlayer")
+        _rule(rule)
+        self.player, self.rule, self._boards = player, rule, None
+
+    def __call__(self, engine, actions, active=None):
+        if self._boards is None or self._boards.shape[0] != engine.n_envs or self._boards.device != engine.device:
+            self._boards = torch.empty((engine.n_envs, 16), dtype=torch.uint8, device=engine.device)
+        boards = engine.downgraded_boards(self.rule, active=active, out=Downgraded(self._boards, None)).boards
+        p = self.player            # (the plain searches run on the current stream of the boards' device: the engine's)
+        if isinstance(p, DeepPlayer):
+            p.net.deep_search(boards, p.depth, out=NTupleSearch(actions, None))
+        elif isinstance(p, ReducedPlayer):
+            p.net.reduced_search(boards, p.schedule, p.reduce4, out=NTupleAdaptive(actions, None, None))
+        else:
+            p.net.adaptive_search(boards, p.schedule, out=NTupleAdaptive(actions, None, None))
+
+
+def _play_games(engine, net, games, chunk, max_steps, depth, player, downgrade) -> PlayReport:
+    """:func:`play_games`, every argument given."""
+    games = _int_arg("games", games, 1, (1 << 32) - 1)
+    chunk = _int_arg("chunk", chunk, 1, (1 << 32) - 1)
+    if max_steps is not None:
+        max_steps = _int_arg("max_steps", max_steps, 1, 1 << 62)
+    depth = _int_arg("depth", depth, 0, SEARCH_MAX_DEPTH)
+    if player is not None:
+        if not callable(player):
+            raise ValueError("player must be a callable player(engine, actions)")
+        if depth != 0:
+            raise ValueError(f"depth={depth} with a player: depth searches net, a player chooses its own actions")
+    elif not isinstance(net, NTupleNet):
+        raise ValueError("net must be an NTupleNet (or give a player)")
+    if downgrade is not None:
+        _rule(downgrade)
+        if player is not None:
+            raise ValueError("downgrade with a player: wrap the player in DowngradedPlayer(player, rule) instead")
+    n, dev = engine.n_envs, engine.device
+    engine.reset()
+    # (filled as the signed types of the same width and viewed: every torch build fills and sums those on the device)
+    left = torch.full((n,), games - (1 << 32) if games >> 31 else games, dtype=torch.int32, device=dev).view(torch.uint32)
+    hist = torch.zeros(32, dtype=torch.int64, device=dev).view(torch.uint64)
+    moves = torch.zeros(1, dtype=torch.int64, device=dev).view(torch.uint64)
+    before, steps = engine.episode_stats(), 0
+    act = torch.empty(n, dtype=torch.uint8, device=dev) if player is not None or depth else None
+    takes_active = bool(getattr(player, "takes_active", False))
+    low = Downgraded(torch.empty((n, 16), dtype=torch.uint8, device=dev), None) if downgrade is not None and depth else None
+    while max_steps is None or steps < max_steps:
+        if act is None:
+            engine.ntuple_play(net, chunk, games_left=left, hist=hist, moves=moves, downgrade=downgrade)
+        else:
+            for _ in range(chunk):        # (a chunk that outlives every game steps resting boards: launches, no work)
+                if takes_active:
+                    player(engine, act, active=left)
+                elif player is not None:
+                    player(engine, act)
+                elif low is not None:
+                    engine.downgraded_boards(downgrade, active=left, out=low)
+                    net.search(low.boards, depth, out=NTupleSearch(act, None))
+                else:
+                    engine.ntuple_search(net, depth, out=NTupleSearch(act, None), active=left)
+                engine.play_step(act, games_left=left, hist=hist, moves=moves)
+        steps += chunk
+        if not bool(left.view(torch.int32).any()):
+            break
+    after = engine.episode_stats()
+    played = after["episodes"] - before["episodes"]
+    counts = [int(c) for c in hist.view(torch.int64).tolist()]
+    reach = {tile: (sum(counts[tile.bit_length() - 1:]) / played if played else 0.0) for tile in REACH_TILES}
+    scores = engine.last_scores() if games == 1 and engine.last_records_enabled else None
+    return PlayReport(played, n * games - played, (after["return_sum"] - before["return_sum"]) / played if played else 0.0, counts,
+                      reach, int(moves.view(torch.int64).item()), scores)
+
+
+def _downgrade_keyword(fn):
+    """``fn`` with the keyword-only ``downgrade=`` (a :class:`Downgrade`) added; the positional arguments are
+    ``fn``'s, unchanged."""
+    params = inspect.signature(fn)
+
+    @functools.wraps(fn)
+    def call(*args, downgrade=None, **kw):
+        bound = params.bind(*args, **kw)
+        bound.apply_defaults()
+        return _play_games(*bound.args, **bound.kwargs, downgrade=downgrade)
+    return call
+
+
+@_downgrade_keyword
 def play_games(engine, net, games=1, chunk=1024, max_steps=None, depth=0, player=None) -> PlayReport:
     """Exactly ``games`` games on every board of ``engine`` (a spawn-stream ``Batched2048``), played to the end, by one of
     three players.  ``depth=0`` (the default): the greedy player of ``net`` -- resets the engine, then
@@ -1497,47 +1678,9 @@ def play_games(engine, net, games=1, chunk=1024, max_steps=None, depth=0, player
     over-weighted the way counting every episode of a fixed step budget over-weights them.  ``max_steps``: stop after at
     least that many steps per board (a multiple of ``chunk``) and report what is missing as ``unfinished``.  The engine's
     statistics keep running: the report is the difference of two ``episode_stats()`` readings.  The games are a function of
-    the engine's seed and of its clock at the reset: ``engine.seed(s)`` first makes a report reproducible."""
-    games = _int_arg("games", games, 1, (1 << 32) - 1)
-    chunk = _int_arg("chunk", chunk, 1, (1 << 32) - 1)
-    if max_steps is not None:
-        max_steps = _int_arg("max_steps", max_steps, 1, 1 << 62)
-    depth = _int_arg("depth", depth, 0, SEARCH_MAX_DEPTH)
-    if player is not None:
-        if not callable(player):
-            raise ValueError("player must be a callable player(engine, actions)")
-        if depth != 0:
-            raise ValueError(f"depth={depth} with a player: depth searches net, a player chooses its own actions")
-    elif not isinstance(net, NTupleNet):
-        raise ValueError("net must be an NTupleNet (or give a player)")
-    n, dev = engine.n_envs, engine.device
-    engine.reset()
-    # (filled as the signed types of the same width and viewed: every torch build fills and sums those on the device)
-    left = torch.full((n,), games - (1 << 32) if games >> 31 else games, dtype=torch.int32, device=dev).view(torch.uint32)
-    hist = torch.zeros(32, dtype=torch.int64, device=dev).view(torch.uint64)
-    moves = torch.zeros(1, dtype=torch.int64, device=dev).view(torch.uint64)
-    before, steps = engine.episode_stats(), 0
-    act = torch.empty(n, dtype=torch.uint8, device=dev) if player is not None or depth else None
-    takes_active = bool(getattr(player, "takes_active", False))
-    while max_steps is None or steps < max_steps:
-        if act is None:
-            engine.ntuple_play(net, chunk, games_left=left, hist=hist, moves=moves)
-        else:
-            for _ in range(chunk):        # (a chunk that outlives every game steps resting boards: launches, no work)
-                if takes_active:
-                    player(engine, act, active=left)
-                elif player is not None:
-                    player(engine, act)
-                else:
-                    engine.ntuple_search(net, depth, out=NTupleSearch(act, None), active=left)
-                engine.play_step(act, games_left=left, hist=hist, moves=moves)
-        steps += chunk
-        if not bool(left.view(torch.int32).any()):
-            break
-    after = engine.episode_stats()
-    played = after["episodes"] - before["episodes"]
-    counts = [int(c) for c in hist.view(torch.int64).tolist()]
-    reach = {tile: (sum(counts[tile.bit_length() - 1:]) / played if played else 0.0) for tile in REACH_TILES}
-    scores = engine.last_scores() if games == 1 and engine.last_records_enabled else None
-    return PlayReport(played, n * games - played, (after["return_sum"] - before["return_sum"]) / played if played else 0.0, counts,
-                      reach, int(moves.view(torch.int64).item()), scores)
+    the engine's seed and of its clock at the reset: ``engine.seed(s)`` first makes a report reproducible.
+    ``downgrade`` (a :class:`Downgrade`): every move is chosen on the translated board -- the greedy player
+    through ``engine.ntuple_play(..., downgrade=)``, one launch per chunk as before; ``depth`` 1..2 through
+    ``engine.downgraded_boards(downgrade, active=left)`` and ``net.search`` of those boards.  A ``player`` is wrapped by the
+    caller (:class:`DowngradedPlayer`); ``downgrade`` with a ``player`` is refused.  Keyword only; None: today's call."""
+    return _play_games(engine, net, games, chunk, max_steps, depth, player, None)

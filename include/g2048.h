@@ -1118,6 +1118,54 @@ int g2048_ntuple_staged_log_train_restart(g2048_engine *e, const g2048_ntuple_st
                                           const g2048_ntuple_log *log, int64_t *delta, const g2048_ntuple_tc *tc,
                                           const g2048_restart *restart, void *stream);
 
+/* Tile-downgrading (after Guei, Chen & Wu, "Optimistic Temporal Difference Learning for 2048", IEEE
+ * Transactions on Games 2022): at play time a board with very large tiles is translated into a board the network knows far
+ * better, and the move is chosen on the translated board.  The choice of k and the guard below are this project's own -- the
+ * paper could not be consulted while building, and it activates on the 32768 tile where activation is a parameter here.
+ * The rule, in exponents e_c = byte & 0x1f of cell c (so it reads an engine record as well as a plain board; the score bits of
+ * a record never reach the result), with min_exp in 1..31 and floor_exp in G2048_DOWNGRADE_MIN_FLOOR..31:
+ *   P = the set of exponents e >= 1 on the board;  D = the set of exponents held by two or more cells
+ *   m = max P                                                    (empty board: identity, k = 0)
+ *   m < min_exp: identity, k = 0
+ *   k = the LARGEST c with floor_exp <= c < m, c not in P and (c - 1) not in D;   none: identity, k = 0
+ *   out_c = e_c - 1 where e_c > k, else e_c
+ * k is the "missing tile".  The third condition keeps the translated board honest one move ahead: two tiles 2^(k-1) could
+ * merge into a real 2^k, which would sit beside the halved 2^(k+1) and look mergeable with it; deeper collisions of this kind
+ * are accepted.  The floor keeps the spawn tiles (exponents 1, 2) and their first merge away from k.  The map is injective and
+ * order-preserving on the tiles of one board: a move is legal on the translated board exactly where it is legal on the board,
+ * and slides and merges the same cells; only the gains of halved tiles differ.  One application per board: a 65536 board at
+ * min_exp = 15 becomes a 32768 board. */
+#define G2048_DOWNGRADE_MIN_FLOOR 4
+#define G2048_DOWNGRADE_SKIPPED 0xff
+typedef struct g2048_downgrade {
+    uint32_t min_exp;              /* 1..31: boards whose largest exponent is below it are left alone */
+    uint32_t floor_exp;            /* G2048_DOWNGRADE_MIN_FLOOR..31: the smallest k */
+} g2048_downgrade;
+/* out[i] = the translation of boards[i] (plain uint8[n][16], device memory, 16-byte aligned; 1 <= n <= 2^32 - 256) and, where
+ * `missing` is not NULL, missing[i] = its k (0: unchanged).  One launch on the current device, 16 bytes in and 16 (+ 1) out per
+ * board.  out == boards is allowed. */
+int g2048_downgrade_plain(const uint8_t *boards, uint64_t n, const g2048_downgrade *rule, uint8_t *out /* [n][16] */,
+                          uint8_t *missing /* [n], or NULL */, void *stream);
+/* The same of the engine's live records, in either RNG mode; nothing of the engine changes.  active (uint32[n], 4-byte
+ * aligned, or NULL): a board at 0 gets the all-empty board and missing = G2048_DOWNGRADE_SKIPPED -- the input every *_plain
+ * search answers at once with action 0 and four G2048_NTUPLE_ILLEGAL, so g2048_downgrade_boards(active = games_left) -> any
+ * *_plain search -> g2048_play_step plays a budgeted game with look-ahead on translated boards with no host read, and resting
+ * boards are not searched. */
+int g2048_downgrade_boards(const g2048_engine *e, const g2048_downgrade *rule, const uint32_t *active /* [n] or NULL */,
+                           uint8_t *out /* [n][16] */, uint8_t *missing /* [n], or NULL */, void *stream);
+/* g2048_ntuple_play with one difference: each move's action is the greedy player's on the TRANSLATED cells of the record (a
+ * staged network takes the stage of the translated board).  The record itself is stepped, reset and counted as before: the
+ * gains, hist, moves, games_left, the episode slots and the terminal records describe the real game.  The contract in one
+ * sentence: the records, the clock, the episode slots, the terminal records, the side outputs and the engine's randomness end
+ * as the same bits as after k_steps rounds of g2048_downgrade_boards -> g2048_ntuple_evaluate_plain -> g2048_play_step(its
+ * `action`) with the same io.  G2048_ERR_INVALID, before any HIP call: what g2048_ntuple_play refuses (the numpy-RNG engine
+ * included), a NULL rule, min_exp outside 1..31 and floor_exp outside G2048_DOWNGRADE_MIN_FLOOR..31; for the two calls above a
+ * NULL engine / boards, rule or out, `out` or `boards` not 16-byte or `active` not 4-byte aligned, and n out of range. */
+int g2048_ntuple_play_downgraded(g2048_engine *e, const g2048_ntuple_net *net, const g2048_downgrade *rule, uint32_t k_steps,
+                                 const g2048_ntuple_play_io *io /* may be NULL */, void *stream);
+int g2048_ntuple_staged_play_downgraded(g2048_engine *e, const g2048_ntuple_staged_net *net, const g2048_downgrade *rule,
+                                        uint32_t k_steps, const g2048_ntuple_play_io *io, void *stream);
+
 /* Game2048Env.add_tile (game2048_env.py:166-176): one spawn from slot `slot` of the current
  * transaction on every board that has an empty cell. */
 int g2048_add_tile(g2048_engine *e, uint32_t slot, void *stream);
